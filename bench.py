@@ -8,8 +8,10 @@ as the per-layer (K, V) tensors LMCacheEngine.store() receives.
 
 One "step" = one pass of the encode path over the whole context through the C ABI (lmc_encode_chunks):
 gather from the per-layer tensors, quantise, CDF, entropy-encode, compact into 64 blobs in an HBM arena.
-`value` is that rate (inputs and outputs in HBM; PCIe never inside `value`).  Everything else is measured
-outside the timed region, on rank 0, and reported as extra objects of the same JSON line:
+`value` is that rate (inputs and outputs in HBM; PCIe never inside `value`).  A plain run sets up, ramps the clock,
+warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what the last timed step computed
+(dump_outputs).  With --full, everything else is measured outside the timed region, on rank 0, and reported as extra
+objects of the same JSON line:
 
   roofline       HBM roof of the step (algorithmic bytes / HIP-event time) + the VALU-issue roof the coder sits under
   offload        the product's store leg: encode + exact-size pinned hipMemcpyAsync D2H (PCIe-inclusive), >= 5 reps
@@ -24,8 +26,8 @@ outside the timed region, on rank 0, and reported as extra objects of the same J
 
 N>1 (torch.distributed, one rank per GPU): the path shards by chunk with no data-path collective
 (SURVEY.md section 8e), so every rank encodes its own 16k-token context (weak scaling); the barrier and the
-max-over-ranks timing use RCCL, the data path does not.  Every rank also runs the offload leg at the same
-time (its own PCIe link, NUMA-local pinned arena) and, for the sharing path (BASELINE configs[2]), one
+max-over-ranks timing use RCCL, the data path does not.  With --full, every rank also runs the offload leg at
+the same time (its own PCIe link, NUMA-local pinned arena) and, for the sharing path (BASELINE configs[2]), one
 exchange step of encoded chunks through the xgmi:// connector.
 
 LMC_BENCH_STUB=1 rehearses the launch plumbing on CPU (gloo, the timed kernel replaced by a sleep): that is how
@@ -527,6 +529,37 @@ def shape_rate(native, ctx, dev, name, nl, nh, hd, dtype, ntok, model, paged=Fal
     return row
 
 
+DUMP_SAMPLE_BYTES = 1 << 16  # bytes of every blob written to blob_sample.npy (first 256 + seeded offsets within its size)
+
+
+def dump_outputs(out_dir, blobs, sizes, stride, n):
+    """What the timed step hands its caller -- n blobs (uint8, blob i at i * stride, sizes[i] bytes) and their sizes --
+    as float arrays under out_dir, small enough to keep (16 MB at the bench shape):
+      sizes.npy           float64 [n]: bytes of every blob
+      blob_checksums.npy  float64 [n, 2]: per blob the sum of its bytes and the sum of byte * (offset % 65521 + 1),
+                          exact integers over every byte of the blob (the slack after sizes[i] is left out)
+      blob_sample.npy     float32 [n, DUMP_SAMPLE_BYTES]: byte values of every blob at its first 256 offsets and at sorted
+                          offsets drawn from a generator seeded with the blob's index and size (the same blob, the same
+                          sample)"""
+    os.makedirs(out_dir, exist_ok=True)
+    szs = [int(s) for s in sizes[:n].cpu().tolist()]
+    sums = np.zeros((n, 2), np.float64)
+    sample = np.zeros((n, DUMP_SAMPLE_BYTES), np.float32)
+    for i, sz in enumerate(szs):
+        b = blobs[i * stride:i * stride + sz].to(torch.int64)
+        w = torch.arange(sz, device=b.device, dtype=torch.int64) % 65521 + 1
+        sums[i] = (int(b.sum()), int((b * w).sum()))
+        head = min(256, sz, DUMP_SAMPLE_BYTES)
+        rest = np.random.default_rng([i, sz]).integers(0, max(sz, 1), DUMP_SAMPLE_BYTES - head) if sz else np.zeros(0, np.int64)
+        offs = np.concatenate([np.arange(head), np.sort(rest)])
+        if sz:
+            sample[i] = b[torch.from_numpy(offs).to(b.device)].cpu().numpy()
+        del b, w
+    np.save(os.path.join(out_dir, "sizes.npy"), np.array(szs, np.float64))
+    np.save(os.path.join(out_dir, "blob_checksums.npy"), sums)
+    np.save(os.path.join(out_dir, "blob_sample.npy"), sample)
+
+
 # ---------------------------------------------------------------------------------------------- main
 def arm_watchdog(seconds, res, rank):
     """If the multi-GPU legs are not done after `seconds`, rank 0 prints the result of the timed region (which is
@@ -560,17 +593,27 @@ def main(argv=None):
                          "values assume); strong = ONE 16 k context, rank r takes chunks r, r + N, ... (SURVEY.md 8e: the "
                          "replicated-instance split, lmcache_amd.distributed.shard_chunks), value = the context's bytes / "
                          "max-over-ranks time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (blob sizes, per-blob checksums, a seeded "
+                         "sample of the blob bytes) as float .npy files under DIR (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: clock / power sampling, roofline and per-kernel figures, both "
+                         "launch paths, cold store, the store / retrieve / TTFT legs, other seeds, distributions and "
+                         "geometries, the CPU baselines, and for N > 1 the offload and exchange legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--profile-legs", action="store_true",
-                    help="for the rocprofv3 passes: after the timed region also 5 jobs of the two-kernel path and 5 HBM-resident "
-                         "decodes of the context (k_quantize, k_cdf_encode, k_decode rows in the same database), then the line")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region and the roofline")
+                    help="with --full, for the rocprofv3 passes: after the timed region also 5 jobs of the two-kernel path and "
+                         "5 HBM-resident decodes of the context (k_quantize, k_cdf_encode, k_decode rows in the same "
+                         "database), then the line")
+    ap.add_argument("--no-extras", action="store_true", help="--full with only the timed region and the roofline")
     ap.add_argument("--cpu-chunks", type=int, default=0, help="chunks in the cpu_baseline sample (0 = auto)")
     ap.add_argument("--no-exchange", action="store_true", help="N>1: skip the exchange leg")
     ap.add_argument("--legs-timeout", type=int, default=180, help="N>1: seconds the offload / exchange legs may take")
     ap.add_argument("--exchange-transport", choices=("both", "ipc", "rccl"), default="both",
                     help="N>1 exchange leg: HIP-IPC connector (xgmi://), RCCL batch_isend_irecv (XgmiShardStore), or both")
     args = ap.parse_args(argv)
+    if args.profile_legs and not args.full:
+        ap.error("--profile-legs runs behind the timed region of a --full run")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -643,7 +686,7 @@ def main(argv=None):
     # first ~50 ms of work below its sustained clock (tools/probes/encode_ab.hip, alternating rounds: the first 40
     # jobs average 1.23 ms, every later round 1.185), which is longer than W + K steps of this workload.  The
     # same full steps on the same buffers, ~0.25 s of them.
-    sampler = GpuSampler(local_rank) if (not STUB and rank == 0) else None
+    sampler = GpuSampler(local_rank) if (args.full and not STUB and rank == 0) else None
     if sampler:
         sampler.start()
     t_ramp0 = time.perf_counter()
@@ -706,12 +749,14 @@ def main(argv=None):
            "clock_ramp": {"untimed_steps_before_warmup": ramp_steps, "ms": args.ramp_ms,
                           "why": "a GPU fresh out of idle runs its first ~50 ms below its sustained clock; W + K steps "
                                  "of this workload are shorter than that (--ramp-ms 0 turns it off)"}}
+    if args.dump_outputs and rank == 0 and not STUB:  # before anything else reuses the blob arena
+        dump_outputs(args.dump_outputs, blobs, sizes, stride, len(my_chunks))
     # ---- N>1: every rank's own offload leg at the same time (its PCIe link, its NUMA-local arena), and one
     # exchange step of encoded chunks (BASELINE configs[2]) by HIP-IPC and by RCCL; outside the timed region.  A
     # watchdog guards the contract: should a multi-GPU leg hang (a peer that died, a collective out of step), rank 0
     # still prints the JSON line of the timed region and every rank leaves.
     offload_all = exchange = None
-    if use_dist and not STUB and not args.no_extras:
+    if use_dist and not STUB and args.full and not args.no_extras:
         wd = arm_watchdog(args.legs_timeout, res, rank)
         offload_all = all_ranks_offload(ctx, layout, bins, dev, local_rank, world)
         if not args.no_exchange:
@@ -734,7 +779,15 @@ def main(argv=None):
             dist.destroy_process_group()
         return
 
-    # ---- rank 0 extras (outside the timed region) -------------------------------
+    if not args.full:  # a plain run: the headline line and nothing else
+        print(json.dumps(res))
+        if use_dist:
+            dist.barrier()
+            torch.cuda.synchronize()
+            dist.destroy_process_group()
+        return
+
+    # ---- rank 0 extras (--full, outside the timed region) -------------------------------
     from lmcache_amd import native
     sz = sizes.cpu().numpy().astype(np.int64)
     blob_bytes = int(sz.sum())
