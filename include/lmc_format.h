@@ -19,7 +19,7 @@
  *
  *   header   128 B          struct lmc_blob_header
  *   bins     u8  [P]        quantisation bins of each plane (32 or 16 ...)
- *   scales   u16 [P][T]     per-(plane,token) absmax, raw bits of the KV dtype
+ *   scales   u16 [P][T]     per-(plane,token) absmax, raw bits of header.dtype (fp8 KV: the bf16 image of the fp8 max)
  *                           (= max_tensors_key ++ max_tensors_value)
  *   scsum    u32 [P]        checksum of each plane's scales (v4): sum over t of (t + 1) * (bits_t + 1)
  *                           mod 2^32 -- lmc_scale_checksum_term.  The entropy coder detects damage to the
@@ -111,6 +111,11 @@ extern "C" {
 
 #define LMC_DTYPE_BF16 0
 #define LMC_DTYPE_FP16 1
+/* 8-bit KV (OCP formats, gfx950's: not the MI300 "fnuz" ones).  Every fp8 value, NaN and inf included, has an exact bf16
+ * image, so an fp8 chunk is encoded as the bf16 chunk of those images: header.dtype stays LMC_DTYPE_BF16 (the type of the
+ * scales and of the encoded values) and header.kv_dtype says which type the chunk was stored in. */
+#define LMC_DTYPE_FP8_E4M3 2 /* torch.float8_e4m3fn */
+#define LMC_DTYPE_FP8_E5M2 3 /* torch.float8_e5m2 */
 
 #define LMC_LANES 64        /* channels per group stream = wavefront width  */
 #define LMC_MAX_BINS 32     /* torchac_cuda.calculate_cdf(sym, 32)          */
@@ -149,7 +154,11 @@ typedef struct lmc_blob_header {
   uint32_t zero18[3];    /* (v2-v5: off_rowpre, cdf_rows, count_bytes) */
   uint32_t off_scsum;    /* per-plane scale checksums */
   uint32_t model;        /* LMC_MODEL_*: = lmc_model_for(ntokens) */
-  uint32_t reserved[9];
+  uint32_t kv_dtype;     /* word 23: LMC_DTYPE_* the KV was stored in when it differs from `dtype` (fp8: LMC_DTYPE_FP8_*,
+                            with dtype = BF16); 0 = the same as `dtype` (every blob of a 16-bit KV, every blob written
+                            before the field existed: it was reserved and 0).  Only the engine's choice of the dtype a
+                            retrieve returns reads it: the encoded bytes are those of the bf16 images. */
+  uint32_t reserved[8];
 } lmc_blob_header;
 
 static inline uint32_t lmc_r16(uint32_t x) { return (x + 15u) & ~15u; }

@@ -51,7 +51,7 @@ int lmc_abi_version(void);
 /* KV addressing                                                       */
 /* ------------------------------------------------------------------ */
 /*
- * Where the 16-bit element (layer l, kv, token t, head h, dim d) of a KV cache
+ * Where the element (layer l, kv, token t, head h, dim d) of a KV cache
  * lives.  One descriptor covers every layout the reference's engine and the
  * (external) vLLM connector hand over:
  *   - chunk blob  [L,2,T,H,D]  "vllm" fmt          (cache_engine.py:137-138)
@@ -67,7 +67,8 @@ int lmc_abi_version(void);
  *                               s = slot_mapping[t]
  *                             : t*stride_token
  * d is contiguous.  A plane has a multiple of 8 channels (num_heads * head_size % 8 == 0).  Layouts the ENCODERS read
- * (lmc_quantize, lmc_encode_chunks, lmc_store_*) are read with 16-byte vectors of 8 channels: base 16-byte aligned,
+ * (lmc_quantize, lmc_encode_chunks, lmc_store_*) are read with vectors of 8 channels -- 16 bytes for the 16-bit dtypes, 8 bytes
+ * for fp8 -- : base aligned to one vector (16 B; fp8: 8 B),
  * stride_layer / stride_kv / stride_token / stride_block multiples of 8 elements, and either head_size % 8 == 0 with
  * stride_head % 8 == 0, or stride_head == head_size (the heads of a token row back to back -- the vllm chunk, the
  * per-layer [T,H,D] tensors, NBHD blocks -- where any head_size will do).  The DECODERS' destination and both sides of
@@ -75,7 +76,7 @@ int lmc_abi_version(void);
  * the way to bring such a range into a chunk the encoders take; lmcache_amd's codec does that by itself).
  */
 typedef struct lmc_kv_layout {
-  int32_t dtype;      /* LMC_DTYPE_BF16 / LMC_DTYPE_FP16 */
+  int32_t dtype;      /* LMC_DTYPE_BF16 / FP16 / FP8_E4M3 / FP8_E5M2 (elements of 2 or 1 bytes; strides count elements) */
   int32_t num_layers; /* L */
   int32_t num_heads;  /* H (KV heads held by this rank) */
   int32_t head_size;  /* D */
@@ -159,7 +160,8 @@ int lmc_ctx_profile_read(lmc_ctx* ctx, float* ms_out, int cap);
  *   bins_h   host int32 [2L], plane order (key_bins ++ value_bins,
  *            cachegen_encoder.py:339-350)
  *   sym_out  int8  [2L][ntok][C]   (= encode_input)
- *   scale_out u16  [2L][ntok]      raw bits of src dtype (= max_tensors_key ++ max_tensors_value)
+ *   scale_out u16  [2L][ntok]      raw bits of src dtype (= max_tensors_key ++ max_tensors_value); fp8 src: of the
+ *                                  bf16 image of the max
  */
 int lmc_quantize(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok,
                  const int32_t* bins_h, int8_t* sym_out, uint16_t* scale_out, lmc_stream_t stream);
@@ -378,7 +380,8 @@ int lmc_event_elapsed_ms(lmc_event_t start, lmc_event_t stop, float* ms);
 
 /* Host-side blob header check/parse (no GPU).  Stands where
  * CacheGenEncoderOutput.from_bytes is used to inspect a blob
- * (tests/test_serde.py:60-62). */
+ * (tests/test_serde.py:60-62).  A kv_dtype other than 0, LMC_DTYPE_FP8_E4M3 or LMC_DTYPE_FP8_E5M2, or an fp8 kv_dtype on a
+ * blob whose dtype is not bf16, is refused like any other damaged header. */
 int lmc_blob_info(const void* blob_h, size_t nbytes, lmc_blob_header* out);
 
 #ifdef __cplusplus

@@ -49,3 +49,33 @@ __global__ __launch_bounds__(256) void k_copy_kv_elem(CopyArgs a) {
     *dp = *sp;
   }
 }
+
+// The two copies for 1-byte elements (fp8 KV): a vector of 8 channels is 8 bytes, an element one byte.  Same addressing
+// as above with the byte as unit; raw tiers move the fp8 bytes unchanged.
+__global__ __launch_bounds__(256) void k_copy_kv_b8(CopyArgs a) {
+  const int C8 = a.C >> 3;
+  for (long long id = (long long)blockIdx.x * 256 + threadIdx.x; id < a.nvec; id += (long long)gridDim.x * 256) {
+    const int j = (int)(id % C8);
+    const long long r = id / C8;
+    const int t = (int)(r % a.ntok);
+    const int p = (int)(r / a.ntok);
+    const int c0 = j * 8;
+    const int hs = c0 / a.src.D, ds = c0 - hs * a.src.D;
+    const u8* sp = lmc_plane_base<u8>(a.src, p) + lmc_tok_off(a.src, a.tok_begin + t) + (long long)hs * a.src.stride_head + ds;
+    u8* dp = const_cast<u8*>(lmc_plane_base<u8>(a.dst, p)) + lmc_tok_off(a.dst, a.dst_tok0 + t) + (long long)hs * a.dst.stride_head + ds;
+    *reinterpret_cast<LMC_GLOBAL u32x2_t*>((LMC_GLOBAL u8*)dp) = *reinterpret_cast<const LMC_GLOBAL u32x2_t*>((const LMC_GLOBAL u8*)sp);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_copy_kv_elem_b8(CopyArgs a) {
+  for (long long id = (long long)blockIdx.x * 256 + threadIdx.x; id < a.nvec; id += (long long)gridDim.x * 256) {
+    const int ch = (int)(id % a.C);
+    const long long r = id / a.C;
+    const int t = (int)(r % a.ntok);
+    const int p = (int)(r / a.ntok);
+    const int hs = ch / a.src.D, ds = ch - hs * a.src.D;
+    const u8* sp = lmc_plane_base<u8>(a.src, p) + lmc_tok_off(a.src, a.tok_begin + t) + (long long)hs * a.src.stride_head + ds;
+    u8* dp = const_cast<u8*>(lmc_plane_base<u8>(a.dst, p)) + lmc_tok_off(a.dst, a.dst_tok0 + t) + (long long)hs * a.dst.stride_head + ds;
+    *dp = *sp;
+  }
+}

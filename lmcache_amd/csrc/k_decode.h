@@ -106,6 +106,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   __shared__ __attribute__((aligned(16))) u8 lds_all[DEC_WAVES * (DEC_LUT_BYTES + DEC_WAVE_BYTES)];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform -> SGPRs
+  constexpr bool OUT8 = lmc_dtype_fp8(DT_OUT);  // fp8 destination: one byte per element
+  constexpr int ESZ = OUT8 ? 1 : 2;
   // (32-bit work-item arithmetic: lmc_api.hip rejects a launch of 2^31 streams or more, and a 64-bit division costs
   // more than a hundred instructions per stream)
   u32 gid = blockIdx.x * (u32)DEC_WAVES + (u32)wave;
@@ -446,10 +448,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     lane_off = (u32)c;
   } else {
     const int h = c / a.dst.D, d = c - h * a.dst.D;
-    lane_off = (u32)(((long long)h * a.dst.stride_head + d) * 2);
-    ubase = uniform_ptr(lmc_plane_base(a.dst, p));
+    lane_off = (u32)(((long long)h * a.dst.stride_head + d) * ESZ);
+    ubase = uniform_ptr(lmc_plane_base<typename KvElem<DT_OUT>::T>(a.dst, p));
   }
   const int tdst0 = a.dst_tok0 + chunk * a.chunk_tokens;
+  const u32 fp8_lim = OUT8 ? fp8_fast_scale_limit<OUT8 ? DT_OUT : LMC_DTYPE_FP8_E4M3>(nsym + 1u) : 0u;  // (wave-uniform)
 
   // the ring bookkeeping is wave-uniform (SGPRs: its tests are scalar branches); runs when e <= trig
   auto ring_event = [&]() {
@@ -705,7 +708,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     // !PAGED: the rows of this stream through a raw buffer descriptor: base = row of the first stored token,
     // soffset (scalar) = one stride_token further each token, voffset = the lane's channel.  The descriptor's range
     // check (on voffset only) drops the stores of idle lanes, whose voffset is out of range: no exec masking.
-    const long long row_step = a.dst.stride_token * 2;
+    const long long row_step = a.dst.stride_token * ESZ;
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(ubase + (u64)((long long)(tdst0 + (int)nskip) * row_step)), (short)0, (int)0xfffffff0u, 0x00020000);
     const u32 voff = active ? lane_off : 0xfffffff8u;
@@ -730,7 +733,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     // block that is not (slots in any order, a first token in the middle of a group of eight of its block) sends the
     // whole stream through the one-token loop.
     u32 tgen = nskip;
-    if constexpr (!SYMOUT && SRC_BF16 && DT_OUT == LMC_DTYPE_BF16 && decltype(model_tag)::value) {
+    // fp8 destinations take the same blocks: two tokens' bytes leave as buffer_store_byte + buffer_store_byte_d16_hi.
+    if constexpr (!SYMOUT && SRC_BF16 && (DT_OUT == LMC_DTYPE_BF16 || OUT8) && decltype(model_tag)::value) {
       typedef u32x4_t __attribute__((aligned(4))) u32x4_a4;
       const u64 sc_addr = uniform_ptr(scl) + 2ull * nskip;
       if ((sc_addr & 2ull) == 0ull && nskip + 8u <= T) {
@@ -754,7 +758,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
             if (all_runs && 64u * r < 8u * nblk) {  // (a mapping that fails in its first 64 tokens costs one round)
               const u32 sl = slot[r];
               const u32 blk = pow2 ? sl >> bsh : sl / bs, w = sl - blk * bs;
-              const long long off = a.dst.slot_mapping ? ((long long)blk * a.dst.stride_block + (long long)w * a.dst.stride_token) * 2
+              const long long off = a.dst.slot_mapping ? ((long long)blk * a.dst.stride_block + (long long)w * a.dst.stride_token) * ESZ
                                                        : (long long)(tfirst + (int)(64u * r) + lane) * row_step;
               const u32 olo = (u32)(unsigned long long)off, ohi = (u32)((unsigned long long)off >> 32);
               const u32 blo = (u32)__builtin_amdgcn_ds_bpermute(first, (int)olo), bhi = (u32)__builtin_amdgcn_ds_bpermute(first, (int)ohi);
@@ -776,16 +780,35 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
             (void)decode_token(top_tag, model_tag, lvb, BoolTag<true>{});
             const float va = lva * __uint_as_float(s2 << 16), vb = lvb * __uint_as_float(s2 & 0xffff0000u);
             u32 w;
-            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(va), "v"(vb));
+            if constexpr (OUT8) {
+              // the two tokens' bytes at bits 0..7 and 16..23; both scales in range (wave-uniform): the instruction
+              if (max((s2 << 16) & 0x7fffffffu, s2 & 0x7fff0000u) <= fp8_lim) {
+                w = fp8_cvt_pk<DT_OUT>(va, vb);
+                w |= w << 8;
+              } else {
+                w = lmc_f32_to_fp8<DT_OUT>(va) | (lmc_f32_to_fp8<DT_OUT>(vb) << 16);
+              }
+            } else {
+              asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(va), "v"(vb));
+            }
 #ifdef LMC_EXP_NO_STORE  // (timing experiment: what the stores and the waits behind them cost; output is wrong)
             asm volatile("" :: "v"(w), "v"(voff), "s"(desc), "s"(soff));
 #elif defined(LMC_EXP_ONE_STORE)
-            asm volatile("buffer_store_short %0, %1, %2, %3 offen nt"
-                         :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
+            if constexpr (OUT8)
+              asm volatile("buffer_store_byte %0, %1, %2, %3 offen nt"
+                           :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
+            else
+              asm volatile("buffer_store_short %0, %1, %2, %3 offen nt"
+                           :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
 #else
-            asm volatile("buffer_store_short %0, %1, %2, %3 offen nt\n\t"
-                         "buffer_store_short_d16_hi %0, %1, %2, %4 offen nt"
-                         :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
+            if constexpr (OUT8)
+              asm volatile("buffer_store_byte %0, %1, %2, %3 offen nt\n\t"
+                           "buffer_store_byte_d16_hi %0, %1, %2, %4 offen nt"
+                           :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
+            else
+              asm volatile("buffer_store_short %0, %1, %2, %3 offen nt\n\t"
+                           "buffer_store_short_d16_hi %0, %1, %2, %4 offen nt"
+                           :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
 #endif
             soff += 2u * (u32)row_step;
 #if LMC_DEC_RING_AGPR && !defined(LMC_EXP_NO_STORE) && !defined(LMC_EXP_ONE_STORE)
@@ -820,7 +843,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
       // PAGED: lane i works out the block row of token t0 + i once (slot_mapping load + division); every token
       // then takes its row with two v_readlane and the store goes through a descriptor based at that row
       long long tok_off2 = 0;
-      if (PAGED && !SYMOUT) tok_off2 = (t0 + (u32)lane < T) ? dec_tok_off(a.dst, tdst0 + (int)(t0 + (u32)lane)) * 2 : 0ll;
+      if (PAGED && !SYMOUT) tok_off2 = (t0 + (u32)lane < T) ? dec_tok_off(a.dst, tdst0 + (int)(t0 + (u32)lane)) * ESZ : 0ll;
       auto one_token = [&](u32 i) {
         float lv = 0.0f;
         const u32 sa = decode_token(top_tag, model_tag, lv, BoolTag<true>{});
@@ -831,7 +854,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
           const float scale = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc), (int)i));
           float val = lv * scale;
           u16 bits;
-          if (DT_OUT == LMC_DTYPE_BF16) bits = __builtin_bit_cast(unsigned short, (__bf16)val);  // v_cvt_pk_bf16_f32, RNE
+          if constexpr (OUT8) {  // ONE rounding, fp32 -> fp8, torch's rules (lmc_device.h: fp8_fast_scale_limit)
+            if (((u32)__float_as_uint(scale) & 0x7fffffffu) <= fp8_lim) bits = (u16)fp8_cvt_pk<DT_OUT>(val, val);
+            else bits = (u16)lmc_f32_to_fp8<DT_OUT>(val);
+          }
+          else if (DT_OUT == LMC_DTYPE_BF16) bits = __builtin_bit_cast(unsigned short, (__bf16)val);  // v_cvt_pk_bf16_f32, RNE
           else {
             // The product is rounded to fp32 FIRST and to fp16 second, as the reference does (x = xq / C * max1 in fp32,
             // then .to(float16): cachegen_decoder.py:20, 190-200).  Left to itself the compiler fuses the two into ONE
@@ -846,9 +873,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
             const u32 ohi = (u32)__builtin_amdgcn_readlane((int)(u32)((unsigned long long)tok_off2 >> 32), (int)i);
             __amdgpu_buffer_rsrc_t prow = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)(ubase + (((u64)ohi << 32) | (u64)olo)), (short)0, (int)0xfffffff0u, 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b16((short)bits, prow, (int)voff, 0, 2 /* nt */);
+            if constexpr (OUT8) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bits, prow, (int)voff, 0, 2 /* nt */);
+            else __builtin_amdgcn_raw_buffer_store_b16((short)bits, prow, (int)voff, 0, 2 /* nt */);
           } else {
-            __builtin_amdgcn_raw_buffer_store_b16((short)bits, rsrc, (int)voff, (int)soff, 2 /* nt */);
+            if constexpr (OUT8) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bits, rsrc, (int)voff, (int)soff, 2 /* nt */);
+            else __builtin_amdgcn_raw_buffer_store_b16((short)bits, rsrc, (int)voff, (int)soff, 2 /* nt */);
             soff += (u32)row_step;
           }
 #if LMC_DEC_RING_AGPR

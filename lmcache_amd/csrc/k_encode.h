@@ -74,7 +74,17 @@ __device__ __forceinline__ unsigned long long agg_load(unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Header, bins and the zero pads between sections (what the oracle memsets): by one wave.
+// The header's kv_dtype word (word 23) of `n` blobs, `stride` bytes apart: the fp8 jobs of the two-kernel path, behind
+// their coder on the same stream (the coder wrote 0 there).
+__global__ __launch_bounds__(64) void k_set_kv_dtype(u8* blobs, long long stride, int n, u32 kv_dtype) {
+  const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+  if (i < n) reinterpret_cast<u32*>(blobs + (long long)i * stride)[23] = kv_dtype;
+}
+
+// Header, bins and the zero pads between sections (what the oracle memsets): by one wave.  KV_DT: the header's kv_dtype
+// word (lmc_format.h), 0 but in the fused encoder's fp8 instances (the two-kernel path's coder does not know the KV
+// dtype: lmc_api.hip sets the word behind it, k_set_kv_dtype).
+template <int KV_DT = 0>
 __device__ __forceinline__ void write_blob_static(u8* blob, const BlobOff& bo, const EncodeArgs& a, u32 T,
                                                   u32 stream_bytes, int lane) {
   const u32 P = (u32)a.P, n = (u32)(a.P * a.G);
@@ -105,6 +115,9 @@ __device__ __forceinline__ void write_blob_static(u8* blob, const BlobOff& bo, c
       case 21: v = bo.scsum; break;
       case 22: v = lmc_model_for_dev(T); break;
       default: v = 0;
+    }
+    if constexpr (KV_DT != 0) {
+      if (lane == 23) v = (u32)KV_DT;
     }
     reinterpret_cast<u32*>(blob)[lane] = v;
   }

@@ -131,7 +131,7 @@ __device__ __forceinline__ long long fused_tok_off(const KvAddr& a, int t) {
 // ALLROWS: all eight rows of the oct are tokens of the chunk (every oct but the last one of a chunk whose length is no
 // multiple of 8): no per-row test, no zero fill -- what the kernel had when it only took 256-token chunks.
 template <int NITER, int DT, bool NIB, bool FULL = false, bool ALLROWS = true, bool PSRC = false>
-__device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const u16* pbase, int tok0, int Tc, int t_first,
+__device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const typename KvElem<DT>::T* pbase, int tok0, int Tc, int t_first,
                                                    bool q1valid, int C, float maxf, u32* sym_out, u16* scale_out,
                                                    uint4* park, int lane) {
   long long coff[NITER];
@@ -156,10 +156,10 @@ __device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const u16*
       for (int r = 0; r < 2; r++) {
         const int t = t_first + 4 * hq + r0 + r;
         tv[r] = ALLROWS || t < Tc;
-        const u16* rowp = pbase + (tv[r] ? fused_tok_off<PSRC>(src, tok0 + t) : 0);
+        const typename KvElem<DT>::T* rowp = pbase + (tv[r] ? fused_tok_off<PSRC>(src, tok0 + t) : 0);
 #pragma unroll
         for (int it = 0; it < NITER; it++) {
-          if (tv[r] && (FULL || cval[it])) v[r][it] = ld_global_u4_nt(rowp + coff[it]);  // streamed once
+          if (tv[r] && (FULL || cval[it])) v[r][it] = kv_ld8<DT, true>(rowp + coff[it]);  // streamed once
           else v[r][it] = make_uint4(0, 0, 0, 0);
         }
       }
@@ -169,14 +169,13 @@ __device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const u16*
         u32 m = 0;
 #pragma unroll
         for (int it = 0; it < NITER; it++) {
-          m = pk_max_u16(m, v[r][it].x & 0x7fff7fffu);
-          m = pk_max_u16(m, v[r][it].y & 0x7fff7fffu);
-          m = pk_max_u16(m, v[r][it].z & 0x7fff7fffu);
-          m = pk_max_u16(m, v[r][it].w & 0x7fff7fffu);
+          m = kv_absmax8<DT>(m, v[r][it]);
         }
         mrow[r] = max(m & 0xffffu, m >> 16);
       }
       wave_max2_u32(mrow[0], mrow[1]);  // wave-uniform from here on
+      mrow[0] = kv_max_scale<DT>(mrow[0]);  // (fp8: the max's bf16 image; else the max itself)
+      mrow[1] = kv_max_scale<DT>(mrow[1]);
       if (lane == 0) {
 #pragma unroll
         for (int r = 0; r < 2; r++)
@@ -188,15 +187,15 @@ __device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const u16*
                      // costs two vector instructions in front of every block of eight elements)
       // both row maxes are wave-uniform: one scalar branch picks the short division for the pair -- and a max inside
       // its range is finite, non-zero and has a finite factor, so such a pair cannot be special: no tests at all
-      const bool short_div = LMC_SHORT_ROW_DIV && row_div_in_range(mrow[0], DT) && row_div_in_range(mrow[1], DT);
+      const bool short_div = LMC_SHORT_ROW_DIV && row_div_in_range(mrow[0], lmc_math_dtype(DT)) && row_div_in_range(mrow[1], lmc_math_dtype(DT));
       if (short_div) {
 #pragma unroll
-        for (int r = 0; r < 2; r++) factor[r] = row_div_short(maxf, h2f_rt(mrow[r], DT));
+        for (int r = 0; r < 2; r++) factor[r] = row_div_short(maxf, h2f_rt(mrow[r], lmc_math_dtype(DT)));
       } else {
         bool any_special = false;
 #pragma unroll
         for (int r = 0; r < 2; r++) {
-          const float sf = h2f_rt(mrow[r], DT);
+          const float sf = h2f_rt(mrow[r], lmc_math_dtype(DT));
           factor[r] = maxf / sf;  // IEEE fp32 division (lmc_device.h)
           special[r] = !(__builtin_fabsf(factor[r]) < __builtin_inff()) || !(sf < __builtin_inff());
           any_special |= special[r];
@@ -217,14 +216,14 @@ __device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const u16*
             const f32x2_t f2 = {factor[r], factor[r]};
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-              const f32x2_t z = quant_z2(h_lo<DT>(w[k]), h_hi<DT>(w[k]), f2, maxf2);
+              const f32x2_t z = quant_z2(kv_lo<DT>(w, k), kv_hi<DT>(w, k), f2, maxf2);
               o[it][2 * k] = __builtin_amdgcn_cvt_pk_u8_f32(z.x, r0 + r, r0 + r ? o[it][2 * k] : 0u);
               o[it][2 * k + 1] = __builtin_amdgcn_cvt_pk_u8_f32(z.y, r0 + r, r0 + r ? o[it][2 * k + 1] : 0u);
             }
           } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-              const float xl = h_lo<DT>(w[k]), xh = h_hi<DT>(w[k]);
+              const float xl = kv_lo<DT>(w, k), xh = kv_hi<DT>(w, k);
               const u32 sl_ = (special[r] ? quant_special(xl, factor[r], maxf) : quant_fast(xl, factor[r], maxf)) & 0xffu;
               const u32 sh_ = (special[r] ? quant_special(xh, factor[r], maxf) : quant_fast(xh, factor[r], maxf)) & 0xffu;
               o[it][2 * k] = (r0 + r ? o[it][2 * k] : 0u) | sl_ << (8 * (r0 + r));
@@ -287,7 +286,7 @@ __device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const u16*
 // quantize_oct_fused with the histogram: one row oct by one wave, symbols to the workspace AND into the plane's counters.
 // skip0: the oct holds token 0 of the chunk (byte planes leave it out of the counters).
 template <int NITER, int DT, bool NIB, bool FULL, bool ALLROWS, bool PSRC = false>
-__device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const u16* pbase, int tok0, int Tc, int t_first,
+__device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const typename KvElem<DT>::T* pbase, int tok0, int Tc, int t_first,
                                                   bool q1valid, bool skip0, int C, float maxf, u32* sym_out, u16* scale_out,
                                                   int lane) {
   long long coff[NITER];
@@ -319,10 +318,10 @@ __device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const u16* 
     for (int r = 0; r < 2; r++) {
       const int t = t_first + rowi[r];
       tv[r] = ALLROWS || t < Tc;
-      const u16* rowp = pbase + (tv[r] ? fused_tok_off<PSRC>(src, tok0 + t) : 0);
+      const typename KvElem<DT>::T* rowp = pbase + (tv[r] ? fused_tok_off<PSRC>(src, tok0 + t) : 0);
 #pragma unroll
       for (int it = 0; it < NITER; it++) {
-        if (tv[r] && (FULL || cval[it])) v[r][it] = ld_global_u4_nt(rowp + coff[it]);  // streamed once
+        if (tv[r] && (FULL || cval[it])) v[r][it] = kv_ld8<DT, true>(rowp + coff[it]);  // streamed once
         else v[r][it] = make_uint4(0, 0, 0, 0);
       }
     }
@@ -332,14 +331,13 @@ __device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const u16* 
       u32 m = 0;
 #pragma unroll
       for (int it = 0; it < NITER; it++) {
-        m = pk_max_u16(m, v[r][it].x & 0x7fff7fffu);
-        m = pk_max_u16(m, v[r][it].y & 0x7fff7fffu);
-        m = pk_max_u16(m, v[r][it].z & 0x7fff7fffu);
-        m = pk_max_u16(m, v[r][it].w & 0x7fff7fffu);
+        m = kv_absmax8<DT>(m, v[r][it]);
       }
       mrow[r] = max(m & 0xffffu, m >> 16);
     }
     wave_max2_u32(mrow[0], mrow[1]);  // wave-uniform from here on
+    mrow[0] = kv_max_scale<DT>(mrow[0]);  // (fp8: the max's bf16 image; else the max itself)
+    mrow[1] = kv_max_scale<DT>(mrow[1]);
     if (lane == 0) {
 #pragma unroll
       for (int r = 0; r < 2; r++)
@@ -348,15 +346,15 @@ __device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const u16* 
     float factor[2];
     bool special[2] = {false, false};
     u32 slow = 0;  // (an integer: see quantize_oct_fused)
-    const bool short_div = LMC_SHORT_ROW_DIV && row_div_in_range(mrow[0], DT) && row_div_in_range(mrow[1], DT);
+    const bool short_div = LMC_SHORT_ROW_DIV && row_div_in_range(mrow[0], lmc_math_dtype(DT)) && row_div_in_range(mrow[1], lmc_math_dtype(DT));
     if (short_div) {
 #pragma unroll
-      for (int r = 0; r < 2; r++) factor[r] = row_div_short(maxf, h2f_rt(mrow[r], DT));
+      for (int r = 0; r < 2; r++) factor[r] = row_div_short(maxf, h2f_rt(mrow[r], lmc_math_dtype(DT)));
     } else {
       bool any_special = false;
 #pragma unroll
       for (int r = 0; r < 2; r++) {
-        const float sf = h2f_rt(mrow[r], DT);
+        const float sf = h2f_rt(mrow[r], lmc_math_dtype(DT));
         factor[r] = maxf / sf;  // IEEE fp32 division (lmc_device.h)
         special[r] = !(__builtin_fabsf(factor[r]) < __builtin_inff()) || !(sf < __builtin_inff());
         any_special |= special[r];
@@ -377,7 +375,7 @@ __device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const u16* 
           const f32x2_t f2 = {factor[r], factor[r]};
 #pragma unroll
           for (int k = 0; k < 4; k++) {
-            const f32x2_t z = quant_z2(h_lo<DT>(w[k]), h_hi<DT>(w[k]), f2, maxf2);
+            const f32x2_t z = quant_z2(kv_lo<DT>(w, k), kv_hi<DT>(w, k), f2, maxf2);
             if (high) {
               // (opaque: left to itself the compiler re-associates the four high rows of a dword into an accumulator of
               // their own -- 16 more live registers, spilled -- and merges at the end)
@@ -391,7 +389,7 @@ __device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const u16* 
         } else {
 #pragma unroll
           for (int k = 0; k < 4; k++) {
-            const float xl = h_lo<DT>(w[k]), xh = h_hi<DT>(w[k]);
+            const float xl = kv_lo<DT>(w, k), xh = kv_hi<DT>(w, k);
             const u32 sl_ = (special[r] ? quant_special(xl, factor[r], maxf) : quant_fast(xl, factor[r], maxf)) & 0xffu;
             const u32 sh_ = (special[r] ? quant_special(xh, factor[r], maxf) : quant_fast(xh, factor[r], maxf)) & 0xffu;
             o[it][2 * k] = (fresh ? 0u : o[it][2 * k]) | sl_ << (8 * bpos + (high ? 4 : 0));
@@ -544,7 +542,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
       const bool full = a.C == NITER * 512;  // no absent channels: the variant without per-lane validity
       u32* const sym_pc = const_cast<u32*>(a.sym4) + ((long long)chunk * a.P + p) * a.sym_stride;
       u16* const scl = reinterpret_cast<u16*>(scl0) + (long long)p * Tc;
-      const u16* const pbase = lmc_plane_base(fa.src, p);
+      const typename KvElem<DT>::T* const pbase = lmc_plane_base<typename KvElem<DT>::T>(fa.src, p);
 #ifdef LMC_EXP_SKIP_PHASE_A
       if (false)
 #endif
@@ -662,7 +660,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
 #endif
   // The chunk's last item knows the chunk's size: header, static sections, size word.
   if (p0 + np == a.P && wave == NW - 1) {
-    write_blob_static(blob, bo, a, (u32)Tc, wg_excl + wg_total, lane);
+    write_blob_static<lmc_dtype_fp8(DT) ? DT : 0>(blob, bo, a, (u32)Tc, wg_excl + wg_total, lane);
     if (lane == 0) a.sizes[chunk] = bo.streams + wg_excl + wg_total;
   }
 }

@@ -101,7 +101,7 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
     int h = c0[it] / src.D, d = c0[it] - h * src.D;
     coff[it] = (long long)h * src.stride_head + d;
   }
-  const u16* pbase = lmc_plane_base(src, p);
+  const typename KvElem<DT>::T* pbase = lmc_plane_base<typename KvElem<DT>::T>(src, p);
   const f32x2_t maxf2 = {maxf, maxf};
   // QUAD: o[hq][it][e] byte r = symbol of (token t_first + 4 hq + r, channel c0[it] + e); bytes of tokens past
   // the end of a ragged chunk are never read by the coder, so they need no masking
@@ -121,10 +121,10 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
     for (int r = 0; r < ROWS; r++) {
       int t = t_first + r0 + r;
       tv[r] = qvalid && t < Tc;
-      const u16* rowp = pbase + (tv[r] ? lmc_tok_off(src, tok0 + t) : 0);
+      const typename KvElem<DT>::T* rowp = pbase + (tv[r] ? lmc_tok_off(src, tok0 + t) : 0);
 #pragma unroll
       for (int it = 0; it < NITER; it++) {
-        if (tv[r] && cval[it]) v[r][it] = ld_global_u4(rowp + coff[it]);  // (non-temporal here: two-kernel path +0.5 %)
+        if (tv[r] && cval[it]) v[r][it] = kv_ld8<DT>(rowp + coff[it]);  // (non-temporal here: two-kernel path +0.5 %)
         else v[r][it] = make_uint4(0, 0, 0, 0);
       }
     }
@@ -136,10 +136,7 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
       u32 m = 0;
 #pragma unroll
       for (int it = 0; it < NITER; it++) {
-        m = pk_max_u16(m, v[r][it].x & 0x7fff7fffu);
-        m = pk_max_u16(m, v[r][it].y & 0x7fff7fffu);
-        m = pk_max_u16(m, v[r][it].z & 0x7fff7fffu);
-        m = pk_max_u16(m, v[r][it].w & 0x7fff7fffu);
+        m = kv_absmax8<DT>(m, v[r][it]);
       }
       mrow[r] = max(m & 0xffffu, m >> 16);
     }
@@ -166,6 +163,8 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
         mrow[r] = m;
       }
     }
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) mrow[r] = kv_max_scale<DT>(mrow[r]);  // (fp8: the max's bf16 image; else the max itself)
     // scales: first lane of the group (of the first slice)
     if (sl == 0 && slice == 0) {
 #pragma unroll
@@ -178,7 +177,7 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
     bool any_special = false;
 #pragma unroll
     for (int r = 0; r < ROWS; r++) {
-      float sf = h2f_rt(mrow[r], DT);
+      float sf = h2f_rt(mrow[r], lmc_math_dtype(DT));
       factor[r] = maxf / sf;  // IEEE fp32 division
       special[r] = !(__builtin_fabsf(factor[r]) < __builtin_inff()) || !(sf < __builtin_inff());
       any_special |= special[r];
@@ -200,15 +199,15 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
             const f32x2_t f2 = {factor[r], factor[r]};
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-              const f32x2_t z = quant_z2(h_lo<DT>(w[k]), h_hi<DT>(w[k]), f2, maxf2);
+              const f32x2_t z = quant_z2(kv_lo<DT>(w, k), kv_hi<DT>(w, k), f2, maxf2);
               o[(r0 + r) >> 2][it][2 * k] = __builtin_amdgcn_cvt_pk_u8_f32(z.x, (r0 + r) & 3, o[(r0 + r) >> 2][it][2 * k]);
               o[(r0 + r) >> 2][it][2 * k + 1] = __builtin_amdgcn_cvt_pk_u8_f32(z.y, (r0 + r) & 3, o[(r0 + r) >> 2][it][2 * k + 1]);
             }
           } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-              o[(r0 + r) >> 2][it][2 * k] |= sym_of(r, h_lo<DT>(w[k])) << (8 * ((r0 + r) & 3));
-              o[(r0 + r) >> 2][it][2 * k + 1] |= sym_of(r, h_hi<DT>(w[k])) << (8 * ((r0 + r) & 3));
+              o[(r0 + r) >> 2][it][2 * k] |= sym_of(r, kv_lo<DT>(w, k)) << (8 * ((r0 + r) & 3));
+              o[(r0 + r) >> 2][it][2 * k + 1] |= sym_of(r, kv_hi<DT>(w, k)) << (8 * ((r0 + r) & 3));
             }
           }
         }
@@ -220,8 +219,8 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
           u32 lo = 0, hi = 0;
 #pragma unroll
           for (int k = 0; k < 2; k++) {
-            lo |= (sym_of(r, h_lo<DT>(w[k])) << (16 * k)) | (sym_of(r, h_hi<DT>(w[k])) << (16 * k + 8));
-            hi |= (sym_of(r, h_lo<DT>(w[k + 2])) << (16 * k)) | (sym_of(r, h_hi<DT>(w[k + 2])) << (16 * k + 8));
+            lo |= (sym_of(r, kv_lo<DT>(w, k)) << (16 * k)) | (sym_of(r, kv_hi<DT>(w, k)) << (16 * k + 8));
+            hi |= (sym_of(r, kv_lo<DT>(w, k + 2)) << (16 * k)) | (sym_of(r, kv_hi<DT>(w, k + 2)) << (16 * k + 8));
           }
           int8_t* dst = sym8_plane + ((long long)(t_first + r0 + r)) * C + c0[it];
           *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);

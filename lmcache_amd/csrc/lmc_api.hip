@@ -193,7 +193,7 @@ int lmc_device_status(lmc_ctx* c, int clear) {
 // element-wise copy): any strides.  Either way a plane has a multiple of 8 channels (the blob's geometry).
 static bool layout_ok(const lmc_kv_layout* l, bool vec = true) {
   if (!l) return false;
-  if (l->dtype != LMC_DTYPE_BF16 && l->dtype != LMC_DTYPE_FP16) return false;
+  if (l->dtype != LMC_DTYPE_BF16 && l->dtype != LMC_DTYPE_FP16 && !lmc_dtype_fp8(l->dtype)) return false;
   if (l->num_layers < 1 || 2 * l->num_layers > LMC_MAX_PLANES) return false;
   if (l->num_heads < 1 || l->head_size < 1) return false;
   const long long C = (long long)l->num_heads * l->head_size;
@@ -205,7 +205,9 @@ static bool layout_ok(const lmc_kv_layout* l, bool vec = true) {
     if (l->stride_head != l->head_size) return false;
   } else if (l->stride_head & 7) return false;
   if (l->stride_token & 7) return false;
-  if (!l->plane_ptrs && ((l->stride_layer & 7) || (l->stride_kv & 7) || ((uintptr_t)l->base & 15))) return false;
+  // (a vector is 8 elements: 16 bytes of a 16-bit dtype, 8 of fp8 -- the alignment of the base follows the vector)
+  const uintptr_t vec_align = lmc_dtype_fp8(l->dtype) ? 7 : 15;
+  if (!l->plane_ptrs && ((l->stride_layer & 7) || (l->stride_kv & 7) || ((uintptr_t)l->base & vec_align))) return false;
   if (l->slot_mapping && (l->stride_block & 7)) return false;
   return true;
 }
@@ -266,8 +268,12 @@ static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
 
 template <bool QUAD>
 static int launch_quant(const QuantArgs& a, hipStream_t s) {
-  return a.src.dtype == LMC_DTYPE_BF16 ? launch_quant_dt<LMC_DTYPE_BF16, QUAD>(a, s)
-                                       : launch_quant_dt<LMC_DTYPE_FP16, QUAD>(a, s);
+  switch (a.src.dtype) {
+    case LMC_DTYPE_BF16: return launch_quant_dt<LMC_DTYPE_BF16, QUAD>(a, s);
+    case LMC_DTYPE_FP16: return launch_quant_dt<LMC_DTYPE_FP16, QUAD>(a, s);
+    case LMC_DTYPE_FP8_E4M3: return launch_quant_dt<LMC_DTYPE_FP8_E4M3, QUAD>(a, s);
+    default: return launch_quant_dt<LMC_DTYPE_FP8_E5M2, QUAD>(a, s);
+  }
 }
 
 static int ws_grow(void** p, size_t* have, size_t need) {
@@ -461,7 +467,8 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   ea.status = job_status ? job_status : c->status_h;
   ea.bins = bins;
   ea.agg = w->agg; ea.sizes = sizes;
-  ea.L = L; ea.H = H; ea.D = D; ea.dtype = src->dtype;
+  ea.L = L; ea.H = H; ea.D = D;
+  ea.dtype = lmc_math_dtype(src->dtype);  // the header's dtype word: an fp8 chunk is coded as its bf16 images (lmc_format.h)
   u8* const scale_base = (u8*)blobs + hl.off_scales;  // off_scales does not depend on T
 
   if (!w->ticket) {
@@ -513,6 +520,11 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { g_last_hip = (int)le; tickets_reset(); return LMC_ERR_HIP; }
     w->tickets_drawn += nwg;  // only a launch that went out has drawn
+    if (lmc_dtype_fp8(src->dtype)) {  // the coder wrote header word 23 as 0: the KV's dtype goes there
+      hipLaunchKernelGGL(k_set_kv_dtype, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, e2.blobs, e2.blob_stride, n,
+                         (u32)src->dtype);
+      HIP_TRY(hipGetLastError());
+    }
     return prof_mark(c, s);
   };
   if (fused) {
@@ -539,7 +551,9 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
       fa.item_base = (u32)((long long)it0 * nfull);
       fa.e.ticket_base = w->tickets_drawn;
       if (src->dtype == LMC_DTYPE_BF16) launch_fused<LMC_DTYPE_BF16>(C, grid, block, s, fa);
-      else launch_fused<LMC_DTYPE_FP16>(C, grid, block, s, fa);
+      else if (src->dtype == LMC_DTYPE_FP16) launch_fused<LMC_DTYPE_FP16>(C, grid, block, s, fa);
+      else if (src->dtype == LMC_DTYPE_FP8_E4M3) launch_fused<LMC_DTYPE_FP8_E4M3>(C, grid, block, s, fa);
+      else launch_fused<LMC_DTYPE_FP8_E5M2>(C, grid, block, s, fa);
       const hipError_t le = hipGetLastError();
       if (le != hipSuccess) { g_last_hip = (int)le; tickets_reset(); return LMC_ERR_HIP; }
       w->tickets_drawn += grid.x;
@@ -574,6 +588,20 @@ static int decode_common(lmc_ctx* c, const void* blobs, uint64_t blob_stride, in
   return LMC_OK;
 }
 
+// k_decode for a destination dtype: the destination's dtype decides what a blob decodes to (any blob, any of the four)
+static void launch_decode(int dtype, bool paged, dim3 grid, hipStream_t s, const DecodeArgs& a) {
+#define LD(DT)                                                                                       \
+  do {                                                                                               \
+    if (paged) hipLaunchKernelGGL((k_decode<false, DT, true>), grid, dim3(64 * DEC_WAVES), 0, s, a); \
+    else hipLaunchKernelGGL((k_decode<false, DT, false>), grid, dim3(64 * DEC_WAVES), 0, s, a);      \
+  } while (0)
+  if (dtype == LMC_DTYPE_BF16) LD(LMC_DTYPE_BF16);
+  else if (dtype == LMC_DTYPE_FP16) LD(LMC_DTYPE_FP16);
+  else if (dtype == LMC_DTYPE_FP8_E4M3) LD(LMC_DTYPE_FP8_E4M3);
+  else LD(LMC_DTYPE_FP8_E5M2);
+#undef LD
+}
+
 static int decode_launch(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, hipStream_t hs) {
   int rc;
   const long long n = (long long)a.nchunks * 2 * a.layer_count * a.G;
@@ -582,13 +610,7 @@ static int decode_launch(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, hi
   c->pn = 0;
   if ((rc = prof_mark(c, hs))) return rc;
   const bool paged = dst->slot_mapping != nullptr;
-  if (dst->dtype == LMC_DTYPE_BF16) {
-    if (paged) hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_BF16, true>), grid, dim3(64 * DEC_WAVES), 0, hs, a);
-    else hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_BF16, false>), grid, dim3(64 * DEC_WAVES), 0, hs, a);
-  } else {
-    if (paged) hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_FP16, true>), grid, dim3(64 * DEC_WAVES), 0, hs, a);
-    else hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_FP16, false>), grid, dim3(64 * DEC_WAVES), 0, hs, a);
-  }
+  launch_decode(dst->dtype, paged, grid, hs, a);
   HIP_TRY(hipGetLastError());
   if ((rc = prof_mark(c, hs))) return rc;
   return LMC_OK;
@@ -681,7 +703,10 @@ int lmc_copy_kv(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t
   HIP_TRY(hipSetDevice(c->device));
   long long blocks = (a.nvec + 255) / 256;
   if (blocks > 256LL * 64) blocks = 256LL * 64;  // grid-stride beyond 64 blocks per CU
-  if (vec) hipLaunchKernelGGL(k_copy_kv, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  if (lmc_dtype_fp8(src->dtype)) {  // 1-byte elements
+    if (vec) hipLaunchKernelGGL(k_copy_kv_b8, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_copy_kv_elem_b8, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  } else if (vec) hipLaunchKernelGGL(k_copy_kv, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_copy_kv_elem, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return LMC_OK;
@@ -873,13 +898,7 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
     const long long nstreams = (long long)nchunks * 2 * n * da.G;
     const dim3 grid((unsigned)((nstreams + DEC_WAVES - 1) / DEC_WAVES));
     const bool paged = dst->slot_mapping != nullptr;
-    if (dst->dtype == LMC_DTYPE_BF16) {
-      if (paged) hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_BF16, true>), grid, dim3(64 * DEC_WAVES), 0, s, da);
-      else hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_BF16, false>), grid, dim3(64 * DEC_WAVES), 0, s, da);
-    } else {
-      if (paged) hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_FP16, true>), grid, dim3(64 * DEC_WAVES), 0, s, da);
-      else hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_FP16, false>), grid, dim3(64 * DEC_WAVES), 0, s, da);
-    }
+    launch_decode(dst->dtype, paged, grid, s, da);
     HIP_TRY(hipGetLastError());
     if (range_events && range_events[r]) HIP_TRY(hipEventRecord((hipEvent_t)range_events[r], s));
   }
@@ -1115,13 +1134,7 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
     const long long nstreams = (long long)m * 2 * nl * da.G;
     const dim3 grid((unsigned)((nstreams + DEC_WAVES - 1) / DEC_WAVES));
     const bool paged = dst->slot_mapping != nullptr;
-    if (dst->dtype == LMC_DTYPE_BF16) {
-      if (paged) hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_BF16, true>), grid, dim3(64 * DEC_WAVES), 0, s, da);
-      else hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_BF16, false>), grid, dim3(64 * DEC_WAVES), 0, s, da);
-    } else {
-      if (paged) hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_FP16, true>), grid, dim3(64 * DEC_WAVES), 0, s, da);
-      else hipLaunchKernelGGL((k_decode<false, LMC_DTYPE_FP16, false>), grid, dim3(64 * DEC_WAVES), 0, s, da);
-    }
+    launch_decode(dst->dtype, paged, grid, s, da);
     HIP_TRY(hipGetLastError());
     if (range_events && range_events[r]) HIP_TRY(hipEventRecord((hipEvent_t)range_events[r], s));
   }
@@ -1146,6 +1159,8 @@ int lmc_blob_info(const void* blob_h, size_t nbytes, lmc_blob_header* out) {
       h.off_gdir != ref.off_gdir || h.off_streams != ref.off_streams)
     return LMC_ERR_INVALID;
   if (h.total_bytes != h.off_streams + h.stream_bytes || h.total_bytes > nbytes) return LMC_ERR_INVALID;
+  if (h.kv_dtype != 0u && !((h.kv_dtype == LMC_DTYPE_FP8_E4M3 || h.kv_dtype == LMC_DTYPE_FP8_E5M2) && h.dtype == LMC_DTYPE_BF16))
+    return LMC_ERR_INVALID;
   *out = h;
   return LMC_OK;
 }

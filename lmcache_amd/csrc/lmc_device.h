@@ -13,6 +13,7 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 
 #include "../../include/lmc_hip.h"
+#include "k_fp8.h"
 
 #define LMC_WAVE 64
 
@@ -37,11 +38,27 @@ struct BinsArg {
   u8 b[LMC_MAX_PLANES];
 };
 
-__device__ __forceinline__ const u16* lmc_plane_base(const KvAddr& a, int p) {
+// E: the element type of the layout -- u16 (bf16 / fp16) or u8 (fp8); the strides count elements
+template <typename E = u16>
+__device__ __forceinline__ const E* lmc_plane_base(const KvAddr& a, int p) {
   int kv = p >= a.L ? 1 : 0, l = p - kv * a.L;  // planes are K of every layer, then V (P = 2L)
-  if (a.plane_ptrs) return a.plane_ptrs[2 * l + kv];
-  return a.base + (long long)l * a.stride_layer + (long long)kv * a.stride_kv;
+  if (a.plane_ptrs) return reinterpret_cast<const E*>(a.plane_ptrs[2 * l + kv]);
+  return reinterpret_cast<const E*>(a.base) + (long long)l * a.stride_layer + (long long)kv * a.stride_kv;
 }
+
+// ---- fp8 KV (OCP e4m3fn / e5m2, lmc_format.h) ----------------------------------------------------------------------
+// An fp8 chunk is encoded as the bf16 chunk of its values' images (exact: every fp8 value has one): the quantiser's
+// arithmetic, the scales and the blob's dtype word are bf16's.  The kernels read the fp8 bytes themselves -- 8 channels
+// = one 8-byte load where a 16-bit dtype loads 16 bytes -- and widen them in registers.
+__host__ __device__ constexpr bool lmc_dtype_fp8(int dt) { return dt == LMC_DTYPE_FP8_E4M3 || dt == LMC_DTYPE_FP8_E5M2; }
+__host__ __device__ constexpr int lmc_math_dtype(int dt) { return lmc_dtype_fp8(dt) ? LMC_DTYPE_BF16 : dt; }
+template <int DT>
+struct KvElem { typedef u16 T; };
+template <>
+struct KvElem<LMC_DTYPE_FP8_E4M3> { typedef u8 T; };
+template <>
+struct KvElem<LMC_DTYPE_FP8_E5M2> { typedef u8 T; };
+
 
 __device__ __forceinline__ long long lmc_tok_off(const KvAddr& a, int t) {
   if (a.slot_mapping) {
@@ -94,6 +111,7 @@ __device__ __forceinline__ void divmod_small(u32 e, u32 R, float rcpR, u32& q, u
 #define LMC_GLOBAL __attribute__((address_space(1)))
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint4 ld_global_u4(const u16* p) {
   const u32x4_t v = *reinterpret_cast<const LMC_GLOBAL u32x4_t*>((const LMC_GLOBAL u16*)p);
   return make_uint4(v.x, v.y, v.z, v.w);
@@ -132,6 +150,77 @@ __device__ __forceinline__ float h_hi(u32 w) {
 __device__ __forceinline__ float h2f_rt(u32 bits, int dtype) {
   if (dtype == LMC_DTYPE_BF16) return __uint_as_float(bits << 16);
   return (float)__builtin_bit_cast(_Float16, (unsigned short)bits);
+}
+
+// ---- the encoders' view of 8 channels: one vector per lane (16-bit: 16 bytes, fp8: 8 bytes in .x / .y) ---------------
+template <int DT, bool NT = false>
+__device__ __forceinline__ uint4 kv_ld8(const typename KvElem<DT>::T* p) {
+  if constexpr (!lmc_dtype_fp8(DT)) return NT ? ld_global_u4_nt(p) : ld_global_u4(p);
+  else {
+    const LMC_GLOBAL u32x2_t* q = reinterpret_cast<const LMC_GLOBAL u32x2_t*>((const LMC_GLOBAL u8*)p);
+    const u32x2_t v = NT ? __builtin_nontemporal_load(q) : *q;
+    return make_uint4(v.x, v.y, 0u, 0u);
+  }
+}
+// running max of |x| over a vector, two u16 lanes: 16-bit dtypes on the bit patterns without the sign (NaN > inf >
+// finite: torch.amax's NaN propagation); fp8 on the 7-bit magnitude bytes, which order the same way (e4m3fn: 0x7f is
+// NaN; e5m2: 0x7c inf, 0x7d..0x7f NaN), widened to the u16 lanes
+template <int DT>
+__device__ __forceinline__ u32 kv_absmax8(u32 m, const uint4& v) {
+  if constexpr (!lmc_dtype_fp8(DT)) {
+    m = pk_max_u16(m, v.x & 0x7fff7fffu);
+    m = pk_max_u16(m, v.y & 0x7fff7fffu);
+    m = pk_max_u16(m, v.z & 0x7fff7fffu);
+    m = pk_max_u16(m, v.w & 0x7fff7fffu);
+  } else {
+    m = pk_max_u16(m, v.x & 0x007f007fu);
+    m = pk_max_u16(m, (v.x >> 8) & 0x007f007fu);
+    m = pk_max_u16(m, v.y & 0x007f007fu);
+    m = pk_max_u16(m, (v.y >> 8) & 0x007f007fu);
+  }
+  return m;
+}
+// the row max as the scale the blob stores: the 16-bit pattern itself, or the bf16 image of the fp8 magnitude (NaN ->
+// 0x7FC0, which is what torch's fp8 -> bf16 cast gives every NaN)
+template <int DT>
+__device__ __forceinline__ u32 kv_max_scale(u32 m) {
+  if constexpr (!lmc_dtype_fp8(DT)) return m;
+  else if constexpr (DT == LMC_DTYPE_FP8_E4M3) return m >= 0x7fu ? 0x7fc0u : __float_as_uint(__builtin_amdgcn_cvt_f32_fp8((int)m, 0)) >> 16;
+  else return m > 0x7cu ? 0x7fc0u : __float_as_uint(__builtin_amdgcn_cvt_f32_bf8((int)m, 0)) >> 16;
+}
+// channels 2k and 2k + 1 of a vector (w = its four dwords) as fp32 (exact for every dtype)
+template <int DT>
+__device__ __forceinline__ f32x2_t fp8_pair(u32 d, bool high_word) {
+  if constexpr (DT == LMC_DTYPE_FP8_E4M3) return high_word ? __builtin_amdgcn_cvt_pk_f32_fp8((int)d, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)d, false);
+  else return high_word ? __builtin_amdgcn_cvt_pk_f32_bf8((int)d, true) : __builtin_amdgcn_cvt_pk_f32_bf8((int)d, false);
+}
+template <int DT>
+__device__ __forceinline__ float kv_lo(const u32 (&w)[4], int k) {
+  if constexpr (!lmc_dtype_fp8(DT)) return h_lo<DT>(w[k]);
+  else return fp8_pair<DT>(w[k >> 1], (k & 1) != 0).x;
+}
+template <int DT>
+__device__ __forceinline__ float kv_hi(const u32 (&w)[4], int k) {
+  if constexpr (!lmc_dtype_fp8(DT)) return h_hi<DT>(w[k]);
+  else return fp8_pair<DT>(w[k >> 1], (k & 1) != 0).y;
+}
+
+// ---- fp8 destinations of the decoder ---------------------------------------------------------------------------------
+// v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 round to nearest even like torch's cast, but torch's overflow rules (k_fp8.h) are
+// not the instruction's.  A token row whose every value is finite and at most the format's largest finite value in
+// magnitude never meets them: the decoder takes the instruction there, and k_fp8.h's integer restatement for the other
+// rows.  |value| <= |lv| * scale, |lv| = |q - C| / C <= 1 for the symbols 0 .. 2C an even bin count allows and <= 2 for
+// an odd one (its last symbol 2C + 1): the row qualifies when its scale is at most fmax (even bins) or fmax / 2 (odd).
+template <int DT>
+__device__ __forceinline__ u32 fp8_fast_scale_limit(u32 bins) {  // fp32 bits
+  const u32 fmax = DT == LMC_DTYPE_FP8_E4M3 ? 0x43e00000u /* 448 */ : 0x47600000u /* 57344 */;
+  return (bins & 1u) ? fmax - 0x00800000u : fmax;
+}
+// fp8 of a and b in bytes 0 and 1
+template <int DT>
+__device__ __forceinline__ u32 fp8_cvt_pk(float a, float b) {
+  if constexpr (DT == LMC_DTYPE_FP8_E4M3) return (u32)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  else return (u32)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false);
 }
 
 // fp32 -> bf16 bits, round-to-nearest-even; NaN -> 0x7FC0 (c10::BFloat16).

@@ -22,6 +22,7 @@ SO_PATH = os.environ.get("LMCACHE_AMD_SO") or os.path.join(CSRC, "liblmc_hip.so"
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 BF16, FP16 = 0, 1
+FP8_E4M3, FP8_E5M2 = 2, 3  # OCP fp8 (torch.float8_e4m3fn / float8_e5m2): stored as the bf16 blob of their images
 LANES, MAX_BINS, LP = 64, 32, 33
 HEADER_BYTES = 128
 BLOB_MAGIC = 0x31434D4C
@@ -115,8 +116,8 @@ class BlobHeader(ctypes.Structure):
                 ("off_bins", ctypes.c_uint32), ("off_scales", ctypes.c_uint32), ("zero13", ctypes.c_uint32),
                 ("off_gdir", ctypes.c_uint32), ("off_streams", ctypes.c_uint32), ("stream_bytes", ctypes.c_uint32),
                 ("total_bytes", ctypes.c_uint32), ("zero18", ctypes.c_uint32 * 3),
-                ("off_scsum", ctypes.c_uint32), ("model", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32 * 9)]
+                ("off_scsum", ctypes.c_uint32), ("model", ctypes.c_uint32), ("kv_dtype", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 8)]
 
 
 class PackHeader(ctypes.Structure):
@@ -209,16 +210,36 @@ def check(rc: int, what: str = "") -> None:
         raise NativeError(f"{what or 'lmc call'} failed: {msg} (rc={rc}, hip={L.lmc_last_hip_error()})")
 
 
+_CODES = {torch.bfloat16: BF16, torch.float16: FP16, torch.float8_e4m3fn: FP8_E4M3, torch.float8_e5m2: FP8_E5M2}
+_DTYPES = {v: k for k, v in _CODES.items()}
+
+
 def dtype_code(dt: torch.dtype) -> int:
-    if dt == torch.bfloat16:
-        return BF16
-    if dt == torch.float16:
-        return FP16
-    raise ValueError(f"KV dtype must be bfloat16 or float16, got {dt}")
+    code = _CODES.get(dt)
+    if code is not None:
+        return code
+    if dt == torch.uint8:
+        raise ValueError("KV dtype torch.uint8: an fp8 cache allocated as bytes (vLLM does that) has to be passed as "
+                         "its fp8 view, e.g. kv_cache.view(torch.float8_e4m3fn) (or torch.float8_e5m2); the view copies nothing")
+    if dt in (getattr(torch, "float8_e4m3fnuz", None), getattr(torch, "float8_e5m2fnuz", None)):
+        raise ValueError(f"KV dtype {dt} is an MI300 (fnuz) fp8 format; gfx950 caches use the OCP formats "
+                         "torch.float8_e4m3fn / torch.float8_e5m2")
+    raise ValueError(f"KV dtype must be bfloat16, float16, float8_e4m3fn or float8_e5m2, got {dt} "
+                     "(float32 KV is not supported: convert it to bfloat16)")
 
 
 def torch_dtype(code: int) -> torch.dtype:
-    return torch.bfloat16 if code == BF16 else torch.float16
+    return _DTYPES[int(code)]
+
+
+def elem_bytes(code: int) -> int:
+    """Bytes of one KV element of dtype code `code`."""
+    return 1 if int(code) in (FP8_E4M3, FP8_E5M2) else 2
+
+
+def stored_dtype(h) -> torch.dtype:
+    """The dtype a blob's KV was stored in (its header's kv_dtype, else its dtype): what the engine retrieves."""
+    return torch_dtype(int(h.kv_dtype) or int(h.dtype))
 
 
 def pack_info(pack_ptr: int, nbytes: int) -> PackHeader:
@@ -370,9 +391,10 @@ class KVLayout:
             return False
         if s.stride_token % 8 or (s.slot_mapping and s.stride_block % 8):
             return False
+        vec = 8 * elem_bytes(s.dtype)  # a vector of 8 channels: 16 bytes, fp8 8
         if s.plane_ptrs:
-            return all(x.data_ptr() % 16 == 0 for x in self._keep if isinstance(x, torch.Tensor) and x.dtype in (torch.bfloat16, torch.float16))
-        return s.stride_layer % 8 == 0 and s.stride_kv % 8 == 0 and (s.base or 0) % 16 == 0
+            return all(x.data_ptr() % vec == 0 for x in self._keep if isinstance(x, torch.Tensor) and x.dtype in _CODES)
+        return s.stride_layer % 8 == 0 and s.stride_kv % 8 == 0 and (s.base or 0) % vec == 0
 
     @staticmethod
     def from_chunk(t: torch.Tensor, fmt: str) -> "KVLayout":

@@ -40,7 +40,7 @@ from lmcache_amd.config import LMCacheEngineConfig, LMCacheEngineMetadata
 from lmcache_amd.logging import init_logger
 from lmcache_amd.storage_backend.abstract_backend import LMCBackendInterface
 from lmcache_amd.storage_backend.serde.cachegen_basics import CacheGenConfig
-from lmcache_amd.storage_backend.serde.cachegen_decoder import output_spec
+from lmcache_amd.storage_backend.serde.cachegen_decoder import output_spec, retrieve_spec
 from lmcache_amd.storage_backend.serde.cachegen_device import DeviceArena, HostBlob, HostPack, PinnedArena, get_codec
 from lmcache_amd.utils import CacheEngineKey, _lmcache_nvtx_annotate
 
@@ -85,6 +85,14 @@ def _chunk_shape(fmt: str, L: int, T: int, H: int, D: int) -> Tuple[int, ...]:
     if fmt == "huggingface":
         return (L, 2, H, T, D)
     raise ValueError(f"Invalid format: {fmt}")
+
+
+def _coded_dtype(fmt: str, kv_dtype: torch.dtype) -> torch.dtype:
+    """The dtype a cachegen-tier chunk is retrieved as: the reference's rule for 16-bit KV (output_spec: bf16 for vllm,
+    fp16 for huggingface), the stored dtype for fp8 KV."""
+    if kv_dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
+        return kv_dtype
+    return output_spec(fmt, 1, 1, 1, 8)[1]
 
 
 def _fmt_of_chunk(t: torch.Tensor, fmt_hint: Optional[str]) -> str:
@@ -238,7 +246,7 @@ class LMCLocalBackend(LMCBackendInterface):
         lay = native.KVLayout.from_chunk(kv_chunk, fmt)
         shape = _chunk_shape(fmt, lay.L, lay.ntokens, lay.H, lay.D)
         if self.mode in ("cachegen", "hbm-cachegen"):
-            _, out_dt = output_spec(fmt, 1, 1, 1, 8)
+            out_dt = _coded_dtype(fmt, kv_chunk.dtype)
             with torch.cuda.device(kv_chunk.device):
                 job = self._codec().encode(lay, 0, lay.ntokens, lay.ntokens, self.cachegen_config.plane_bins(lay.L))
             self._finish_encoded([key], job, [shape], out_dt)
@@ -339,7 +347,7 @@ class LMCLocalBackend(LMCBackendInterface):
         ctx = native.get_context(self._cuda_device)
         dev = src.device
         if self.mode in ("cachegen", "hbm-cachegen"):
-            _, out_dt = output_spec(fmt, 1, 1, 1, 8)
+            out_dt = _coded_dtype(fmt, dt)
             if self.pack_stores and n >= 2:
                 with torch.cuda.device(dev):
                     pjob = self._codec().store_pack(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L),
@@ -366,7 +374,8 @@ class LMCLocalBackend(LMCBackendInterface):
         # raw: gather every chunk into a device staging arena with the copy kernel, then D2H on the side stream
         codec = self._codec()
         cur = torch.cuda.current_stream(dev)
-        chunk_bytes = L * 2 * chunk_tokens * H * D * 2
+        eb = native.elem_bytes(src.dtype)
+        chunk_bytes = L * 2 * chunk_tokens * H * D * eb
         stage = self._stage_tensor(n * chunk_bytes, dev)
         if self._stage_free is not None:
             cur.wait_event(self._stage_free)
@@ -375,7 +384,7 @@ class LMCLocalBackend(LMCBackendInterface):
             numel = 1
             for s in shp:
                 numel *= s
-            v = stage[i * chunk_bytes:i * chunk_bytes + numel * 2].view(dt).view(shp)
+            v = stage[i * chunk_bytes:i * chunk_bytes + numel * eb].view(dt).view(shp)
             T = shp[2] if fmt == "vllm" else shp[3]
             ctx.copy_kv(src, tok_begin + i * chunk_tokens, T, native.KVLayout.from_chunk(v, fmt), 0)
             views.append(v)
@@ -384,7 +393,7 @@ class LMCLocalBackend(LMCBackendInterface):
         codec.copy_stream.wait_event(gathered)
         entries = []
         for v in views:
-            nb = v.numel() * 2
+            nb = v.numel() * eb
             hb = self.host_arena.alloc(nb)
             native.memcpy_async(hb.ptr, v.data_ptr(), nb, "d2h", codec.copy_stream.cuda_stream)
             entries.append(_HostChunk(hb, None, tuple(v.shape), dt, False))
@@ -482,7 +491,7 @@ class LMCLocalBackend(LMCBackendInterface):
             if isinstance(e, torch.Tensor):
                 chunk = e
             else:
-                numel = e.blob.nbytes // 2
+                numel = e.blob.nbytes // e.dtype.itemsize
                 chunk = stage[off:off + e.blob.nbytes].view(e.dtype)[:numel].view(e.shape)
                 native.memcpy_async(chunk.data_ptr(), e.blob.ptr, e.blob.nbytes, "h2d", cur.cuda_stream)
                 off += native.r16(e.blob.nbytes)
@@ -650,7 +659,7 @@ class LMCLocalDiskBackend(LMCBackendInterface):
                 if off != nbytes:
                     raise native.NativeError(f"short read: {off} of {nbytes} bytes")
                 h = native.blob_info(bytes(mv[:native.HEADER_BYTES]), nbytes)
-                shape, dtype = output_spec(fmt, h.num_layers, h.ntokens, h.num_heads, h.head_size)
+                shape, dtype = retrieve_spec(fmt, h)
                 out = torch.empty(shape, dtype=dtype, device=dev)
                 codec = get_codec(dev.index)
                 hb = HostBlob(self._read_buf, 0, nbytes)

@@ -84,7 +84,7 @@ class LMCRemoteBackend(LMCBackendInterface):
         bs = self.connection.get(key.to_string())
         if bs is None or len(bs) == 0:
             return None
-        return self.deserializer.from_bytes(bs).to(self.dst_device)
+        return self.deserializer.from_bytes_as_stored(bs).to(self.dst_device)  # (an fp8 chunk stays fp8)
 
     def close(self):
         if self.put_thread is not None and self.put_thread.is_alive():
@@ -166,20 +166,21 @@ class LMCPipelinedRemoteBackend(LMCRemoteBackend):
     def batched_get(self, keys):
         results: List[Optional[torch.Tensor]] = []
         for _, bs, _ in self._arrivals(keys):
-            results.append(None if bs is None else self.deserializer.from_bytes(bs).to(self.dst_device))
+            # (a CacheGen chunk comes back in the dtype it was stored in: fp8 stays fp8)
+            results.append(None if bs is None else self.deserializer.from_bytes_as_stored(bs).to(self.dst_device))
         return results
 
     # ---- range protocol (cachegen serde) ------------------------------------------------------------------
     def chunk_meta(self, key: CacheEngineKey):
         from lmcache_amd import native
-        from lmcache_amd.storage_backend.serde.cachegen_decoder import output_spec
+        from lmcache_amd.storage_backend.serde.cachegen_decoder import retrieve_spec
         if self._dev_conn:
             got = self.connection.peek(key.to_string(), native.HEADER_BYTES)
             if got is None:
                 self.existing_keys.discard(key)
                 raise KeyError(key)
             h = native.blob_info(got[0], total_len=got[1])
-            return output_spec(self.fmt, h.num_layers, h.ntokens, h.num_heads, h.head_size)
+            return retrieve_spec(self.fmt, h)
         bs = self._prefetched.get(key)
         if bs is None:
             bs = self.connection.get(key.to_string())
@@ -188,7 +189,7 @@ class LMCPipelinedRemoteBackend(LMCRemoteBackend):
                 raise KeyError(key)
             self._prefetched[key] = bs
         h = native.blob_info(bs)
-        return output_spec(self.fmt, h.num_layers, h.ntokens, h.num_heads, h.head_size)
+        return retrieve_spec(self.fmt, h)
 
     def put_kv_range(self, keys, src, fmt: str, tok_begin: int, tok_end: int, chunk_tokens: int,
                      blocking: bool = True) -> int:

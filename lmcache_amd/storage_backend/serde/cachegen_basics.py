@@ -102,7 +102,8 @@ class CacheGenGPUEncoderOutput:
         self.head_size = int(h.head_size)
         self.num_layers = int(h.num_layers)
         self.ntokens = int(h.ntokens)
-        self.dtype = native.torch_dtype(int(h.dtype))
+        self.dtype = native.stored_dtype(h)  # fp8 KV: its fp8 dtype (the scales are held in it, as the reference holds max1)
+        self._scale_dtype = native.torch_dtype(int(h.dtype))
 
     def _section(self, off, count, dt):
         return np.frombuffer(self._blob, dtype=dt, count=count, offset=off)
@@ -162,7 +163,8 @@ class CacheGenGPUEncoderOutput:
     def _scales(self) -> torch.Tensor:
         h = self.header
         a = self._section(h.off_scales, h.nplanes * h.ntokens, np.int16).reshape(h.nplanes, h.ntokens, 1).copy()
-        return torch.from_numpy(a).view(self.dtype)
+        t = torch.from_numpy(a).view(self._scale_dtype)
+        return t if self.dtype == self._scale_dtype else t.to(self.dtype)  # bf16 images of fp8 values: exact
 
     @property
     def max_tensors_key(self) -> torch.Tensor:

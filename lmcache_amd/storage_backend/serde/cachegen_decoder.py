@@ -34,6 +34,13 @@ def output_spec(fmt: str, L: int, T: int, H: int, D: int):
     raise RuntimeError("Unknown format %s" % fmt)
 
 
+def retrieve_spec(fmt: str, h):
+    """Shape and dtype an ENGINE retrieve of the blob with header `h` returns: output_spec's, except that a chunk stored
+    as fp8 (header kv_dtype) comes back as fp8 -- the dtype that was stored."""
+    shape, dtype = output_spec(fmt, h.num_layers, h.ntokens, h.num_heads, h.head_size)
+    return shape, (native.stored_dtype(h) if int(h.kv_dtype) else dtype)
+
+
 class CacheGenDeserializer(Deserializer):
     def __init__(self, config: LMCacheEngineConfig, metadata: LMCacheEngineMetadata):
         native.lib()
@@ -56,7 +63,14 @@ class CacheGenDeserializer(Deserializer):
     @_lmcache_nvtx_annotate
     def from_bytes(self, bs) -> torch.Tensor:
         h = native.blob_info(bs)  # validates magic / geometry / length on the host
-        shape, dtype = output_spec(self.fmt, h.num_layers, h.ntokens, h.num_heads, h.head_size)
+        return self._decode(bs, h, *output_spec(self.fmt, h.num_layers, h.ntokens, h.num_heads, h.head_size))
+
+    def from_bytes_as_stored(self, bs) -> torch.Tensor:
+        """from_bytes for the engine's retrieve: a chunk stored as fp8 comes back as fp8 (retrieve_spec)."""
+        h = native.blob_info(bs)
+        return self._decode(bs, h, *retrieve_spec(self.fmt, h))
+
+    def _decode(self, bs, h, shape, dtype) -> torch.Tensor:
         with self._lock:
             dev = torch.cuda.current_device()
             out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", dev))

@@ -47,7 +47,7 @@ class CacheGenSerializer(Serializer):
 
     @_lmcache_nvtx_annotate
     def to_bytes(self, tensor: torch.Tensor) -> bytes:
-        """[L,2,T,H,D] ("vllm") or [L,2,H,T,D] ("huggingface"), bf16/fp16, any device -> bytes."""
+        """[L,2,T,H,D] ("vllm") or [L,2,H,T,D] ("huggingface"), bf16/fp16/fp8 (e4m3fn, e5m2), any device -> bytes."""
         if self.fmt not in ("vllm", "huggingface"):
             raise ValueError(f"Invalid format: {self.fmt}")
         if not tensor.is_cuda:

@@ -27,6 +27,12 @@ class Deserializer(abc.ABC):
         """bytes / bytearray (never mutated) -> tensor."""
         raise NotImplementedError
 
+    def from_bytes_as_stored(self, bs: BytesLike) -> torch.Tensor:
+        """from_bytes for the engine's retrieve: the tensor in the dtype the chunk was stored in.  A lossless serde
+        returns what was saved anyway; CacheGen's from_bytes follows the reference's dtype rule and overrides this so
+        that an fp8 chunk comes back as fp8."""
+        return self.from_bytes(bs)
+
 
 class SerializerDebugWrapper(Serializer):
     def __init__(self, s: Serializer):
@@ -46,5 +52,11 @@ class DeserializerDebugWrapper(Deserializer):
     def from_bytes(self, bs: BytesLike) -> torch.Tensor:
         t0 = time.perf_counter()
         out = self.d.from_bytes(bs)
+        logger.debug("Deserialization took %.2f ms", (time.perf_counter() - t0) * 1e3)
+        return out
+
+    def from_bytes_as_stored(self, bs: BytesLike) -> torch.Tensor:
+        t0 = time.perf_counter()
+        out = self.d.from_bytes_as_stored(bs)
         logger.debug("Deserialization took %.2f ms", (time.perf_counter() - t0) * 1e3)
         return out
