@@ -346,11 +346,15 @@ int lmc_store_pack(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, in
 /*
  * lmc_store_pack with the encode launched in `nparts` ranges of planes, each range packed as soon as it is coded
  * (round 6): after part r the streams region holds part r's segments at their final offsets, part_info_h[2 r] =
- * the part's offset in the streams region, part_info_h[2 r + 1] = its bytes (0: the pack has failed), and
+ * the part's offset in the streams region, part_info_h[2 r + 1] = its bytes, and
  * part_events[r] is recorded on `stream` -- the caller moves [off_streams + offset, + bytes) to host memory with a
  * DMA copy while the later planes are still being encoded (CacheGenDeviceCodec.store_pack / finish_pack: a 16 k
  * store completes when its last PCIe byte lands, where lmc_store_pack + one copy of the finished pack waits for the
  * whole encode first).  Header, offset table and static slots ([0, off_streams)) are final after the LAST part.
+ * A part of 0 bytes is no verdict on the pack: a part that is not the last packs the planes coded so far BUT the newest
+ * one (whose end its successor writes), so a first range of a single plane ships nothing, and the parts of a pack that
+ * did not fit read 0 bytes too.  Failure is the job's status word (LMC_STATUS_HOST_ARENA_FULL) and a header that is
+ * not a pack's (magic 0, total_bytes 0), both valid after the last part.
  * pack_d must be DEVICE memory (a kernel that posts PCIe writes between the encode's parts would stall them);
  * part_info_h: pinned uint64 [2 nparts]; part_events: [nparts] events or NULL.  A job that cannot be split (a ragged
  * last chunk, a job too small for the fused encode) runs as ONE part: part_info_h[1 .. ) read {0, 0} and the

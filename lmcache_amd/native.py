@@ -775,7 +775,10 @@ class StatusWords:
     def read_release(self, i: int) -> int:
         """Value of word i (the job's work must have completed) and return it to the pool."""
         with self._lock:
-            v = int(self._blocks[i // self.BLOCK][1][i % self.BLOCK]) & 0xffffffff
+            buf, words = self._blocks[i // self.BLOCK]
+            # (a job collected together with its pool -- the codec of a finished process or test module -- may be
+            # finalised after the pool's pinned block has been freed: there is no word to read any more)
+            v = int(words[i % self.BLOCK]) & 0xffffffff if buf.ptr else 0
             self._free.append(i)
         return v
 

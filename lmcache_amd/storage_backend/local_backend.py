@@ -150,8 +150,11 @@ class LMCLocalBackend(LMCBackendInterface):
         """The entries of the leading keys that are present (stop at the first miss).  The last answer is kept for the SAME
         key list object while nothing has been published since (the engine keeps the key lists of its last hash chains:
         the lookup -> retrieve of a warm prefix probes the same 64 keys twice, every call of a serving engine)."""
+        # the generation is read BEFORE the scan: a publish that lands while the dict is being scanned leaves the answer
+        # filed under the older generation, so the next call scans again instead of repeating a short answer
+        gen = self._gen
         m = self._prefix_memo
-        if m is not None and m[0] is keys and m[1] == self._gen:
+        if m is not None and m[0] is keys and m[1] == gen:
             return m[2]
         d, entries = self.dict, []
         for k in keys:
@@ -159,7 +162,7 @@ class LMCLocalBackend(LMCBackendInterface):
             if e is None:
                 break
             entries.append(e)
-        self._prefix_memo = (keys, self._gen, entries)
+        self._prefix_memo = (keys, gen, entries)
         return entries
 
     def contains_prefix(self, keys: Sequence[CacheEngineKey]) -> int:

@@ -14,6 +14,7 @@ here, local_backend.py:83-85).
 import ctypes
 import os
 import threading
+import weakref
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -275,14 +276,14 @@ class CacheGenDeviceCodec:
         self.decode_batch_chunks = 8                         # chunks per H2D/decode pipeline stage
         self._pack_dev: Optional[torch.Tensor] = None        # HBM staging of a pack on its way to pinned memory (store_pack)
         self._pack_dev_free: Optional[torch.cuda.Event] = None
-        self._pack_prev: Optional[PackJob] = None
+        self._pack_prev = None                               # weak reference to the last PackJob that took _pack_dev
         self._hdr: Optional[native.PinnedBuffer] = None
         # plane ranges a pack's encode is launched in (store_pack, dma): LMCACHE_AMD_PACK_PARTS=1 is the round-5 behaviour
         # (the whole encode, then the pack, then its copies), for A/B
         self.pack_parts = max(1, min(16, int(os.environ.get("LMCACHE_AMD_PACK_PARTS", "8"))))
         self._part_info_pool: List[native.PinnedBuffer] = []
-        self._same_blobs: dict = {}                          # id(caller's list) -> (the list, its blobs' address tuple)
-        self._table_cache: dict = {}                         # blob-address tuple -> (device table, largest blob, upload stream)
+        self._same_blobs: dict = {}                          # id(caller's list) -> (the list, its blobs' address tuple, largest blob)
+        self._table_cache: dict = {}                         # blob-address tuple -> (device table, upload stream)
 
     # ---- encode ------------------------------------------------------------------
     def _readable(self, src: native.KVLayout, tok_begin: int, tok_end: int):
@@ -470,29 +471,33 @@ class CacheGenDeviceCodec:
             # same_blobs_as: an object the caller hands over again whenever -- and only when -- `blobs` are the same
             # tensors (the backend's kept entry list of a prefix): then not even the 64 data_ptr() calls are repeated.  The
             # object is kept alive beside its key, so its id cannot be recycled while the entry exists.
-            ptrs = None
+            # The largest blob of the call -- what k_decode holds every header's total against -- is NOT a function of the
+            # addresses (an arena closed and reopened hands out the same address for a blob of another size), so it is
+            # never kept beside the table: it is taken from THIS call's blobs, or kept with same_blobs_as, whose promise of
+            # "the same tensors" covers their sizes.
+            ptrs = bound = None
             if same_blobs_as is not None:
                 known = self._same_blobs.get(id(same_blobs_as))
                 if known is not None and known[0] is same_blobs_as:
-                    ptrs = known[1]
+                    ptrs, bound = known[1], known[2]
             if ptrs is None:
                 ptrs = tuple(b.data_ptr() for b in blobs)
+                bound = max(b.numel() for b in blobs)
                 if same_blobs_as is not None:
                     if len(self._same_blobs) >= 8:
                         self._same_blobs.pop(next(iter(self._same_blobs)))
-                    self._same_blobs[id(same_blobs_as)] = (same_blobs_as, ptrs)
+                    self._same_blobs[id(same_blobs_as)] = (same_blobs_as, ptrs, bound)
             hit = self._table_cache.get(ptrs)
             if hit is None:
                 table = torch.tensor(ptrs, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-                bound = max(b.numel() for b in blobs)
                 if len(self._table_cache) >= 8:
                     self._table_cache.pop(next(iter(self._table_cache)))
-                self._table_cache[ptrs] = (table, bound, cur)
+                self._table_cache[ptrs] = (table, cur)
             else:
-                table, bound, up = hit
+                table, up = hit
                 if up is not cur:  # uploaded on another stream: order this one behind that copy (once)
                     cur.wait_stream(up)
-                    self._table_cache[ptrs] = (table, bound, cur)
+                    self._table_cache[ptrs] = (table, cur)
             st = self._status.acquire()
             try:
                 # ONE C-ABI call issues every range's launch and records its event (lmc_decode_chunks_schedule): the
@@ -567,7 +572,10 @@ class CacheGenDeviceCodec:
             cur = torch.cuda.current_stream(self.device)
             region = dev = None
             if dma:
-                prev = self._pack_prev
+                # (a weak reference: a job dropped unfinished -- an exception between store_pack and finish_pack -- has
+                # waited for its kernels in __del__ and queued no copy, so the region is free again; a strong one would keep
+                # such a job, and with it every later store on regions of their own, for the life of the codec)
+                prev = self._pack_prev() if self._pack_prev is not None else None
                 if prev is None or prev.d2h_issued:
                     if self._pack_dev is None or self._pack_dev.numel() < cap:
                         self._pack_dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
@@ -613,7 +621,7 @@ class CacheGenDeviceCodec:
             job.geometry = (L, H, D)
             job.part_events, job.part_info, job.cap = part_events, part_info, cap
             if dma and dev is self._pack_dev:
-                self._pack_prev = job
+                self._pack_prev = weakref.ref(job)
             return job
 
     def finish_pack(self, job: PackJob, arena: PinnedArena) -> HostPack:
@@ -642,7 +650,9 @@ class CacheGenDeviceCodec:
                 ev.synchronize()  # this part only
                 off, nbytes = int(info[2 * r]), int(info[2 * r + 1])
                 if nbytes <= 0:
-                    failed = failed or (r == 0)  # (parts behind the only one of an unsplit job are empty by design)
+                    # no bytes is no verdict: a first range of a single plane ships nothing (a part packs the planes coded
+                    # so far but the newest one), the parts behind the only one of an unsplit job are empty by design, and
+                    # a part that failed reads the same -- the job's status word and the check of the assembled pack decide
                     continue
                 if off_streams + off + nbytes > job.cap:
                     failed = True
@@ -667,9 +677,13 @@ class CacheGenDeviceCodec:
         if st or failed:
             arena.shrink(region, 0)
             raise native.NativeError("CacheGen store (pack): " + (native.describe_status(st) if st else "the device left no pack"))
-        h = native.pack_info(region.ptr, total)  # the pack checks out where it lies now
-        if int(h.total_bytes) != total:
-            raise native.NativeError("CacheGen store (pack): the parts do not add up to the pack")
+        try:
+            h = native.pack_info(region.ptr, total)  # the pack checks out where it lies now
+            if int(h.total_bytes) != total:
+                raise native.NativeError("CacheGen store (pack): the parts do not add up to the pack")
+        except native.NativeError:
+            arena.shrink(region, 0)
+            raise
         return HostPack(arena.shrink(region, total), job.nchunks, job.chunk_tokens)
 
     def _release_pack_words(self, job: PackJob) -> int:

@@ -306,7 +306,6 @@ def _engine_bins(oracle, L):
     return list(np.concatenate([b[:len(b) // 2][:L], b[len(b) // 2:][:L]]))
 
 
-@pytest.mark.parametrize("dt", FP8, ids=IDS)
 def _prefix_hits_of_a_bf16_engine(backend, x, L, H, D, T, n):
     """What the same backend returns for an n-token prefix of a T-token bf16 prompt: (hit count, the tensor [L,2,hits,C])."""
     from lmcache_amd.cache_engine import LMCacheEngine

@@ -516,3 +516,66 @@ def test_pack_cap_covers_the_allocations_of_high_entropy_channels(oracle, T):
         blob = oracle.encode_blob(bits, code, H, D, np.array([bins, bins], np.int32))
         pack = oracle.pack_from_blobs([blob], T)
         assert len(pack) <= pack_cap(1, L, T, H, D, [bins, bins]), (T, bins, len(pack), pack_cap(1, L, T, H, D, [bins, bins]))
+
+
+def _bare_local_backend(d):
+    """An LMCLocalBackend with the five attributes _prefix_entries / contains_prefix / _publish touch, and no GPU."""
+    import threading
+    from lmcache_amd.storage_backend.local_backend import LMCLocalBackend
+    b = LMCLocalBackend.__new__(LMCLocalBackend)
+    b.put_thread = b.host_arena = b.dev_arena = None  # (what close() -- __del__ -- looks at)
+    b.dict, b.update_lock, b._gen, b._prefix_memo, b.last_publish_time = d, threading.Lock(), 0, None, 0.0
+    return b
+
+
+def test_prefix_entries_survive_a_publish_during_the_scan():
+    """A store that publishes a key between _prefix_entries' scan of the dict and its filing of the answer must not
+    leave a short answer standing: the kept answer is valid for the generation read BEFORE the scan.  The dict's get()
+    publishes the key it has just reported missing -- the worker thread of a non-blocking store, made deterministic."""
+    class PublishingDict(dict):
+        backend, armed, gets = None, True, 0
+
+        def get(self, k, default=None):
+            self.gets += 1
+            e = dict.get(self, k, default)
+            if e is None and self.armed:
+                self.armed = False
+                self.backend._publish(k, "entry of " + k)
+            return e
+
+    d = PublishingDict()
+    b = _bare_local_backend(d)
+    d.backend = b
+    keys = ["k0", "k1", "k2"]
+    b._publish("k0", "entry of k0")
+    b._publish("k1", "entry of k1")
+    assert b.contains_prefix(keys) == 2    # k2 was missing when it was asked for ...
+    assert "k2" in d and b._gen == 3       # ... and has been published since, during that very call
+    assert b.contains_prefix(keys) == 3, "a publish during the scan left a short prefix filed under the new generation"
+    assert b._prefix_entries(keys) == ["entry of k0", "entry of k1", "entry of k2"]
+
+
+def test_prefix_entries_memo_is_per_list_object_and_dropped_by_a_publish():
+    class CountingDict(dict):
+        gets = 0
+
+        def get(self, k, default=None):
+            self.gets += 1
+            return dict.get(self, k, default)
+
+    d = CountingDict()
+    b = _bare_local_backend(d)
+    keys = ["a", "b", "c", "d"]
+    for k in keys[:3]:
+        b._publish(k, k.upper())
+    first = b._prefix_entries(keys)
+    assert first == ["A", "B", "C"] and d.gets == 4  # three hits and the miss that ends the run
+    assert b._prefix_entries(keys) is first and b.contains_prefix(keys) == 3 and d.gets == 4  # the same list object: no scan
+    assert b._prefix_entries(list(keys)) == first and d.gets == 8                            # an equal list is another object
+    assert b._prefix_entries(keys) == first and d.gets == 12                                  # (one answer is kept, the last)
+    b._publish("zzz", "unrelated")                                                            # ANY publish drops the answer
+    assert b._prefix_entries(keys) == first and d.gets == 16
+    b._publish("d", "D")
+    assert b.contains_prefix(keys) == 4 and d.gets == 20
+    assert b.contains_prefix(keys) == 4 and d.gets == 20
+    assert b.contains_prefix([]) == 0 and b.contains_prefix(["nope"] + keys) == 0
