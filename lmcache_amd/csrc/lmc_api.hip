@@ -276,6 +276,11 @@ static int launch_quant(const QuantArgs& a, hipStream_t s) {
   }
 }
 
+// The slot of a blob in the arenas and slots of this file: lmc_blob_bound rounded up to 16 bytes.
+static uint64_t blob_stride(int L, int chunk_tokens, int H, int D) {
+  return (lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D) + 15) & ~(uint64_t)15;
+}
+
 static int ws_grow(void** p, size_t* have, size_t need) {
   if (*have >= need) return LMC_OK;
   if (*p) { hipError_t e = hipFree(*p); if (e != hipSuccess) { g_last_hip = (int)e; return LMC_ERR_HIP; } *p = nullptr; *have = 0; }
@@ -602,17 +607,30 @@ static void launch_decode(int dtype, bool paged, dim3 grid, hipStream_t s, const
 #undef LD
 }
 
-static int decode_launch(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, hipStream_t hs) {
-  int rc;
-  const long long n = (long long)a.nchunks * 2 * a.layer_count * a.G;
-  dim3 grid((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES));
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->pn = 0;
-  if ((rc = prof_mark(c, hs))) return rc;
-  const bool paged = dst->slot_mapping != nullptr;
-  launch_decode(dst->dtype, paged, grid, hs, a);
+// One range of layers of a decode: k_decode over the streams of layers [l0, l0 + nl) of the job's chunks, then `ev`
+// (if any) recorded behind it.  The lock is not needed for the launch itself: the load paths call this with c->mu held.
+static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev) {
+  a.layer_begin = l0; a.layer_count = nl;
+  const long long n = (long long)a.nchunks * 2 * nl * a.G;
+  const dim3 grid((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES));
+  launch_decode(dst->dtype, dst->slot_mapping != nullptr, grid, s, a);
   HIP_TRY(hipGetLastError());
-  if ((rc = prof_mark(c, hs))) return rc;
+  if (ev) HIP_TRY(hipEventRecord((hipEvent_t)ev, s));
+  return LMC_OK;
+}
+
+// The same for the decode entry points, which do not hold the lock: taken here, and the launch bracketed by the
+// profiling marks (the range's event follows the second mark).
+static int decode_range(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev) {
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->pn = 0;
+    if ((rc = prof_mark(c, s))) return rc;
+    if ((rc = decode_range_locked(a, dst, l0, nl, s, nullptr))) return rc;
+    if ((rc = prof_mark(c, s))) return rc;
+  }
+  if (ev) HIP_TRY(hipEventRecord((hipEvent_t)ev, s));
   return LMC_OK;
 }
 
@@ -625,7 +643,7 @@ int lmc_decode_chunks(lmc_ctx* c, const void* blobs, uint64_t blob_stride, int32
   if (rc) return rc;
   a.dst = to_addr(dst); a.dst_tok0 = dst_tok0; a.chunk_tokens = chunk_tokens;
   HIP_TRY(hipSetDevice(c->device));
-  return decode_launch(c, a, dst, (hipStream_t)stream);
+  return decode_range(c, a, dst, 0, dst->num_layers, (hipStream_t)stream, nullptr);
 }
 
 int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
@@ -641,10 +659,9 @@ int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t 
                          dst->head_size, job_status, a);
   if (rc) return rc;
   a.blob_ptrs = (const u8* const*)blob_ptrs;
-  a.layer_begin = layer_begin; a.layer_count = layer_count;
   a.dst = to_addr(dst); a.dst_tok0 = dst_tok0; a.chunk_tokens = chunk_tokens;
   HIP_TRY(hipSetDevice(c->device));
-  return decode_launch(c, a, dst, (hipStream_t)stream);
+  return decode_range(c, a, dst, layer_begin, layer_count, (hipStream_t)stream, nullptr);
 }
 
 int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
@@ -663,12 +680,9 @@ int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_
   a.blob_ptrs = (const u8* const*)blob_ptrs;
   a.dst = to_addr(dst); a.dst_tok0 = dst_tok0; a.chunk_tokens = chunk_tokens;
   HIP_TRY(hipSetDevice(c->device));
-  for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++) {
-    a.layer_begin = prev; a.layer_count = layer_ends_h[i] - prev;
-    rc = decode_launch(c, a, dst, (hipStream_t)stream);
-    if (rc) return rc;
-    if (events_h && events_h[i]) HIP_TRY(hipEventRecord((hipEvent_t)events_h[i], (hipStream_t)stream));
-  }
+  for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)
+    if ((rc = decode_range(c, a, dst, prev, layer_ends_h[i] - prev, (hipStream_t)stream, events_h ? events_h[i] : nullptr)))
+      return rc;
   return LMC_OK;
 }
 
@@ -779,6 +793,30 @@ static int next_event(lmc_ctx* c, hipEvent_t* out) {  // caller holds c->mu; 64 
   return LMC_OK;
 }
 
+// caller holds c->mu: `later` runs behind what `first` has queued so far (an event from the rotation)
+static int stream_follows(lmc_ctx* c, hipStream_t later, hipStream_t first) {
+  int rc;
+  hipEvent_t ev;
+  if ((rc = next_event(c, &ev))) return rc;
+  HIP_TRY(hipEventRecord(ev, first));
+  HIP_TRY(hipStreamWaitEvent(later, ev, 0));
+  return LMC_OK;
+}
+// Takes c->mu.  The store arena of at least arena_bytes (and the pack table of table_bytes) for a job on `s`: the host
+// waits for the previous job's copies only when a buffer must grow, the stream always does.
+static int store_acquire(lmc_ctx* c, hipStream_t s, size_t arena_bytes, size_t table_bytes) {
+  int rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if ((rc = legs_init(c))) return rc;
+  if (c->store_bytes < arena_bytes || c->pack_table_bytes < table_bytes) {
+    if (c->store_used) HIP_TRY(hipEventSynchronize(c->store_free));  // growing frees the buffers: this call only
+    if ((rc = ws_grow((void**)&c->store_arena, &c->store_bytes, arena_bytes))) return rc;
+    if ((rc = ws_grow((void**)&c->pack_table, &c->pack_table_bytes, table_bytes))) return rc;
+  }
+  if (c->store_used) HIP_TRY(hipStreamWaitEvent(s, c->store_free, 0));  // the previous job's copies have read the arena
+  return LMC_OK;
+}
+
 int lmc_store_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
                      const int32_t* bins_h, void* host_arena_h, uint64_t host_cap, uint64_t* offsets_h,
                      uint32_t* sizes_h, uint32_t* job_status, lmc_stream_t stream) {
@@ -787,20 +825,11 @@ int lmc_store_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, in
     return LMC_ERR_INVALID;
   const int nchunks = (tok_end - tok_begin + chunk_tokens - 1) / chunk_tokens;
   if (nchunks > 65535) return LMC_ERR_INVALID;
-  const uint64_t stride = (lmc_blob_bound((uint32_t)src->num_layers, (uint32_t)chunk_tokens, (uint32_t)src->num_heads,
-                                          (uint32_t)src->head_size) + 15) & ~(uint64_t)15;
+  const uint64_t stride = blob_stride(src->num_layers, chunk_tokens, src->num_heads, src->head_size);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = legs_init(c))) return rc;
-    if (c->store_bytes < (size_t)nchunks * stride) {
-      if (c->store_used) HIP_TRY(hipEventSynchronize(c->store_free));  // growing frees the arena: this call only
-      if ((rc = ws_grow((void**)&c->store_arena, &c->store_bytes, (size_t)nchunks * stride))) return rc;
-    }
-    if (c->store_used) HIP_TRY(hipStreamWaitEvent(s, c->store_free, 0));  // the previous job's copies have read the arena
-  }
+  if ((rc = store_acquire(c, s, (size_t)nchunks * stride, 0))) return rc;
   // a long job leaves in parts: the copy of part k runs on the context's copy stream beside the encode of part k + 1
   const int nparts = nchunks >= 16 ? 4 : 1, per = (nchunks + nparts - 1) / nparts;
   uint32_t* st = job_status ? job_status : c->status_h;
@@ -811,10 +840,7 @@ int lmc_store_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, in
                                 stride, sizes_h + c0, job_status, stream)))
       return rc;
     std::lock_guard<std::mutex> lk(c->mu);
-    hipEvent_t ev;
-    if ((rc = next_event(c, &ev))) return rc;
-    HIP_TRY(hipEventRecord(ev, s));
-    HIP_TRY(hipStreamWaitEvent(c->copy_stream, ev, 0));
+    if ((rc = stream_follows(c, c->copy_stream, s))) return rc;
     OffloadArgs oa;
     memset(&oa, 0, sizeof oa);
     oa.blobs = c->store_arena; oa.stride = (long long)stride; oa.sizes_d = sizes_h; oa.nchunks = nchunks; oa.chunk0 = c0;
@@ -847,7 +873,7 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
     return LMC_ERR_INVALID;
   const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
   if (H * D > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
-  const uint64_t stride = (lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D) + 15) & ~(uint64_t)15;
+  const uint64_t stride = blob_stride(L, chunk_tokens, H, D);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   int rc;
@@ -881,12 +907,8 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
   for (int i = 0; i < nchunks; i++)
     HIP_TRY(hipMemcpyAsync(c->load_slots + (size_t)i * stride, host_blob_ptrs_h[i], (sizes_h[i] + 15u) & ~15u,
                            hipMemcpyHostToDevice, cs[i & 1]));
-  for (int q = 0; q < 2; q++) {  // the decodes wait for both queues
-    hipEvent_t ev;
-    if ((rc = next_event(c, &ev))) return rc;
-    HIP_TRY(hipEventRecord(ev, cs[q]));
-    HIP_TRY(hipStreamWaitEvent(s, ev, 0));
-  }
+  for (int q = 0; q < 2; q++)  // the decodes wait for both queues
+    if ((rc = stream_follows(c, s, cs[q]))) return rc;
   DecodeArgs da;
   memset(&da, 0, sizeof da);
   if ((rc = decode_common(c, c->load_slots, stride, nchunks, L, H, D, job_status, da))) return rc;
@@ -894,13 +916,7 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
   int r = 0;
   for (int l0 = 0; l0 < L; l0 += step, r++) {
     const int n = l0 + step <= L ? step : L - l0;
-    da.layer_begin = l0; da.layer_count = n;
-    const long long nstreams = (long long)nchunks * 2 * n * da.G;
-    const dim3 grid((unsigned)((nstreams + DEC_WAVES - 1) / DEC_WAVES));
-    const bool paged = dst->slot_mapping != nullptr;
-    launch_decode(dst->dtype, paged, grid, s, da);
-    HIP_TRY(hipGetLastError());
-    if (range_events && range_events[r]) HIP_TRY(hipEventRecord((hipEvent_t)range_events[r], s));
+    if ((rc = decode_range_locked(da, dst, l0, n, s, range_events ? range_events[r] : nullptr))) return rc;
   }
   HIP_TRY(hipEventRecord(c->load_free, s));
   c->load_used = true;
@@ -927,24 +943,12 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
   lmc_pack_layout((uint32_t)nchunks, (uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)src->num_heads, (uint32_t)src->head_size, &pa.hdr);
   pa.hdr.ntokens = (uint32_t)(tok_end - tok_begin);
   if (pa.hdr.off_streams > pack_cap) return LMC_ERR_INVALID;
-  const uint64_t stride = (lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)src->num_heads,
-                                          (uint32_t)src->head_size) + 15) & ~(uint64_t)15;
+  const uint64_t stride = blob_stride(L, chunk_tokens, src->num_heads, src->head_size);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   int rc;
   const size_t table_bytes = 8 * ((size_t)P * nchunks + 2);  // the table, and the running total of the parts
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = legs_init(c))) return rc;
-    if (c->store_bytes < (size_t)nchunks * stride || c->pack_table_bytes < table_bytes) {
-      if (c->store_used) HIP_TRY(hipEventSynchronize(c->store_free));  // growing frees the buffers: this call only
-      if (c->store_bytes < (size_t)nchunks * stride &&
-          (rc = ws_grow((void**)&c->store_arena, &c->store_bytes, (size_t)nchunks * stride)))
-        return rc;
-      if (c->pack_table_bytes < table_bytes && (rc = ws_grow((void**)&c->pack_table, &c->pack_table_bytes, table_bytes))) return rc;
-    }
-    if (c->store_used) HIP_TRY(hipStreamWaitEvent(s, c->store_free, 0));  // the previous job's copies have read the arena
-  }
+  if ((rc = store_acquire(c, s, (size_t)nchunks * stride, table_bytes))) return rc;
   pa.blobs = c->store_arena; pa.stride = (long long)stride; pa.sizes_d = sizes_h;
   pa.n = nchunks; pa.L = L; pa.G = (int)pa.hdr.ngroups;
   pa.host = (u8*)pack_h; pa.cap = pack_cap; pa.table_d = c->pack_table;
@@ -954,10 +958,7 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
     if ((rc = lmc_encode_chunks(c, src, tok_begin, tok_end, chunk_tokens, bins_h, c->store_arena, stride, sizes_h, job_status, stream)))
       return rc;
     std::lock_guard<std::mutex> lk(c->mu);
-    hipEvent_t ev;
-    if ((rc = next_event(c, &ev))) return rc;
-    HIP_TRY(hipEventRecord(ev, s));
-    HIP_TRY(hipStreamWaitEvent(c->copy_stream, ev, 0));
+    if ((rc = stream_follows(c, c->copy_stream, s))) return rc;
     pa.p_begin = 0; pa.p_end = P; pa.last = 1; pa.part_h = nullptr;
     hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(256), 0, c->copy_stream, pa);
     HIP_TRY(hipGetLastError());
@@ -1126,17 +1127,8 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
         }
       }
     }
-    hipEvent_t ev;
-    if ((rc = next_event(c, &ev))) return rc;
-    HIP_TRY(hipEventRecord(ev, cs));
-    HIP_TRY(hipStreamWaitEvent(s, ev, 0));
-    da.layer_begin = l0; da.layer_count = nl;
-    const long long nstreams = (long long)m * 2 * nl * da.G;
-    const dim3 grid((unsigned)((nstreams + DEC_WAVES - 1) / DEC_WAVES));
-    const bool paged = dst->slot_mapping != nullptr;
-    launch_decode(dst->dtype, paged, grid, s, da);
-    HIP_TRY(hipGetLastError());
-    if (range_events && range_events[r]) HIP_TRY(hipEventRecord((hipEvent_t)range_events[r], s));
+    if ((rc = stream_follows(c, s, cs))) return rc;
+    if ((rc = decode_range_locked(da, dst, l0, nl, s, range_events ? range_events[r] : nullptr))) return rc;
   }
   HIP_TRY(hipEventRecord(c->load_free, s));
   c->load_used = true;

@@ -354,6 +354,20 @@ def pointer_table(ptrs: Sequence[int], device: torch.device) -> torch.Tensor:
     return _pointer_tables.get(ptrs, device)
 
 
+def _layout_struct(dt: torch.dtype, L: int, H: int, D: int, stride_token: int, stride_head: int, base: Optional[int] = None,
+                   stride_layer: int = 0, stride_kv: int = 0, plane_ptrs: Optional[int] = None,
+                   slot_mapping: Optional[int] = None, block_size: int = 0, stride_block: int = 0) -> KvLayoutStruct:
+    """A filled lmc_kv_layout: the planes are addressed from `base` with layer / kv strides or through the device table
+    `plane_ptrs`, the tokens directly or (paged) through `slot_mapping` in blocks of `block_size`."""
+    s = KvLayoutStruct()
+    s.dtype = dtype_code(dt)
+    s.num_layers, s.num_heads, s.head_size = L, H, D
+    s.base, s.plane_ptrs = base, plane_ptrs
+    s.stride_layer, s.stride_kv, s.stride_token, s.stride_head = stride_layer, stride_kv, stride_token, stride_head
+    s.slot_mapping, s.block_size, s.stride_block = slot_mapping, block_size, stride_block
+    return s
+
+
 class KVLayout:
     """Python owner of a lmc_kv_layout; keeps the tensors it points into alive."""
 
@@ -402,25 +416,18 @@ class KVLayout:
         (cache_engine.py:137-140).  Any strides are fine (permuted views included) as long as
         the head dimension is contiguous; what the ENCODERS read must also be vector_readable()."""
         assert t.is_cuda and t.dim() == 5 and t.shape[1] == 2, f"bad chunk shape {tuple(t.shape)}"
-        s = KvLayoutStruct()
         st = t.stride()
         if fmt == "vllm":
             L, _, T, H, D = t.shape
-            s.stride_token, s.stride_head = st[2], st[3]
+            stride_token, stride_head = st[2], st[3]
         elif fmt == "huggingface":
             L, _, H, T, D = t.shape
-            s.stride_token, s.stride_head = st[3], st[2]
+            stride_token, stride_head = st[3], st[2]
         else:
             raise ValueError(f"Invalid format: {fmt}")
         if st[4] != 1:
             raise ValueError("head dimension must be contiguous")
-        s.dtype = dtype_code(t.dtype)
-        s.num_layers, s.num_heads, s.head_size = L, H, D
-        s.base = t.data_ptr()
-        s.plane_ptrs = None
-        s.stride_layer, s.stride_kv = st[0], st[1]
-        s.slot_mapping = None
-        s.block_size, s.stride_block = 0, 0
+        s = _layout_struct(t.dtype, L, H, D, stride_token, stride_head, base=t.data_ptr(), stride_layer=st[0], stride_kv=st[1])
         return KVLayout(s, [t], T, t.device)
 
     @staticmethod
@@ -442,22 +449,15 @@ class KVLayout:
                 ptrs.append(x.data_ptr())
                 keep.append(x)
         table = _pointer_tables.get(ptrs, k0.device)
-        s = KvLayoutStruct()
         if fmt == "vllm":
             T, H, D = k0.shape
-            s.stride_token, s.stride_head = st[0], st[1]
+            stride_token, stride_head = st[0], st[1]
         elif fmt == "huggingface":
             H, T, D = k0.shape
-            s.stride_token, s.stride_head = st[1], st[0]
+            stride_token, stride_head = st[1], st[0]
         else:
             raise ValueError(f"Invalid format: {fmt}")
-        s.dtype = dtype_code(k0.dtype)
-        s.num_layers, s.num_heads, s.head_size = len(kv), H, D
-        s.base = None
-        s.plane_ptrs = table.data_ptr()
-        s.stride_layer = s.stride_kv = 0
-        s.slot_mapping = None
-        s.block_size, s.stride_block = 0, 0
+        s = _layout_struct(k0.dtype, len(kv), H, D, stride_token, stride_head, plane_ptrs=table.data_ptr())
         return KVLayout(s, keep + [table], T, k0.device)
 
     @staticmethod
@@ -476,23 +476,17 @@ class KVLayout:
             keep.append(c)
         table = _pointer_tables.get(ptrs, c0.device)
         sm = slot_mapping.to(device=c0.device, dtype=torch.int64).contiguous()
-        s = KvLayoutStruct()
         if layout == "NBHD":
             _, _, bs, H, D = c0.shape
-            s.stride_token, s.stride_head = st[2], st[3]
+            stride_token, stride_head = st[2], st[3]
         elif layout == "NHBD":
             _, _, H, bs, D = c0.shape
-            s.stride_token, s.stride_head = st[3], st[2]
+            stride_token, stride_head = st[3], st[2]
         else:
             raise ValueError(layout)
         assert bs == block_size and st[4] == 1
-        s.dtype = dtype_code(c0.dtype)
-        s.num_layers, s.num_heads, s.head_size = len(kv_caches), H, D
-        s.base = None
-        s.plane_ptrs = table.data_ptr()
-        s.stride_layer = s.stride_kv = 0
-        s.slot_mapping = sm.data_ptr()
-        s.block_size, s.stride_block = block_size, st[1]
+        s = _layout_struct(c0.dtype, len(kv_caches), H, D, stride_token, stride_head, plane_ptrs=table.data_ptr(),
+                           slot_mapping=sm.data_ptr(), block_size=block_size, stride_block=st[1])
         return KVLayout(s, keep + [table, sm], sm.numel(), c0.device)
 
 
@@ -605,24 +599,29 @@ class Context:
         arr = (ctypes.c_int32 * len(bins))(*[int(b) for b in bins])
         return arr
 
+    def _call(self, name: str, device, stream: Optional[int], *args) -> None:
+        """The C-ABI call `name`(ctx, *args, stream), checked; stream None: the current stream of `device`."""
+        st = current_stream_ptr(device) if stream is None else stream
+        check(getattr(lib(), name)(self.handle, *args, st), name)
+
+    @staticmethod
+    def _nchunks(tok_begin: int, tok_end: int, chunk_tokens: int) -> int:
+        return (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
+
     def quantize(self, src: KVLayout, tok_begin: int, ntok: int, bins, stream: Optional[int] = None
                  ) -> Tuple[torch.Tensor, torch.Tensor]:
         P, C = 2 * src.L, src.H * src.D
         sym = torch.empty((P, ntok, C), dtype=torch.int8, device=src.device)
         scale = torch.empty((P, ntok), dtype=torch.int16, device=src.device)
-        b = self._bins(bins)
-        st = current_stream_ptr(src.device) if stream is None else stream
-        check(lib().lmc_quantize(self.handle, ctypes.byref(src.struct), tok_begin, ntok, b, sym.data_ptr(),
-                                 scale.data_ptr(), st), "lmc_quantize")
+        self._call("lmc_quantize", src.device, stream, ctypes.byref(src.struct), tok_begin, ntok, self._bins(bins),
+                   sym.data_ptr(), scale.data_ptr())
         return sym, scale
 
     def calculate_cdf(self, sym: torch.Tensor, max_bins: int = MAX_BINS, stream: Optional[int] = None) -> torch.Tensor:
         assert sym.is_cuda and sym.dtype == torch.int8 and sym.is_contiguous() and sym.dim() == 3
         P, T, C = sym.shape
         out = torch.empty((P, C, max_bins + 1), dtype=torch.int16, device=sym.device)
-        st = current_stream_ptr(sym.device) if stream is None else stream
-        check(lib().lmc_calculate_cdf(self.handle, sym.data_ptr(), P, T, C, max_bins, out.data_ptr(), st),
-              "lmc_calculate_cdf")
+        self._call("lmc_calculate_cdf", sym.device, stream, sym.data_ptr(), P, T, C, max_bins, out.data_ptr())
         return out
 
     def encode_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
@@ -630,26 +629,21 @@ class Context:
                       status_ptr: Optional[int] = None) -> int:
         """status_ptr: device-accessible uint32 (pinned host) that receives THIS job's LMC_STATUS_* bits
         (None: the context's sticky word)."""
-        b = self._bins(bins)
-        st = current_stream_ptr(src.device) if stream is None else stream
-        check(lib().lmc_encode_chunks(self.handle, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens, b,
-                                      blobs_ptr, blob_stride, sizes_ptr, status_ptr, st), "lmc_encode_chunks")
-        return (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
+        self._call("lmc_encode_chunks", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
+                   self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
+        return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
     def decode_chunks(self, blobs_ptr: int, blob_stride: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                       chunk_tokens: int, stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
-        st = current_stream_ptr(dst.device) if stream is None else stream
-        check(lib().lmc_decode_chunks(self.handle, blobs_ptr, blob_stride, nchunks, ctypes.byref(dst.struct),
-                                      dst_tok0, chunk_tokens, status_ptr, st), "lmc_decode_chunks")
+        self._call("lmc_decode_chunks", dst.device, stream, blobs_ptr, blob_stride, nchunks, ctypes.byref(dst.struct),
+                   dst_tok0, chunk_tokens, status_ptr)
 
     def decode_chunks_layers(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                              chunk_tokens: int, layer_begin: int, layer_count: int, stream: Optional[int] = None,
                              status_ptr: Optional[int] = None) -> None:
         """Decode layers [layer_begin, +layer_count) of blobs addressed through a device pointer table."""
-        st = current_stream_ptr(dst.device) if stream is None else stream
-        check(lib().lmc_decode_chunks_layers(self.handle, blob_ptrs, max_blob_bytes, nchunks, ctypes.byref(dst.struct),
-                                             dst_tok0, chunk_tokens, layer_begin, layer_count, status_ptr, st),
-              "lmc_decode_chunks_layers")
+        self._call("lmc_decode_chunks_layers", dst.device, stream, blob_ptrs, max_blob_bytes, nchunks,
+                   ctypes.byref(dst.struct), dst_tok0, chunk_tokens, layer_begin, layer_count, status_ptr)
 
     def decode_chunks_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                                chunk_tokens: int, layer_ends, events, stream: Optional[int] = None,
@@ -657,7 +651,6 @@ class Context:
         """lmc_decode_chunks_schedule: one launch per range of layers [layer_ends[i - 1], layer_ends[i]) and one event
         record behind each (events: NativeEvent objects), in ONE call.  layer_ends / events may be prebuilt ctypes arrays
         (a cached retrieval plan passes the same ones every time)."""
-        st = current_stream_ptr(dst.device) if stream is None else stream
         if isinstance(layer_ends, ctypes.Array):
             ends, n = layer_ends, len(layer_ends)
         else:
@@ -667,37 +660,31 @@ class Context:
             evs = events
         else:
             evs = (ctypes.c_void_p * n)(*[e.handle for e in events])
-        check(lib().lmc_decode_chunks_schedule(self.handle, blob_ptrs, max_blob_bytes, nchunks, ctypes.byref(dst.struct),
-                                               dst_tok0, chunk_tokens, n, ends, evs, status_ptr, st),
-              "lmc_decode_chunks_schedule")
+        self._call("lmc_decode_chunks_schedule", dst.device, stream, blob_ptrs, max_blob_bytes, nchunks,
+                   ctypes.byref(dst.struct), dst_tok0, chunk_tokens, n, ends, evs, status_ptr)
 
     def store_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, host_arena_ptr: int,
                      host_cap: int, offsets_ptr: int, sizes_ptr: int, stream: Optional[int] = None,
                      status_ptr: Optional[int] = None) -> int:
         """lmc_store_chunks: encode + exact-size copies into a pinned arena, no host wait.  offsets_ptr / sizes_ptr:
         pinned uint64 [n + 1] / uint32 [n], valid once `stream` has completed."""
-        b = self._bins(bins)
-        st = current_stream_ptr(src.device) if stream is None else stream
-        check(lib().lmc_store_chunks(self.handle, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens, b,
-                                     host_arena_ptr, host_cap, offsets_ptr, sizes_ptr, status_ptr, st), "lmc_store_chunks")
-        return (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
+        self._call("lmc_store_chunks", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
+                   self._bins(bins), host_arena_ptr, host_cap, offsets_ptr, sizes_ptr, status_ptr)
+        return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
     def load_chunks(self, host_ptrs_ptr: int, sizes_ptr: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                     chunk_tokens: int, layers_per_range: int = 0, range_events_ptr: Optional[int] = None,
                     stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
         """lmc_load_chunks: blobs in pinned host memory -> decoded KV, gathered and decoded layer range by layer range."""
-        st = current_stream_ptr(dst.device) if stream is None else stream
-        check(lib().lmc_load_chunks(self.handle, host_ptrs_ptr, sizes_ptr, nchunks, ctypes.byref(dst.struct), dst_tok0,
-                                    chunk_tokens, layers_per_range, range_events_ptr, status_ptr, st), "lmc_load_chunks")
+        self._call("lmc_load_chunks", dst.device, stream, host_ptrs_ptr, sizes_ptr, nchunks, ctypes.byref(dst.struct),
+                   dst_tok0, chunk_tokens, layers_per_range, range_events_ptr, status_ptr)
 
     def store_pack(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, pack_ptr: int, pack_cap: int,
                    sizes_ptr: int, stream: Optional[int] = None, status_ptr: Optional[int] = None) -> int:
         """lmc_store_pack: encode + the job's blobs transposed plane-major into one region, no host wait."""
-        b = self._bins(bins)
-        st = current_stream_ptr(src.device) if stream is None else stream
-        check(lib().lmc_store_pack(self.handle, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens, b, pack_ptr, pack_cap,
-                                   sizes_ptr, status_ptr, st), "lmc_store_pack")
-        return (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
+        self._call("lmc_store_pack", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
+                   self._bins(bins), pack_ptr, pack_cap, sizes_ptr, status_ptr)
+        return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
     def store_pack_parts(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, pack_ptr: int,
                          pack_cap: int, sizes_ptr: int, nparts: int, part_info_ptr: int, part_events,
@@ -705,36 +692,29 @@ class Context:
         """lmc_store_pack_parts: the encode in `nparts` plane ranges, each packed into the DEVICE region at pack_ptr as soon
         as it is coded; part_info_ptr: pinned uint64 [2 nparts] ({offset in the streams region, bytes} per part);
         part_events: NativeEvent per part (recorded behind the part's pack kernels)."""
-        b = self._bins(bins)
-        st = current_stream_ptr(src.device) if stream is None else stream
         evs = None if part_events is None else (ctypes.c_void_p * nparts)(*[e.handle for e in part_events])
-        check(lib().lmc_store_pack_parts(self.handle, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens, b, pack_ptr,
-                                         pack_cap, sizes_ptr, nparts, part_info_ptr, evs, status_ptr, st),
-              "lmc_store_pack_parts")
-        return (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
+        self._call("lmc_store_pack_parts", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
+                   self._bins(bins), pack_ptr, pack_cap, sizes_ptr, nparts, part_info_ptr, evs, status_ptr)
+        return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
     def load_pack(self, pack_ptr: int, pack_bytes: int, chunk_begin: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                   layers_per_range: int = 0, range_events_ptr: Optional[int] = None, stream: Optional[int] = None,
                   status_ptr: Optional[int] = None) -> None:
         """lmc_load_pack: chunks [chunk_begin, chunk_begin + nchunks) (nchunks 0 = all that follow) of a pack in pinned
         host memory -> decoded KV, one transfer and one decode per range of layers."""
-        st = current_stream_ptr(dst.device) if stream is None else stream
-        check(lib().lmc_load_pack(self.handle, pack_ptr, pack_bytes, chunk_begin, nchunks, ctypes.byref(dst.struct), dst_tok0,
-                                  layers_per_range, range_events_ptr, status_ptr, st), "lmc_load_pack")
+        self._call("lmc_load_pack", dst.device, stream, pack_ptr, pack_bytes, chunk_begin, nchunks, ctypes.byref(dst.struct),
+                   dst_tok0, layers_per_range, range_events_ptr, status_ptr)
 
     def decode_symbols(self, blob: torch.Tensor, L: int, H: int, D: int, T: int, stream: Optional[int] = None
                        ) -> torch.Tensor:
         sym = torch.empty((2 * L, T, H * D), dtype=torch.int8, device=blob.device)
-        st = current_stream_ptr(blob.device) if stream is None else stream
-        check(lib().lmc_decode_symbols(self.handle, blob.data_ptr(), L, H, D, sym.data_ptr(), st),
-              "lmc_decode_symbols")
+        self._call("lmc_decode_symbols", blob.device, stream, blob.data_ptr(), L, H, D, sym.data_ptr())
         return sym
 
     def copy_kv(self, src: KVLayout, tok_begin: int, ntok: int, dst: KVLayout, dst_tok0: int,
                 stream: Optional[int] = None) -> None:
-        st = current_stream_ptr(src.device) if stream is None else stream
-        check(lib().lmc_copy_kv(self.handle, ctypes.byref(src.struct), tok_begin, ntok, ctypes.byref(dst.struct),
-                                dst_tok0, st), "lmc_copy_kv")
+        self._call("lmc_copy_kv", src.device, stream, ctypes.byref(src.struct), tok_begin, ntok, ctypes.byref(dst.struct),
+                   dst_tok0)
 
 
 def describe_status(st: int) -> str:
@@ -778,9 +758,18 @@ class StatusWords:
             buf, words = self._blocks[i // self.BLOCK]
             # (a job collected together with its pool -- the codec of a finished process or test module -- may be
             # finalised after the pool's pinned block has been freed: there is no word to read any more)
-            v = int(words[i % self.BLOCK]) & 0xffffffff if buf.ptr else 0
+            if not buf.ptr:
+                return 0
             self._free.append(i)
-        return v
+            return int(words[i % self.BLOCK]) & 0xffffffff
+
+    def close(self) -> None:
+        """Free the pinned blocks (the work of every job must have completed).  A word that is still out reads 0 from
+        then on, and a pool that is used again starts on a fresh block."""
+        with self._lock:
+            for buf, _ in self._blocks:
+                buf.free()
+            self._free = []
 
 
 def memcpy_async(dst_ptr: int, src_ptr: int, nbytes: int, kind: str, stream: int) -> None:

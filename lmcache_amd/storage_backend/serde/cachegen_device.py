@@ -11,6 +11,7 @@ with pinned `hipMemcpyAsync` on a side stream ordered by events (no device-wide
 synchronisation: the reference itself flags torch.cuda.synchronize() as harmful
 here, local_backend.py:83-85).
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -105,25 +106,95 @@ class HostBlob:
         return ctypes.string_at(self.ptr, self.nbytes)
 
 
-@dataclass
-class EncodeJob:
-    nchunks: int
-    stride: int
-    arena: torch.Tensor        # device uint8, blob i at i*stride
-    sizes: Optional[native.PinnedBuffer]  # this job's own uint32 [nchunks], written by the GPU; back in the pool once read
-    done: torch.cuda.Event     # recorded after the last encode kernel
-    geometry: tuple            # (L, H, D, chunk_tokens)
-    status_idx: int = -1       # this job's status word (native.StatusWords); -1 once read
-    size_list: Optional[List[int]] = None  # filled by sizes_of / offload
-    # a long job is launched as a few consecutive ranges of chunks, each with its own event, so that the
-    # host-DRAM offload of range r can start while range r+1 is still being encoded: (chunk0, chunk1, event)
-    parts: Optional[list] = None
-    offload_issued: bool = False  # its device -> host copies are on the copy streams (the arena may be reused after them)
-    pool: Optional[native.StatusWords] = None  # where status_idx goes back to if nobody reads it (see __del__)
+class PinnedWords:
+    """Pool of small pinned buffers the jobs in flight borrow (size words, pointer / size arrays, part words): hipHostMalloc
+    stalls the device, so a buffer is allocated once and lent again and again."""
 
-    def __del__(self):  # a job dropped unread (an exception between launch and completion): its status word returns
-        if _return_status_word is not None:  # (module globals are gone at interpreter shutdown)
-            _return_status_word(self)
+    def __init__(self):
+        self._bufs: List[native.PinnedBuffer] = []
+
+    def __len__(self) -> int:
+        return len(self._bufs)
+
+    def take(self, min_bytes: int, alloc_bytes: int) -> native.PinnedBuffer:
+        """The first buffer of at least min_bytes, else a new one of alloc_bytes."""
+        for k, b in enumerate(self._bufs):
+            if b.nbytes >= min_bytes:
+                return self._bufs.pop(k)
+        return native.PinnedBuffer(alloc_bytes)
+
+    def give(self, buf: native.PinnedBuffer) -> None:
+        self._bufs.append(buf)
+
+    def close(self) -> None:
+        for b in self._bufs:
+            b.free()
+        self._bufs = []
+
+
+def _borrow(loans: list, words: PinnedWords, min_bytes: int, alloc_bytes: int) -> native.PinnedBuffer:
+    """A buffer of `words`, entered in the launch's `loans` (whoever holds the list gives it back)."""
+    buf = words.take(min_bytes, alloc_bytes)
+    loans.append((buf, words))
+    return buf
+
+
+def _raise_on(st: int, what: str) -> None:
+    if st:
+        raise native.NativeError(f"{what}: " + native.describe_status(st))
+
+
+class Job:
+    """What every job in flight owns: the event behind its last kernel, its own status word, and its loans -- pinned
+    buffers its kernels read or write, each with the PinnedWords it goes back to."""
+
+    def __init__(self, done, status_idx: int, pool: native.StatusWords, loans=()):
+        self.done = done                # recorded after the job's last kernel
+        self.status_idx = status_idx    # this job's status word (native.StatusWords); -1 once read
+        self.pool = pool                # where status_idx goes back to
+        self._loans = list(loans)       # [(PinnedBuffer, PinnedWords)]
+
+    def retire(self) -> int:
+        """`done` has fired: the status word is read and returned, every loan goes back to its pool -> the status
+        (0 for a job that has been retired before)."""
+        st = 0
+        if self.status_idx >= 0:
+            st, self.status_idx = self.pool.read_release(self.status_idx), -1
+        for buf, words in self._loans:
+            words.give(buf)
+        self._loans = []
+        return st
+
+    def __del__(self):  # a job dropped unread (an exception between launch and completion): its words return once its
+        if getattr(self, "status_idx", -1) < 0:  # kernels can no longer write them
+            return
+        try:
+            self.done.synchronize()
+        except Exception:
+            pass
+        try:
+            self.retire()
+        except Exception:
+            pass
+
+
+class EncodeJob(Job):
+    def __init__(self, nchunks: int, stride: int, arena: torch.Tensor, sizes: native.PinnedBuffer, geometry: tuple,
+                 parts: list, **base):
+        super().__init__(parts[-1][2], **base)
+        self.nchunks, self.stride = nchunks, stride
+        self.arena = arena          # device uint8, blob i at i*stride
+        self.sizes = sizes          # this job's own uint32 [nchunks], written by the GPU; back in the pool once read
+        self.geometry = geometry    # (L, H, D, chunk_tokens)
+        self.size_list: Optional[List[int]] = None  # filled by sizes_of / offload
+        # a long job is launched as a few consecutive ranges of chunks, each with its own event, so that the
+        # host-DRAM offload of range r can start while range r+1 is still being encoded: (chunk0, chunk1, event)
+        self.parts = parts
+        self.offload_issued = False  # its device -> host copies are on the copy streams (the arena may be reused after them)
+
+    def retire(self) -> int:
+        self.sizes = None
+        return super().retire()
 
 
 @dataclass
@@ -138,28 +209,24 @@ class HostPack:
         return native.pack_extract(self.blob.ptr, self.blob.nbytes, chunk)
 
 
-@dataclass
-class PackJob:
+class PackJob(Job):
     """One store_pack() in flight."""
-    region: HostBlob           # where the GPU writes the pack (allocated at an upper bound)
-    nchunks: int
-    chunk_tokens: int
-    sizes: Optional[native.PinnedBuffer]
-    done: torch.cuda.Event
-    status_idx: int = -1
-    pool: Optional[native.StatusWords] = None
-    dev: Optional[torch.Tensor] = None   # dma=True: the HBM region the pack is written to first
-    d2h_issued: bool = True              # ... and whether its copies to pinned memory have been queued
-    # dma=True: the encode went out in plane ranges (lmc_store_pack_parts); part r's bytes may leave once part_events[r]
-    # has fired: part_info (pinned uint64 [2 nparts]) says where they lie
-    part_events: Optional[list] = None
-    part_info: Optional[native.PinnedBuffer] = None
-    cap: int = 0
-    geometry: tuple = ()                 # (L, H, D)
 
-    def __del__(self):
-        if _return_status_word is not None:
-            _return_status_word(self)
+    def __init__(self, nchunks: int, chunk_tokens: int, geometry: tuple, dev: torch.Tensor, cap: int,
+                 sizes: native.PinnedBuffer, part_info: native.PinnedBuffer, part_events: list, **base):
+        super().__init__(**base)
+        self.nchunks, self.chunk_tokens = nchunks, chunk_tokens
+        self.geometry = geometry    # (L, H, D)
+        self.dev, self.cap = dev, cap   # the HBM region the pack is written to first (allocated at an upper bound)
+        self.d2h_issued = False     # ... and whether its copies to pinned memory have been queued
+        self.sizes = sizes
+        # the encode went out in plane ranges (lmc_store_pack_parts); part r's bytes may leave once part_events[r]
+        # has fired: part_info (pinned uint64 [2 nparts]) says where they lie
+        self.part_events, self.part_info = part_events, part_info
+
+    def retire(self) -> int:
+        self.sizes = self.part_info = None
+        return super().retire()
 
 
 def pack_cap(n: int, L: int, T: int, H: int, D: int, bins: Sequence[int]) -> int:
@@ -194,35 +261,23 @@ def layer_ranges(L: int, layers_per_launch) -> list:
     return out
 
 
-@dataclass
-class DecodeJob:
+def range_step(L: int, layers_per_range) -> int:
+    """Layers per range of the loads that take ONE range size (lmc_load_chunks, lmc_load_pack): None / 0 is a single
+    range of all L layers, an int is held to 1..L, and of a schedule of sizes the first entry is used."""
+    if layers_per_range and not isinstance(layers_per_range, int):
+        layers_per_range = list(layers_per_range)[0]
+    return max(1, min(L, int(layers_per_range or L)))
+
+
+class DecodeJob(Job):
     """One decode() call in flight: `done` fires after its last kernel, `status_idx` is its own status word.
     layer_events (decode_device with layers_per_launch): (first layer after the range, event) per launch, in layer
     order -- the KV of layers below `first layer after` is complete once the event has fired."""
-    done: torch.cuda.Event
-    status_idx: int
-    layer_events: Optional[list] = None
-    pool: Optional[native.StatusWords] = None
 
-    def __del__(self):  # a DecodeJob / LayerwiseRetrieval nobody finished
-        if _return_status_word is not None:
-            _return_status_word(self)
-
-
-def _return_status_word(job) -> None:
-    """Give an unread status word back to its pool once the job's kernels can no longer write it."""
-    idx, pool = getattr(job, "status_idx", -1), getattr(job, "pool", None)
-    if pool is None or idx is None or idx < 0:
-        return
-    try:
-        job.done.synchronize()
-    except Exception:
-        pass
-    try:
-        pool.read_release(idx)
-    except Exception:
-        pass
-    job.status_idx = -1
+    def __init__(self, done, layer_events: Optional[list] = None, table: Optional[torch.Tensor] = None, **base):
+        super().__init__(done, **base)
+        self.layer_events = layer_events
+        self._table = table  # decode_device: the address table the kernels read, alive as long as the job
 
 
 class DeviceArena:
@@ -266,8 +321,9 @@ class CacheGenDeviceCodec:
         self._lock = threading.RLock()
         self._enc_arena: Optional[torch.Tensor] = None
         self._dec_arena: Optional[torch.Tensor] = None
-        self._size_pool: List[native.PinnedBuffer] = []      # pinned size words, one buffer per job in flight
-        self._meta_pool: List[native.PinnedBuffer] = []      # pinned pointer / size arrays of decode_host_layerwise jobs
+        self._size_pool = PinnedWords()                      # pinned size words, one buffer per job in flight
+        self._meta_pool = PinnedWords()                      # pinned pointer / size arrays of decode_host_layerwise jobs
+        self._part_info_pool = PinnedWords()                 # pinned part words of store_pack jobs
         self._status = native.StatusWords()                  # one status word per job in flight
         self._arena_free: Optional[torch.cuda.Event] = None  # D2H of the last job that used the shared arena done
         self._dec_free: Optional[torch.cuda.Event] = None    # previous decode kernel done
@@ -277,11 +333,9 @@ class CacheGenDeviceCodec:
         self._pack_dev: Optional[torch.Tensor] = None        # HBM staging of a pack on its way to pinned memory (store_pack)
         self._pack_dev_free: Optional[torch.cuda.Event] = None
         self._pack_prev = None                               # weak reference to the last PackJob that took _pack_dev
-        self._hdr: Optional[native.PinnedBuffer] = None
-        # plane ranges a pack's encode is launched in (store_pack, dma): LMCACHE_AMD_PACK_PARTS=1 is the round-5 behaviour
+        # plane ranges a pack's encode is launched in (store_pack): LMCACHE_AMD_PACK_PARTS=1 is the round-5 behaviour
         # (the whole encode, then the pack, then its copies), for A/B
         self.pack_parts = max(1, min(16, int(os.environ.get("LMCACHE_AMD_PACK_PARTS", "8"))))
-        self._part_info_pool: List[native.PinnedBuffer] = []
         self._same_blobs: dict = {}                          # id(caller's list) -> (the list, its blobs' address tuple, largest blob)
         self._table_cache: dict = {}                         # blob-address tuple -> (device table, upload stream)
 
@@ -322,16 +376,10 @@ class CacheGenDeviceCodec:
                 # every job owns its size words and its status word: a second store never waits for the first
                 # one's sizes to be read (the reference's own note on this path: "synchronize is harmful",
                 # local_backend.py:83-90), and never sees its failures
-                sizes = None
-                for k, b in enumerate(self._size_pool):
-                    if b.nbytes >= 4 * n:
-                        sizes = self._size_pool.pop(k)
-                        break
-                if sizes is None:
-                    sizes = native.PinnedBuffer(4 * max(n, 256))
-                st = self._status.acquire()
                 cur = torch.cuda.current_stream(self.device)
-                try:
+                loans = []
+                with self._launch(cur, loans) as (st, st_ptr):
+                    sizes = _borrow(loans, self._size_pool, 4 * n, 4 * max(n, 256))
                     if arena is self._enc_arena and self._arena_free is not None:
                         cur.wait_event(self._arena_free)  # previous job's D2H has read the arena
                     nparts = self.encode_parts if n >= 4 * self.encode_parts else 1
@@ -341,50 +389,41 @@ class CacheGenDeviceCodec:
                         c1 = min(n, c0 + per)
                         self.ctx.encode_chunks(src, tok_begin + c0 * chunk_tokens, min(tok_end, tok_begin + c1 * chunk_tokens),
                                                chunk_tokens, bins, arena.data_ptr() + c0 * stride, stride,
-                                               sizes.ptr + 4 * c0, stream=cur.cuda_stream, status_ptr=self._status.ptr(st))
+                                               sizes.ptr + 4 * c0, stream=cur.cuda_stream, status_ptr=st_ptr)
                         ev = torch.cuda.Event()
                         ev.record(cur)
                         parts.append((c0, c1, ev))
-                    done = parts[-1][2]
-                except BaseException:
-                    self._abandon_status(st, cur)
-                    self._size_pool.append(sizes)
-                    raise
-            job = EncodeJob(n, stride, arena, sizes, done, (L, H, D, chunk_tokens), st, None, parts, pool=self._status)
+            job = EncodeJob(n, stride, arena, sizes, (L, H, D, chunk_tokens), parts, status_idx=st, pool=self._status, loans=loans)
             if arena is self._enc_arena:
                 self._shared_job = job
             return job
 
-    def _abandon_status(self, st: int, stream) -> None:
-        """A launch sequence failed half way: whatever was queued may still write the word, so it goes back to the
-        pool only after the stream has drained (an error path: the host wait does not matter)."""
+    @contextlib.contextmanager
+    def _launch(self, stream, loans=()):
+        """The guard around every launch sequence: acquires the job's status word and yields (its index, its address).
+        A sequence that fails half way may have queued kernels that still write the word and the `loans` taken so far
+        (_borrow), so they go back to their pools only after the stream has drained (an error path: the host wait does
+        not matter)."""
+        st = self._status.acquire()
         try:
-            stream.synchronize()
-        except Exception:
-            pass
-        self._status.read_release(st)
-
-    def _check_job(self, job: EncodeJob) -> None:
-        """The job's kernels have completed: read its status word (once) and raise on a device error."""
-        if job.status_idx >= 0:
-            st = self._status.read_release(job.status_idx)
-            job.status_idx = -1
-            if st:
-                raise native.NativeError("CacheGen encode: " + native.describe_status(st))
-
-    def _release_sizes(self, job: EncodeJob) -> None:
-        if job.sizes is not None:
-            self._size_pool.append(job.sizes)
-            job.sizes = None
+            yield st, self._status.ptr(st)
+        except BaseException:
+            try:
+                stream.synchronize()
+            except Exception:
+                pass
+            self._status.read_release(st)
+            for buf, words in loans:
+                words.give(buf)
+            raise
 
     def sizes_of(self, job: EncodeJob) -> List[int]:
         """Wait for THIS job only (event, not device) and read the blob sizes the GPU wrote to pinned memory."""
         with self._lock:
             if job.size_list is None:
                 job.done.synchronize()
-                job.size_list = job.sizes.tensor[:4 * job.nchunks].view(torch.int32).tolist()
-                self._release_sizes(job)
-                self._check_job(job)
+                job.size_list = job.sizes.tensor[:4 * job.nchunks].view(torch.int32).tolist()  # before the words go back
+                _raise_on(job.retire(), "CacheGen encode")
             return job.size_list
 
     def offload(self, job: EncodeJob, sizes: Optional[Sequence[int]], arena: PinnedArena) -> (List[HostBlob], torch.cuda.Event):
@@ -414,18 +453,23 @@ class CacheGenDeviceCodec:
                     blobs.append(hb)
             if progressive:
                 job.size_list = list(sizes)
-                self._release_sizes(job)
-                self._check_job(job)  # every range's event has fired
-            if len(streams) > 1:  # fold the second queue into the first: one event covers both
-                ev2 = torch.cuda.Event()
-                ev2.record(self.copy_stream2)
-                self.copy_stream.wait_event(ev2)
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
+                _raise_on(job.retire(), "CacheGen encode")  # every range's event has fired
+            ev = self._join_copy_streams(both=len(streams) > 1)
             job.offload_issued = True
             if job.arena is self._enc_arena:
                 self._arena_free = ev
         return blobs, ev
+
+    def _join_copy_streams(self, both: bool = True) -> torch.cuda.Event:
+        """-> an event behind what has been queued on the copy streams: the second queue is folded into the first (if it
+        was used at all), so one event covers both."""
+        if both:
+            ev2 = torch.cuda.Event()
+            ev2.record(self.copy_stream2)
+            self.copy_stream.wait_event(ev2)
+        ev = torch.cuda.Event()
+        ev.record(self.copy_stream)
+        return ev
 
     def keep_on_device(self, job: EncodeJob, arena: DeviceArena) -> List[torch.Tensor]:
         """The job's blobs copied (exact sizes, device to device, on the current stream) into a persistent HBM arena
@@ -498,21 +542,22 @@ class CacheGenDeviceCodec:
                 if up is not cur:  # uploaded on another stream: order this one behind that copy (once)
                     cur.wait_stream(up)
                     self._table_cache[ptrs] = (table, cur)
-            st = self._status.acquire()
-            try:
+            with self._launch(cur) as (st, st_ptr):
                 # ONE C-ABI call issues every range's launch and records its event (lmc_decode_chunks_schedule): the
                 # ranges used to be one ctypes call + one torch event each
                 ends = [l1 for _, l1 in ranges]
                 evs = [native.NativeEvent() for _ in ranges]
                 self.ctx.decode_chunks_schedule(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
-                                                stream=cur.cuda_stream, status_ptr=self._status.ptr(st))
+                                                stream=cur.cuda_stream, status_ptr=st_ptr)
                 events = list(zip(ends, evs))
-            except BaseException:
-                self._abandon_status(st, cur)
-                raise
-            job = DecodeJob(events[-1][1], st, events if layers_per_launch else None, pool=self._status)
-            job._table = table  # the kernels read it: alive as long as the job
-            return job
+            return DecodeJob(evs[-1], events if layers_per_launch else None, table, status_idx=st, pool=self._status)
+
+    @staticmethod
+    def _range_events(L: int, step: int):
+        """An event per range of `step` layers for the loads that record them in ONE C-ABI call
+        -> ([(first layer after the range, event)], the ctypes array of their handles)."""
+        events = [(l1, native.NativeEvent()) for _, l1 in layer_ranges(L, step)]
+        return events, (ctypes.c_void_p * len(events))(*[ev.handle for _, ev in events])
 
     def decode_host_layerwise(self, host_blobs: Sequence["HostBlob"], dst: native.KVLayout, dst_tok0: int,
                               chunk_tokens: int, layers_per_range) -> Optional[DecodeJob]:
@@ -520,122 +565,72 @@ class CacheGenDeviceCodec:
         kernel pulls the bytes of a range of layers over PCIe while the previous range is decoded, an event per
         range (DecodeJob.layer_events) lets the model start on layer 0 after 1/L of the transfer -- where decode()
         moves whole chunks first (the first layer is complete when the last chunk has landed).
-        layers_per_range: an int (a schedule is not supported by the single call: its first entry is used)."""
+        layers_per_range: see range_step (a schedule is not supported by the single call: its first entry is used)."""
         n = len(host_blobs)
         if n == 0:
             return None
-        step = layers_per_range if isinstance(layers_per_range, int) else int(list(layers_per_range)[0])
-        step = max(1, min(dst.L, int(step or dst.L)))
-        ranges = layer_ranges(dst.L, step)
+        step = range_step(dst.L, layers_per_range)
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
-            meta = None
-            for k, b in enumerate(self._meta_pool):
-                if b.nbytes >= 12 * n:
-                    meta = self._meta_pool.pop(k)
-                    break
-            if meta is None:
-                meta = native.PinnedBuffer(12 * max(n, 256))
-            meta.tensor[:8 * n].view(torch.int64).copy_(torch.tensor([hb.ptr for hb in host_blobs], dtype=torch.int64))
-            meta.tensor[8 * n:12 * n].view(torch.int32).copy_(torch.tensor([hb.nbytes for hb in host_blobs], dtype=torch.int32))
-            events = [native.NativeEvent() for _ in ranges]
-            handles = (ctypes.c_void_p * len(events))(*[e.handle for e in events])
-            st = self._status.acquire()
-            try:
+            loans = []
+            with self._launch(cur, loans) as (st, st_ptr):
+                # (the kernels read the arrays: back in the pool at finish)
+                meta = _borrow(loans, self._meta_pool, 12 * n, 12 * max(n, 256))
+                meta.tensor[:8 * n].view(torch.int64).copy_(torch.tensor([hb.ptr for hb in host_blobs], dtype=torch.int64))
+                meta.tensor[8 * n:12 * n].view(torch.int32).copy_(torch.tensor([hb.nbytes for hb in host_blobs], dtype=torch.int32))
+                events, handles = self._range_events(dst.L, step)
                 self.ctx.load_chunks(meta.ptr, meta.ptr + 8 * n, n, dst, dst_tok0, chunk_tokens, step,
-                                     ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream,
-                                     status_ptr=self._status.ptr(st))
-            except BaseException:
-                self._abandon_status(st, cur)
-                self._meta_pool.append(meta)
-                raise
-            job = DecodeJob(events[-1], st, [(l1, ev) for (_, l1), ev in zip(ranges, events)], pool=self._status)
-            job._meta, job._meta_pool = meta, self._meta_pool  # the kernels read the arrays: back in the pool at finish
-            return job
+                                     ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream, status_ptr=st_ptr)
+            return DecodeJob(events[-1][1], events, status_idx=st, pool=self._status, loans=loans)
 
     # ---- packs: the plane-major pinned tier ---------------------------------------------------------------
     def store_pack(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins: Sequence[int],
-                   arena: PinnedArena, dma: bool = True) -> PackJob:
-        """lmc_store_pack on the CURRENT stream: encode every chunk of [tok_begin, tok_end), then a copy kernel writes
+                   arena: PinnedArena) -> PackJob:
+        """lmc_store_pack_parts on the CURRENT stream: encode every chunk of [tok_begin, tok_end), then a copy kernel writes
         the blobs transposed (static sections, then streams ordered layer / K,V / chunk) into one region.  No host
-        wait here; finish_pack() returns the pack in pinned host DRAM.
-        dma=True (default): the region is in HBM and finish_pack() moves the finished pack with two DMA copies of its
-        exact size -- the copy kernel then runs at HBM speed (0.3 ms) and the PCIe leg disturbs nobody.
-        dma=False: the region IS the pinned arena and the copy kernel's stores cross PCIe themselves: one call, no host
-        wait at all, but kernels that run beside 11 ms of shader stores to host memory were measured 4.3x slower
-        (bench.py store_hidden), so this is for callers with an otherwise idle GPU."""
+        wait here; finish_pack() returns the pack in pinned host DRAM (`arena` is taken there, not here).
+        The region is in HBM and finish_pack() moves the pack with copies of its exact size -- the copy kernel then runs
+        at HBM speed (0.3 ms) and the PCIe leg disturbs nobody (a copy kernel whose own stores crossed PCIe made the
+        kernels beside its 11 ms 4.3x slower: bench.py store_hidden)."""
         src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end)
         L, H, D = src.L, src.H, src.D
         n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
         with self._lock, torch.cuda.device(self.device):
             cap = pack_cap(n, L, chunk_tokens, H, D, bins)
             cur = torch.cuda.current_stream(self.device)
-            region = dev = None
-            if dma:
-                # (a weak reference: a job dropped unfinished -- an exception between store_pack and finish_pack -- has
-                # waited for its kernels in __del__ and queued no copy, so the region is free again; a strong one would keep
-                # such a job, and with it every later store on regions of their own, for the life of the codec)
-                prev = self._pack_prev() if self._pack_prev is not None else None
-                if prev is None or prev.d2h_issued:
-                    if self._pack_dev is None or self._pack_dev.numel() < cap:
-                        self._pack_dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
-                    dev = self._pack_dev
-                    if self._pack_dev_free is not None:
-                        cur.wait_event(self._pack_dev_free)  # the previous pack has left the buffer
-                else:
-                    dev = torch.empty(cap, dtype=torch.uint8, device=self.device)  # the previous store has not been finished yet
+            # (a weak reference: a job dropped unfinished -- an exception between store_pack and finish_pack -- has
+            # waited for its kernels in __del__ and queued no copy, so the region is free again; a strong one would keep
+            # such a job, and with it every later store on regions of their own, for the life of the codec)
+            prev = self._pack_prev() if self._pack_prev is not None else None
+            if prev is None or prev.d2h_issued:
+                if self._pack_dev is None or self._pack_dev.numel() < cap:
+                    self._pack_dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
+                dev = self._pack_dev
+                if self._pack_dev_free is not None:
+                    cur.wait_event(self._pack_dev_free)  # the previous pack has left the buffer
             else:
-                region = arena.alloc(cap, slab_hint=min(4 * cap, 4 << 30))
-            sizes = None
-            for k, b in enumerate(self._size_pool):
-                if b.nbytes >= 4 * n:
-                    sizes = self._size_pool.pop(k)
-                    break
-            if sizes is None:
-                sizes = native.PinnedBuffer(4 * max(n, 256))
-            st = self._status.acquire()
-            part_events = part_info = None
-            try:
-                if dma:
-                    # the encode in plane ranges, each packed as soon as it is coded (lmc_store_pack_parts): finish_pack
-                    # sends a range over PCIe while the later planes are still being encoded
-                    nparts = self.pack_parts if n * 2 * L >= 16 * self.pack_parts else 1
-                    part_events = [native.NativeEvent() for _ in range(nparts)]
-                    part_info = self._part_info_pool.pop() if self._part_info_pool else native.PinnedBuffer(16 * 16)
-                    self.ctx.store_pack_parts(src, tok_begin, tok_end, chunk_tokens, bins, dev.data_ptr(), cap, sizes.ptr,
-                                              nparts, part_info.ptr, part_events, stream=cur.cuda_stream,
-                                              status_ptr=self._status.ptr(st))
-                else:
-                    self.ctx.store_pack(src, tok_begin, tok_end, chunk_tokens, bins, region.ptr, cap,
-                                        sizes.ptr, stream=cur.cuda_stream, status_ptr=self._status.ptr(st))
+                dev = torch.empty(cap, dtype=torch.uint8, device=self.device)  # the previous store has not been finished yet
+            loans = []
+            with self._launch(cur, loans) as (st, st_ptr):
+                sizes = _borrow(loans, self._size_pool, 4 * n, 4 * max(n, 256))
+                # the encode in plane ranges, each packed as soon as it is coded (lmc_store_pack_parts): finish_pack
+                # sends a range over PCIe while the later planes are still being encoded
+                nparts = self.pack_parts if n * 2 * L >= 16 * self.pack_parts else 1
+                part_events = [native.NativeEvent() for _ in range(nparts)]
+                part_info = _borrow(loans, self._part_info_pool, 16 * 16, 16 * 16)
+                self.ctx.store_pack_parts(src, tok_begin, tok_end, chunk_tokens, bins, dev.data_ptr(), cap, sizes.ptr,
+                                          nparts, part_info.ptr, part_events, stream=cur.cuda_stream, status_ptr=st_ptr)
                 done = torch.cuda.Event()
                 done.record(cur)
-            except BaseException:
-                self._abandon_status(st, cur)
-                self._size_pool.append(sizes)
-                if part_info is not None:
-                    self._part_info_pool.append(part_info)
-                raise
-            job = PackJob(region, n, chunk_tokens, sizes, done, st, pool=self._status)
-            job.dev, job.d2h_issued = dev, not dma
-            job.geometry = (L, H, D)
-            job.part_events, job.part_info, job.cap = part_events, part_info, cap
-            if dma and dev is self._pack_dev:
+            job = PackJob(n, chunk_tokens, (L, H, D), dev, cap, sizes, part_info, part_events,
+                          done=done, status_idx=st, pool=self._status, loans=loans)
+            if dev is self._pack_dev:
                 self._pack_prev = weakref.ref(job)
             return job
 
     def finish_pack(self, job: PackJob, arena: PinnedArena) -> HostPack:
-        """Wait for THIS store (its event), raise NativeError if a kernel flagged it, return the pack in pinned host DRAM
-        (dma=True: its size is read from the header the GPU wrote, the pinned region is allocated at that size and two
-        DMA queues move one half each)."""
-        if job.dev is None:
-            job.done.synchronize()
-            st = self._release_pack_words(job)
-            if st:
-                raise native.NativeError("CacheGen store (pack): " + native.describe_status(st))
-            h = native.pack_info(job.region.ptr, job.region.nbytes)
-            return HostPack(arena.shrink(job.region, h.total_bytes), job.nchunks, job.chunk_tokens)
-        # dma: the pack is being built in HBM part by part.  Part r leaves as soon as its event has fired -- the host waits
+        """Wait for THIS store (its events), raise NativeError if a kernel flagged it, return the pack in pinned host DRAM."""
+        # The pack is being built in HBM part by part.  Part r leaves as soon as its event has fired -- the host waits
         # for that event only, reads where the part lies (two pinned words the GPU wrote) and queues ONE DMA copy, on
         # alternating copy streams (two DMA queues) -- while the later plane ranges are still being encoded; behind the
         # last part the static sections (header, offset table, static slots) follow.  The pinned region is taken at the
@@ -660,17 +655,13 @@ class CacheGenDeviceCodec:
                 native.memcpy_async(region.ptr + off_streams + off, job.dev.data_ptr() + off_streams + off, nbytes, "d2h",
                                     streams[r % 2].cuda_stream)
                 total = off_streams + off + nbytes
-            # (the last part's event has fired: every kernel of the store is done)
-            st = self._release_pack_words(job)
+            # (the last part's event has fired: every kernel of the store is done, every part's words have been read)
             with self._lock:
+                st = job.retire()
                 if st == 0 and not failed:
                     native.memcpy_async(region.ptr, job.dev.data_ptr(), off_streams, "d2h", streams[0].cuda_stream)
-                ev2 = torch.cuda.Event()
-                ev2.record(self.copy_stream2)
-                self.copy_stream.wait_event(ev2)
-                evd = torch.cuda.Event()
-                evd.record(self.copy_stream)
-                job.d2h_issued = True
+                evd = self._join_copy_streams()
+                job.d2h_issued = True  # (whatever the status: the HBM region may be reused behind evd)
                 if job.dev is self._pack_dev:
                     self._pack_dev_free = evd
             evd.synchronize()
@@ -686,41 +677,20 @@ class CacheGenDeviceCodec:
             raise
         return HostPack(arena.shrink(region, total), job.nchunks, job.chunk_tokens)
 
-    def _release_pack_words(self, job: PackJob) -> int:
-        """The store's kernels are done: its status word (returned), its size words and part words go back to their pools."""
-        with self._lock:
-            st, job.status_idx = self._status.read_release(job.status_idx), -1
-            if job.sizes is not None:
-                self._size_pool.append(job.sizes)
-                job.sizes = None
-            if job.part_info is not None:
-                self._part_info_pool.append(job.part_info)
-                job.part_info = None
-            if st:
-                job.d2h_issued = True
-        return st
-
     def load_pack(self, pack: HostPack, chunk_begin: int, nchunks: int, dst: native.KVLayout, dst_tok0: int,
                   layers_per_range) -> DecodeJob:
         """Chunks [chunk_begin, chunk_begin + nchunks) of a pack -> decoded KV through ONE C-ABI call (lmc_load_pack): the streams of a
         range of layers are one contiguous transfer, the range's decode follows it, an event per range
-        (DecodeJob.layer_events) lets the model run layer 0 while the later ranges are still crossing PCIe."""
-        step = layers_per_range if isinstance(layers_per_range, int) or not layers_per_range else int(list(layers_per_range)[0])
-        step = max(1, min(dst.L, int(step or dst.L)))
-        ranges = layer_ranges(dst.L, step)
+        (DecodeJob.layer_events) lets the model run layer 0 while the later ranges are still crossing PCIe.
+        layers_per_range: see range_step."""
+        step = range_step(dst.L, layers_per_range)
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
-            events = [native.NativeEvent() for _ in ranges]
-            handles = (ctypes.c_void_p * len(events))(*[e.handle for e in events])
-            st = self._status.acquire()
-            try:
+            with self._launch(cur) as (st, st_ptr):
+                events, handles = self._range_events(dst.L, step)
                 self.ctx.load_pack(pack.blob.ptr, pack.blob.nbytes, chunk_begin, nchunks, dst, dst_tok0, step,
-                                   ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream,
-                                   status_ptr=self._status.ptr(st))
-            except BaseException:
-                self._abandon_status(st, cur)
-                raise
-            return DecodeJob(events[-1], st, [(l1, ev) for (_, l1), ev in zip(ranges, events)], pool=self._status)
+                                   ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream, status_ptr=st_ptr)
+            return DecodeJob(events[-1][1], events, status_idx=st, pool=self._status)
 
     def _dec_slots(self, n: int, stride: int, cur) -> torch.Tensor:
         if self._dec_arena is None or self._dec_arena.numel() < n * stride:
@@ -749,8 +719,7 @@ class CacheGenDeviceCodec:
             with torch.cuda.device(self.device):
                 cur = torch.cuda.current_stream(self.device)
                 arena = self._dec_slots(n, stride, cur)
-                st = self._status.acquire()
-                try:
+                with self._launch(cur) as (st, st_ptr):
                     if self._dec_free is not None:
                         self.copy_stream.wait_event(self._dec_free)  # previous decode has read the slots
                     cs = self.copy_stream.cuda_stream
@@ -790,14 +759,11 @@ class CacheGenDeviceCodec:
                         cur.wait_event(ready)
                         self.ctx.decode_chunks(arena.data_ptr() + b0 * stride, stride, b1 - b0, dst,
                                                dst_tok0 + b0 * chunk_tokens, chunk_tokens, stream=cur.cuda_stream,
-                                               status_ptr=self._status.ptr(st))
+                                               status_ptr=st_ptr)
                         last = torch.cuda.Event()
                         last.record(cur)
                     self._dec_free = last
-                    return DecodeJob(last, st, pool=self._status)
-                except BaseException:
-                    self._abandon_status(st, cur)
-                    raise
+                return DecodeJob(last, status_idx=st, pool=self._status)
 
     def finish_decode(self, job: Optional[DecodeJob], what: str = "CacheGen decode") -> None:
         """Wait for THIS decode (its event, not the device) and raise NativeError if a kernel flagged its blobs
@@ -805,22 +771,18 @@ class CacheGenDeviceCodec:
         if job is None:
             return
         job.done.synchronize()
-        st, job.status_idx = self._status.read_release(job.status_idx), -1
-        meta = getattr(job, "_meta", None)
-        if meta is not None:
-            job._meta_pool.append(meta)
-            job._meta = None
-        if st:
-            raise native.NativeError(f"{what}: " + native.describe_status(st))
+        _raise_on(job.retire(), what)
 
     def close(self):
+        """Return every pinned buffer the codec owns (its jobs must have been finished) and drop its device memory."""
         with self._lock:
-            for b in self._size_pool + [self._stage]:
-                if b is not None:
-                    b.free()
-            self._size_pool = []
-            self._stage = None
-            self._enc_arena = self._dec_arena = None
+            for words in (self._size_pool, self._meta_pool, self._part_info_pool, self._status):
+                words.close()
+            if self._stage is not None:
+                self._stage.free()
+                self._stage = None
+            self._enc_arena = self._dec_arena = self._pack_dev = None
+            self._table_cache, self._same_blobs = {}, {}
 
 
 _codecs = {}

@@ -534,3 +534,97 @@ def test_decode_device_layer_events_cover_the_layers_below(oracle, codec):
         assert np.array_equal(_u16(got).reshape(end, 2, T, H * D), ref[:end]), f"layers below {end}"
     codec.finish_decode(job)
     assert np.array_equal(_u16(out).reshape(L, 2, T, H * D), ref)
+
+
+# ---- f. a launch that fails half way, and close() ------------------------------------------------------------------
+def _words_out(codec):
+    """What a job in flight holds of the codec's: free status words, and the buffers lying in each pool of pinned words."""
+    return len(codec._status._free), len(codec._size_pool), len(codec._meta_pool), len(codec._part_info_pool)
+
+
+def _boom(*a, **k):
+    raise RuntimeError("the launch failed half way")
+
+
+def _small_chunk(seed, L=4, H=8, D=128, n=2, cs=256):
+    g = torch.Generator().manual_seed(seed)
+    x = _make(L, n * cs, H, D, torch.bfloat16, g).reshape(L, 2, n * cs, H, D).to(DEV)
+    return x, native.KVLayout.from_chunk(x, "vllm"), _bins(L, g), n * cs, cs
+
+
+def test_a_store_pack_that_fails_half_way_gives_its_words_back(codec, arena, monkeypatch):
+    x, lay, bins, T, cs = _small_chunk(71)
+    want = codec.finish_pack(codec.store_pack(lay, 0, T, cs, bins, arena), arena).blob.tobytes()  # (and the pools are filled)
+    before = _words_out(codec)
+    with monkeypatch.context() as m:
+        m.setattr(codec.ctx, "store_pack_parts", _boom)
+        with pytest.raises(RuntimeError, match="failed half way"):
+            codec.store_pack(lay, 0, T, cs, bins, arena)
+    assert _words_out(codec) == before
+    job = codec.store_pack(lay, 0, T, cs, bins, arena)
+    assert _words_out(codec) == (before[0] - 1, before[1] - 1, before[2], before[3] - 1)
+    assert codec.finish_pack(job, arena).blob.tobytes() == want
+    assert _words_out(codec) == before
+
+
+def test_a_layerwise_load_that_fails_half_way_gives_its_words_back(codec, arena, monkeypatch):
+    x, lay, bins, T, cs = _small_chunk(72)
+    blobs, ev = codec.offload(codec.encode(lay, 0, T, cs, bins), None, arena)
+    ev.synchronize()
+
+    def load():
+        out = torch.zeros_like(x)
+        job = codec.decode_host_layerwise(blobs, native.KVLayout.from_chunk(out, "vllm"), 0, cs, 2)
+        return out, job
+
+    want, job = load()
+    codec.finish_decode(job)  # (and the pools are filled)
+    before = _words_out(codec)
+    with monkeypatch.context() as m:
+        m.setattr(codec.ctx, "load_chunks", _boom)
+        with pytest.raises(RuntimeError, match="failed half way"):
+            load()
+    assert _words_out(codec) == before
+    got, job = load()
+    assert _words_out(codec) == (before[0] - 1, before[1], before[2] - 1, before[3])
+    codec.finish_decode(job)
+    assert _words_out(codec) == before and torch.equal(got.view(torch.int16), want.view(torch.int16))
+
+
+def test_close_frees_every_pinned_buffer_of_the_codec(monkeypatch):
+    """A codec of this test's own through every path that borrows pinned memory -- size words (encode, store_pack), part
+    words (store_pack), pointer / size arrays (decode_host_layerwise), staging of pageable blobs (decode), the status
+    words' block -- then close(): every native.PinnedBuffer made on the way has been freed.  A second close() is a no-op."""
+    arena = PinnedArena(slab_bytes=64 << 20)
+    arena.reserve(1)  # the arena's slab is allocated before PinnedBuffer is wrapped: only the codec's buffers are counted
+    made = []
+
+    class Counted(native.PinnedBuffer):
+        def __init__(self, nbytes):
+            super().__init__(nbytes)
+            made.append(self)
+
+    monkeypatch.setattr(native, "PinnedBuffer", Counted)
+    c = CacheGenDeviceCodec(0)
+    try:
+        x, lay, bins, T, cs = _small_chunk(73)
+        blobs, ev = c.offload(c.encode(lay, 0, T, cs, bins), None, arena)
+        ev.synchronize()
+        pack = c.finish_pack(c.store_pack(lay, 0, T, cs, bins, arena), arena)
+        outs = [torch.zeros_like(x) for _ in range(3)]
+        dst = [native.KVLayout.from_chunk(o, "vllm") for o in outs]
+        c.finish_decode(c.decode_host_layerwise(blobs, dst[0], 0, cs, 2))
+        c.finish_decode(c.decode([hb.tobytes() for hb in blobs], dst[1], 0, cs))
+        c.finish_decode(c.load_pack(pack, 0, 0, dst[2], 0, None))
+        assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
+        assert torch.equal(outs[0].view(torch.int16), outs[2].view(torch.int16))
+        assert len(made) >= 5 and all(b.ptr for b in made)
+        assert c._stage is not None and c._pack_dev is not None
+    finally:
+        c.close()
+        arena_slabs = len(arena._slabs) + len(arena._spare)
+        arena.close()
+    assert arena_slabs == 1  # (nothing of the arena's is in `made`)
+    assert all(b.ptr == 0 for b in made), [b.nbytes for b in made if b.ptr]
+    assert c._stage is None and c._pack_dev is None and not c._table_cache and not c._same_blobs
+    c.close()

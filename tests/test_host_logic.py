@@ -301,6 +301,15 @@ def test_layer_range_schedules():
             assert r[0][0] == 0 and r[-1][1] == L and all(a[1] == b[0] for a, b in zip(r, r[1:]))
 
 
+def test_range_step_of_the_single_call_loads():
+    """layers_per_range of decode_host_layerwise / load_pack (one range size per call): None and 0 are one range of all
+    layers, an int is held to 1..L, of a schedule the first entry counts."""
+    from lmcache_amd.storage_backend.serde.cachegen_device import range_step
+    assert range_step(32, None) == 32 and range_step(32, 0) == 32 and range_step(32, ()) == 32
+    assert range_step(32, 8) == 8 and range_step(32, 32) == 32 and range_step(32, 100) == 32 and range_step(32, -3) == 1
+    assert range_step(32, (2, 6, 24)) == 2 and range_step(32, [100, 1]) == 32 and range_step(4, (0, 2)) == 4
+
+
 def test_encode_path_names_follow_the_header():
     """native.ENCODE_PATHS (what Context.set_encode_path takes) == the LMC_ENCODE_PATH_* constants of lmc_hip.h."""
     from lmcache_amd import native
