@@ -336,6 +336,8 @@ static inline uint64_t lmc_blob_bound(uint32_t L, uint32_t T, uint32_t H, uint32
  *                   of the section for the last plane)
  * Every offset is a multiple of 16.  The blob of chunk i is recovered byte for byte from its static slot and its 2 L
  * segments (lmc_pack_extract, lmc_hip.h); the pack is written by the GPU (lmc_store_pack) and read by lmc_load_pack.
+ * A pack may also be written from the blobs of EARLIER stores (lmc_pack_blobs: an HBM tier demoting a group) and turned
+ * back into them (lmc_unpack_blobs): it is a function of its blobs, whoever wrote them and when.
  * Version 3 (round 6): plane order.  Version 2 ordered the segments (layer, K/V, chunk) -- one region per range of
  * layers, but a region that is complete only when the encoder has reached the layers' V planes, i.e. at the very end;
  * in plane order the K half of a range is final after a fraction of the encode, and a store that launches its encode

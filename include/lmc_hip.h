@@ -369,6 +369,41 @@ int lmc_load_pack(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t
                   const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
                   uint32_t* job_status, lmc_stream_t stream);
 
+/*
+ * Moving encoded chunks BETWEEN the two local tiers without re-encoding them (bounded tiers: the HBM tier demotes its
+ * coldest store group to the pinned tier, a pinned group that is hit again is promoted back).
+ *
+ * lmc_pack_blobs -- the demotion leg: n already-encoded v6 blobs that lie ANYWHERE in device memory -> one v3 pack in
+ *   DEVICE memory, byte for byte the pack lmc_store_pack writes for the same chunks.  No encode, no host wait: the scan
+ *   and the copy of one "last" part, both on `stream` (the store path's kernels over a pointer table instead of
+ *   base + stride).
+ *   blob_ptrs    device array [nchunks] of blob addresses, each 16-byte aligned
+ *   blob_bytes   device-accessible uint32 [nchunks]: the room each pointer may be read for (0 = no blob there).  It
+ *                stands where the arena stride and the size words stand on the store path: the read bound, and the
+ *                test that the chunk was encoded
+ *   ntokens      tokens of all chunks together (every chunk chunk_tokens long but, possibly, the last)
+ *   A bad header, a blob shorter than its header claims, or a pack that does not fit pack_cap: LMC_STATUS_HOST_ARENA_FULL
+ *   in the job's word and a header that is not a pack's (magic 0, total_bytes 0), as lmc_store_pack fails a pack.
+ *   The caller knows every blob's size, so it knows the pack's: off_streams + the sum of the blobs' stream_bytes; it
+ *   moves the finished pack to pinned memory with DMA copies of that size (never a kernel that stores over PCIe).
+ * lmc_unpack_blobs -- the promotion leg, the inverse: chunks [chunk_begin, chunk_begin + nchunks) of a pack in pinned
+ *   host memory -> the blobs lmc_encode_chunks wrote, byte for byte, chunk chunk_begin + i at blob_ptrs_h[i] (device
+ *   memory, 16-byte aligned, blob_caps_h[i] bytes of room; both arrays are read during the call only).  The host checks
+ *   the pack first (LMC_ERR_INVALID with nothing queued, like lmc_load_pack); offset table, static slots and the wanted
+ *   segments cross PCIe as DMA copies on the context's copy streams into its load staging, and a kernel on `stream`
+ *   writes every static slot's [0, off_streams) and every segment to its place in the blob (the place of plane p comes
+ *   from the slot's own stream directory).  A blob that would outgrow its room, or a static slot whose header or
+ *   directory does not match the pack's table: LMC_STATUS_BAD_HEADER, and nothing is written for that chunk.
+ * lmc_pack_chunk_bytes -- host only: the size lmc_pack_extract would report for chunk `chunk`, without extracting
+ *   (how the caller sizes the destinations of lmc_unpack_blobs).
+ */
+int lmc_pack_blobs(lmc_ctx* ctx, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks, int32_t L,
+                   int32_t H, int32_t D, int32_t chunk_tokens, uint32_t ntokens, void* pack_d, uint64_t pack_cap,
+                   uint32_t* job_status, lmc_stream_t stream);
+int lmc_unpack_blobs(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
+                     void* const* blob_ptrs_h, const uint32_t* blob_caps_h, uint32_t* job_status, lmc_stream_t stream);
+int lmc_pack_chunk_bytes(const void* pack_h, uint64_t nbytes, int32_t chunk, uint32_t* size_out);
+
 
 int lmc_stream_create(lmc_stream_t* out);
 int lmc_stream_destroy(lmc_stream_t s);

@@ -101,7 +101,18 @@ struct PackArgs {
   u32* status;
   int p_begin, p_end, last;     // this part: planes [p_begin, p_end) of every chunk; last: p_end == 2 L
   unsigned long long* part_h;   // NULL, or two words for the caller: {offset of the part in the streams region, its bytes}
+  // PTRS instances only (lmc_pack_blobs: blobs of EARLIER stores, each where its store left it).  At the end of the struct:
+  // the store path's instances read neither, and their other arguments lie where they always did.
+  const u8* const* blob_ptrs;   // device [n]: blob i at blob_ptrs[i]
+  const u32* blob_bytes;        // [n]: the room blob i may be read for -- what `stride` bounds and `sizes_d` attests above
 };
+
+// Blob `chunk` of the job: base + stride (the arena the encode of the same call filled), or -- PTRS -- the pointer table.
+template <bool PTRS>
+__device__ __forceinline__ const u8* pack_blob(const PackArgs& a, int chunk) {
+  if constexpr (PTRS) return a.blob_ptrs[chunk];
+  else return a.blobs + (long long)chunk * a.stride;
+}
 
 // Bytes of segment idx = (plane, chunk) -- the streams of one plane of one chunk: from the beginning of the plane's
 // first stream to the beginning of the next plane's (the end of the streams section for the last plane) -- and where
@@ -112,20 +123,29 @@ struct PackArgs {
 // the stream directory alone: the caller hands them planes whose SUCCESSOR has been coded too (the end of a plane is the
 // `beg` its successor's first stream wrote), of full chunks only (lmc_api.hip splits a store only when it has no ragged
 // chunk: every blob then has the layout of a chunk_tokens-token blob).
+// PTRS (always with check): the blob comes from the pointer table and blob_bytes[chunk] is its read bound -- no header
+// word is read from a pointer that is null, off a 16-byte boundary or has less room than a header.
+template <bool PTRS>
 __device__ __forceinline__ u32 pack_seg_bytes(const PackArgs& a, int idx, u32* begin, bool check) {
   const int p = idx / a.n, chunk = idx - p * a.n;
   const int P = 2 * a.L;
-  const u8* blob = a.blobs + (long long)chunk * a.stride;
+  const u8* blob = pack_blob<PTRS>(a, chunk);
   const u32* hd = reinterpret_cast<const u32*>(blob);
   if (begin) *begin = 0u;
   BlobOff bo = lmc_blob_off((u32)P, (u32)a.hdr.chunk_tokens, (u32)a.G);
-  u32 stream_bytes = (u32)min((unsigned long long)a.stride - bo.streams, 0xfffffff0ull);
+  unsigned long long room = (unsigned long long)a.stride;
+  if constexpr (PTRS) {
+    room = (unsigned long long)a.blob_bytes[chunk];
+    if (!check || !blob || ((unsigned long long)(uintptr_t)blob & 15ull) || room < (unsigned long long)LMC_HEADER_BYTES) return 0u;
+    if (hd[4] - 1u >= a.hdr.chunk_tokens) return 0u;  // (no chunk is longer than the pack's chunks)
+  }
+  u32 stream_bytes = PTRS ? 0u : (u32)min(room - bo.streams, 0xfffffff0ull);
   if (check) {
-    if (a.sizes_d[chunk] == 0u || hd[0] != LMC_BLOB_MAGIC || (hd[1] & 0xffffu) != LMC_BLOB_VERSION || hd[8] != (u32)P ||
+    if ((!PTRS && a.sizes_d[chunk] == 0u) || hd[0] != LMC_BLOB_MAGIC || (hd[1] & 0xffffu) != LMC_BLOB_VERSION || hd[8] != (u32)P ||
         hd[9] != (u32)a.G)
       return 0u;
     bo = lmc_blob_off((u32)P, hd[4], (u32)a.G);  // the chunk's own length (a ragged last chunk is shorter)
-    if (hd[14] != bo.gdir || hd[15] != bo.streams || (unsigned long long)bo.streams + hd[16] > (unsigned long long)a.stride) return 0u;
+    if (hd[14] != bo.gdir || hd[15] != bo.streams || (unsigned long long)bo.streams + hd[16] > room) return 0u;
     stream_bytes = hd[16];
   } else if (p + 1 >= P) {
     return 0u;  // (the last plane ends with the section: the last part's)
@@ -139,6 +159,7 @@ __device__ __forceinline__ u32 pack_seg_bytes(const PackArgs& a, int idx, u32* b
 
 // One part of a pack: planes [p_begin, p_end).  table_d[N + 1] carries the running total from part to part (the host
 // zeroes it in front of the first part); table_d[N] == ~0 says "the pack has failed": later parts do nothing.
+template <bool PTRS>
 __global__ __launch_bounds__(256) void k_pack_scan(PackArgs a) {
   __shared__ unsigned long long sums[256];
   const int N = 2 * a.L * a.n;
@@ -149,7 +170,7 @@ __global__ __launch_bounds__(256) void k_pack_scan(PackArgs a) {
   unsigned long long mine = 0;
   int empty = 0;  // a segment of no bytes: its chunk's encode did not finish, or its header does not check out
   for (int i = i0; i < i1; i++) {
-    const u32 b = pack_seg_bytes(a, i, nullptr, check);
+    const u32 b = pack_seg_bytes<PTRS>(a, i, nullptr, check);
     empty |= b == 0u;
     mine += b;
   }
@@ -167,7 +188,7 @@ __global__ __launch_bounds__(256) void k_pack_scan(PackArgs a) {
   for (int i = i0; i < i1; i++) {
     a.table_d[i] = off;
     if (fits) table_h[i] = off;
-    off += pack_seg_bytes(a, i, nullptr, check);
+    off += pack_seg_bytes<PTRS>(a, i, nullptr, check);
   }
   __syncthreads();  // (every thread has read table_d[N + 1] before thread 0 moves it on)
   if (t == 0) {
@@ -193,9 +214,25 @@ __global__ __launch_bounds__(256) void k_pack_scan(PackArgs a) {
   }
 }
 
+// NT: both sides are global memory touched once (lmc_pack_blobs, lmc_unpack_blobs: HBM to HBM) -- non-temporal loads and
+// stores, as the other streamed-once kernels use; the store path's instances keep their plain accesses (their
+// destination may be mapped host memory).
+template <bool NT = false>
 __device__ __forceinline__ void pack_copy16(uint4* dst, const uint4* src, u32 n16) {
   const u32 step = 256u;
   u32 i = threadIdx.x;
+  if constexpr (NT) {
+    const LMC_GLOBAL u32x4_t* s = reinterpret_cast<const LMC_GLOBAL u32x4_t*>((const LMC_GLOBAL uint4*)src);
+    LMC_GLOBAL u32x4_t* d = reinterpret_cast<LMC_GLOBAL u32x4_t*>((LMC_GLOBAL uint4*)dst);
+    for (; i + 3u * step < n16; i += 4u * step) {
+      const u32x4_t v0 = __builtin_nontemporal_load(s + i), v1 = __builtin_nontemporal_load(s + i + step),
+                    v2 = __builtin_nontemporal_load(s + i + 2u * step), v3 = __builtin_nontemporal_load(s + i + 3u * step);
+      __builtin_nontemporal_store(v0, d + i); __builtin_nontemporal_store(v1, d + i + step);
+      __builtin_nontemporal_store(v2, d + i + 2u * step); __builtin_nontemporal_store(v3, d + i + 3u * step);
+    }
+    for (; i < n16; i += step) __builtin_nontemporal_store(__builtin_nontemporal_load(s + i), d + i);
+    return;
+  }
   for (; i + 3u * step < n16; i += 4u * step) {
     const uint4 v0 = src[i], v1 = src[i + step], v2 = src[i + 2u * step], v3 = src[i + 3u * step];
     dst[i] = v0; dst[i + step] = v1; dst[i + 2u * step] = v2; dst[i + 3u * step] = v3;
@@ -205,6 +242,7 @@ __device__ __forceinline__ void pack_copy16(uint4* dst, const uint4* src, u32 n1
 
 // grid = (workgroups), 256 threads: workgroup w takes items w, w + gridDim.x, ... of the part's segments (+ the n static
 // slots in the last part)
+template <bool PTRS>
 __global__ __launch_bounds__(256) void k_pack_copy(PackArgs a) {
   const int N = 2 * a.L * a.n;
   if (a.table_d[N] == ~0ull) return;
@@ -213,16 +251,16 @@ __global__ __launch_bounds__(256) void k_pack_copy(PackArgs a) {
   for (int item = (int)blockIdx.x; item < M + (a.last ? a.n : 0); item += (int)gridDim.x) {
     if (item < M) {
       u32 begin;
-      const u32 bytes = pack_seg_bytes(a, s0 + item, &begin, check);
+      const u32 bytes = pack_seg_bytes<PTRS>(a, s0 + item, &begin, check);
       const int chunk = (s0 + item) % a.n;
-      pack_copy16(reinterpret_cast<uint4*>(a.host + a.hdr.off_streams + a.table_d[s0 + item]),
-                  reinterpret_cast<const uint4*>(a.blobs + (long long)chunk * a.stride + begin), bytes >> 4);
+      pack_copy16<PTRS>(reinterpret_cast<uint4*>(a.host + a.hdr.off_streams + a.table_d[s0 + item]),
+                        reinterpret_cast<const uint4*>(pack_blob<PTRS>(a, chunk) + begin), bytes >> 4);
     } else {
       const int chunk = item - M;
-      const u8* blob = a.blobs + (long long)chunk * a.stride;
+      const u8* blob = pack_blob<PTRS>(a, chunk);
       const u32 bytes = min((reinterpret_cast<const u32*>(blob)[15] + 15u) & ~15u, a.hdr.static_stride);
       uint4* slot = reinterpret_cast<uint4*>(a.host + a.hdr.off_static + (unsigned long long)chunk * a.hdr.static_stride);
-      pack_copy16(slot, reinterpret_cast<const uint4*>(blob), bytes >> 4);
+      pack_copy16<PTRS>(slot, reinterpret_cast<const uint4*>(blob), bytes >> 4);
       // a ragged last chunk has shorter static sections than its slot: the rest reads zero (a pack is a function of
       // its blobs, byte for byte)
       for (u32 i = (bytes >> 4) + threadIdx.x; i < (a.hdr.static_stride >> 4); i += 256u) slot[i] = make_uint4(0, 0, 0, 0);

@@ -20,6 +20,7 @@
 #include "k_fused.h"
 #include "k_offload.h"
 #include "k_quantize.h"
+#include "k_repack.h"
 
 static thread_local int g_last_hip = 0;
 
@@ -960,9 +961,9 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = stream_follows(c, c->copy_stream, s))) return rc;
     pa.p_begin = 0; pa.p_end = P; pa.last = 1; pa.part_h = nullptr;
-    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(256), 0, c->copy_stream, pa);
+    hipLaunchKernelGGL(k_pack_scan<false>, dim3(1), dim3(256), 0, c->copy_stream, pa);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_pack_copy, dim3(64), dim3(256), 0, c->copy_stream, pa);  // PCIe-bound: 64 workgroups fill the link
+    hipLaunchKernelGGL(k_pack_copy<false>, dim3(64), dim3(256), 0, c->copy_stream, pa);  // PCIe-bound: 64 workgroups fill the link
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->store_free, c->copy_stream));
     c->store_used = true;
@@ -981,9 +982,9 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
       PackArgs q = pa;
       q.p_begin = packed; q.p_end = upto; q.last = last ? 1 : 0;
       q.part_h = (unsigned long long*)(part_info_h + 2 * parts_out);
-      hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(256), 0, s, q);
+      hipLaunchKernelGGL(k_pack_scan<false>, dim3(1), dim3(256), 0, s, q);
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_pack_copy, dim3(64), dim3(256), 0, s, q);
+      hipLaunchKernelGGL(k_pack_copy<false>, dim3(64), dim3(256), 0, s, q);
       HIP_TRY(hipGetLastError());
       packed = upto;
     }
@@ -1130,6 +1131,146 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
     if ((rc = stream_follows(c, s, cs))) return rc;
     if ((rc = decode_range_locked(da, dst, l0, nl, s, range_events ? range_events[r] : nullptr))) return rc;
   }
+  HIP_TRY(hipEventRecord(c->load_free, s));
+  c->load_used = true;
+  return LMC_OK;
+}
+
+// ---- bounded tiers: blobs of earlier stores -> a pack (demotion), a pack -> blobs (promotion) ------------------------
+int lmc_pack_blobs(lmc_ctx* c, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks, int32_t L, int32_t H,
+                   int32_t D, int32_t chunk_tokens, uint32_t ntokens, void* pack_d, uint64_t pack_cap, uint32_t* job_status,
+                   lmc_stream_t stream) {
+  if (!c || !blob_ptrs || !blob_bytes || nchunks < 1 || nchunks > 65535 || L < 1 || 2 * L > LMC_MAX_PLANES || H < 1 || D < 1 ||
+      chunk_tokens < 1 || chunk_tokens > 65535 || !pack_d || ((uintptr_t)pack_d & 15))
+    return LMC_ERR_INVALID;
+  const long long C = (long long)H * D;
+  const int P = 2 * L;
+  if (C < 8 || (C & 7) || C > LMC_MAX_CHANNELS || (long long)P * nchunks > (1ll << 22)) return LMC_ERR_INVALID;
+  // every chunk is chunk_tokens long but, possibly, the last
+  if ((uint64_t)ntokens > (uint64_t)nchunks * (uint32_t)chunk_tokens || (uint64_t)ntokens <= (uint64_t)(nchunks - 1) * (uint32_t)chunk_tokens)
+    return LMC_ERR_INVALID;
+  PackArgs pa;
+  memset(&pa, 0, sizeof pa);
+  lmc_pack_layout((uint32_t)nchunks, (uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, &pa.hdr);
+  pa.hdr.ntokens = ntokens;
+  if (pa.hdr.off_streams > pack_cap) return LMC_ERR_INVALID;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  // the offset table's device copy is the store path's (c->pack_table): taken like a store takes it, behind the copies of
+  // the previous job (no arena is needed: the blobs are read where they lie)
+  if ((rc = store_acquire(c, s, 0, 8 * ((size_t)P * nchunks + 2)))) return rc;
+  pa.blob_ptrs = (const u8* const*)blob_ptrs; pa.blob_bytes = blob_bytes;
+  pa.n = nchunks; pa.L = L; pa.G = (int)pa.hdr.ngroups;
+  pa.host = (u8*)pack_d; pa.cap = pack_cap; pa.table_d = c->pack_table;
+  pa.status = job_status ? job_status : c->status_h;
+  pa.p_begin = 0; pa.p_end = P; pa.last = 1; pa.part_h = nullptr;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->pn = 0;
+  if ((rc = prof_mark(c, s))) return rc;
+  hipLaunchKernelGGL(k_pack_scan<true>, dim3(1), dim3(256), 0, s, pa);
+  HIP_TRY(hipGetLastError());
+  // HBM to HBM: as many workgroups as there are items to walk, up to one per CU
+  const int items = (P + 1) * nchunks;
+  hipLaunchKernelGGL(k_pack_copy<true>, dim3((unsigned)std::max(1, std::min(items, c->num_cus))), dim3(256), 0, s, pa);
+  HIP_TRY(hipGetLastError());
+  if ((rc = prof_mark(c, s))) return rc;
+  HIP_TRY(hipEventRecord(c->store_free, s));  // the next job may rewrite the table behind this
+  c->store_used = true;
+  return LMC_OK;
+}
+
+int lmc_pack_chunk_bytes(const void* pack_h, uint64_t nbytes, int32_t chunk, uint32_t* size_out) {
+  lmc_pack_header h;
+  const u8* b = (const u8*)pack_h;
+  if (!pack_ok(b, nbytes, &h) || chunk < 0 || (uint32_t)chunk >= h.nchunks || !size_out) return LMC_ERR_INVALID;
+  lmc_blob_header bh;
+  memcpy(&bh, b + h.off_static + (uint64_t)chunk * h.static_stride, sizeof bh);
+  // lmc_pack_extract's checks, and its walk over the chunk's segments, without the copies
+  if (bh.magic != LMC_BLOB_MAGIC || bh.off_streams > h.static_stride || bh.off_streams < sizeof bh ||
+      bh.total_bytes != bh.off_streams + bh.stream_bytes || bh.num_layers != h.num_layers)
+    return LMC_ERR_INVALID;
+  const uint64_t* t = (const uint64_t*)(b + h.off_table);
+  uint64_t at = bh.off_streams;
+  for (uint32_t p = 0; p < 2 * h.num_layers; p++) {
+    const uint64_t i = (uint64_t)p * h.nchunks + (uint32_t)chunk;
+    at += t[i + 1] - t[i];
+    if (at > bh.total_bytes) return LMC_ERR_INVALID;
+  }
+  if (at != bh.total_bytes) return LMC_ERR_INVALID;
+  *size_out = bh.total_bytes;
+  return LMC_OK;
+}
+
+int lmc_unpack_blobs(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
+                     void* const* blob_ptrs_h, const uint32_t* blob_caps_h, uint32_t* job_status, lmc_stream_t stream) {
+  lmc_pack_header h;
+  if (!c || !blob_ptrs_h || !blob_caps_h || nchunks < 1 || chunk_begin < 0 || !pack_ok((const u8*)pack_h, pack_bytes, &h))
+    return LMC_ERR_INVALID;
+  if ((uint32_t)chunk_begin >= h.nchunks || (uint32_t)nchunks > h.nchunks - (uint32_t)chunk_begin) return LMC_ERR_INVALID;
+  {  // the kernel computes section offsets from the pack's geometry words: they must be a geometry's
+    const uint64_t C = (uint64_t)h.num_heads * h.head_size;
+    if (C < 8 || (C & 7) || C > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
+    lmc_pack_header ref;
+    lmc_pack_layout(h.nchunks, h.num_layers, h.chunk_tokens, h.num_heads, h.head_size, &ref);
+    if (h.ngroups != ref.ngroups || h.static_stride != ref.static_stride) return LMC_ERR_INVALID;
+  }
+  for (int i = 0; i < nchunks; i++)
+    if (!blob_ptrs_h[i] || ((uintptr_t)blob_ptrs_h[i] & 15)) return LMC_ERR_INVALID;
+  const int n = (int)h.nchunks, c0 = chunk_begin, m = nchunks, L = (int)h.num_layers, P = 2 * L;
+  const u8* b = (const u8*)pack_h;
+  const uint64_t* t = (const uint64_t*)(b + h.off_table);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if ((rc = legs_init(c))) return rc;
+  if (!c->copy_stream2) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking));
+  // the load staging holds the pack at its own offsets (as for lmc_load_pack), and behind it the destinations' addresses
+  // and their room
+  const size_t meta_off = (size_t)lmc_r16_64(h.total_bytes), caps_off = meta_off + (size_t)lmc_r16_64(8 * (uint64_t)m);
+  const size_t need = caps_off + (size_t)lmc_r16_64(4 * (uint64_t)m);
+  if (c->load_bytes < need) {
+    if (c->load_used) HIP_TRY(hipEventSynchronize(c->load_free));
+    if ((rc = ws_grow((void**)&c->load_slots, &c->load_bytes, need))) return rc;
+  }
+  hipStream_t cs[2] = {c->copy_stream, c->copy_stream2};  // the order of arrival does not matter here: two DMA queues
+  if (c->load_used) {  // the previous load's kernels have read the buffer
+    HIP_TRY(hipStreamWaitEvent(cs[0], c->load_free, 0));
+    HIP_TRY(hipStreamWaitEvent(cs[1], c->load_free, 0));
+  }
+  u8* dev = c->load_slots;
+  // (the two arrays are the caller's pageable memory: hipMemcpyAsync has read them when it returns)
+  HIP_TRY(hipMemcpyAsync(dev + meta_off, blob_ptrs_h, 8 * (size_t)m, hipMemcpyHostToDevice, cs[0]));
+  HIP_TRY(hipMemcpyAsync(dev + caps_off, blob_caps_h, 4 * (size_t)m, hipMemcpyHostToDevice, cs[0]));
+  HIP_TRY(hipMemcpyAsync(dev + h.off_table, b + h.off_table, 8 * ((size_t)P * n + 1), hipMemcpyHostToDevice, cs[0]));
+  HIP_TRY(hipMemcpyAsync(dev + h.off_static + (size_t)c0 * h.static_stride, b + h.off_static + (size_t)c0 * h.static_stride,
+                         (size_t)m * h.static_stride, hipMemcpyHostToDevice, cs[1]));
+  if (m == n) {  // the whole streams region, a half per queue
+    const uint64_t all = t[(uint64_t)P * n], half = (all / 2) & ~(uint64_t)15;
+    if (half) HIP_TRY(hipMemcpyAsync(dev + h.off_streams, b + h.off_streams, half, hipMemcpyHostToDevice, cs[0]));
+    if (all > half) HIP_TRY(hipMemcpyAsync(dev + h.off_streams + half, b + h.off_streams + half, all - half, hipMemcpyHostToDevice, cs[1]));
+  } else {
+    for (int p = 0; p < P; p++) {  // a run of the m chunks per plane
+      const uint64_t lo = t[(uint64_t)p * n + c0], hi = t[(uint64_t)p * n + c0 + m];
+      if (hi > lo) HIP_TRY(hipMemcpyAsync(dev + h.off_streams + lo, b + h.off_streams + lo, hi - lo, hipMemcpyHostToDevice, cs[p & 1]));
+    }
+  }
+  for (int q = 0; q < 2; q++)
+    if ((rc = stream_follows(c, s, cs[q]))) return rc;
+  UnpackArgs ua;
+  memset(&ua, 0, sizeof ua);
+  ua.pack = dev; ua.off_table = h.off_table; ua.off_static = h.off_static; ua.off_streams = h.off_streams;
+  ua.streams_bytes = h.total_bytes - h.off_streams; ua.static_stride = h.static_stride;
+  ua.n = n; ua.c0 = c0; ua.m = m; ua.L = L; ua.G = (int)h.ngroups; ua.chunk_tokens = h.chunk_tokens;
+  ua.dst_ptrs = (u8* const*)(dev + meta_off); ua.dst_caps = (const u32*)(dev + caps_off);
+  ua.status = job_status ? job_status : c->status_h;
+  c->pn = 0;
+  if ((rc = prof_mark(c, s))) return rc;
+  const int items = (P + 1) * m;
+  hipLaunchKernelGGL(k_unpack, dim3((unsigned)std::max(1, std::min(items, c->num_cus))), dim3(256), 0, s, ua);
+  HIP_TRY(hipGetLastError());
+  if ((rc = prof_mark(c, s))) return rc;
   HIP_TRY(hipEventRecord(c->load_free, s));
   c->load_used = true;
   return LMC_OK;

@@ -157,6 +157,9 @@ SYMBOLS = {
     "lmc_pack_info": (ctypes.c_int, [_vp, _u64, ctypes.POINTER(PackHeader)]),
     "lmc_pack_extract": (ctypes.c_int, [_vp, _u64, _i32, _vp, _u64, _vp]),
     "lmc_load_pack": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _PL, _i32, _i32, _vp, _vp, _vp]),
+    "lmc_pack_blobs": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _u64, _vp, _vp]),
+    "lmc_unpack_blobs": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "lmc_pack_chunk_bytes": (ctypes.c_int, [_vp, _u64, _i32, ctypes.POINTER(ctypes.c_uint32)]),
     "lmc_copy_kv": (ctypes.c_int, [_vp, _PL, _i32, _i32, _PL, _i32, _vp]),
     "lmc_pinned_alloc": (ctypes.c_int, [_sz, ctypes.POINTER(_vp)]),
     "lmc_pinned_free": (ctypes.c_int, [_vp]),
@@ -257,6 +260,13 @@ def pack_extract(pack_ptr: int, nbytes: int, chunk: int) -> bytes:
     size = ctypes.c_uint32(0)
     check(lib().lmc_pack_extract(pack_ptr, nbytes, chunk, buf, cap, ctypes.byref(size)), "lmc_pack_extract")
     return buf.raw[:size.value]
+
+
+def pack_chunk_bytes(pack_ptr: int, nbytes: int, chunk: int) -> int:
+    """Size of chunk `chunk` of a pack as a blob (lmc_pack_chunk_bytes): what pack_extract would return, not extracted."""
+    size = ctypes.c_uint32(0)
+    check(lib().lmc_pack_chunk_bytes(pack_ptr, nbytes, chunk, ctypes.byref(size)), "lmc_pack_chunk_bytes")
+    return int(size.value)
 
 
 def pack_bound(n: int, L: int, chunk_tokens: int, H: int, D: int) -> int:
@@ -704,6 +714,22 @@ class Context:
         host memory -> decoded KV, one transfer and one decode per range of layers."""
         self._call("lmc_load_pack", dst.device, stream, pack_ptr, pack_bytes, chunk_begin, nchunks, ctypes.byref(dst.struct),
                    dst_tok0, layers_per_range, range_events_ptr, status_ptr)
+
+    def pack_blobs(self, blob_ptrs: int, blob_bytes_ptr: int, nchunks: int, L: int, H: int, D: int, chunk_tokens: int,
+                   ntokens: int, pack_ptr: int, pack_cap: int, device, stream: Optional[int] = None,
+                   status_ptr: Optional[int] = None) -> None:
+        """lmc_pack_blobs: nchunks encoded blobs anywhere in device memory (blob_ptrs: device int64 [n]; blob_bytes_ptr:
+        device-accessible uint32 [n], the room of each) -> one pack in the DEVICE region at pack_ptr.  No encode."""
+        self._call("lmc_pack_blobs", device, stream, blob_ptrs, blob_bytes_ptr, nchunks, L, H, D, chunk_tokens, ntokens,
+                   pack_ptr, pack_cap, status_ptr)
+
+    def unpack_blobs(self, pack_ptr: int, pack_bytes: int, chunk_begin: int, nchunks: int, dst_ptrs: Sequence[int],
+                     dst_caps: Sequence[int], device, stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
+        """lmc_unpack_blobs: chunks [chunk_begin, +nchunks) of a pack in pinned host memory -> the blobs they were made
+        of, chunk chunk_begin + i at device address dst_ptrs[i] (dst_caps[i] bytes of room)."""
+        ptrs = (ctypes.c_void_p * nchunks)(*[int(p) for p in dst_ptrs])
+        caps = (ctypes.c_uint32 * nchunks)(*[int(c) for c in dst_caps])
+        self._call("lmc_unpack_blobs", device, stream, pack_ptr, pack_bytes, chunk_begin, nchunks, ptrs, caps, status_ptr)
 
     def decode_symbols(self, blob: torch.Tensor, L: int, H: int, D: int, T: int, stream: Optional[int] = None
                        ) -> torch.Tensor:

@@ -20,6 +20,32 @@ Three storage modes, chosen by the config:
                                            no PCIe) can hide behind the model layer by layer
                                            (get_kv_range(..., layers_per_launch=...))
 
+Bounded tiers.  LMCACHE_AMD_HBM_BYTES / LMCACHE_AMD_PINNED_BYTES (integers, optional K / M / G suffix; read at
+construction, unset = unbounded) or set_capacity() give the HBM and the pinned tier a byte budget.  The unit of
+eviction is the GROUP -- the chunks of one put / put_kv_range call: what a pack holds, consecutive links of one hash
+chain -- in LRU order (a hit touches the groups it read from the last to the first: chains are eaten from the tail).
+Over budget, the LRU groups are dropped; an "hbm-cachegen" backend with BOTH budgets is tiered instead: its LRU group
+is demoted -- two or more chunks repacked on the GPU into one pinned pack (lmc_pack_blobs, then DMA), a single chunk
+copied as it is -- and a group that is hit in the pinned tier is served where it lies and afterwards promoted on the
+worker thread (lmc_unpack_blobs), demoting colder groups to make room.  What holds:
+  1. A key is in exactly one tier, and `contains` never reads False during a demotion or promotion: the new entry is
+     published before the old memory is released.  Every change of `dict` bumps `_gen`, so neither the kept prefix
+     answer nor the codec's table of a kept entry list can be served stale.
+  2. A retrieve that took its entries before an eviction completes bit-exact: a released region carries the events of
+     the jobs that read it, and its next owner's stream waits for them.
+  3. After a blocking put has returned, and after drain() behind a non-blocking one, each tier's live bytes are within
+     its budget.
+  4. A group larger than a tier's whole budget is not kept there: tiered, it goes straight to the pinned tier; if it
+     fits nowhere it is not cached (logged once) and nothing else is evicted for it.
+  5. A demotion or promotion that fails (its status word, the check of the landed pack, an exception) leaves the group
+     where it was or drops it; bytes that were not checked are never published.
+tier_of(), tier_stats() and drain() show what happened.
+One lock (`_tier_lock`) covers every change of a tier and every launch that reads one.  Without a budget a store holds it
+only to file its group.  WITH budgets it is held across the host waits of a bounded store, a demotion and a promotion (the
+DMA of a whole pack: about 10 ms for a 16 k context), so a retrieve that arrives while the worker thread moves a group waits
+that long before its first launch; "promotion adds no work in front of the hit" holds for the hit that queued it, not for
+one that arrives during the move.  Narrowing the lock to the publish-and-release step is left for later.
+
 All three implement the optional put_kv_range / get_kv_range protocol
 (abstract_backend.py) so the engine never materialises the [L,2,T,H,D] blob
 (cache_engine.py:98-161) nor the final torch.cat (:362-368): KV is gathered
@@ -30,7 +56,7 @@ import os
 import queue
 import time
 import threading
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -41,7 +67,9 @@ from lmcache_amd.logging import init_logger
 from lmcache_amd.storage_backend.abstract_backend import LMCBackendInterface
 from lmcache_amd.storage_backend.serde.cachegen_basics import CacheGenConfig
 from lmcache_amd.storage_backend.serde.cachegen_decoder import output_spec, retrieve_spec
-from lmcache_amd.storage_backend.serde.cachegen_device import DeviceArena, HostBlob, HostPack, PinnedArena, get_codec
+from lmcache_amd.storage_backend.serde.cachegen_device import (ArenaFull, DeviceArena, HostBlob, HostPack, PinnedArena,
+                                                               get_codec)
+from lmcache_amd.storage_backend.tiering import GroupLRU, Tiers, parse_bytes, r16
 from lmcache_amd.utils import CacheEngineKey, _lmcache_nvtx_annotate
 
 logger = init_logger(__name__)
@@ -77,6 +105,30 @@ class _PackChunk:
     blob: Optional[HostBlob] = None    # the chunk as a blob of its own, reassembled on first single-chunk use
     encoded: bool = True
     ready: Optional[torch.cuda.Event] = None
+
+
+@dataclass
+class _Group:
+    """The chunks of one put call: the unit of the LRU, of eviction, demotion and promotion."""
+    gid: int
+    keys: List[CacheEngineKey]
+    nbytes: int                        # what it counts for in its tier
+    geometry: Optional[Tuple[int, int, int]]  # (L, H, D) of an encoded group
+    chunk_tokens: int
+    ntokens: int
+    readers: list                      # events of the jobs that wrote or read its memory: a release is fenced by them
+    orphans: list = field(default_factory=list)  # pack chunks whose key a later store took: the pack goes back with the group
+
+    def live_readers(self) -> list:
+        out = []
+        for ev in self.readers:
+            try:
+                if ev.query():
+                    continue
+            except Exception:
+                pass
+            out.append(ev)
+        return out
 
 
 def _chunk_shape(fmt: str, L: int, T: int, H: int, D: int) -> Tuple[int, ...]:
@@ -136,11 +188,24 @@ class LMCLocalBackend(LMCBackendInterface):
         self._stage_free: Optional[torch.cuda.Event] = None
         self._cuda_device = torch.cuda.current_device()
         self.last_publish_time = 0.0
-        self._gen = 0               # bumped by every _publish: what _prefix_entries' kept answer is valid for
+        self._gen = 0               # bumped by every change of `dict`: what _prefix_entries' kept answer is valid for
         self._prefix_memo = None
+        # bounded tiers (module docstring): groups in LRU order, budgets, and one lock around every change of a tier and
+        # every launch that reads one
+        self._tier_lock = threading.RLock()
+        self._lru = GroupLRU()
+        self._groups: Dict[int, "_Group"] = {}
+        self._key_gid: Dict[CacheEngineKey, int] = {}
+        self._next_gid = 0
+        self._promoting: set = set()
+        self._oversize_logged = False
+        self._tiers = Tiers(self._lru, self._demote_group if self.mode == "hbm-cachegen" else None, self._drop_group,
+                            self._demoted_size)
         self.put_queue: "queue.Queue" = queue.Queue()
         self.put_thread = threading.Thread(target=self.put_worker, daemon=True)
         self.put_thread.start()
+        self.set_capacity(parse_bytes(os.environ.get("LMCACHE_AMD_HBM_BYTES")),
+                          parse_bytes(os.environ.get("LMCACHE_AMD_PINNED_BYTES")), _keep_unset=True)
 
     # ------------------------------------------------------------------ basics
     def contains(self, key: CacheEngineKey) -> bool:
@@ -175,6 +240,279 @@ class LMCLocalBackend(LMCBackendInterface):
             self.dict[key] = entry
             self._gen += 1
             self.last_publish_time = time.perf_counter()  # (when a non-blocking store became visible: bench.py store_hidden)
+
+    def _unpublish(self, key: CacheEngineKey) -> None:
+        with self.update_lock:
+            if self.dict.pop(key, None) is not None:
+                self._gen += 1
+
+    # ------------------------------------------------------------------ bounded tiers
+    def _tier_name(self) -> str:
+        """The tier a store of this backend's mode lands in."""
+        return "hbm" if self.mode in ("hbm", "hbm-cachegen") else "pinned"
+
+    def set_capacity(self, hbm_bytes: Optional[int] = None, pinned_bytes: Optional[int] = None, _keep_unset: bool = False) -> None:
+        """Byte budgets of the HBM and the pinned tier (None: unbounded).  A budget that shrinks evicts -- or, tiered,
+        demotes -- at once."""
+        with self._tier_lock:
+            self._tiers.budget["hbm"], self._tiers.budget["pinned"] = hbm_bytes, pinned_bytes
+            if _keep_unset and hbm_bytes is None and pinned_bytes is None:
+                return
+            if self.mode == "hbm-cachegen" and pinned_bytes is not None and self.host_arena is None:
+                self.host_arena = PinnedArena()
+            if self.host_arena is not None:
+                self.host_arena.set_budget(pinned_bytes)
+            if self.dev_arena is not None:
+                self.dev_arena.set_budget(hbm_bytes)
+            self._tiers.enforce()
+
+    def tier_of(self, key: CacheEngineKey) -> Optional[str]:
+        e = self.dict.get(key)
+        if e is None:
+            return None
+        return "hbm" if isinstance(e, (_DevChunk, torch.Tensor)) else "pinned"
+
+    def tier_stats(self) -> dict:
+        with self._tier_lock:
+            out = {"demotions": self._tiers.demotions, "promotions": self._tiers.promotions, "evictions": self._tiers.evictions}
+            for tier, arena in (("hbm", self.dev_arena), ("pinned", self.host_arena)):
+                live = self._lru.live(tier)
+                out[tier] = {"live_bytes": live, "reserved_bytes": arena.reserved_bytes if arena is not None else live,
+                             "groups": self._lru.count(tier), "budget": self._tiers.budget[tier]}
+            return out
+
+    def drain(self) -> None:
+        """Wait until the worker thread has done everything queued so far (non-blocking puts, promotions)."""
+        while True:
+            done = threading.Event()
+            self.put_queue.put(done.set)
+            done.wait()
+            with self._tier_lock:
+                if not self._promoting and self.put_queue.empty():
+                    return
+
+    def _new_group(self, tier: str, keys: Sequence[CacheEngineKey], entries: Sequence, nbytes: int, geometry=None,
+                   chunk_tokens: int = 0, ntokens: int = 0, ready=None) -> None:
+        """File the chunks of one put call as a group and publish them (caller holds _tier_lock)."""
+        gid, self._next_gid = self._next_gid, self._next_gid + 1
+        self._groups[gid] = _Group(gid, list(keys), nbytes, geometry, chunk_tokens, ntokens, [ready] if ready is not None else [])
+        self._lru.add(tier, gid, nbytes)
+        for key, e in zip(keys, entries):
+            old_gid, old_e = self._key_gid.get(key), self.dict.get(key)
+            self._key_gid[key] = gid
+            self._publish(key, e)
+            if old_gid is not None and old_e is not None:
+                self._release_replaced(old_gid, old_e)
+
+    def _release_replaced(self, old_gid: int, old_e) -> None:
+        """A key was stored again: the entry it had leaves its older group.  A chunk with memory of its own gives it back
+        now (fenced by that group's readers) and the group counts for less; a chunk of a pack waits for its pack, which
+        goes back with the group; a group that has lost its last key goes altogether."""
+        g = self._groups.get(old_gid)
+        if g is None:
+            return
+        if isinstance(old_e, _PackChunk):
+            g.orphans.append(old_e)
+        else:
+            self._release([old_e], g.live_readers())
+            if isinstance(old_e, _DevChunk):
+                nb = r16(old_e.blob.numel())
+            elif isinstance(old_e, _HostChunk):
+                nb = r16(old_e.blob.nbytes)
+            else:
+                nb = old_e.numel() * old_e.element_size()
+            g.nbytes = max(0, g.nbytes - nb)
+            if self._lru.tier_of(old_gid) is not None:
+                self._lru.resize(old_gid, g.nbytes)
+        if not self._own_keys(g):
+            self._drop_group(old_gid)
+            self._lru.remove(old_gid)
+
+    def _demoted_size(self, gid: int) -> int:
+        """Bytes group `gid` of the HBM tier takes in the pinned tier: its pack's exact size, or its one blob's."""
+        g = self._groups[gid]
+        sizes = [self.dict[k].blob.numel() for k in self._own_keys(g) if isinstance(self.dict.get(k), _DevChunk)]
+        if len(sizes) >= 2 and len(sizes) == len(g.keys) and g.geometry is not None:
+            return r16(self._codec().demoted_bytes(sizes, g.geometry, g.chunk_tokens, g.ntokens))
+        return sum(r16(n) for n in sizes) or g.nbytes
+
+    def _own_keys(self, g: "_Group") -> list:
+        return [k for k in g.keys if self._key_gid.get(k) == g.gid]
+
+    def _release(self, entries: Sequence, events: Sequence) -> None:
+        """Give the memory of a group's entries back to its arena, fenced by `events` (who may still read it)."""
+        packs = []
+        for e in entries:
+            if isinstance(e, _DevChunk):
+                if self.dev_arena is not None:
+                    self.dev_arena.free(e.blob, events)
+            elif isinstance(e, _PackChunk):
+                if not any(e.pack is p for p in packs):
+                    packs.append(e.pack)
+                if e.blob is not None and self.host_arena is not None:
+                    self.host_arena.free(e.blob, events)
+            elif isinstance(e, _HostChunk) and self.host_arena is not None:
+                self.host_arena.free(e.blob, events)
+        for p in packs:
+            if self.host_arena is not None:
+                self.host_arena.free(p.blob, events)
+
+    def _drop_group(self, gid: int) -> None:
+        """Forget a group: its keys leave the dict, then its memory goes back (Tiers removes it from the LRU)."""
+        g = self._groups.pop(gid)
+        entries = []
+        for k in self._own_keys(g):
+            e = self.dict.get(k)
+            if e is not None:
+                entries.append(e)
+            self._unpublish(k)
+            del self._key_gid[k]
+        self._release(entries + g.orphans, g.live_readers())
+
+    def _demote_group(self, gid: int) -> bool:
+        """HBM blobs of a group -> the pinned tier (Tiers has made room there): republished first, released after.
+        False: nothing changed, the caller drops the group."""
+        g = self._groups[gid]
+        keys = self._own_keys(g)
+        old = [self.dict[k] for k in keys]
+        if len(keys) != len(g.keys) or not all(isinstance(e, _DevChunk) for e in old):
+            return False  # (a group that lost a key to a later store is no whole chain link any more)
+        codec = self._codec()
+
+        def move():
+            if len(old) >= 2:
+                pack = codec.demote_blobs([e.blob for e in old], g.geometry, g.chunk_tokens, g.ntokens, self.host_arena,
+                                          ready=g.readers[:1])
+                return [_PackChunk(pack, i, e.shape, e.dtype) for i, e in enumerate(old)], r16(pack.blob.nbytes)
+            e = old[0]
+            hb = self.host_arena.alloc(e.blob.numel(), streams=[codec.copy_stream])
+            for ev in g.readers[:1]:
+                codec.copy_stream.wait_event(ev)
+            native.memcpy_async(hb.ptr, e.blob.data_ptr(), e.blob.numel(), "d2h", codec.copy_stream.cuda_stream)
+            codec.copy_stream.synchronize()
+            return [_HostChunk(hb, None, e.shape, e.dtype, True)], r16(hb.nbytes)
+
+        new = None
+        try:
+            with torch.cuda.device(self._cuda_device):
+                while new is None:
+                    try:
+                        new, nbytes = move()
+                    except ArenaFull:
+                        # the byte count allowed it, the holes did not: the pinned tier's LRU group goes, and again
+                        if not self._tiers.take_lru("pinned", keep=[gid]):
+                            raise
+        except Exception as exc:
+            logger.warning("demotion failed (%s: %s): the group is dropped", type(exc).__name__, exc)
+            return False
+        for k, e in zip(keys, new):
+            self._publish(k, e)
+        self._release(old, g.live_readers())
+        g.readers, g.nbytes = [], nbytes
+        self._lru.add("pinned", gid, nbytes)
+        return True
+
+    def _promote_group(self, gid: int) -> None:
+        """Worker thread: a pinned group that was hit goes back to HBM, colder groups making room."""
+        with self._tier_lock:
+            self._promoting.discard(gid)
+            g = self._groups.get(gid)
+            if g is None or self._lru.tier_of(gid) != "pinned" or not self._tiers.tiered():
+                return
+            keys = self._own_keys(g)
+            old = [self.dict[k] for k in keys]
+            packed = len(old) >= 2 and all(isinstance(e, _PackChunk) and e.pack is old[0].pack and e.index == i
+                                           for i, e in enumerate(old)) and old[0].pack.nchunks == len(old)
+            single = len(old) == 1 and isinstance(old[0], _HostChunk) and old[0].encoded
+            if len(keys) != len(g.keys) or not (packed or single):
+                return
+            codec = self._codec()
+            try:
+                if packed:
+                    pack = old[0].pack
+                    sizes = [native.pack_chunk_bytes(pack.blob.ptr, pack.blob.nbytes, i) for i in range(len(old))]
+                else:
+                    sizes = [old[0].blob.nbytes]
+                nbytes = sum(r16(n) for n in sizes)
+                if nbytes > self._tiers.budget["hbm"] or not self._tiers.make_room("hbm", nbytes, keep=[gid]):
+                    return
+                if self._lru.tier_of(gid) != "pinned":
+                    return
+                if self.dev_arena is None:
+                    self.dev_arena = DeviceArena(torch.device("cuda", self._cuda_device), budget=self._tiers.budget["hbm"])
+                with torch.cuda.device(self._cuda_device):
+                    if packed:
+                        blobs = codec.promote_pack(pack, self.dev_arena)
+                    else:
+                        cur = torch.cuda.current_stream()
+                        t = self.dev_arena.alloc(sizes[0], stream=cur)
+                        native.memcpy_async(t.data_ptr(), old[0].blob.ptr, sizes[0], "h2d", cur.cuda_stream)
+                        cur.synchronize()
+                        blobs = [t]
+            except Exception:
+                logger.exception("promotion failed: the group stays in the pinned tier")
+                return
+            for k, e, t in zip(keys, old, blobs):
+                self._publish(k, _DevChunk(t, e.shape, e.dtype))
+            self._release(old, g.live_readers())
+            g.readers, g.nbytes = [], nbytes
+            self._lru.add("hbm", gid, nbytes)
+            self._tiers.promotions += 1
+            self._tiers.enforce(keep=[gid])
+
+    def _touch(self, keys: Sequence[CacheEngineKey], events: Sequence = ()) -> None:
+        """A hit read these keys (caller holds _tier_lock): their groups move up the LRU, remember `events` (the jobs
+        that read them: a later release is fenced by those), and -- tiered -- pinned ones are queued for promotion."""
+        gids = []
+        for k in keys:
+            gid = self._key_gid.get(k)
+            if gid is not None and (not gids or gids[-1] != gid):
+                gids.append(gid)
+        self._lru.touch_chain(gids)
+        for gid in set(gids):
+            g = self._groups.get(gid)
+            if g is None:
+                continue
+            if events:
+                g.readers = g.live_readers() + list(events)
+            if self._lru.tier_of(gid) == "pinned" and self._tiers.tiered() and gid not in self._promoting:
+                self._promoting.add(gid)
+                self.put_queue.put(lambda gid=gid: self._promote_group(gid))
+
+    def _not_cached(self, nbytes: int) -> None:
+        if not self._oversize_logged:
+            self._oversize_logged = True
+            logger.warning("a group of %d bytes fits no tier's budget: not cached (logged once)", nbytes)
+
+    def _store(self, tier: str, need: int, make, keys: Sequence[CacheEngineKey], **group) -> bool:
+        """File a new group in `tier`.  make() -> (entries, bytes, ready event or None) allocates and fills its memory.
+        Unbounded tier: make() runs outside the tier lock (a store in flight never holds up a retrieve).  Bounded: room for
+        `need` bytes is made first; an arena that is still full (fragmented) has its LRU group taken out and make() runs
+        again.  -> False: the group fits nowhere and was not cached."""
+        b = self._tiers.budget[tier]
+        if b is None:
+            got = make()
+            with self._tier_lock:
+                if self._tiers.budget[tier] is not None and tier == "hbm" and self.dev_arena is not None:
+                    self.dev_arena.set_budget(self._tiers.budget[tier])  # (bounded in the meantime)
+                self._new_group(tier, keys, got[0], got[1], ready=got[2], **group)
+                self._tiers.enforce()
+            return True
+        with self._tier_lock:
+            got = None
+            if need <= b and self._tiers.make_room(tier, need):
+                while got is None:
+                    try:
+                        got = make()
+                    except ArenaFull:
+                        if not self._tiers.take_lru(tier):
+                            break
+            if got is None:
+                self._not_cached(need)
+                return False
+            self._new_group(tier, keys, got[0], got[1], ready=got[2], **group)
+            self._tiers.enforce()
+            return True
 
     @_lmcache_nvtx_annotate
     def put_worker(self):
@@ -214,21 +552,72 @@ class LMCLocalBackend(LMCBackendInterface):
 
     def _finish_encoded(self, keys: Sequence[CacheEngineKey], job, shapes, dtype) -> None:
         codec = self._codec()
+        L, H, D, cs = job.geometry
+        tok = 2 if (self.fmt or "vllm") == "vllm" else 3
+        group = dict(geometry=(L, H, D), chunk_tokens=cs, ntokens=sum(shp[tok] for shp in shapes))
         if self.mode == "hbm-cachegen":
-            if self.dev_arena is None:
-                self.dev_arena = DeviceArena(torch.device("cuda", self._cuda_device))
-            for key, t, shp in zip(keys, codec.keep_on_device(job, self.dev_arena), shapes):
-                self._publish(key, _DevChunk(t, shp, dtype))
+            def keep():
+                if self.dev_arena is None:
+                    self.dev_arena = DeviceArena(torch.device("cuda", self._cuda_device), budget=self._tiers.budget["hbm"])
+                blobs = codec.keep_on_device(job, self.dev_arena)
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(self._cuda_device))
+                return [_DevChunk(t, shp, dtype) for t, shp in zip(blobs, shapes)], sum(r16(t.numel()) for t in blobs), ready
+            if self._tiers.budget["hbm"] is None:
+                self._store("hbm", 0, keep, keys, **group)
+                return
+            sizes = codec.sizes_of(job)
+            nbytes = sum(r16(n) for n in sizes)
+            where = self._tiers.place(nbytes)
+            if where == "hbm":
+                ok = self._store("hbm", nbytes, keep, keys, **group)
+            elif where == "pinned":  # larger than the whole HBM budget: straight to the pinned tier, a blob per chunk
+                ok = self._store("pinned", nbytes, lambda: self._offload_entries(job, sizes, shapes, dtype), keys, **group)
+            else:
+                self._not_cached(nbytes)
+                ok = False
+            if not ok:
+                job.offload_issued = True  # (nothing reads the encode arena any more)
             return
-        blobs, done = codec.offload(job, None, self.host_arena)  # range by range, overlapping the rest of the encode
+        if self._tiers.budget["pinned"] is None:
+            # range by range, overlapping the rest of the encode
+            self._store("pinned", 0, lambda: self._offload_entries(job, None, shapes, dtype), keys, **group)
+            return
+        sizes = codec.sizes_of(job)
+        nbytes = sum(r16(n) for n in sizes)
+        if not self._store("pinned", nbytes, lambda: self._offload_entries(job, sizes, shapes, dtype), keys, **group):
+            job.offload_issued = True
+
+    def _offload_entries(self, job, sizes, shapes, dtype):
+        """The job's blobs in pinned host DRAM -> (entries, bytes, None)."""
+        blobs, done = self._codec().offload(job, sizes, self.host_arena)
         done.synchronize()
-        for key, hb, shp in zip(keys, blobs, shapes):
-            self._publish(key, _HostChunk(hb, None, shp, dtype, True))
+        return [_HostChunk(hb, None, shp, dtype, True) for hb, shp in zip(blobs, shapes)], sum(r16(hb.nbytes) for hb in blobs), None
 
     def _finish_pack(self, keys: Sequence[CacheEngineKey], job, shapes, dtype) -> None:
-        pack = self._codec().finish_pack(job, self.host_arena)
-        for i, (key, shp) in enumerate(zip(keys, shapes)):
-            self._publish(key, _PackChunk(pack, i, shp, dtype))
+        L, H, D = job.geometry
+        tok = 2 if (self.fmt or "vllm") == "vllm" else 3
+
+        def finish():
+            pack = self._codec().finish_pack(job, self.host_arena)
+            return [_PackChunk(pack, i, shp, dtype) for i, shp in enumerate(shapes)], r16(pack.blob.nbytes), None
+
+        # bounded: the region is taken at the pack's bound and cut to size while the tier has room for the bound (the parts
+        # then leave while the later planes are coded, as in an unbounded tier); a tier that would have to evict for the
+        # bound waits for the last part instead and makes room for the pack's exact size
+        b = self._tiers.budget["pinned"]
+        need = 0
+        if b is not None:
+            need = r16(job.cap)
+            if self._lru.live("pinned") + need > b:
+                need = r16(max(self._codec().pack_bytes(job), 16))
+        if not self._store("pinned", need, finish, keys, geometry=(L, H, D), chunk_tokens=job.chunk_tokens,
+                           ntokens=sum(shp[tok] for shp in shapes)):
+            if not job.d2h_issued:  # never taken by finish_pack: its kernels finish, its words and the staging go back
+                job.done.synchronize()
+                with self._codec()._lock:
+                    job.retire()
+                    job.d2h_issued = True
 
     def _own_blob(self, e: _PackChunk) -> HostBlob:
         """A pack's chunk as a blob of its own in the pinned arena (the single-chunk paths: get(), a retrieve that mixes
@@ -244,7 +633,7 @@ class LMCLocalBackend(LMCBackendInterface):
         if not kv_chunk.is_cuda:
             kv_chunk = kv_chunk.to(self.dst_device)
         if self.mode == "hbm":
-            self._publish(key, kv_chunk if kv_chunk.is_contiguous() else kv_chunk.contiguous())
+            self._keep_tensors([key], [kv_chunk if kv_chunk.is_contiguous() else kv_chunk.contiguous()])
             return
         lay = native.KVLayout.from_chunk(kv_chunk, fmt)
         shape = _chunk_shape(fmt, lay.L, lay.ntokens, lay.H, lay.D)
@@ -257,16 +646,25 @@ class LMCLocalBackend(LMCBackendInterface):
         # raw: contiguous chunk -> pinned host
         src = kv_chunk if kv_chunk.is_contiguous() else kv_chunk.contiguous()
         nbytes = src.numel() * src.element_size()
-        hb = self.host_arena.alloc(nbytes)
         codec = self._codec()
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(src.device))
-        codec.copy_stream.wait_event(ev)
-        native.memcpy_async(hb.ptr, src.data_ptr(), nbytes, "d2h", codec.copy_stream.cuda_stream)
-        done = torch.cuda.Event()
-        done.record(codec.copy_stream)
-        done.synchronize()  # `src` may be freed by the caller after we return
-        self._publish(key, _HostChunk(hb, None, tuple(src.shape), src.dtype, False))
+
+        def copy_out():
+            hb = self.host_arena.alloc(nbytes, streams=[codec.copy_stream])
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(src.device))
+            codec.copy_stream.wait_event(ev)
+            native.memcpy_async(hb.ptr, src.data_ptr(), nbytes, "d2h", codec.copy_stream.cuda_stream)
+            done = torch.cuda.Event()
+            done.record(codec.copy_stream)
+            done.synchronize()  # `src` may be freed by the caller after we return
+            return [_HostChunk(hb, None, tuple(src.shape), src.dtype, False)], r16(nbytes), None
+
+        self._store("pinned", r16(nbytes), copy_out, [key])
+
+    def _keep_tensors(self, keys: Sequence[CacheEngineKey], chunks: Sequence[torch.Tensor]) -> None:
+        """Raw chunks that stay in HBM as the tensors they are ("hbm" mode): one group."""
+        nbytes = sum(c.numel() * c.element_size() for c in chunks)
+        self._store("hbm", nbytes, lambda: (list(chunks), nbytes, None), keys)
 
     def put(self, key: CacheEngineKey, kv_chunk: torch.Tensor, blocking: bool = True) -> None:
         fmt = _fmt_of_chunk(kv_chunk, self.fmt)
@@ -287,6 +685,19 @@ class LMCLocalBackend(LMCBackendInterface):
 
     @_lmcache_nvtx_annotate
     def get(self, key: CacheEngineKey) -> Optional[torch.Tensor]:
+        # (the tier lock is held to the end: every path below has finished reading the entry when it returns, but for the
+        # raw copy, whose event fences a later release)
+        with self._tier_lock:
+            out = self._get_locked(key)
+            if out is not None:
+                ev = None
+                if self.mode == "raw":
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(out.device))
+                self._touch([key], [ev] if ev is not None else ())
+            return out
+
+    def _get_locked(self, key: CacheEngineKey) -> Optional[torch.Tensor]:
         entry = self.dict.get(key, None)
         if entry is None:
             return None
@@ -368,11 +779,18 @@ class LMCLocalBackend(LMCBackendInterface):
                 self.put_queue.put(lambda: self._finish_encoded(list(keys), job, shapes, out_dt))
             return n
         if self.mode == "hbm":
-            for key, shp, i in zip(keys, shapes, range(n)):
+            b = self._tiers.budget["hbm"]
+            if b is not None and sum(L * 2 * shp[2 if fmt == "vllm" else 3] * H * D for shp in shapes) * dt.itemsize > b:
+                # (not even gathered: it fits nowhere)
+                self._not_cached(sum(L * 2 * shp[2 if fmt == "vllm" else 3] * H * D for shp in shapes) * dt.itemsize)
+                return n
+            chunks = []
+            for shp, i in zip(shapes, range(n)):
                 chunk = torch.empty(shp, dtype=dt, device=dev)
                 T = shp[2] if fmt == "vllm" else shp[3]
                 ctx.copy_kv(src, tok_begin + i * chunk_tokens, T, native.KVLayout.from_chunk(chunk, fmt), 0)
-                self._publish(key, chunk)
+                chunks.append(chunk)
+            self._keep_tensors(list(keys), chunks)
             return n
         # raw: gather every chunk into a device staging arena with the copy kernel, then D2H on the side stream
         codec = self._codec()
@@ -394,25 +812,49 @@ class LMCLocalBackend(LMCBackendInterface):
         gathered = torch.cuda.Event()
         gathered.record(cur)
         codec.copy_stream.wait_event(gathered)
-        entries = []
-        for v in views:
-            nb = v.numel() * eb
-            hb = self.host_arena.alloc(nb)
-            native.memcpy_async(hb.ptr, v.data_ptr(), nb, "d2h", codec.copy_stream.cuda_stream)
-            entries.append(_HostChunk(hb, None, tuple(v.shape), dt, False))
-        done = torch.cuda.Event()
-        done.record(codec.copy_stream)
-        self._stage_free = done
+        total = sum(r16(v.numel() * eb) for v in views)
+
+        def copy_out():
+            entries = []
+            try:
+                for v in views:
+                    nb = v.numel() * eb
+                    hb = self.host_arena.alloc(nb, streams=[codec.copy_stream])
+                    native.memcpy_async(hb.ptr, v.data_ptr(), nb, "d2h", codec.copy_stream.cuda_stream)
+                    entries.append(_HostChunk(hb, None, tuple(v.shape), dt, False))
+            except ArenaFull:
+                evf = torch.cuda.Event()
+                evf.record(codec.copy_stream)
+                for e in entries:
+                    self.host_arena.free(e.blob, [evf])
+                raise
+            return entries, total, None
+
+        # (the group is visible once its copies have landed: blocking here, on the worker thread otherwise)
+        box = {}
+
+        def copy_and_wait():
+            entries, nb, _ = copy_out()
+            box["done"] = torch.cuda.Event()
+            box["done"].record(codec.copy_stream)
+            self._stage_free = box["done"]
+            if blocking or self._tiers.budget["pinned"] is not None:
+                box["done"].synchronize()
+            return entries, nb, None
+
+        if blocking or self._tiers.budget["pinned"] is not None:
+            self._store("pinned", total, copy_and_wait, list(keys))
+            return n
+        entries, _, _ = copy_and_wait()
+        done = box["done"]
 
         def finish():
             done.synchronize()
-            for key, e in zip(keys, entries):
-                self._publish(key, e)
+            with self._tier_lock:
+                self._new_group("pinned", list(keys), entries, total)
+                self._tiers.enforce()
 
-        if blocking:
-            finish()
-        else:
-            self.put_queue.put(finish)
+        self.put_queue.put(finish)
         return n
 
     def get_kv_range(self, keys: Sequence[CacheEngineKey], dst: native.KVLayout, fmt: str, dst_tok0: int,
@@ -421,12 +863,18 @@ class LMCLocalBackend(LMCBackendInterface):
         below 0 are dropped (retrieve()'s first-chunk trim, cache_engine.py:360-365).  Returns the number of
         leading chunks written (a key that has gone since `contains` ends the run, like the reference's break on
         the first None chunk, cache_engine.py:339-345); raises NativeError if a stored blob does not decode."""
+        # the tier lock is held from taking the entries to the last launch: an eviction either happens before (the keys
+        # are gone: a shorter run) or after (the jobs launched here are among the events its release is fenced by)
+        with self._tier_lock:
+            return self._get_kv_range_locked(keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out)
+
+    def _get_kv_range_locked(self, keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out) -> int:
         entries = self._prefix_entries(keys)
         if not entries:
             return 0
         ctx = native.get_context(self._cuda_device)
         dev = dst.device
-        if self.mode == "hbm-cachegen":
+        if self.mode == "hbm-cachegen" and all(isinstance(e, _DevChunk) for e in entries):
             # blobs in HBM: one decode launch per range of layers, an event after each; with jobs_out the call
             # returns at once and the caller finishes the job (engine.retrieve_layerwise)
             codec = self._codec()
@@ -435,38 +883,49 @@ class LMCLocalBackend(LMCBackendInterface):
                 # keeps the uploaded address table of the last few lists it has seen)
                 job = codec.decode_device([e.blob for e in entries], dst, dst_tok0, chunk_tokens, layers_per_launch,
                                           same_blobs_as=entries)
+            self._touch(keys[:len(entries)], [job.done])
             if jobs_out is not None:
                 jobs_out.append((codec, job))
             else:
                 codec.finish_decode(job)
             return len(entries)
-        if self.mode == "cachegen":
+        if self.mode in ("cachegen", "hbm-cachegen"):
             # The entries split into maximal RUNS: consecutive chunks of one pack (what one put_kv_range stored) are one
             # lmc_load_pack -- a transfer and a decode per range of layers, straight from the pack --, a run of chunks
             # with blobs of their own is one decode over those blobs.  A retrieve that spans several stores (every turn
             # of a conversation, every prompt behind a shared prefix adds a pack) is a few such jobs on the same
             # streams, one behind the other; nothing is reassembled on the host and no pinned memory is allocated.
+            # (A tiered hbm-cachegen backend whose prefix lies partly in HBM, partly demoted: its HBM blobs are runs of
+            # a third kind, decoded where they lie.)
             codec = self._codec()
             runs, i = [], 0
+
+            def kind_of(e):
+                if isinstance(e, _DevChunk):
+                    return "dev"
+                return "pack" if isinstance(e, _PackChunk) and e.pack.chunk_tokens == chunk_tokens else "blobs"
             while i < len(entries):
                 e = entries[i]
                 j = i + 1
-                if isinstance(e, _PackChunk) and e.pack.chunk_tokens == chunk_tokens:
+                kind = kind_of(e)
+                if kind == "pack":
                     while (j < len(entries) and isinstance(entries[j], _PackChunk) and entries[j].pack is e.pack
                            and entries[j].index == e.index + (j - i)):
                         j += 1
-                    runs.append(("pack", i, j))
                 else:
-                    while j < len(entries) and not (isinstance(entries[j], _PackChunk)
-                                                    and entries[j].pack.chunk_tokens == chunk_tokens):
+                    while j < len(entries) and kind_of(entries[j]) == kind:
                         j += 1
-                    runs.append(("blobs", i, j))
+                runs.append((kind, i, j))
                 i = j
+            # (the HBM tier hands its jobs out whenever the caller takes them, as above; the pinned tier only cut by layers)
             layerwise = bool(layers_per_launch) and jobs_out is not None
+            events = []
             for kind, i, j in runs:
                 tok0 = dst_tok0 + i * chunk_tokens
                 with torch.cuda.device(dev):
-                    if kind == "pack":
+                    if kind == "dev":
+                        job = codec.decode_device([e.blob for e in entries[i:j]], dst, tok0, chunk_tokens, layers_per_launch)
+                    elif kind == "pack":
                         job = codec.load_pack(entries[i].pack, entries[i].index, j - i, dst, tok0, layers_per_launch)
                     else:
                         # (a pack chunk of another chunk length -- never stored by this engine -- takes its blob from the pack)
@@ -477,10 +936,12 @@ class LMCLocalBackend(LMCBackendInterface):
                             job = codec.decode_host_layerwise(blobs, dst, tok0, chunk_tokens, layers_per_launch)
                         else:
                             job = codec.decode(blobs, dst, tok0, chunk_tokens)
-                if layerwise:
+                events.append(job.done)
+                if layerwise or (kind == "dev" and jobs_out is not None):
                     jobs_out.append((codec, job))
                 else:
                     codec.finish_decode(job)  # this decode's event, then its own status word
+            self._touch(keys[:len(entries)], events)
             return len(entries)
         cur = torch.cuda.current_stream(dev)
         stage = None
@@ -503,10 +964,12 @@ class LMCLocalBackend(LMCBackendInterface):
             skip = max(0, -t0)
             if skip < T:
                 ctx.copy_kv(native.KVLayout.from_chunk(chunk, fmt), skip, T - skip, dst, t0 + skip)
+        ev = None
         if stage is not None:
             ev = torch.cuda.Event()
             ev.record(cur)
             self._stage_free = ev
+        self._touch(keys[:len(entries)], [ev] if ev is not None else ())
         return len(entries)
 
 

@@ -23,31 +23,154 @@ import torch
 
 from lmcache_amd import native
 from lmcache_amd.logging import init_logger
+from lmcache_amd.storage_backend.tiering import FreeList
 
 logger = init_logger(__name__)
 
 
-class PinnedArena:
-    """Bump allocator over hipHostMalloc'ed slabs.  The reference never evicts
-    (hybrid_backend.py:24), so neither do we: memory is returned at close()."""
+class ArenaFull(MemoryError):
+    """A bounded arena cannot take the allocation: over its budget, or no hole is large enough."""
 
-    def __init__(self, slab_bytes: int = 256 << 20):
+
+def _event_done(ev) -> bool:
+    try:
+        return bool(ev.query())
+    except Exception:
+        return False
+
+
+def _stream_waits(stream, events) -> None:
+    """`stream` runs behind `events` (torch events or native.NativeEvent): a stream-side wait, never a host wait."""
+    for ev in events:
+        if isinstance(ev, native.NativeEvent):
+            ev.wait(stream.cuda_stream)
+        else:
+            stream.wait_event(ev)
+
+
+class PinnedArena:
+    """Allocator over hipHostMalloc'ed slabs.  Without a budget it is a bump allocator that returns memory at close()
+    (the reference never evicts, hybrid_backend.py:24): free() only counts.  With a byte budget (constructor, or
+    set_budget() later) regions come from a first-fit free list with coalescing (storage_backend/tiering.py), free()
+    gives them back, and the bytes reserved from the system -- the sum of the slab sizes -- never exceed the budget
+    (an arena that was unbounded before keeps the slabs it has; it takes no new one while it is over).  A freed
+    region carries the events of whoever may still read it; alloc() makes the streams of the next owner wait for them."""
+
+    def __init__(self, slab_bytes: int = 256 << 20, budget: Optional[int] = None, buffer_factory=None):
         self.slab_bytes = slab_bytes
+        self._new_buffer = buffer_factory or native.PinnedBuffer
         self._slabs: List[native.PinnedBuffer] = []
         self._spare: List[native.PinnedBuffer] = []   # slabs allocated ahead of need (reserve)
+        self._tops: List[int] = []                    # bump pointer each earlier slab was left at
         self._used = 0
         self._lock = threading.Lock()
         self.total_allocated = 0
+        self._fl: Optional[FreeList] = None
+        if budget is not None:
+            self.set_budget(budget)
 
-    def alloc(self, nbytes: int, slab_hint: int = 0) -> "HostBlob":
+    # ---- bounded -------------------------------------------------------------------------------------------------
+    @property
+    def budget(self) -> Optional[int]:
+        return self._fl.budget if self._fl is not None else None
+
+    def set_budget(self, budget: Optional[int]) -> None:
+        """Bound the arena from now on (None on an unbounded arena: nothing changes; a bounded arena stays a free list
+        and only loses its limit).  What the bump allocator has handed out so far counts as live."""
+        with self._lock:
+            if self._fl is None:
+                if budget is None:
+                    return
+                fl = FreeList(budget, _event_done)
+                for k, b in enumerate(self._slabs):
+                    last = k == len(self._slabs) - 1
+                    fl.add_slab(b, b.nbytes, self._used if last else self._tops[k])
+                for b in self._spare:
+                    fl.add_slab(b, b.nbytes, 0)
+                self._slabs, self._spare = self._slabs + self._spare, []
+                self._fl = fl
+            else:
+                self._fl.budget = budget
+
+    @property
+    def live_bytes(self) -> int:
+        return self._fl.live if self._fl is not None else self.total_allocated
+
+    @property
+    def reserved_bytes(self) -> int:
+        return sum(b.nbytes for b in self._slabs + self._spare)
+
+    def _alloc_bounded(self, nbytes: int, need: int, slab_hint: int, streams) -> "HostBlob":
+        fl = self._fl
+        got = fl.alloc(need)
+        if got is None and fl.fits_budget(need):
+            room = fl.room_for_slab()
+            if room is not None and room < need:
+                # no hole takes it and the budget leaves no slab of its size: slabs that are one hole go back to the
+                # system first (an arena whose groups have all gone must take a region larger than any slab it has)
+                self._release_empty_locked(until=need)
+                room = fl.room_for_slab()
+            size = max(self.slab_bytes, need, slab_hint)
+            if room is not None:
+                size = min(size, room) & ~15
+            if size >= need:
+                buf = self._new_buffer(size)
+                self._slabs.append(buf)
+                fl.add_slab(buf, size)
+                got = fl.alloc(need)
+        if got is None:
+            raise ArenaFull(f"pinned arena: {need} bytes do not fit ({fl.live} live of a budget of {fl.budget})")
+        slab, off, events = got
+        for st in streams:
+            _stream_waits(st, events)
+        self.total_allocated = fl.live
+        return HostBlob(slab, off, nbytes)
+
+    def free(self, hb: "HostBlob", events: Sequence = ()) -> None:
+        """Give `hb` back; `events`: what may still read or write it.  An unbounded arena reuses nothing: it only counts."""
+        size = native.r16(max(hb.nbytes, 16))
+        with self._lock:
+            if self._fl is None:
+                self.total_allocated -= size
+                return
+            self._fl.free(hb.slab, hb.offset, size, events)
+            self.total_allocated = self._fl.live
+            self._release_empty_locked()
+
+    def _release_empty_locked(self, until: int = 0) -> None:
+        """Slabs that are one hole go back to the system while the arena is over its budget (an arena bounded after the
+        fact), or -- until > 0 -- until the budget leaves room for a new slab of `until` bytes.  A slab whose last
+        readers have not finished is waited for: the one host wait of the arena, on the rare path where memory has to
+        change hands with the system."""
+        fl = self._fl
+        if fl.budget is None:
+            return
+        for b in list(self._slabs):
+            if fl.reserved <= fl.budget and (until <= 0 or fl.budget - fl.reserved >= until):
+                break
+            if fl.is_empty(b):
+                for e in fl.holes[b][0][2]:
+                    if not _event_done(e) and hasattr(e, "synchronize"):
+                        e.synchronize()
+                fl.drop_slab(b)
+                self._slabs.remove(b)
+                b.free()
+
+    # ---- both ----------------------------------------------------------------------------------------------------
+    def alloc(self, nbytes: int, slab_hint: int = 0, streams: Sequence = ()) -> "HostBlob":
         """slab_hint: size of the slab to allocate if a new one is needed (a pack is allocated at its bound and cut
-        to its size afterwards: a slab of a few bounds keeps the cut-off tails usable)."""
+        to its size afterwards: a slab of a few bounds keeps the cut-off tails usable).  streams: who will write the
+        region (bounded arena: they wait for the events of its previous owner).  Bounded and full: ArenaFull."""
         need = native.r16(max(nbytes, 16))
         with self._lock:
+            if self._fl is not None:
+                return self._alloc_bounded(nbytes, need, slab_hint, streams)
             if not self._slabs or self._used + need > self._slabs[-1].nbytes:
                 k = next((i for i, b in enumerate(self._spare) if b.nbytes >= need), None)
+                if self._slabs:
+                    self._tops.append(self._used)
                 self._slabs.append(self._spare.pop(k) if k is not None
-                                   else native.PinnedBuffer(max(self.slab_bytes, need, slab_hint)))
+                                   else self._new_buffer(max(self.slab_bytes, need, slab_hint)))
                 self._used = 0
             slab = self._slabs[-1]
             off = self._used
@@ -56,23 +179,35 @@ class PinnedArena:
         return HostBlob(slab, off, nbytes)
 
     def shrink(self, hb: "HostBlob", nbytes: int) -> "HostBlob":
-        """Give back the tail of `hb` if it is still the arena's last allocation (a pack is allocated at its bound and
-        cut to its size once the GPU has written it); otherwise the tail stays unused."""
+        """Give back the tail of `hb`.  Unbounded: only if it is still the arena's last allocation (a pack is allocated
+        at its bound and cut to its size once the GPU has written it); otherwise the tail stays unused.  Bounded: the
+        tail is freed like any region -- the budget was tested against the bound at alloc() and is corrected here
+        (nbytes 0: the whole region goes back)."""
         keep = native.r16(max(nbytes, 16))
         with self._lock:
-            if self._slabs and hb.slab is self._slabs[-1] and hb.offset + native.r16(max(hb.nbytes, 16)) == self._used:
+            if self._fl is not None:
+                old = native.r16(max(hb.nbytes, 16))
+                if nbytes <= 0:
+                    keep = 0
+                if old > keep:
+                    self._fl.free(hb.slab, hb.offset + keep, old - keep)
+                    self.total_allocated = self._fl.live
+            elif self._slabs and hb.slab is self._slabs[-1] and hb.offset + native.r16(max(hb.nbytes, 16)) == self._used:
                 self.total_allocated -= self._used - (hb.offset + keep)
                 self._used = hb.offset + keep
         return HostBlob(hb.slab, hb.offset, nbytes)
 
     def reserve(self, nbytes: int, slab_bytes: int = 0) -> None:
         """Allocate slabs for `nbytes` more bytes now (hipHostMalloc of hundreds of MB takes tens of ms and stalls
-        the device: a backend sized for its working set pays that at start-up, not inside a store)."""
+        the device: a backend sized for its working set pays that at start-up, not inside a store).  A bounded arena
+        takes its slabs as it needs them."""
         slab = max(self.slab_bytes, slab_bytes)
         with self._lock:
+            if self._fl is not None:
+                return
             have = sum(b.nbytes for b in self._spare)
             while have < nbytes:
-                self._spare.append(native.PinnedBuffer(slab))
+                self._spare.append(self._new_buffer(slab))
                 have += slab
 
     def reset(self):
@@ -81,14 +216,22 @@ class PinnedArena:
             for s in self._slabs[:-1]:
                 s.free()
             self._slabs = self._slabs[-1:]
+            self._tops = []
             self._used = 0
             self.total_allocated = 0
+            if self._fl is not None:
+                budget = self._fl.budget
+                self._fl = FreeList(budget, _event_done)
+                for b in self._slabs:
+                    self._fl.add_slab(b, b.nbytes, 0)
 
     def close(self):
         with self._lock:
             for s in self._slabs + self._spare:
                 s.free()
-            self._slabs, self._spare = [], []
+            self._slabs, self._spare, self._tops = [], [], []
+            if self._fl is not None:
+                self._fl = FreeList(self._fl.budget, _event_done)
 
 
 @dataclass
@@ -281,29 +424,133 @@ class DecodeJob(Job):
 
 
 class DeviceArena:
-    """Bump allocator over HBM slabs for encoded chunks that stay on the GPU (LMCLocalBackend, local_device="cuda" +
-    local_serde="cachegen": 4.2x more warm context in the 288 GB than raw chunks).  No eviction, like the
-    reference (hybrid_backend.py:24)."""
+    """Allocator over HBM slabs for encoded chunks that stay on the GPU (LMCLocalBackend, local_device="cuda" +
+    local_serde="cachegen": 4.2x more warm context in the 288 GB than raw chunks).  Unbounded it is a bump allocator
+    (free() only counts); with a byte budget it is PinnedArena's free list over HBM slabs: free() gives a blob's bytes
+    back with the events of the decodes and copies that may still read them, and alloc() makes the stream that writes
+    the region next wait for those."""
 
-    def __init__(self, device, slab_bytes: int = 512 << 20):
+    def __init__(self, device, slab_bytes: int = 512 << 20, budget: Optional[int] = None):
         self.device, self.slab_bytes = device, slab_bytes
         self._slabs: List[torch.Tensor] = []
+        self._tops: List[int] = []
         self._used = 0
         self._lock = threading.Lock()
+        self._fl: Optional[FreeList] = None
+        self._live = 0
+        self._ids: List[int] = []    # bounded: the free list's id of each slab
+        self._next_id = 0
+        if budget is not None:
+            self.set_budget(budget)
 
-    def alloc(self, nbytes: int) -> torch.Tensor:
+    @property
+    def budget(self) -> Optional[int]:
+        return self._fl.budget if self._fl is not None else None
+
+    @property
+    def live_bytes(self) -> int:
+        return self._fl.live if self._fl is not None else self._live
+
+    def _new_slab(self, size: int) -> torch.Tensor:
+        return torch.empty(size, dtype=torch.uint8, device=self.device)
+
+    def _release_empty_locked(self, until: int = 0) -> None:
+        """See PinnedArena._release_empty_locked."""
+        fl = self._fl
+        if fl.budget is None:
+            return
+        for k in range(len(self._slabs) - 1, -1, -1):
+            if fl.reserved <= fl.budget and (until <= 0 or fl.budget - fl.reserved >= until):
+                break
+            sid = self._ids[k]
+            if fl.is_empty(sid):
+                for e in fl.holes[sid][0][2]:
+                    if not _event_done(e) and hasattr(e, "synchronize"):
+                        e.synchronize()
+                fl.drop_slab(sid)
+                del self._slabs[k], self._ids[k]
+
+    @property
+    def reserved_bytes(self) -> int:
+        return sum(t.numel() for t in self._slabs)
+
+    def set_budget(self, budget: Optional[int]) -> None:
+        """See PinnedArena.set_budget."""
+        with self._lock:
+            if self._fl is None:
+                if budget is None:
+                    return
+                fl = FreeList(budget, _event_done)
+                for k, t in enumerate(self._slabs):
+                    fl.add_slab(k, t.numel(), self._used if k == len(self._slabs) - 1 else self._tops[k])
+                # (what was freed while unbounded was only counted: those bytes stay lost to the old slabs)
+                self._ids = list(range(len(self._slabs)))
+                self._next_id = len(self._slabs)
+                self._fl = fl
+            else:
+                self._fl.budget = budget
+
+    def alloc(self, nbytes: int, stream=None) -> torch.Tensor:
+        """stream: who writes the region (bounded arena: it waits for the events of the previous owner; None: the
+        current stream).  Bounded and full: ArenaFull."""
         need = native.r16(max(nbytes, 16))
         with self._lock:
+            if self._fl is not None:
+                fl = self._fl
+                got = fl.alloc(need)
+                if got is None and fl.fits_budget(need):
+                    room = fl.room_for_slab()
+                    if room is not None and room < need:
+                        self._release_empty_locked(until=need)
+                        room = fl.room_for_slab()
+                    size = max(self.slab_bytes, need)
+                    if room is not None:  # (None: a bounded arena whose limit has been taken away again)
+                        size = min(size, room) & ~15
+                    if size >= need:
+                        self._slabs.append(self._new_slab(size))
+                        self._ids.append(self._next_id)
+                        fl.add_slab(self._next_id, size)
+                        self._next_id += 1
+                        got = fl.alloc(need)
+                if got is None:
+                    raise ArenaFull(f"HBM arena: {need} bytes do not fit ({fl.live} live of a budget of {fl.budget})")
+                sid, off, events = got
+                if events:
+                    _stream_waits(stream if stream is not None else torch.cuda.current_stream(self.device), events)
+                return self._slabs[self._ids.index(sid)][off:off + nbytes]
             if not self._slabs or self._used + need > self._slabs[-1].numel():
-                self._slabs.append(torch.empty(max(self.slab_bytes, need), dtype=torch.uint8, device=self.device))
+                if self._slabs:
+                    self._tops.append(self._used)
+                self._slabs.append(self._new_slab(max(self.slab_bytes, need)))
                 self._used = 0
             off = self._used
             self._used += need
+            self._live += need
             return self._slabs[-1][off:off + nbytes]
+
+    def free(self, t: torch.Tensor, events: Sequence = ()) -> None:
+        """Give the blob `t` (a view alloc() returned) back; `events`: what may still read it."""
+        size = native.r16(max(t.numel(), 16))
+        with self._lock:
+            if self._fl is None:
+                self._live -= size
+                return
+            p = t.data_ptr()
+            for k, slab in enumerate(self._slabs):
+                base = slab.data_ptr()
+                if base <= p < base + slab.numel():
+                    self._fl.free(self._ids[k], p - base, size, events)
+                    break
+            else:
+                raise ValueError("DeviceArena.free: not a region of this arena")
+            self._release_empty_locked()  # over budget (bounded after the fact): empty slabs go back
 
     def close(self):
         with self._lock:
-            self._slabs = []
+            self._slabs, self._tops, self._used, self._live = [], [], 0, 0
+            if self._fl is not None:
+                self._fl = FreeList(self._fl.budget, _event_done)
+                self._ids, self._next_id = [], 0
 
 
 class CacheGenDeviceCodec:
@@ -447,7 +694,13 @@ class CacheGenDeviceCodec:
                 for st in streams:
                     st.wait_event(ev)
                 for i in range(c0, c1):
-                    hb = arena.alloc(sizes[i])
+                    try:
+                        hb = arena.alloc(sizes[i], streams=streams)
+                    except ArenaFull:
+                        evf = self._join_copy_streams(both=len(streams) > 1)
+                        for b in blobs:  # (the copies queued so far still write them)
+                            arena.free(b, [evf])
+                        raise
                     native.memcpy_async(hb.ptr, job.arena.data_ptr() + i * job.stride, sizes[i], "d2h",
                                         streams[i % len(streams)].cuda_stream)
                     blobs.append(hb)
@@ -479,10 +732,17 @@ class CacheGenDeviceCodec:
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(job.done)
-            for i, n in enumerate(sizes):
-                t = arena.alloc(n)
-                native.memcpy_async(t.data_ptr(), job.arena.data_ptr() + i * job.stride, n, "d2d", cur.cuda_stream)
-                out.append(t)
+            try:
+                for i, n in enumerate(sizes):
+                    t = arena.alloc(n, stream=cur)
+                    native.memcpy_async(t.data_ptr(), job.arena.data_ptr() + i * job.stride, n, "d2d", cur.cuda_stream)
+                    out.append(t)
+            except ArenaFull:
+                ev = torch.cuda.Event()
+                ev.record(cur)
+                for t in out:  # (the copies queued so far still write them)
+                    arena.free(t, [ev])
+                raise
             ev = torch.cuda.Event()
             ev.record(cur)
             job.offload_issued = True
@@ -628,6 +888,19 @@ class CacheGenDeviceCodec:
                 self._pack_prev = weakref.ref(job)
             return job
 
+    def pack_bytes(self, job: PackJob) -> int:
+        """Wait for the store's last part and -> the size of its pack from the part words (0: the parts say it failed;
+        finish_pack reads the verdict)."""
+        off_streams = native.pack_off_streams(job.nchunks, job.geometry[0], job.chunk_tokens, job.geometry[1], job.geometry[2])
+        job.part_events[-1].synchronize()
+        info = job.part_info.tensor.view(torch.int64)
+        total = 0
+        for r in range(len(job.part_events)):
+            off, nbytes = int(info[2 * r]), int(info[2 * r + 1])
+            if nbytes > 0:
+                total = off_streams + off + nbytes
+        return total if total <= job.cap else 0
+
     def finish_pack(self, job: PackJob, arena: PinnedArena) -> HostPack:
         """Wait for THIS store (its events), raise NativeError if a kernel flagged it, return the pack in pinned host DRAM."""
         # The pack is being built in HBM part by part.  Part r leaves as soon as its event has fired -- the host waits
@@ -636,9 +909,18 @@ class CacheGenDeviceCodec:
         # last part the static sections (header, offset table, static slots) follow.  The pinned region is taken at the
         # pack's upper bound and cut to its size afterwards.
         off_streams = native.pack_off_streams(job.nchunks, job.geometry[0], job.chunk_tokens, job.geometry[1], job.geometry[2])
-        region = arena.alloc(job.cap, slab_hint=min(4 * job.cap, 4 << 30))
-        info = job.part_info.tensor.view(torch.int64)
         streams = [self.copy_stream, self.copy_stream2]
+        # A BOUNDED arena is asked for the bound too, while it has room for it: the budget is tested against the bound here
+        # and corrected by the cut below (shrink frees the tail).  When it has not -- an arena kept full by its budget is
+        # the steady state -- it is asked for the pack's exact size instead, which the last part's words give: a hole of
+        # the bound would evict groups for room the pack never uses.  The parts then leave behind the whole encode: that
+        # store loses the overlap of its DMA with its encode.  (ArenaFull from here: nothing has been done to the job yet,
+        # the caller makes room and calls again, or drops the job.)
+        try:
+            region = arena.alloc(job.cap, slab_hint=min(4 * job.cap, 4 << 30), streams=streams)
+        except ArenaFull:
+            region = arena.alloc(max(self.pack_bytes(job), off_streams), streams=streams)
+        info = job.part_info.tensor.view(torch.int64)
         total, failed = off_streams, False
         with torch.cuda.device(self.device):
             for r, ev in enumerate(job.part_events):
@@ -649,7 +931,7 @@ class CacheGenDeviceCodec:
                     # so far but the newest one), the parts behind the only one of an unsplit job are empty by design, and
                     # a part that failed reads the same -- the job's status word and the check of the assembled pack decide
                     continue
-                if off_streams + off + nbytes > job.cap:
+                if off_streams + off + nbytes > min(job.cap, native.r16(max(region.nbytes, 16))):
                     failed = True
                     break
                 native.memcpy_async(region.ptr + off_streams + off, job.dev.data_ptr() + off_streams + off, nbytes, "d2h",
@@ -691,6 +973,105 @@ class CacheGenDeviceCodec:
                 self.ctx.load_pack(pack.blob.ptr, pack.blob.nbytes, chunk_begin, nchunks, dst, dst_tok0, step,
                                    ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream, status_ptr=st_ptr)
             return DecodeJob(events[-1][1], events, status_idx=st, pool=self._status)
+
+    # ---- bounded tiers: HBM blobs <-> pinned pack, no re-encode ---------------------------------------------------------
+    def demote_blobs(self, blobs: Sequence[torch.Tensor], geometry: tuple, chunk_tokens: int, ntokens: int,
+                     arena: PinnedArena, ready: Sequence = ()) -> HostPack:
+        """The demotion leg: the HBM blobs of one store group (exact-size uint8 tensors, anywhere) -> one pack in pinned
+        host DRAM, byte for byte the pack store_pack would have written.  lmc_pack_blobs repacks them on the GPU into the
+        HBM pack staging, two DMA copies move the pack into a region of `arena` taken at its exact size (the blobs'
+        sizes say what it is), and lmc_pack_info checks it where it landed.  Blocks until the pack is there (a worker's
+        call, or set_capacity's); raises NativeError -- nothing kept -- if the job's status word or the check says no,
+        ArenaFull if `arena` has no room.  ready: events behind the writes of the blobs."""
+        L, H, D = geometry
+        n = len(blobs)
+        total = self.demoted_bytes([b.numel() for b in blobs], geometry, chunk_tokens, ntokens)
+        with self._lock, torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            streams = [self.copy_stream, self.copy_stream2]
+            region = arena.alloc(total, streams=streams)
+            try:
+                prev = self._pack_prev() if self._pack_prev is not None else None
+                shared = prev is None or prev.d2h_issued
+                if shared:
+                    if self._pack_dev is None or self._pack_dev.numel() < total:
+                        self._pack_dev = torch.empty(total, dtype=torch.uint8, device=self.device)
+                    dev = self._pack_dev
+                    if self._pack_dev_free is not None:
+                        cur.wait_event(self._pack_dev_free)  # the previous pack has left the buffer
+                else:
+                    dev = torch.empty(total, dtype=torch.uint8, device=self.device)  # a store has not been finished yet
+                _stream_waits(cur, ready)
+                # the blobs' addresses and room in DEVICE memory (the scan reads them dozens of times per thread): one
+                # stream-ordered upload from pinned memory of torch's caching host allocator, as decode_device's table
+                words = [b.data_ptr() for b in blobs]
+                sizes = [b.numel() for b in blobs]
+                words += [sizes[i] | (sizes[i + 1] << 32 if i + 1 < n else 0) for i in range(0, n, 2)]  # uint32 pairs
+                table = torch.tensor(words, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+                with self._launch(cur) as (st, st_ptr):
+                    self.ctx.pack_blobs(table.data_ptr(), table.data_ptr() + 8 * n, n, L, H, D, chunk_tokens, ntokens,
+                                        dev.data_ptr(), total, self.device, stream=cur.cuda_stream, status_ptr=st_ptr)
+                    done = torch.cuda.Event()
+                    done.record(cur)
+                job = Job(done, status_idx=st, pool=self._status)
+                half = (total // 2) & ~15
+                for q, (lo, hi) in enumerate(((0, half), (half, total))):
+                    streams[q].wait_event(done)
+                    if hi > lo:
+                        native.memcpy_async(region.ptr + lo, dev.data_ptr() + lo, hi - lo, "d2h", streams[q].cuda_stream)
+                evd = self._join_copy_streams()
+                if shared:
+                    self._pack_dev_free = evd
+                evd.synchronize()
+                _raise_on(job.retire(), "CacheGen demotion (lmc_pack_blobs)")
+                h = native.pack_info(region.ptr, total)  # only a pack that checks out where it lies is published
+                if int(h.total_bytes) != total or int(h.nchunks) != n:
+                    raise native.NativeError("CacheGen demotion: the pack is not the size its blobs add up to")
+            except BaseException:
+                arena.free(region)
+                raise
+        return HostPack(region, n, chunk_tokens)
+
+    @staticmethod
+    def demoted_bytes(blob_sizes: Sequence[int], geometry: tuple, chunk_tokens: int, ntokens: int) -> int:
+        """Exact size of the pack demote_blobs writes for blobs of these sizes: header, table and static slots, and every
+        blob's streams section."""
+        L, H, D = geometry
+        n = len(blob_sizes)
+        total = native.pack_off_streams(n, L, chunk_tokens, H, D)
+        for i, nb in enumerate(blob_sizes):
+            T = chunk_tokens if i < n - 1 else ntokens - (n - 1) * chunk_tokens
+            total += nb - native.blob_static_bytes(L, T, H, D)
+        return total
+
+    def promote_pack(self, pack: HostPack, arena: "DeviceArena") -> List[torch.Tensor]:
+        """The promotion leg: every chunk of a pack in pinned host DRAM -> the blob it was made of, each in a region of
+        its own size in the HBM arena (lmc_unpack_blobs: DMA into the context's load staging, one kernel that scatters
+        static slots and segments).  Blocks until the blobs are there; NativeError (nothing kept) if the job's status
+        word says no, ArenaFull if `arena` has no room."""
+        n = pack.nchunks
+        sizes = [native.pack_chunk_bytes(pack.blob.ptr, pack.blob.nbytes, i) for i in range(n)]
+        out: List[torch.Tensor] = []
+        with self._lock, torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            try:
+                for nb in sizes:
+                    out.append(arena.alloc(nb, stream=cur))
+                with self._launch(cur) as (st, st_ptr):
+                    self.ctx.unpack_blobs(pack.blob.ptr, pack.blob.nbytes, 0, n, [t.data_ptr() for t in out], sizes,
+                                          self.device, stream=cur.cuda_stream, status_ptr=st_ptr)
+                    done = torch.cuda.Event()
+                    done.record(cur)
+                job = Job(done, status_idx=st, pool=self._status)
+                done.synchronize()
+                _raise_on(job.retire(), "CacheGen promotion (lmc_unpack_blobs)")
+            except BaseException:
+                ev = torch.cuda.Event()
+                ev.record(cur)
+                for t in out:
+                    arena.free(t, [ev])
+                raise
+        return out
 
     def _dec_slots(self, n: int, stride: int, cur) -> torch.Tensor:
         if self._dec_arena is None or self._dec_arena.numel() < n * stride:
