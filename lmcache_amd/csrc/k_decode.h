@@ -349,7 +349,10 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   // the words were late: -6 % decode time, and one ring event per block instead of two):
   // their latency is off the per-token dependency chain.  Slots 256..319 mirror slots 0..63, so a token's words
   // are at consecutive slots whatever e.  A corrupt stream cannot leave the ring (slot index masked, rank < 64,
-  // loads guarded); the final state / count check reports it.
+  // loads guarded); the final state / count check reports it.  (The "at most 64 words, one block below" argument is
+  // held by tests/test_gpu_patterns.py::test_bursts_and_silence_on_the_gpu and
+  // ::test_cdf16_blobs_of_the_short_patterns_still_decode: streams whose 64 lanes renormalise in lockstep -- 64 words
+  // at a token and again at the next -- with such a run at eight offsets e mod 128, and streams with no words at all.)
   typedef __attribute__((address_space(3))) u32* lds_u32w;
   const lds_u32w ring32 = (lds_u32w)reinterpret_cast<u32*>(ring);
   const LMC_GLOBAL u32* const words32 = (const LMC_GLOBAL u32*)words;  // streams start 16-byte aligned
@@ -504,7 +507,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   // `check_tag`: whether the ring is looked after behind this token.  The block path does so behind every SECOND token
   // (round 6): a token takes at most 64 words and a whole block lies below the upper one, so the token after the one
   // that emptied the upper block still finds its words -- half the tests, and every ring event falls just in front of a
-  // pair's stores.
+  // pair's stores.  (Held by the lockstep runs of tests/test_gpu_patterns.py: 128 words between two looks at the ring.)
   auto decode_token = [&](auto top_tag, auto model_tag, float& lv, auto check_tag) -> u32 {
     constexpr bool CHECK = decltype(check_tag)::value;
     constexpr int TOP = decltype(top_tag)::value;

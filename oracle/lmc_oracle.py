@@ -70,6 +70,8 @@ def lib() -> ctypes.CDLL:
         L.lmco_decode_blob_symbols.restype = i32
         L.lmco_decode_blob.argtypes = [vp, sz, vp, i32]
         L.lmco_decode_blob.restype = i32
+        L.lmco_trace_group_words.argtypes = [vp, i32, i32, i32, i32, i32, vp]
+        L.lmco_trace_group_words.restype = ctypes.c_long
         L.lmco_rans_magic.argtypes = [ctypes.c_uint32, vp, vp]
         L.lmco_blob_bound.argtypes = [i32, i32, i32, i32]
         L.lmco_blob_bound.restype = ctypes.c_uint64
@@ -81,9 +83,16 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+class _ArrayPtr(ctypes.c_void_p):
+    """A pointer that keeps its array alive: `_p(np.ascontiguousarray(x))` makes a temporary copy when x is not
+    contiguous, and a bare c_void_p would leave the C call reading memory that was freed when _p returned."""
+
+
 def _p(a: np.ndarray) -> ctypes.c_void_p:
     assert a.flags["C_CONTIGUOUS"]
-    return ctypes.c_void_p(a.ctypes.data)
+    ptr = _ArrayPtr(a.ctypes.data)
+    ptr.array = a
+    return ptr
 
 
 def rans_magic(count: int):
@@ -165,6 +174,19 @@ def decode_group(stream: bytes, T: int, C: int, g: int, cdf_plane: np.ndarray,
     buf = np.frombuffer(stream, dtype=np.uint16).copy()
     return lib().lmco_decode_group(_p(buf), len(stream), T, C, g, _p(np.ascontiguousarray(cdf_plane)),
                                    _p(sym_plane))
+
+
+def trace_group_words(sym_plane: np.ndarray, g: int, bins: int, model: int = -1) -> np.ndarray:
+    """Words stream (plane, g) takes at each token (int64 [T]): what the encoder appends when it codes token t and the
+    decoder pops behind token t.  sym_plane int8 [T, C] symbols of one plane with `bins` bins; model as encode_blob's.
+    The sum is the stream's word count in front of its 64 states."""
+    T, C = sym_plane.shape
+    assert sym_plane.dtype == np.int8
+    per_token = np.zeros(T, np.uint32)
+    n = lib().lmco_trace_group_words(_p(np.ascontiguousarray(sym_plane)), T, C, g, int(bins), model, _p(per_token))
+    assert n >= 0, f"lmco_trace_group_words rc={n}"
+    assert int(per_token.sum()) == n
+    return per_token.astype(np.int64)
 
 
 def blob_bound(L: int, T: int, H: int, D: int) -> int:
