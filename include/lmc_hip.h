@@ -74,7 +74,23 @@ int lmc_abi_version(void);
  * per-layer [T,H,D] tensors, NBHD blocks -- where any head_size will do).  The DECODERS' destination and both sides of
  * lmc_copy_kv take any strides and any head_size (lmc_copy_kv copies element-wise when a side is not vector-readable:
  * the way to bring such a range into a chunk the encoders take; lmcache_amd's codec does that by itself).
+ *
+ * paged_kind = LMC_PAGED_ROWS (0) is all of the above: a token's head is a row of D contiguous elements.
+ * paged_kind = LMC_PAGED_SPLIT (1) is the cache of vLLM's ROCm paged-attention kernels (paged_attention_rocm,
+ * paged_attention_v1 / v2; PagedAttention.split_kv_cache): key_cache [num_blocks, H, D/x, block_size, x] with
+ * x = 16 / element bytes (8 for bf16 / fp16, 16 for fp8), value_cache [num_blocks, H, D, block_size].  slot_mapping and
+ * block_size are required, head_size % x == 0, stride_token is ignored; the plane bases are found as above, K planes
+ * (kv = 0) are x-split, V planes token-innermost.  With s = slot_mapping[t], b = s / block_size, w = s % block_size:
+ *   K addr = plane_base(l,0) + b*stride_block + h*stride_head + (d / x)*(block_size*x) + w*x + d % x      [elements]
+ *   V addr = plane_base(l,1) + b*stride_block + h*stride_head + d*block_size + w
+ * (a dense cache: stride_head = D*block_size, stride_block = H*D*block_size).  A token's channels are not contiguous
+ * there, so ONLY lmc_copy_kv takes such a layout, as its source or as its destination (not both; the other side is
+ * any LMC_PAGED_ROWS layout): k_copy_split.h.  Every other entry point reads and writes rows and returns
+ * LMC_ERR_INVALID for it -- bring the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot
+ * read.  Any other paged_kind is LMC_ERR_INVALID; a caller that zeroes the struct gets LMC_PAGED_ROWS.
  */
+#define LMC_PAGED_ROWS 0
+#define LMC_PAGED_SPLIT 1
 typedef struct lmc_kv_layout {
   int32_t dtype;      /* LMC_DTYPE_BF16 / FP16 / FP8_E4M3 / FP8_E5M2 (elements of 2 or 1 bytes; strides count elements) */
   int32_t num_layers; /* L */
@@ -88,7 +104,7 @@ typedef struct lmc_kv_layout {
   int64_t stride_head;
   const int64_t* slot_mapping; /* device [ntokens] or NULL */
   int32_t block_size;
-  int32_t _pad;
+  int32_t paged_kind; /* LMC_PAGED_ROWS / LMC_PAGED_SPLIT (this word was padding, zero, before) */
   int64_t stride_block;
 } lmc_kv_layout;
 
@@ -257,6 +273,7 @@ int lmc_decode_symbols(lmc_ctx* ctx, const void* blob, int32_t L, int32_t H, int
  * connector's slot_mapping gather / reshape_and_cache_flash scatter
  * (LLM_Engine.rst:91-122).  Both layouts share L, H, D and dtype.
  * dst token index = dst_tok0 + (t - tok_begin).
+ * One side (not both) may be LMC_PAGED_SPLIT: the gather from / scatter into vLLM's ROCm paged-attention cache.
  */
 int lmc_copy_kv(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok,
                 const lmc_kv_layout* dst, int32_t dst_tok0, lmc_stream_t stream);

@@ -168,8 +168,14 @@ class LMCacheEngine:
         read the blocks where they lie.
           kv_caches     per layer a tensor [2, num_blocks, block_size, H, D] (layout "NBHD", vLLM's flash layout)
                         or [2, num_blocks, H, block_size, D] ("NHBD", BASELINE.json's north star), bf16 / fp16
+                        or, layout "NHDB", the cache of vLLM's ROCm paged-attention kernels: [2, num_blocks, H, D,
+                        block_size] (a view of vLLM's [2, num_blocks, block_size * H * D]) or the (key_cache,
+                        value_cache) pair of PagedAttention.split_kv_cache (native.KVLayout.paged); bf16 / fp16 / fp8
           slot_mapping  int64 [len(tokens)]: token t lives in slot slot_mapping[t] = block * block_size + offset
-        The engine's fmt must be "vllm" (chunks are keyed and laid out [L,2,T,H,D])."""
+        The engine's fmt must be "vllm" (chunks are keyed and laid out [L,2,T,H,D]).
+        An "NHDB" cache has no token rows for the encoders to read: every tier first brings the range into a vllm chunk
+        on the device with one lmc_copy_kv (k_copy_split.h) -- the codec's staging of any layout it cannot read, the
+        raw tiers' own gather -- instead of the connector's torch gather of every layer."""
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens.shape) == 1, f"Invalid shape of tokens: {tokens.shape}"
         assert len(kv_caches) > 0, "Empty kv_caches"
@@ -244,17 +250,34 @@ class LMCacheEngine:
         reshape_and_cache_flash scatter (LLM_Engine.rst:101-122) fused into the decode kernel's store.  Slots
         need not be contiguous or ordered (CacheBlend-style placement of a non-prefix segment, BASELINE
         configs[4]).  Returns ret_mask (True where KV was written); the caches of tokens outside it are untouched.
-          slot_mapping  int64 [len(tokens)] (entries of tokens the mask skips are ignored)"""
+          slot_mapping  int64 [len(tokens)] (entries of tokens the mask skips are ignored)
+        layout "NHDB" (the cache of vLLM's ROCm paged-attention kernels, see store_paged) is STAGED, the same way for
+        every tier: the decoders write rows, and such a cache has none.  The hit chunks are decoded (or copied) into a
+        contiguous [L,2,nret,H,D] chunk on the current stream, as retrieve() fills its own blob, and one lmc_copy_kv on
+        that stream scatters tokens 0 .. got-1 into the cache (k_copy_split.h); nothing is launched when nothing was
+        retrieved.  Costs: device memory the size of the retrieved KV for the duration of the call, and one more pass
+        over it.  A side effect: a stored chunk that fails to decode never touches the live
+        cache, because the miss is decided before the scatter."""
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
+        staged = {}
 
         def make_dst(nret, L, H, D, dtype, dev):
-            c0 = kv_caches[0]
-            assert len(kv_caches) == L and c0.dtype == dtype, "cache geometry / dtype differs from the stored chunks"
-            return native.KVLayout.paged(kv_caches, slot_mapping[num_skip_tok:num_skip_tok + nret], block_size, layout)
+            dst = native.KVLayout.paged(kv_caches, slot_mapping[num_skip_tok:num_skip_tok + nret], block_size, layout)
+            assert dst.L == L and native.torch_dtype(dst.dtype) == dtype, "cache geometry / dtype differs from the stored chunks"
+            if layout != "NHDB":
+                return dst
+            assert (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
+            staged["dst"] = dst
+            staged["chunk"] = torch.empty((L, 2, nret, H, D), dtype=dtype, device=dst.device)
+            return native.KVLayout.from_chunk(staged["chunk"], "vllm")
 
-        _, ret_mask = self._retrieve_into(tokens, mask, make_dst)
+        got, ret_mask = self._retrieve_into(tokens, mask, make_dst)
+        if staged and got > 0:
+            dst = staged["dst"]
+            with torch.cuda.device(dst.device):
+                native.get_context(dst.device.index).copy_kv(native.KVLayout.from_chunk(staged["chunk"], "vllm"), 0, got, dst, 0)
         return ret_mask
 
     @_lmcache_nvtx_annotate

@@ -15,6 +15,7 @@
 
 #include "../../include/lmc_hip.h"
 #include "k_copy.h"
+#include "k_copy_split.h"
 #include "k_decode.h"
 #include "k_encode_counts.h"
 #include "k_fused.h"
@@ -192,8 +193,15 @@ int lmc_device_status(lmc_ctx* c, int clear) {
 // (stride_head == head_size: the vllm chunk, the per-layer [T,H,D] tensors, NBHD paged blocks), where a vector that
 // crosses a head boundary is still 8 consecutive elements.  !vec: element-wise access (the decoder's scatter, the
 // element-wise copy): any strides.  Either way a plane has a multiple of 8 channels (the blob's geometry).
-static bool layout_ok(const lmc_kv_layout* l, bool vec = true) {
+// `split`: the caller addresses LMC_PAGED_SPLIT itself (lmc_copy_kv alone); everybody else reads and writes rows and must
+// refuse such a layout rather than address it as rows.
+static bool layout_ok(const lmc_kv_layout* l, bool vec = true, bool split = false) {
   if (!l) return false;
+  if (l->paged_kind != LMC_PAGED_ROWS && l->paged_kind != LMC_PAGED_SPLIT) return false;
+  if (l->paged_kind == LMC_PAGED_SPLIT) {
+    if (!split || vec || !l->slot_mapping || l->block_size < 1) return false;
+    if (l->head_size < 1 || l->head_size % (lmc_dtype_fp8(l->dtype) ? 16 : 8)) return false;  // whole x-granules
+  }
   if (l->dtype != LMC_DTYPE_BF16 && l->dtype != LMC_DTYPE_FP16 && !lmc_dtype_fp8(l->dtype)) return false;
   if (l->num_layers < 1 || 2 * l->num_layers > LMC_MAX_PLANES) return false;
   if (l->num_heads < 1 || l->head_size < 1) return false;
@@ -702,12 +710,64 @@ int lmc_decode_symbols(lmc_ctx* c, const void* blob, int32_t L, int32_t H, int32
   return LMC_OK;
 }
 
+}  // extern "C"
+
+// One side of lmc_copy_kv is LMC_PAGED_SPLIT (k_copy_split.h): a wave per (plane, head, tile of TT tokens).
+template <typename E, bool GATHER>
+static void launch_copy_split(const SplitCopyArgs& a, int tt, unsigned blocks, size_t lds, hipStream_t s) {
+  const dim3 g(blocks), b(64 * SPLIT_WAVES);
+  if (tt == 32) hipLaunchKernelGGL((k_copy_split<E, GATHER, 32>), g, b, lds, s, a);
+  else if (tt == 16) hipLaunchKernelGGL((k_copy_split<E, GATHER, 16>), g, b, lds, s, a);
+  else hipLaunchKernelGGL((k_copy_split<E, GATHER, 8>), g, b, lds, s, a);
+}
+
+static int copy_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst,
+                      int32_t dst_tok0, hipStream_t stream) {
+  const bool gather = src->paged_kind == LMC_PAGED_SPLIT;
+  const lmc_kv_layout* sp = gather ? src : dst;
+  const lmc_kv_layout* rw = gather ? dst : src;
+  const bool b8 = lmc_dtype_fp8(sp->dtype);
+  const int X = b8 ? 16 : 8;  // elements of a 16-byte granule
+  const int tt = sp->block_size % 32 == 0 ? 32 : sp->block_size % 16 == 0 ? 16 : 8;
+  SplitCopyArgs a;
+  memset(&a, 0, sizeof a);
+  a.sp = to_addr(sp); a.rw = to_addr(rw);
+  a.sp_tok0 = gather ? tok_begin : dst_tok0; a.rw_tok0 = gather ? dst_tok0 : tok_begin; a.ntok = ntok;
+  a.P = 2 * sp->num_layers;
+  a.ntiles = (int)(((long long)ntok + 2 * tt - 2) / tt);  // the first tile may begin tt - 1 positions in front of the range
+  const size_t image = (size_t)tt * sp->head_size * (b8 ? 1 : 2);
+  auto mult = [X](int64_t v) { return v % X == 0; };
+  a.fast = sp->head_size / X >= 4 && image <= SPLIT_MAX_IMAGE && mult(sp->stride_block) && mult(sp->stride_head) &&
+           (sp->plane_ptrs || (mult(sp->stride_layer) && mult(sp->stride_kv))) && mult(rw->stride_token) &&
+           mult(rw->stride_head) && (!rw->slot_mapping || mult(rw->stride_block)) &&
+           (rw->plane_ptrs || (mult(rw->stride_layer) && mult(rw->stride_kv)));
+  HIP_TRY(hipSetDevice(c->device));
+  const long long items = (long long)a.P * a.ntiles * sp->num_heads;
+  long long blocks = (items + SPLIT_WAVES - 1) / SPLIT_WAVES;
+  if (blocks > 8LL * c->num_cus) blocks = 8LL * c->num_cus;  // grid-stride beyond eight workgroups per CU
+  const size_t lds = a.fast ? SPLIT_WAVES * image : 0;
+  if (b8) {
+    if (gather) launch_copy_split<u8, true>(a, tt, (unsigned)blocks, lds, stream);
+    else launch_copy_split<u8, false>(a, tt, (unsigned)blocks, lds, stream);
+  } else if (gather) launch_copy_split<u16, true>(a, tt, (unsigned)blocks, lds, stream);
+  else launch_copy_split<u16, false>(a, tt, (unsigned)blocks, lds, stream);
+  HIP_TRY(hipGetLastError());
+  return LMC_OK;
+}
+
+extern "C" {
+
 int lmc_copy_kv(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst,
                 int32_t dst_tok0, lmc_stream_t stream) {
-  if (!c || !layout_ok(src, false) || !layout_ok(dst, false) || ntok < 1 || tok_begin < 0 || dst_tok0 < 0) return LMC_ERR_INVALID;
+  if (!c || !layout_ok(src, false, true) || !layout_ok(dst, false, true) || ntok < 1 || tok_begin < 0 || dst_tok0 < 0)
+    return LMC_ERR_INVALID;
   if (src->num_layers != dst->num_layers || src->num_heads != dst->num_heads || src->head_size != dst->head_size ||
       src->dtype != dst->dtype)
     return LMC_ERR_INVALID;
+  if (src->paged_kind == LMC_PAGED_SPLIT || dst->paged_kind == LMC_PAGED_SPLIT) {
+    if (src->paged_kind == dst->paged_kind) return LMC_ERR_INVALID;  // one side is rows
+    return copy_split(c, src, tok_begin, ntok, dst, dst_tok0, (hipStream_t)stream);
+  }
   const bool vec = layout_ok(src) && layout_ok(dst);  // else one element per thread (any strides, any head_size)
   CopyArgs a;
   memset(&a, 0, sizeof a);

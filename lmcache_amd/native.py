@@ -105,7 +105,10 @@ class KvLayoutStruct(ctypes.Structure):
                 ("head_size", ctypes.c_int32), ("base", ctypes.c_void_p), ("plane_ptrs", ctypes.c_void_p),
                 ("stride_layer", ctypes.c_int64), ("stride_kv", ctypes.c_int64), ("stride_token", ctypes.c_int64),
                 ("stride_head", ctypes.c_int64), ("slot_mapping", ctypes.c_void_p), ("block_size", ctypes.c_int32),
-                ("_pad", ctypes.c_int32), ("stride_block", ctypes.c_int64)]
+                ("paged_kind", ctypes.c_int32), ("stride_block", ctypes.c_int64)]
+
+
+PAGED_ROWS, PAGED_SPLIT = 0, 1  # LMC_PAGED_*: lmc_kv_layout.paged_kind
 
 
 class BlobHeader(ctypes.Structure):
@@ -366,15 +369,18 @@ def pointer_table(ptrs: Sequence[int], device: torch.device) -> torch.Tensor:
 
 def _layout_struct(dt: torch.dtype, L: int, H: int, D: int, stride_token: int, stride_head: int, base: Optional[int] = None,
                    stride_layer: int = 0, stride_kv: int = 0, plane_ptrs: Optional[int] = None,
-                   slot_mapping: Optional[int] = None, block_size: int = 0, stride_block: int = 0) -> KvLayoutStruct:
+                   slot_mapping: Optional[int] = None, block_size: int = 0, stride_block: int = 0,
+                   paged_kind: int = PAGED_ROWS) -> KvLayoutStruct:
     """A filled lmc_kv_layout: the planes are addressed from `base` with layer / kv strides or through the device table
-    `plane_ptrs`, the tokens directly or (paged) through `slot_mapping` in blocks of `block_size`."""
+    `plane_ptrs`, the tokens directly or (paged) through `slot_mapping` in blocks of `block_size`; `paged_kind`
+    PAGED_SPLIT: the blocks are those of vLLM's ROCm paged-attention kernels (include/lmc_hip.h)."""
     s = KvLayoutStruct()
     s.dtype = dtype_code(dt)
     s.num_layers, s.num_heads, s.head_size = L, H, D
     s.base, s.plane_ptrs = base, plane_ptrs
     s.stride_layer, s.stride_kv, s.stride_token, s.stride_head = stride_layer, stride_kv, stride_token, stride_head
     s.slot_mapping, s.block_size, s.stride_block = slot_mapping, block_size, stride_block
+    s.paged_kind = paged_kind
     return s
 
 
@@ -406,8 +412,11 @@ class KVLayout:
     def vector_readable(self) -> bool:
         """Whether the encoders can read this layout with their 16-byte vectors of 8 channels (the rule of layout_ok in
         lmc_api.hip / include/lmc_hip.h): rows on 16-byte boundaries, strides multiples of 8 elements, and head_size a
-        multiple of 8 unless the heads of a token row lie back to back.  The decoders and lmc_copy_kv take any layout."""
+        multiple of 8 unless the heads of a token row lie back to back.  The decoders and lmc_copy_kv take any layout.
+        A PAGED_SPLIT layout ("NHDB") has no rows at all: only lmc_copy_kv reads or writes it."""
         s = self.struct
+        if s.paged_kind != PAGED_ROWS:
+            return False
         if s.head_size % 8:
             if s.stride_head != s.head_size:
                 return False
@@ -474,7 +483,10 @@ class KVLayout:
     def paged(kv_caches, slot_mapping: torch.Tensor, block_size: int, layout: str = "NBHD") -> "KVLayout":
         """vLLM paged KV: per layer a tensor [2, num_blocks, ...] addressed through slot_mapping
         (LLM_Engine.rst:91-122).  layout "NBHD" = [num_blocks, block_size, H, D] (flash layout),
-        "NHBD" = [num_blocks, H, block_size, D] (BASELINE.json north star)."""
+        "NHBD" = [num_blocks, H, block_size, D] (BASELINE.json north star), "NHDB" = the cache of vLLM's ROCm
+        paged-attention kernels (_paged_split below)."""
+        if layout == "NHDB":
+            return KVLayout._paged_split(kv_caches, slot_mapping, block_size)
         c0 = kv_caches[0]
         assert c0.is_cuda and c0.dim() == 5 and c0.shape[0] == 2
         st = c0.stride()
@@ -498,6 +510,69 @@ class KVLayout:
         s = _layout_struct(c0.dtype, len(kv_caches), H, D, stride_token, stride_head, plane_ptrs=table.data_ptr(),
                            slot_mapping=sm.data_ptr(), block_size=block_size, stride_block=st[1])
         return KVLayout(s, keep + [table, sm], sm.numel(), c0.device)
+
+    @staticmethod
+    def _paged_split(kv_caches, slot_mapping: torch.Tensor, block_size: int) -> "KVLayout":
+        """layout "NHDB": the cache that paged_attention_rocm and paged_attention_v1 / v2 read, as
+        PagedAttention.split_kv_cache views it.  With x = 16 / element bytes (8 for bf16 / fp16, 16 for fp8), per layer
+          - one tensor [2, num_blocks, H, D, block_size]: a copy-free .view of vLLM's [2, num_blocks, block_size * H * D];
+            index 1 IS the value cache, index 0 holds the keys in the x-split order of the next form, or
+          - the pair (key_cache [num_blocks, H, D / x, block_size, x], value_cache [num_blocks, H, D, block_size]).
+        A token's channels are not contiguous there (K: x-element granules block_size * x apart, V: every element
+        block_size apart), so the layout is not vector_readable() and only lmc_copy_kv takes it (k_copy_split.h)."""
+        first = kv_caches[0]
+        pair = isinstance(first, (tuple, list))
+        v0 = first[1] if pair else first
+        if not v0.is_cuda:
+            raise ValueError("the paged KV cache must live on the GPU")
+        x = 16 // elem_bytes(dtype_code(v0.dtype))  # (a uint8 cache is refused here: pass its fp8 view)
+        planes = []  # per layer (K base, V base, H, D, block size, (stride_block, stride_head, inner strides...) of K and of V)
+        for c in kv_caches:
+            if pair:
+                k, v = c
+                if k.dim() != 5 or v.dim() != 4:
+                    raise ValueError(f"NHDB pair: key_cache [num_blocks, H, D/x, block_size, x] and value_cache [num_blocks, H, D, "
+                                     f"block_size] expected, got {tuple(k.shape)} and {tuple(v.shape)}")
+                nb, H, D, bs = v.shape
+                if tuple(k.shape) != (nb, H, D // x, bs, x) or D % x:
+                    raise ValueError(f"NHDB pair: key_cache {tuple(k.shape)} is not [num_blocks, H, D/x, block_size, x] of "
+                                     f"value_cache {tuple(v.shape)} with x = {x} (head_size % x must be 0)")
+                ks, vs = k.stride(), v.stride()
+                dense = ks[2:] == (bs * x, x, 1) and vs[2:] == (bs, 1)
+                outer = (ks[0], ks[1]) if (ks[0], ks[1]) == (vs[0], vs[1]) else None
+            else:
+                if c.dim() != 5 or c.shape[0] != 2:
+                    raise ValueError(f"NHDB: a layer cache is [2, num_blocks, H, D, block_size], got {tuple(c.shape)}")
+                _, nb, H, D, bs = c.shape
+                k, v = c[0], c[1]
+                cs = c.stride()
+                dense = cs[3:] == (bs, 1)
+                outer = (cs[1], cs[2])
+            if k.dtype != v0.dtype or v.dtype != v0.dtype or k.device != v0.device or v.device != v0.device:
+                raise ValueError("all layer caches must share dtype and device")
+            if bs != block_size:
+                raise ValueError(f"NHDB: the cache's blocks hold {bs} slots, block_size is {block_size}")
+            if D % x:
+                raise ValueError(f"NHDB: head_size {D} is no multiple of x = {x} (16 bytes of {v0.dtype}): the key cache "
+                                 "splits a head into x-element granules")
+            if not dense:
+                raise ValueError("NHDB: the inner dimensions of a block's head (D/x, block_size, x for keys; D, block_size "
+                                 "for values) must be dense")
+            if outer is None:
+                raise ValueError("NHDB pair: key_cache and value_cache must share their block and head strides")
+            planes.append((k, v, H, D, outer))
+        _, _, H, D, (stride_block, stride_head) = planes[0]
+        if any(pl[2:] != planes[0][2:] for pl in planes):
+            raise ValueError("all layer caches must share shape and strides")
+        ptrs, keep = [], []
+        for k, v, *_ in planes:
+            ptrs += [k.data_ptr(), v.data_ptr()]
+            keep += [k, v]
+        table = _pointer_tables.get(ptrs, v0.device)
+        sm = slot_mapping.to(device=v0.device, dtype=torch.int64).contiguous()
+        s = _layout_struct(v0.dtype, len(planes), H, D, 0, stride_head, plane_ptrs=table.data_ptr(), slot_mapping=sm.data_ptr(),
+                           block_size=block_size, stride_block=stride_block, paged_kind=PAGED_SPLIT)
+        return KVLayout(s, keep + [table, sm], sm.numel(), v0.device)
 
 
 class PinnedBuffer:

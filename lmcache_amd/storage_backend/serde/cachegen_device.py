@@ -590,8 +590,9 @@ class CacheGenDeviceCodec:
     def _readable(self, src: native.KVLayout, tok_begin: int, tok_end: int):
         """The encoders read 16-byte vectors (native.KVLayout.vector_readable).  The reference's serde takes any shape
         (torch_quant_vectorized, cachegen_encoder.py:40-61), so a range of a layout that is not -- a head_size that is no
-        multiple of 8 under a huggingface / NHBD layout, rows off a 16-byte boundary -- is first brought into a
-        contiguous vllm chunk on the device (lmc_copy_kv copies element-wise then) and encoded from there."""
+        multiple of 8 under a huggingface / NHBD layout, rows off a 16-byte boundary, or the "NHDB" cache of vLLM's ROCm
+        paged-attention kernels, which has no rows at all -- is first brought into a contiguous vllm chunk on the device
+        (lmc_copy_kv: element-wise for the former, k_copy_split.h's gather for the latter) and encoded from there."""
         if src.vector_readable():
             return src, tok_begin, tok_end
         n = tok_end - tok_begin
