@@ -130,6 +130,7 @@ int lmc_ctx_reserve(lmc_ctx* ctx, int L, int H, int D, int chunk_tokens, int max
 #define LMC_STATUS_LOOKBACK_TIMEOUT 8u
 #define LMC_STATUS_BAD_SCALES 16u     /* decode: a plane's scales do not match their checksum (lmc_format.h: scsum) */
 #define LMC_STATUS_HOST_ARENA_FULL 32u /* lmc_store_chunks: the pinned arena cannot take the job's blobs */
+#define LMC_STATUS_BAD_POSITION 64u  /* rope shift: a token's |delta| is outside the table; that token is left as it was */
 /* A decode that raises any bit leaves the destination rows of the blobs concerned UNDEFINED (some of a plane's
  * waves may have stored before another wave saw the damage: BAD_SCALES is found by the plane's first wave only,
  * BAD_STREAM at the end of a stream).  A caller that decodes into live storage -- the paged entry points -- must
@@ -277,6 +278,39 @@ int lmc_decode_symbols(lmc_ctx* ctx, const void* blob, int32_t L, int32_t H, int
  */
 int lmc_copy_kv(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok,
                 const lmc_kv_layout* dst, int32_t dst_tok0, lmc_stream_t stream);
+
+/* ------------------------------------------------------------------ */
+/* RoPE shift: stored keys to new positions                            */
+/* ------------------------------------------------------------------ */
+/*
+ * Re-rotate, IN PLACE, the keys of tokens [tok_begin, +ntok) of `kv` by a position difference: a segment that was
+ * prefilled on its own carries the rotary embedding of positions 0 .. n-1, and placed at offset p in a later prompt
+ * (BASELINE.json configs[4]) every key needs R(p) applied first -- RoPE is a rotation group, R(new) = R(new - old) R(old),
+ * so the difference and the model's own table suffice.  Stands where the external connector gathers K by slot mapping,
+ * applies rotary_emb in torch and scatters K back (three passes and a temporary per layer): one pass over the K planes
+ * (k_rope.h), queued behind the decode / copy that filled them, on the same stream, with no host wait.
+ *   touches   the K planes (kv = 0) of ALL layers, the given tokens, channels [0, rot_dim) of every head; V planes,
+ *             channels >= rot_dim, other tokens and other slots are not written at all
+ *   cos_sin   device fp32 [table_rows][rot_dim]: row r = cos(r f_i) for i < rot_dim / 2, then sin(r f_i) -- the layout of
+ *             vLLM's cos_sin_cache widened to fp32; any scaling (llama-3, YaRN, ...) is whatever the caller baked in
+ *   delta     token tok_begin + i is shifted by d = deltas ? deltas[i] : delta; deltas: device int32 [ntok] or NULL
+ *   is_neox   != 0: x1 = channel i, x2 = channel i + rot_dim / 2 (NeoX);  0: x1 = channel 2i, x2 = channel 2i + 1 (GPT-J)
+ * With c = row |d| cos and s = sign(d) * row |d| sin:  o1 = x1 c - x2 s,  o2 = x2 c + x1 s, every product and sum rounded
+ * to fp32 by itself, then one round-to-nearest-even cast to the layout's dtype.  (The shifted key has then been rounded
+ * to 16 bits twice: when it was stored and now.)
+ * LMC_ERR_INVALID, with nothing launched: a layout the decoders would refuse; LMC_PAGED_SPLIT (only lmc_copy_kv takes
+ * it: shift the chunk before it is scattered); an fp8 dtype (rotating fp8 would round the key to 3 or 2 mantissa bits a
+ * second time: not offered); rot_dim odd, < 2 or > head_size; table_rows < 1; a uniform |delta| >= table_rows; ntok < 1,
+ * tok_begin < 0, a NULL table; ntok * num_heads * rot_dim / 2 >= 2^31 (split the range).
+ * A per-token |deltas[i]| >= table_rows leaves that token untouched and raises LMC_STATUS_BAD_POSITION in job_status (or
+ * in the context's sticky word when job_status is NULL), the way the decoders report.
+ * Two tokens of the range mapped to one slot: undefined, as for the scatter.  Rows on 16-byte boundaries with
+ * head_size % 8 == 0, whole 8-channel vectors per pair half (NeoX: rot_dim % 16 == 0, GPT-J: rot_dim % 8 == 0) and a
+ * 16-byte aligned table are rotated with 16-byte accesses; anything else one pair per thread (correct, not fast).
+ */
+int lmc_rope_shift(lmc_ctx* ctx, const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const float* cos_sin,
+                   int32_t table_rows, int32_t rot_dim, int32_t is_neox, int32_t delta, const int32_t* deltas,
+                   uint32_t* job_status, lmc_stream_t stream);
 
 /* ------------------------------------------------------------------ */
 /* host DRAM offload plumbing                                          */

@@ -27,6 +27,7 @@ import torch
 from lmcache_amd import native
 from lmcache_amd.config import LMCacheEngineConfig, LMCacheEngineMetadata
 from lmcache_amd.logging import init_logger
+from lmcache_amd.rope import RopeShift
 from lmcache_amd.storage_backend import CreateStorageBackend
 from lmcache_amd.utils import CacheEngineKey, KVCache, _lmcache_nvtx_annotate
 
@@ -244,7 +245,8 @@ class LMCacheEngine:
     @_lmcache_nvtx_annotate
     @torch.no_grad()
     def retrieve_into_paged(self, tokens: torch.Tensor, kv_caches, slot_mapping: torch.Tensor, block_size: int,
-                            layout: str = "NBHD", mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            layout: str = "NBHD", mask: Optional[torch.Tensor] = None,
+                            rope: Optional[RopeShift] = None) -> torch.Tensor:
         """retrieve() straight into a serving engine's PAGED KV cache: the decoded (or copied) KV of token t is
         written to slot slot_mapping[t] of every layer's cache -- the connector's `lmcache_retrieve_kv` +
         reshape_and_cache_flash scatter (LLM_Engine.rst:101-122) fused into the decode kernel's store.  Slots
@@ -257,16 +259,27 @@ class LMCacheEngine:
         that stream scatters tokens 0 .. got-1 into the cache (k_copy_split.h); nothing is launched when nothing was
         retrieved.  Costs: device memory the size of the retrieved KV for the duration of the call, and one more pass
         over it.  A side effect: a stored chunk that fails to decode never touches the live
-        cache, because the miss is decided before the scatter."""
+        cache, because the miss is decided before the scatter.
+          rope  a lmcache_amd.rope.RopeShift: the keys of the retrieved tokens are re-rotated to new positions on the way
+                (a segment that was prefilled on its own and is placed at offset p: delta = p; a per-token delta tensor
+                has one entry per token of `tokens`).  One lmc_rope_shift (k_rope.h) on the current stream behind the
+                decode or copy launches: on the paged cache itself for "NBHD" / "NHBD", on the staged chunk BEFORE the
+                scatter for "NHDB".  Nothing is launched on a miss.  The cache must be bf16 / fp16 and rope.rot_dim at
+                most its head size (ValueError before anything is queued).  A per-token delta outside the table leaves
+                that token's keys as stored and raises LMC_STATUS_BAD_POSITION in the context's status word (a delta
+                tensor that lives on the CPU is checked here instead: ValueError)."""
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
-        staged = {}
+        if rope is not None:
+            self._check_rope(rope, kv_caches, layout, len(tokens))
+        staged, made = {}, {}
 
         def make_dst(nret, L, H, D, dtype, dev):
             dst = native.KVLayout.paged(kv_caches, slot_mapping[num_skip_tok:num_skip_tok + nret], block_size, layout)
             assert dst.L == L and native.torch_dtype(dst.dtype) == dtype, "cache geometry / dtype differs from the stored chunks"
             if layout != "NHDB":
+                made["dst"] = dst
                 return dst
             assert (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
             staged["dst"] = dst
@@ -274,11 +287,40 @@ class LMCacheEngine:
             return native.KVLayout.from_chunk(staged["chunk"], "vllm")
 
         got, ret_mask = self._retrieve_into(tokens, mask, make_dst)
-        if staged and got > 0:
-            dst = staged["dst"]
+        if got > 0 and (staged or rope is not None):
+            dst = staged["dst"] if staged else made["dst"]
+            rows = native.KVLayout.from_chunk(staged["chunk"], "vllm") if staged else dst  # where the tokens lie as rows
             with torch.cuda.device(dst.device):
-                native.get_context(dst.device.index).copy_kv(native.KVLayout.from_chunk(staged["chunk"], "vllm"), 0, got, dst, 0)
+                ctx = native.get_context(dst.device.index)
+                if rope is not None:
+                    ctx.rope_shift(rows, 0, got, rope.cos_sin.to(dst.device), rope.rot_dim, rope.is_neox,
+                                   delta=0 if isinstance(rope.delta, torch.Tensor) else rope.delta,
+                                   deltas=rope.deltas_for(num_skip_tok, got, len(tokens), dst.device))
+                if staged:
+                    ctx.copy_kv(rows, 0, got, dst, 0)
         return ret_mask
+
+    @staticmethod
+    def _check_rope(rope: RopeShift, kv_caches, layout: str, ntokens: int) -> None:
+        """What retrieve_into_paged refuses of a RopeShift before anything is queued (ValueError)."""
+        first = kv_caches[0]
+        if layout == "NHDB":  # [2, num_blocks, H, D, block_size], or the (key_cache, value_cache [num_blocks, H, D, block_size]) pair
+            pair = isinstance(first, (tuple, list))
+            ref = first[1] if pair else first
+            D = ref.shape[2] if pair else ref.shape[3]
+        else:
+            ref, D = first, first.shape[-1]
+        if ref.dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"rope: a {ref.dtype} cache cannot be shifted (rotating fp8 keys would round them to 3 or 2 "
+                             "mantissa bits a second time); only bfloat16 / float16 caches are")
+        if rope.rot_dim > D:
+            raise ValueError(f"rope: rot_dim {rope.rot_dim} is larger than the cache's head size {D}")
+        if isinstance(rope.delta, torch.Tensor):
+            if rope.delta.numel() != ntokens:
+                raise ValueError(f"rope: a per-token delta needs one entry per token of the call: {rope.delta.numel()} "
+                                 f"for {ntokens} tokens")
+            if not rope.delta.is_cuda and ntokens and int(rope.delta.abs().max()) >= rope.table_rows:
+                raise ValueError(f"rope: a per-token delta is outside the table of {rope.table_rows} rows")
 
     @_lmcache_nvtx_annotate
     @torch.no_grad()

@@ -22,6 +22,7 @@
 #include "k_offload.h"
 #include "k_quantize.h"
 #include "k_repack.h"
+#include "k_rope.h"
 
 static thread_local int g_last_hip = 0;
 
@@ -755,6 +756,16 @@ static int copy_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, i
   return LMC_OK;
 }
 
+// Re-rotate the keys of tokens [tok_begin, +ntok) by a position difference, in place (k_rope.h).  The access form is
+// chosen as lmc_copy_kv chooses `vec`: 16-byte vectors where the rows, the head and the pair halves are whole vectors
+// (and the table's rows are), one pair per thread for everything else.
+template <int DT>
+static void launch_rope(bool vec, bool neox, dim3 grid, size_t lds, hipStream_t s, const RopeArgs& a) {
+  if (!vec) hipLaunchKernelGGL((k_rope_elem<DT>), grid, dim3(256), 0, s, a);
+  else if (neox) hipLaunchKernelGGL((k_rope_vec<DT, true>), grid, dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((k_rope_vec<DT, false>), grid, dim3(256), lds, s, a);
+}
+
 extern "C" {
 
 int lmc_copy_kv(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst,
@@ -783,6 +794,36 @@ int lmc_copy_kv(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t
     else hipLaunchKernelGGL(k_copy_kv_elem_b8, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   } else if (vec) hipLaunchKernelGGL(k_copy_kv, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_copy_kv_elem, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return LMC_OK;
+}
+
+int lmc_rope_shift(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const float* cos_sin,
+                   int32_t table_rows, int32_t rot_dim, int32_t is_neox, int32_t delta, const int32_t* deltas,
+                   uint32_t* job_status, lmc_stream_t stream) {
+  if (!c || !layout_ok(kv, false) || lmc_dtype_fp8(kv->dtype) || ntok < 1 || tok_begin < 0 || !cos_sin || table_rows < 1)
+    return LMC_ERR_INVALID;
+  if (rot_dim < 2 || (rot_dim & 1) || rot_dim > kv->head_size) return LMC_ERR_INVALID;
+  if (!deltas && (delta <= -table_rows || delta >= table_rows)) return LMC_ERR_INVALID;
+  const bool neox = is_neox != 0;
+  const bool vec = layout_ok(kv) && kv->head_size % 8 == 0 && rot_dim % (neox ? 16 : 8) == 0 && ((uintptr_t)cos_sin & 15) == 0;
+  RopeArgs a;
+  memset(&a, 0, sizeof a);
+  a.kv = to_addr(kv);
+  a.cos_sin = cos_sin; a.deltas = deltas; a.status = job_status ? job_status : c->status_h;
+  a.tok_begin = tok_begin; a.ntok = ntok; a.rot = rot_dim; a.table_rows = table_rows; a.delta = delta; a.neox = neox;
+  a.per_head = (u32)(vec ? rot_dim / (neox ? 16 : 8) : rot_dim / 2);
+  const long long nitems = (long long)ntok * kv->num_heads * a.per_head;  // of one layer: the kernels index it with 32 bits
+  if (nitems >= (1ll << 31)) return LMC_ERR_INVALID;
+  a.nitems = (u32)nitems;
+  HIP_TRY(hipSetDevice(c->device));
+  long long blocks = (nitems + 255) / 256;
+  const long long cap = std::max(1ll, 64ll * c->num_cus / kv->num_layers);  // grid-stride beyond 64 blocks per CU
+  if (blocks > cap) blocks = cap;
+  const dim3 grid((unsigned)blocks, (unsigned)kv->num_layers);
+  const size_t lds = vec && !deltas ? (size_t)rot_dim * sizeof(float) : 0;  // the one table row of a uniform delta
+  if (kv->dtype == LMC_DTYPE_BF16) launch_rope<LMC_DTYPE_BF16>(vec, neox, grid, lds, (hipStream_t)stream, a);
+  else launch_rope<LMC_DTYPE_FP16>(vec, neox, grid, lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return LMC_OK;
 }

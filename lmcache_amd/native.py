@@ -164,6 +164,7 @@ SYMBOLS = {
     "lmc_unpack_blobs": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "lmc_pack_chunk_bytes": (ctypes.c_int, [_vp, _u64, _i32, ctypes.POINTER(ctypes.c_uint32)]),
     "lmc_copy_kv": (ctypes.c_int, [_vp, _PL, _i32, _i32, _PL, _i32, _vp]),
+    "lmc_rope_shift": (ctypes.c_int, [_vp, _PL, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "lmc_pinned_alloc": (ctypes.c_int, [_sz, ctypes.POINTER(_vp)]),
     "lmc_pinned_free": (ctypes.c_int, [_vp]),
     "lmc_memcpy_async": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, _vp]),
@@ -818,9 +819,27 @@ class Context:
                    dst_tok0)
 
 
+    def rope_shift(self, layout: KVLayout, tok_begin: int, ntok: int, cos_sin: torch.Tensor, rot_dim: int,
+                   is_neox: bool = True, delta: int = 0, deltas: Optional[torch.Tensor] = None,
+                   job_status: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """lmc_rope_shift: the keys of tokens [tok_begin, +ntok) of `layout` re-rotated in place by `delta` positions (or
+        by deltas[i] for token tok_begin + i: device int32 [ntok]).  cos_sin: device fp32 [table_rows, rot_dim], the
+        model's cos_sin_cache (lmcache_amd.rope.RopeShift builds or widens one).  job_status: pinned word that receives
+        LMC_STATUS_BAD_POSITION for a per-token delta outside the table (None: the context's sticky word)."""
+        if not (cos_sin.is_cuda and cos_sin.dtype == torch.float32 and cos_sin.dim() == 2 and cos_sin.is_contiguous()
+                and cos_sin.shape[1] == rot_dim):
+            raise ValueError(f"cos_sin must be a contiguous device float32 [table_rows, rot_dim = {rot_dim}] tensor")
+        if deltas is not None and not (deltas.is_cuda and deltas.dtype == torch.int32 and deltas.is_contiguous()
+                                       and deltas.numel() == ntok):
+            raise ValueError(f"deltas must be a contiguous device int32 tensor of ntok = {ntok} entries")
+        self._call("lmc_rope_shift", layout.device, stream, ctypes.byref(layout.struct), tok_begin, ntok, cos_sin.data_ptr(),
+                   cos_sin.shape[0], rot_dim, 1 if is_neox else 0, int(delta), None if deltas is None else deltas.data_ptr(),
+                   job_status)
+
+
 def describe_status(st: int) -> str:
     names = [(1, "stream overflow"), (2, "bad blob header"), (4, "bad stream"), (8, "look-back timeout"), (16, "scale checksum mismatch"),
-             (32, "host arena full")]
+             (32, "host arena full"), (64, "rope delta outside the table")]
     return f"device status 0x{st:x} (" + ", ".join(n for b, n in names if st & b) + ")"
 
 
