@@ -74,6 +74,14 @@ int lmc_abi_version(void);
  * per-layer [T,H,D] tensors, NBHD blocks -- where any head_size will do).  The DECODERS' destination and both sides of
  * lmc_copy_kv take any strides and any head_size (lmc_copy_kv copies element-wise when a side is not vector-readable:
  * the way to bring such a range into a chunk the encoders take; lmcache_amd's codec does that by itself).
+ * "Any strides" of a DECODE destination ends where the decoder's 32-bit store offsets do.  With E = element bytes (2 or
+ * 1), row = ((H-1)*stride_head + D)*E (a token row, first channel to last) and row_step = stride_token*E:
+ *   stride_head >= 0 and stride_token >= 0;
+ *   without a slot_mapping   (chunk_tokens-1)*row_step + row <= 0xfffffff0   (the rows of one chunk, the last one's last
+ *                            channel included, lie within the store's range of the chunk's first row);
+ *   with a slot_mapping      row <= 0xfffffff0, and 7*row_step + row <= 0xfffffff0 while row_step < 2^28.
+ * Every decode and load entry point returns LMC_ERR_INVALID beyond that, before anything is queued.  (Planes, blocks and
+ * chunks may lie any distance apart: those offsets are 64-bit.)
  *
  * paged_kind = LMC_PAGED_ROWS (0) is all of the above: a token's head is a row of D contiguous elements.
  * paged_kind = LMC_PAGED_SPLIT (1) is the cache of vLLM's ROCm paged-attention kernels (paged_attention_rocm,

@@ -222,6 +222,34 @@ static bool layout_ok(const lmc_kv_layout* l, bool vec = true, bool split = fals
   return true;
 }
 
+// What k_decode's stores can address in a destination that layout_ok(dst, false) has passed (k_decode.h).  A stored
+// element of E bytes (2, fp8: 1) leaves through a raw buffer descriptor of 0xfffffff0 records: address = base (a token
+// row, 64-bit) + soffset (u32, scalar) + voffset (u32, the lane).  On gfx950 the range check covers the SUM, not voffset
+// alone as k_decode.h's comment has it: the store is dropped unless soffset + voffset + E <= 0xfffffff0 (idle lanes are
+// parked at voffset 0xfffffff8 for that reason).  tests/test_gpu_far_offsets.py holds this against the hardware: of a
+// chunk whose last row reached past the range, exactly the bytes at soffset + voffset >= 0xfffffff0 were missing (of a
+// head stride at the voffset-only limit, every row of a chunk but its first), and nothing was written anywhere else.
+//   voffset = lane_off = (u32)((h * stride_head + d) * E), at most  row - E  with  row = ((H - 1) * stride_head + D) * E;
+//   a negative or larger offset would be truncated to 32 bits: stride_head >= 0.
+//   soffset: without a slot mapping the descriptor stays at the chunk's first stored row and soffset grows by
+//   row_step = stride_token * E per token, u32 arithmetic, up to (rows stored - 1) * row_step with at most chunk_tokens
+//   rows (the kernel refuses a longer blob).  With a slot mapping every row has a descriptor based at the row itself
+//   (soffset 0), except on the block path -- taken only while row_step < 2^28 -- where the descriptor stands at the first
+//   of eight rows and soffset reaches 7 * row_step.  stride_token >= 0 for every destination: one rule.
+//       reach = slot_mapping ? (row_step < 2^28 ? 7 * row_step : 0) : (chunk_tokens - 1) * row_step
+//       admitted:  stride_head >= 0,  stride_token >= 0,  reach + row <= 0xfffffff0
+// (so a row always fits the range, and without a slot mapping a chunk's rows end within 4 GiB of its first row).
+// Every entry point that launches k_decode with a destination asks this before anything is queued.
+static bool decode_dst_ok(const lmc_kv_layout* d, long long chunk_tokens) {
+  typedef __int128 wide;  // (the products of two 64-bit strides and counts)
+  const wide E = lmc_dtype_fp8(d->dtype) ? 1 : 2;
+  if (d->stride_head < 0 || d->stride_token < 0) return false;
+  const wide row = ((wide)(d->num_heads - 1) * d->stride_head + d->head_size) * E;
+  const wide row_step = (wide)d->stride_token * E;
+  const wide reach = d->slot_mapping ? (row_step < ((wide)1 << 28) ? 7 * row_step : (wide)0) : (wide)(chunk_tokens - 1) * row_step;
+  return reach + row <= (wide)0xfffffff0ll;
+}
+
 static KvAddr to_addr(const lmc_kv_layout* l) {
   KvAddr a;
   a.base = (const u16*)l->base;
@@ -646,7 +674,7 @@ static int decode_range(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, int
 
 int lmc_decode_chunks(lmc_ctx* c, const void* blobs, uint64_t blob_stride, int32_t nchunks, const lmc_kv_layout* dst,
                       int32_t dst_tok0, int32_t chunk_tokens, uint32_t* job_status, lmc_stream_t stream) {
-  if (!layout_ok(dst, false) || chunk_tokens < 1) return LMC_ERR_INVALID;
+  if (!layout_ok(dst, false) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens)) return LMC_ERR_INVALID;
   DecodeArgs a;
   memset(&a, 0, sizeof a);
   int rc = decode_common(c, blobs, blob_stride, nchunks, dst->num_layers, dst->num_heads, dst->head_size, job_status, a);
@@ -659,8 +687,8 @@ int lmc_decode_chunks(lmc_ctx* c, const void* blobs, uint64_t blob_stride, int32
 int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
                              const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t layer_begin,
                              int32_t layer_count, uint32_t* job_status, lmc_stream_t stream) {
-  if (!layout_ok(dst, false) || chunk_tokens < 1 || !blob_ptrs || layer_begin < 0 || layer_count < 1 ||
-      layer_begin + layer_count > dst->num_layers)
+  if (!layout_ok(dst, false) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens) || !blob_ptrs || layer_begin < 0 ||
+      layer_count < 1 || layer_begin + layer_count > dst->num_layers)
     return LMC_ERR_INVALID;
   DecodeArgs a;
   memset(&a, 0, sizeof a);
@@ -678,7 +706,8 @@ int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_
                                const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
                                const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
                                lmc_stream_t stream) {
-  if (!layout_ok(dst, false) || chunk_tokens < 1 || !blob_ptrs || nranges < 1 || !layer_ends_h) return LMC_ERR_INVALID;
+  if (!layout_ok(dst, false) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens) || !blob_ptrs || nranges < 1 || !layer_ends_h)
+    return LMC_ERR_INVALID;
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)  // the whole schedule is checked before anything is launched
     if (layer_ends_h[i] <= prev || layer_ends_h[i] > dst->num_layers) return LMC_ERR_INVALID;
   if (layer_ends_h[nranges - 1] != dst->num_layers) return LMC_ERR_INVALID;
@@ -971,7 +1000,8 @@ static bool host_blob_ok(const u8* b, uint32_t size, int L, int H, int D, uint32
 int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint32_t* sizes_h, int32_t nchunks,
                     const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t layers_per_range,
                     lmc_event_t* range_events, uint32_t* job_status, lmc_stream_t stream) {
-  if (!c || !host_blob_ptrs_h || !sizes_h || nchunks < 1 || !layout_ok(dst, false) || chunk_tokens < 1 || layers_per_range < 0)
+  if (!c || !host_blob_ptrs_h || !sizes_h || nchunks < 1 || !layout_ok(dst, false) || chunk_tokens < 1 || layers_per_range < 0 ||
+      !decode_dst_ok(dst, chunk_tokens))
     return LMC_ERR_INVALID;
   const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
   if (H * D > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
@@ -1179,7 +1209,7 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
                   uint32_t* job_status, lmc_stream_t stream) {
   lmc_pack_header h;
   if (!c || !layout_ok(dst, false) || layers_per_range < 0 || nchunks < 0 || chunk_begin < 0 ||
-      !pack_ok((const u8*)pack_h, pack_bytes, &h))
+      !pack_ok((const u8*)pack_h, pack_bytes, &h) || !decode_dst_ok(dst, (long long)h.chunk_tokens))
     return LMC_ERR_INVALID;
   const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
   if ((uint32_t)L != h.num_layers || (uint32_t)H != h.num_heads || (uint32_t)D != h.head_size || H * D > LMC_MAX_CHANNELS ||
