@@ -67,8 +67,11 @@ __device__ __forceinline__ u32 draw_ticket(u32* ticket, u32 base) {
 #define AGG_X 0ull  // not published yet
 #define AGG_A 1ull  // value = this group's own padded length
 #define AGG_P 2ull  // value = inclusive prefix up to and including this group
-__device__ __forceinline__ void agg_store(unsigned long long* p, unsigned long long flag, u32 v) {
-  __hip_atomic_store(p, (flag << 62) | (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// `epoch` (1 .. 2^30 - 1, bits 32 .. 61): the fused kernel's granules carry their launch's (k_fused.h); everybody else's
+// are zeroed before the launch and carry 0.
+__device__ __forceinline__ void agg_store(unsigned long long* p, unsigned long long flag, u32 v, u32 epoch = 0u) {
+  __hip_atomic_store(p, (flag << 62) | ((unsigned long long)epoch << 32) | (unsigned long long)v, __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ unsigned long long agg_load(unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -143,15 +146,20 @@ struct PendingTile {
 // workgroups dispatched no later than ours, in an earlier or the same round, and never wait on us.
 // Exclusive prefix of granule `idx` over the granule array `agg` (decoupled look-back, one wave): walks back 64
 // granules at a time until it meets an inclusive prefix; waits while a granule it needs is unpublished.
-__device__ __forceinline__ u32 lookback_exclusive(unsigned long long* agg, int idx0, int lane, u32* status) {
+// EPOCH (the fused kernel): the granules carry their launch's epoch, and one of another launch reads as "not
+// published" -- nothing zeroes them between jobs.  A waiting fused wave sleeps longer (~0.3 us): it shares its CU with
+// coding workgroups and should cost issue slots as rarely as possible.
+template <bool EPOCH = false>
+__device__ __forceinline__ u32 lookback_exclusive(unsigned long long* agg, int idx0, int lane, u32* status, u32 epoch = 0u) {
   u32 excl = 0;
   if (idx0 > 0) {
     int base = idx0 - 1;
     u32 spins = 0;
     for (;;) {
       const int idx = base - lane;
-      const unsigned long long v = idx >= 0 ? agg_load(agg + idx) : ((AGG_P << 62) | 0ull);  // virtual granule -1
-      const u32 flag = (u32)(v >> 62);
+      const unsigned long long v = idx >= 0 ? agg_load(agg + idx) : ((AGG_P << 62) | ((unsigned long long)epoch << 32));  // virtual granule -1
+      const bool ours = !EPOCH || ((u32)(v >> 32) & 0x3fffffffu) == epoch;
+      const u32 flag = ours ? (u32)(v >> 62) : (u32)AGG_X;
       const u64 mP = __ballot(flag == (u32)AGG_P), mX = __ballot(flag == (u32)AGG_X);
       const int first = mP ? __builtin_ctzll(mP) : 64;  // nearest predecessor with a full prefix
       const u64 below = first >= 64 ? ~0ull : ((1ull << first) - 1ull);
@@ -160,7 +168,7 @@ __device__ __forceinline__ u32 lookback_exclusive(unsigned long long* agg, int i
           if (lane == 0) atomicOr(status, LMC_ST_LOOKBACK_TIMEOUT);
           break;
         }
-        __builtin_amdgcn_s_sleep(2);
+        __builtin_amdgcn_s_sleep(EPOCH ? 10 : 2);
         continue;
       }
       excl += wave_sum_u32(lane <= first ? (u32)v : 0u);
@@ -178,23 +186,21 @@ __device__ __forceinline__ u32 lookback_exclusive(unsigned long long* agg, int i
 // register budget (8 pieces: 144 bytes of spills in the coder loops, measured +20 % on k_cdf_encode).  So the batch
 // lands in LDS: global_load_lds_dwordx4 (gfx950) writes lane l's 16 bytes to M0 + 16 l without a destination
 // register, four of them fill the wave's idle 4 KiB table slice, and the pieces go out from there -- 3 round trips.
-#ifndef LMC_PLACE_BATCH
-#define LMC_PLACE_BATCH 4  // KiB of LDS = loads in flight
-#endif
+constexpr int PLACE_BATCH = 4;  // KiB of LDS = loads in flight: the wave's table slice
 __device__ __forceinline__ void copy_stream16(uint4* dst, const uint4* src, u32 n16_v, u32* lds4k, int lane) {
   typedef __attribute__((address_space(1))) const void* gptr;
   typedef __attribute__((address_space(3))) void* lptr;
   const u32 n16 = (u32)__builtin_amdgcn_readfirstlane((int)n16_v);  // wave-uniform: scalar loop control
 #pragma unroll 1
-  for (u32 base = 0; base < n16; base += 64u * LMC_PLACE_BATCH) {
+  for (u32 base = 0; base < n16; base += 64u * PLACE_BATCH) {
 #pragma unroll
-    for (int k = 0; k < LMC_PLACE_BATCH; k++) {
+    for (int k = 0; k < PLACE_BATCH; k++) {
       const u32 i = base + 64u * k + lane;
       __builtin_amdgcn_global_load_lds((gptr)(src + (i < n16 ? i : n16 - 1u)), (lptr)(lds4k + 256 * k), 16, 0, 0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int k = 0; k < LMC_PLACE_BATCH; k++) {
+    for (int k = 0; k < PLACE_BATCH; k++) {
       const u32 i = base + 64u * k + lane;
       const uint4 v = *reinterpret_cast<const uint4*>(lds4k + 256 * k + 4 * lane);
       // the placed streams are not read again by this kernel: non-temporal stores

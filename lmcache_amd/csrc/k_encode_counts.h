@@ -252,7 +252,7 @@ __device__ __forceinline__ void counts_table_byte_pk(const u32 (&mp)[8], u16* ta
 // lmc_counts_lane_words(S) words per lane -- + the 64 states.  Wave g == 0 also writes the checksum of the plane's
 // scales.  The slice is free again on return.
 // PLANE (round 6, k_fused.h): the counters are already there -- the plane's histogram was taken while the plane was
-// quantised, into the workgroup's eight table slices at LDS address 0 (k_fused.h: quantize_oct_hist has the layout):
+// quantised, into the workgroup's eight table slices at LDS address 0 (k_fused.h: quantize_oct has the layout):
 // the lane reads its channel's 16 / 32 counters instead of 32 / 64 workspace dwords, and its slice is not touched.
 template <bool ALIGNED = false, bool PLANE = false>
 __device__ __forceinline__ u32 counts_hist_stream(const EncodeArgs& a, const CountsStream& s, u32* tabmem,
@@ -472,20 +472,14 @@ __device__ __forceinline__ u32 counts_code_stream(const EncodeArgs& a, const Cou
   // out `pre` bytes full (pre = the distance of the first word from the 256-byte boundary below it: slots nobody
   // writes), the descriptor's base is that boundary, and the FIRST piece leaves without its first `pre` bytes; every
   // later piece is two whole 128-byte lines.  Same bytes in the blob.
-#ifndef LMC_FLUSH_ALIGN
-#define LMC_FLUSH_ALIGN 1
-#endif
-  const u32 pre = LMC_FLUSH_ALIGN ? (u32)__builtin_amdgcn_readfirstlane((int)((u32)(size_t)out & 255u)) : 0u;  // a multiple of 16 (the caller's contract)
+  const u32 pre = (u32)__builtin_amdgcn_readfirstlane((int)((u32)(size_t)out & 255u));  // a multiple of 16 (the caller's contract)
   u32 skip = pre;      // bytes at the front of the next piece that are not the stream's (pre until the first piece has left)
   u32 wb = ring_addr + pre;
   const u32 wlimit = ring_addr + 256u;
   u32 flushed = 0;     // words already in global memory (a multiple of 128, counted from the boundary), wave-uniform
   const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((u8*)out - pre), (short)0, (int)0xfffffff0u, 0x00020000);
   auto flush_ring = [&]() {
-#ifndef LMC_FLUSH_LIKELY
-#define LMC_FLUSH_LIKELY 0  // 0: the flush is laid out behind the loop (the common path falls through an untaken branch)
-#endif
-    if (__builtin_expect(wb >= wlimit, LMC_FLUSH_LIKELY)) {
+    if (__builtin_expect(wb >= wlimit, 0)) {  // the flush is laid out behind the loop: the common path falls through an untaken branch
       wave_lds_fence();
       // (the lane's slot address is worked out HERE, behind an opaque asm: hoisted out of the token loop it becomes one
       // more live register, which the 64-VGPR kernels spill -- and its reload in this block waits for vmcnt(0), i.e.
@@ -498,7 +492,7 @@ __device__ __forceinline__ u32 counts_code_stream(const EncodeArgs& a, const Cou
       // (uniform base in the descriptor, the lane in the vector offset, the stream position in the scalar offset)
       const u32 voff = 4u * lane_here;
 #ifndef LMC_EXP_ENC_NO_FLUSH  // (timing experiment: the coder without its stream stores; blobs are wrong)
-      if (!LMC_FLUSH_ALIGN || voff >= skip) __builtin_amdgcn_raw_buffer_store_b32((int)v, out_rsrc, (int)voff, (int)(flushed << 1), NT ? 2 : 0);
+      if (voff >= skip) __builtin_amdgcn_raw_buffer_store_b32((int)v, out_rsrc, (int)voff, (int)(flushed << 1), NT ? 2 : 0);
       skip = 0;
 #else
       asm volatile("" :: "v"(v), "v"(voff));
@@ -644,10 +638,7 @@ __device__ __forceinline__ u32 counts_code_stream(const EncodeArgs& a, const Cou
         emit(E0, E2, ra);  // (wb += 2 * words)
         const u32x2_t R2 = *(const __attribute__((address_space(3))) u32x2_t*)(size_t)(rtab_addr + ra);
         const ET E4 = entry_at(ad4);
-#ifndef LMC_FLUSH_EVERY
-#define LMC_FLUSH_EVERY 2  // tokens between two tests of the staging buffer (1 or 2: the buffer holds 128 + 2 x 64 words)
-#endif
-        if constexpr (LMC_FLUSH_EVERY == 1 || (i & 1) == 0) flush_ring();
+        if constexpr ((i & 1) == 0) flush_ring();  // every second token: the buffer holds 128 + 2 x 64 words
         if constexpr (NIB) rans_put_nib(E0, R0.x, R0.y);
         else rans_put_byte(E0, R0.x, R0.y);
         E0 = E1; E1 = E2; E2 = E3; E3 = E4;

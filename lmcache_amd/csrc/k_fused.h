@@ -2,13 +2,13 @@
 //
 // The two-kernel encode (k_quantize, then k_cdf_encode) runs an HBM-bound phase and a VALU-bound phase one after
 // the other.  Here a workgroup of FUSED_WAVES waves owns one plane-chunk from the raw KV to the streams in the blob:
-//   phase A   its waves quantise the plane-chunk's row octs (quantize_oct_fused, a wave = 8 token rows x all
-//             channels: the row max never leaves the wave), symbols to the plane-chunk's workspace region, scales
-//             to the blob;
+//   phase A   its waves quantise the plane-chunk's row octs (quantize_oct, a wave = 8 token rows x all channels: the
+//             row max never leaves the wave; narrow planes: quantize_task, k_quantize.h), symbols to the plane-chunk's
+//             workspace region AND into the plane's histogram in LDS (GL >= 32), scales to the blob;
 //   barrier   (workgroup scope is enough: the region is written and read by waves of one CU)
-//   pass 1    wave w takes the histograms of the group streams w, w + FUSED_WAVES (counts_hist_stream): the counts stay
-//             in its registers, and every stream's ALLOCATION in the blob follows from them (lmc_format.h, v6: an
-//             upper bound of its length);
+//   pass 1    wave w takes the counts of the group streams w, w + FUSED_WAVES (counts_hist_stream: from phase A's
+//             histogram, GL == 16 from the workspace): they stay in its registers, and every stream's ALLOCATION in
+//             the blob follows from them (lmc_format.h, v6: an upper bound of its length);
 //   placement ONE look-back per plane-chunk over P granules per chunk on the sum of the allocations: every stream of
 //             the plane-chunk knows its final place BEFORE it is coded;
 //   pass 2    head, table, interleaved rANS (counts_open_stream, counts_code_stream) -- the symbols come back from L2,
@@ -24,11 +24,13 @@
 // The look-back granules carry the launch's epoch (flag << 62 | epoch << 32 | value): a granule of another
 // launch reads as "not published", so nothing has to zero them between jobs.
 //
-// Work item = a run of whole planes of one chunk (FusedArgs::pl planes, ipc items per chunk), sized so that an item
-// is about half a megabyte of raw KV whatever the plane width:
-//   C <= 128   (GL = 16)  8 planes per item, <= 16 streams; a wave quantises four row octs at a time, 16 lanes each
-//   C <= 256   (GL = 32)  4 planes per item, <= 16 streams; two row octs at a time
+// Work item = a run of whole planes of one chunk (FusedArgs::pl planes, ipc items per chunk).  Narrow planes are grouped
+// until an item has about eight streams, one per wave (pl = 8 / G, G = streams per plane; lmc_api.hip has the measurement):
+//   C <= 64    (GL = 16)  8 planes per item, 8 streams; a wave quantises four row octs at a time, 16 lanes each
+//   C <= 128   (GL = 16)  4 planes per item, 8 streams
+//   C <= 256   (GL = 32)  2 planes per item, 6 or 8 streams; two row octs at a time
 //   C <= 1024  (GL = 64)  1 plane, <= 16 streams (NITER = 1 or 2 channel runs per lane)
+// (LMC_FUSED_PL, INTEGRATION.md, overrides pl for the narrow planes: up to FUSED_MAX_NS streams per item.)
 // Planes of more than 1024 channels (C = 4096 is BASELINE configs[0]) take the two-kernel path: a fused form for them
 // (2 / 4 waves sharing a row oct, the counts of a wave's 4 / 8 streams parked in a global stash between the passes)
 // was built in round 4, bit-exact, and never beat k_quantize + k_cdf_encode below eight generations of workgroups --
@@ -39,17 +41,13 @@
 #include "k_quantize.h"
 
 #define FUSED_MAX_NS 16  // streams per work item
-#ifndef FUSED_WAVES
-#define FUSED_WAVES 8  // waves per workgroup: 4 workgroups per CU
-#endif
+#define FUSED_WAVES 8    // waves per workgroup: 4 workgroups per CU; their eight 4 KiB table slices are the plane's histogram
 // Cache policy.  The symbol workspace is written and read back within a workgroup's life, and 1024 workgroups' worth
 // of it is what L2 + Infinity Cache should hold -- so everything that is touched ONCE says so: the raw KV is loaded
 // non-temporal, the streams are stored non-temporal (counts_code_stream<true>), the coding pass reads its symbols for
 // the last time non-temporal (LMC_SYM_LAST_LOAD, k_encode_counts.h).  Round 3, same box, alternating processes:
 // 1.017-1.027 ms without, 0.968-0.975 with.
-#ifndef LMC_FUSED_PRIO_A
-#define LMC_FUSED_PRIO_A 3  // wave priority while a wave fetches / quantises (phase A): its few instructions go first
-#endif
+constexpr int FUSED_PRIO_A = 3;  // wave priority while a wave fetches / quantises (phase A): its few instructions go first
 
 #ifdef LMC_EXP_TIMELINE  // experiments only: phase time stamps of every work item (tools/probes/fused_timeline.hip / .py)
 __device__ unsigned long long g_fused_timeline[8192 * 8];
@@ -69,41 +67,6 @@ struct FusedArgs {
                  // granules published
 };
 
-__device__ __forceinline__ void aggE_store(unsigned long long* p, unsigned long long flag, u32 epoch, u32 v) {
-  __hip_atomic_store(p, (flag << 62) | ((unsigned long long)epoch << 32) | (unsigned long long)v, __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// lookback_exclusive (k_encode.h) over epoch-tagged granules.
-__device__ __forceinline__ u32 lookback_exclusive_epoch(unsigned long long* agg, int idx0, u32 epoch, int lane, u32* status) {
-  u32 excl = 0;
-  if (idx0 > 0) {
-    int base = idx0 - 1;
-    u32 spins = 0;
-    for (;;) {
-      const int idx = base - lane;
-      const unsigned long long v = idx >= 0 ? agg_load(agg + idx) : ((AGG_P << 62) | ((unsigned long long)epoch << 32));
-      const bool ours = ((u32)(v >> 32) & 0x3fffffffu) == epoch;
-      const u32 flag = ours ? (u32)(v >> 62) : (u32)AGG_X;
-      const u64 mP = __ballot(flag == (u32)AGG_P), mX = __ballot(flag == (u32)AGG_X);
-      const int first = mP ? __builtin_ctzll(mP) : 64;
-      const u64 below = first >= 64 ? ~0ull : ((1ull << first) - 1ull);
-      if (mX & below) {
-        if (++spins > (1u << 24)) {
-          if (lane == 0) atomicOr(status, LMC_ST_LOOKBACK_TIMEOUT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(10);  // ~0.3 us: a waiting wave should cost issue slots as rarely as possible
-        continue;
-      }
-      excl += wave_sum_u32(lane <= first ? (u32)v : 0u);
-      if (mP) break;
-      base -= 64;
-    }
-  }
-  return excl;
-}
-
 // The offset of token t's row.  PSRC (round 6): the kernel instance for a PAGED source whose block size is a power of
 // two.  lmc_tok_off reads the token's slot with a vector load, and the wait for it is an s_waitcnt vmcnt(0) -- which on
 // gfx9 also waits for the acknowledgement of every symbol store issued before: eight such stalls per row oct (the encode
@@ -121,142 +84,6 @@ __device__ __forceinline__ long long fused_tok_off(const KvAddr& a, int t) {
   }
 }
 
-// One row oct (tokens t_first .. t_first + 7 of the plane) by one wave: quantize_task<64, NITER, DT, QUAD, NIB>
-// (k_quantize.h) re-staged for 64 VGPRs -- the same arithmetic (quant_z2 / v_cvt_pk_u8_f32 on regular rows,
-// quant_special on zero / inf / NaN rows), two rows in flight, one row quad of accumulators at a time: a byte
-// plane stores each quad as soon as it is complete; a nibble plane parks the first quad's 8 * NITER dwords in
-// the wave's idle LDS slice and merges them with the second (byte k = token k | token 4 + k << 4).
-// FULL: every lane of every iteration holds channels of the plane (C == NITER * 512: Llama / Mistral GQA
-// shapes), so no per-lane validity is tested and no register is zero-filled for absent channels.
-// ALLROWS: all eight rows of the oct are tokens of the chunk (every oct but the last one of a chunk whose length is no
-// multiple of 8): no per-row test, no zero fill -- what the kernel had when it only took 256-token chunks.
-template <int NITER, int DT, bool NIB, bool FULL = false, bool ALLROWS = true, bool PSRC = false>
-__device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const typename KvElem<DT>::T* pbase, int tok0, int Tc, int t_first,
-                                                   bool q1valid, int C, float maxf, u32* sym_out, u16* scale_out,
-                                                   uint4* park, int lane) {
-  long long coff[NITER];
-  int c0[NITER];
-  bool cval[NITER];
-#pragma unroll
-  for (int it = 0; it < NITER; it++) {
-    c0[it] = (it * 64 + lane) * 8;
-    cval[it] = FULL || c0[it] < C;
-    const int h = c0[it] / src.D, d = c0[it] - h * src.D;
-    coff[it] = (long long)h * src.stride_head + d;
-  }
-  const f32x2_t maxf2 = {maxf, maxf};
-#pragma unroll
-  for (int hq = 0; hq < 2; hq++) {
-    u32 o[NITER][8];  // byte r = symbol of (token t_first + 4 hq + r, channel c0[it] + e); row 0 of the quad defines it
-#pragma unroll
-    for (int r0 = 0; r0 < 4; r0 += 2) {
-      uint4 v[2][NITER];
-      bool tv[2];
-#pragma unroll
-      for (int r = 0; r < 2; r++) {
-        const int t = t_first + 4 * hq + r0 + r;
-        tv[r] = ALLROWS || t < Tc;
-        const typename KvElem<DT>::T* rowp = pbase + (tv[r] ? fused_tok_off<PSRC>(src, tok0 + t) : 0);
-#pragma unroll
-        for (int it = 0; it < NITER; it++) {
-          if (tv[r] && (FULL || cval[it])) v[r][it] = kv_ld8<DT, true>(rowp + coff[it]);  // streamed once
-          else v[r][it] = make_uint4(0, 0, 0, 0);
-        }
-      }
-      u32 mrow[2];
-#pragma unroll
-      for (int r = 0; r < 2; r++) {
-        u32 m = 0;
-#pragma unroll
-        for (int it = 0; it < NITER; it++) {
-          m = kv_absmax8<DT>(m, v[r][it]);
-        }
-        mrow[r] = max(m & 0xffffu, m >> 16);
-      }
-      wave_max2_u32(mrow[0], mrow[1]);  // wave-uniform from here on
-      mrow[0] = kv_max_scale<DT>(mrow[0]);  // (fp8: the max's bf16 image; else the max itself)
-      mrow[1] = kv_max_scale<DT>(mrow[1]);
-      if (lane == 0) {
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-          if (tv[r]) scale_out[4 * hq + r0 + r] = (u16)mrow[r];
-      }
-      float factor[2];
-      bool special[2] = {false, false};
-      u32 slow = 0;  // (an integer, not a bool: a bool merged over the branch below becomes a lane mask, and testing it
-                     // costs two vector instructions in front of every block of eight elements)
-      // both row maxes are wave-uniform: one scalar branch picks the short division for the pair -- and a max inside
-      // its range is finite, non-zero and has a finite factor, so such a pair cannot be special: no tests at all
-      const bool short_div = LMC_SHORT_ROW_DIV && row_div_in_range(mrow[0], lmc_math_dtype(DT)) && row_div_in_range(mrow[1], lmc_math_dtype(DT));
-      if (short_div) {
-#pragma unroll
-        for (int r = 0; r < 2; r++) factor[r] = row_div_short(maxf, h2f_rt(mrow[r], lmc_math_dtype(DT)));
-      } else {
-        bool any_special = false;
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-          const float sf = h2f_rt(mrow[r], lmc_math_dtype(DT));
-          factor[r] = maxf / sf;  // IEEE fp32 division (lmc_device.h)
-          special[r] = !(__builtin_fabsf(factor[r]) < __builtin_inff()) || !(sf < __builtin_inff());
-          any_special |= special[r];
-        }
-        slow = __ballot(any_special) != 0 ? 1u : 0u;  // wave-uniform and rare
-      }
-#pragma unroll
-      for (int it = 0; it < NITER; it++) {
-        if (!FULL && !cval[it]) continue;
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-          const u32 w[4] = {v[r][it].x, v[r][it].y, v[r][it].z, v[r][it].w};
-          // (the test stays inside the loops over runs and rows -- a wave-uniform test and two taken scalar branches per run
-          // and row, the regular path jumping over the special-row code.  ONE branch around the whole pair's conversions
-          // was built in round 5: the scheduler then interleaves both runs and both rows of the straight-line regular path
-          // and the kernel spills 184 bytes per lane instead of 20.)
-          if (slow == 0u) {
-            const f32x2_t f2 = {factor[r], factor[r]};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-              const f32x2_t z = quant_z2(kv_lo<DT>(w, k), kv_hi<DT>(w, k), f2, maxf2);
-              o[it][2 * k] = __builtin_amdgcn_cvt_pk_u8_f32(z.x, r0 + r, r0 + r ? o[it][2 * k] : 0u);
-              o[it][2 * k + 1] = __builtin_amdgcn_cvt_pk_u8_f32(z.y, r0 + r, r0 + r ? o[it][2 * k + 1] : 0u);
-            }
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-              const float xl = kv_lo<DT>(w, k), xh = kv_hi<DT>(w, k);
-              const u32 sl_ = (special[r] ? quant_special(xl, factor[r], maxf) : quant_fast(xl, factor[r], maxf)) & 0xffu;
-              const u32 sh_ = (special[r] ? quant_special(xh, factor[r], maxf) : quant_fast(xh, factor[r], maxf)) & 0xffu;
-              o[it][2 * k] = (r0 + r ? o[it][2 * k] : 0u) | sl_ << (8 * (r0 + r));
-              o[it][2 * k + 1] = (r0 + r ? o[it][2 * k + 1] : 0u) | sh_ << (8 * (r0 + r));
-            }
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < NITER; it++) {
-      if (!FULL && !cval[it]) continue;
-      if (NIB) {
-        uint4* pk = park + (it * 2) * 64 + lane;
-        if (hq == 0) {
-          pk[0] = make_uint4(o[it][0], o[it][1], o[it][2], o[it][3]);
-          pk[64] = make_uint4(o[it][4], o[it][5], o[it][6], o[it][7]);
-        } else {
-          const uint4 a0 = pk[0], a1 = pk[64];
-          u32* dst = sym_out + c0[it];
-          *reinterpret_cast<uint4*>(dst) = make_uint4(a0.x | (o[it][0] << 4), a0.y | (o[it][1] << 4), a0.z | (o[it][2] << 4), a0.w | (o[it][3] << 4));
-          *reinterpret_cast<uint4*>(dst + 4) = make_uint4(a1.x | (o[it][4] << 4), a1.y | (o[it][5] << 4), a1.z | (o[it][6] << 4), a1.w | (o[it][7] << 4));
-        }
-      } else {
-        if (hq == 1 && !q1valid) continue;
-        u32* dst = sym_out + (long long)hq * C + c0[it];  // the oct's row quads are adjacent [quad][channel] rows
-        *reinterpret_cast<uint4*>(dst) = make_uint4(o[it][0], o[it][1], o[it][2], o[it][3]);
-        *reinterpret_cast<uint4*>(dst + 4) = make_uint4(o[it][4], o[it][5], o[it][6], o[it][7]);
-      }
-    }
-  }
-}
-
 // ---- the plane's histogram taken WHILE it is quantised (round 6) ------------------------------------------------------
 // Pass 1 used to read every symbol back from the workspace only to count it: one of the symbols' two re-reads
 // (0.64 GB of the fused kernel's 4.6 GB of fabric traffic per 16 k context).  For planes of 257 .. 1024 channels
@@ -271,24 +98,22 @@ __device__ __forceinline__ void quantize_oct_fused(const KvAddr& src, const type
 // The counters are LDS atomics (eight waves add into the same plane); pass 1 then reads 16 / 32 counters per lane instead
 // of 32 / 64 workspace dwords and 256 ds_add of its own.  The instruction count is the same (2 VALU + 1 ds_add per
 // symbol, moved from pass 1 into phase A); the symbols are read once, by pass 2.
-// Nibble planes pair rows (q, q + 4) -- the two tokens that share a byte of the workspace dword -- instead of parking
-// the first row quad in the table slice: the slices are the histogram now.  The high row costs one v_lshl_or_b32 per
-// element more than the byte insert of v_cvt_pk_u8_f32 alone.
-#ifndef LMC_FUSED_HIST_A
-#define LMC_FUSED_HIST_A 1
-#endif
-#ifndef LMC_FUSED_HIST_A_BYTE
-#define LMC_FUSED_HIST_A_BYTE 1  // ... for the planes with more than 16 symbols as well
-#endif
-#ifndef LMC_FUSED_HIST_A_NARROW
-#define LMC_FUSED_HIST_A_NARROW 1  // ... and for items of several narrow planes (C <= 256)
-#endif
-// quantize_oct_fused with the histogram: one row oct by one wave, symbols to the workspace AND into the plane's counters.
+// Nibble planes pair rows (q, q + 4) -- the two tokens that share a byte of the workspace dword -- so that a dword is
+// complete in registers (the table slices are the histogram: nothing can be parked there).  The high row costs one
+// v_lshl_or_b32 per element more than the byte insert of v_cvt_pk_u8_f32 alone.
+//
+// One row oct (tokens t_first .. t_first + 7 of the plane) by one wave, symbols to the workspace AND into the plane's
+// counters: quantize_task<64, NITER, DT, QUAD, NIB> (k_quantize.h) re-staged for 64 VGPRs -- the same arithmetic
+// (quant_z2 / v_cvt_pk_u8_f32 on regular rows, quant_special on zero / inf / NaN rows), two rows in flight.
+// FULL: every lane of every iteration holds channels of the plane (C == NITER * 512: Llama / Mistral GQA
+// shapes), so no per-lane validity is tested and no register is zero-filled for absent channels.
+// ALLROWS: all eight rows of the oct are tokens of the chunk (every oct but the last one of a chunk whose length is no
+// multiple of 8): no per-row test, no zero fill -- what the kernel had when it only took 256-token chunks.
 // skip0: the oct holds token 0 of the chunk (byte planes leave it out of the counters).
 template <int NITER, int DT, bool NIB, bool FULL, bool ALLROWS, bool PSRC = false>
-__device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const typename KvElem<DT>::T* pbase, int tok0, int Tc, int t_first,
-                                                  bool q1valid, bool skip0, int C, float maxf, u32* sym_out, u16* scale_out,
-                                                  int lane) {
+__device__ __forceinline__ void quantize_oct(const KvAddr& src, const typename KvElem<DT>::T* pbase, int tok0, int Tc, int t_first,
+                                             bool q1valid, bool skip0, int C, float maxf, u32* sym_out, u16* scale_out,
+                                             int lane) {
   long long coff[NITER];
   int c0[NITER];
   bool cval[NITER];
@@ -345,8 +170,11 @@ __device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const typen
     }
     float factor[2];
     bool special[2] = {false, false};
-    u32 slow = 0;  // (an integer: see quantize_oct_fused)
-    const bool short_div = LMC_SHORT_ROW_DIV && row_div_in_range(mrow[0], lmc_math_dtype(DT)) && row_div_in_range(mrow[1], lmc_math_dtype(DT));
+    u32 slow = 0;  // (an integer, not a bool: a bool merged over the branch below becomes a lane mask, and testing it
+                   // costs two vector instructions in front of every block of eight elements)
+    // both row maxes are wave-uniform: one scalar branch picks the short division for the pair -- and a max inside
+    // its range is finite, non-zero and has a finite factor, so such a pair cannot be special: no tests at all
+    const bool short_div = row_div_in_range(mrow[0], lmc_math_dtype(DT)) && row_div_in_range(mrow[1], lmc_math_dtype(DT));
     if (short_div) {
 #pragma unroll
       for (int r = 0; r < 2; r++) factor[r] = row_div_short(maxf, h2f_rt(mrow[r], lmc_math_dtype(DT)));
@@ -371,6 +199,10 @@ __device__ __forceinline__ void quantize_oct_hist(const KvAddr& src, const typen
         const int bpos = NIB ? q : (2 * q + r) & 3;
         const bool fresh = NIB ? (q == 0 && r == 0) : bpos == 0;
         const bool high = NIB && r == 1;
+        // (the test stays inside the loops over runs and rows -- a wave-uniform test and two taken scalar branches per run
+        // and row, the regular path jumping over the special-row code.  ONE branch around the whole pair's conversions
+        // was built in round 5: the scheduler then interleaves both runs and both rows of the straight-line regular path
+        // and the kernel spills 184 bytes per lane instead of 20.)
         if (slow == 0u) {
           const f32x2_t f2 = {factor[r], factor[r]};
 #pragma unroll
@@ -432,14 +264,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
   // of the counts coder uses -- row_addr_cnt ALIGNED)
   // (GL == 64: the eight slices together are the plane's histogram during phase A and pass 1 -- PLANE_HIST_DWORDS, at LDS
   // address 0: plane_hist_row)
-  constexpr bool HISTA = LMC_FUSED_HIST_A && GL == 64 && NW * CNT_TAB_DWORDS == PLANE_HIST_DWORDS;
+  static_assert(NW * CNT_TAB_DWORDS == PLANE_HIST_DWORDS, "the workgroup's table slices are the plane's histogram");
+  constexpr bool HISTA = GL == 64;
   // ... and narrow planes (GL < 64: several planes per item): the same 32 KiB hold the counters of ALL the item's planes,
   // plane pj's lane group on the virtual quantising lanes pj * GL .. (k_hist.h) -- when the item's planes fit 128 of them
   // GL == 32 only (planes of 129 .. 256 channels): a wave pass quantises 64 / GL row octs of one plane, whose lane groups add
   // into the SAME columns -- the same LDS bank.  Two groups (GL = 32) cost a 2-way conflict and the histogram still wins
   // 5 % (0.251 - 0.256 vs 0.262 - 0.270 ms, 32 layers x 2 heads x 128, 16 k tokens, five alternations); four groups
   // (GL = 16) make every ds_add a 4-way conflict: level at C = 128, + 18 % at C = 64 (profiles/r06_experiments.md).
-  constexpr bool HISTN = LMC_FUSED_HIST_A && LMC_FUSED_HIST_A_NARROW && GL == 32 && NW * CNT_TAB_DWORDS == PLANE_HIST_DWORDS;
+  constexpr bool HISTN = GL == 32;
   __shared__ __attribute__((aligned(HISTA ? 32768 : 4096))) u32 lds_all[NW * (CNT_TAB_DWORDS + CNT_RING_DWORDS)];  // the tables, then the staging buffers
   __shared__ __attribute__((aligned(16))) u32 rtab_lds[RTAB_LDS_DWORDS];  // reciprocals of the counts model's frequencies, bound table
   __shared__ u32 st_alloc[FUSED_MAX_NS];  // allocation of the item's group streams
@@ -469,24 +302,21 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
   u16* const ring = reinterpret_cast<u16*>(lds_all + NW * CNT_TAB_DWORDS + wave * CNT_RING_DWORDS);  // ... and staging buffer
 
   rtab_to_lds(rtab_lds);  // visible to the coder waves behind the barrier that ends phase A
-  // the item's plane takes its histogram while it is quantised (wave-uniform per item: GL == 64 items are one plane)
-  bool hist_a = false;
-  if constexpr (HISTN) {
-    typedef __attribute__((address_space(3))) u32* lds_u32w;
-    if ((u32)(size_t)(lds_u32w)lds_all != 0u) __builtin_trap();
-    hist_a = np * GL <= 128;  // (wave-uniform; false only with an LMC_FUSED_PL override that packs more planes into an item)
-    if (hist_a) {
-      uint4* z = reinterpret_cast<uint4*>(lds_all);
-#pragma unroll
-      for (int i = 0; i < PLANE_HIST_DWORDS / 4 / (64 * NW); i++) z[i * 64 * NW + threadIdx.x] = make_uint4(0, 0, 0, 0);
-      __syncthreads();
-    }
-  }
-  if constexpr (HISTA) {
+  // the item's planes take their histogram while they are quantised.  GL == 64: always; GL == 32: when the item's planes
+  // fit the 128 virtual quantising lanes (wave-uniform; false only with an LMC_FUSED_PL override that packs more planes
+  // into an item)
+  const bool hist_a = HISTA || (HISTN && np * GL <= 128);
+  if constexpr (HISTA || HISTN) {
     typedef __attribute__((address_space(3))) u32* lds_u32w;
     if ((u32)(size_t)(lds_u32w)lds_all != 0u) __builtin_trap();  // (static layout: plane_hist_row builds addresses from 0)
-    const int bins0 = (int)a.bins.b[p0];
-    hist_a = LMC_FUSED_HIST_A_BYTE || lmc_sym_nibbles(bins0);  // (a constant with LMC_FUSED_HIST_A_BYTE: quantize_oct_fused is not instantiated then)
+    // (An unused read of the plane's bin count, left over from the time when byte planes could go without the histogram.
+    // The compiler drops it, but the GL == 64 instances come out scheduled differently without it -- 7 instructions in
+    // 50 000 -- and the change that retired that switch promised the same machine code.  It goes with the next change
+    // to this kernel that is timed on the GPU.)
+    if constexpr (HISTA) {
+      const int bins0 = (int)a.bins.b[p0];
+      (void)bins0;
+    }
     if (hist_a) {
       uint4* z = reinterpret_cast<uint4*>(lds_all);
 #pragma unroll
@@ -503,11 +333,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
   // ---- phase A: quantise the item's planes ------------------------------------------------------------------
   {
     const int TO = (Tc + 7) >> 3;  // row octs of a plane-chunk
-    uint4* const park = reinterpret_cast<uint4*>(hist);  // the wave's table slice is idle until pass 1
     u8* const scl0 = fa.scale_base + (long long)chunk * fa.scale_stride;
     // Waves that fetch run at raised priority: their (few) instructions go first, so the loads are out early and
     // return under the other workgroups' coding.
-    __builtin_amdgcn_s_setprio(LMC_FUSED_PRIO_A);
+    __builtin_amdgcn_s_setprio(FUSED_PRIO_A);
     if constexpr (GL < 64) {
       // narrow planes: a wave takes RPW row octs of one plane at a time, GL lanes each (quantize_task, k_quantize.h)
       constexpr int RPW = 64 / GL;                // octs per wave pass
@@ -550,39 +379,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
       for (int oct = wave; oct < TO; oct += NW) {
         const bool q1valid = 2 * oct + 1 < a.TQ;
         const bool allrows = oct * 8 + 8 <= Tc;  // wave-uniform: false only for the last oct of a chunk of 8 k + r tokens
-        if (HISTA && (LMC_FUSED_HIST_A_BYTE || hist_a)) {
-          // round 6: symbols to the workspace AND into the plane's counters (quantize_oct_hist)
-          u32* const so = sym_pc + (long long)oct * (nib ? 1 : 2) * a.C;
-          if (!allrows) {
-            if (nib) quantize_oct_hist<NITER, DT, true, false, false, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
-            else quantize_oct_hist<NITER, DT, false, false, false, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
-          } else if (full) {
-            if (nib) quantize_oct_hist<NITER, DT, true, true, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
-            else quantize_oct_hist<NITER, DT, false, true, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
-          } else if (nib) quantize_oct_hist<NITER, DT, true, false, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
-          else quantize_oct_hist<NITER, DT, false, false, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
-        } else if constexpr (HISTA && LMC_FUSED_HIST_A_BYTE) {
-          // (unreachable: every plane of a GL == 64 item takes the branch above)
-        } else if (!allrows) {  // (the variant with per-lane channel validity takes the per-row test as well: two instances, not four)
-          if (nib)
-            quantize_oct_fused<NITER, DT, true, false, false, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, a.C, maxf,
-                                                              sym_pc + (long long)oct * a.C, scl + oct * 8, park, lane);
-          else
-            quantize_oct_fused<NITER, DT, false, false, false, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, a.C, maxf,
-                                                               sym_pc + (long long)oct * 2 * a.C, scl + oct * 8, park, lane);
+        u32* const so = sym_pc + (long long)oct * (nib ? 1 : 2) * a.C;
+        // (the variant with per-lane channel validity takes the per-row test as well: two instances, not four)
+        if (!allrows) {
+          if (nib) quantize_oct<NITER, DT, true, false, false, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
+          else quantize_oct<NITER, DT, false, false, false, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
         } else if (full) {  // wave-uniform
-          if (nib)
-            quantize_oct_fused<NITER, DT, true, true, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, a.C, maxf,
-                                                      sym_pc + (long long)oct * a.C, scl + oct * 8, park, lane);
-          else
-            quantize_oct_fused<NITER, DT, false, true, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, a.C, maxf,
-                                                       sym_pc + (long long)oct * 2 * a.C, scl + oct * 8, park, lane);
-        } else if (nib)
-          quantize_oct_fused<NITER, DT, true, false, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, a.C, maxf,
-                                                     sym_pc + (long long)oct * a.C, scl + oct * 8, park, lane);
-        else
-          quantize_oct_fused<NITER, DT, false, false, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, a.C, maxf,
-                                                      sym_pc + (long long)oct * 2 * a.C, scl + oct * 8, park, lane);
+          if (nib) quantize_oct<NITER, DT, true, true, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
+          else quantize_oct<NITER, DT, false, true, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
+        } else if (nib) quantize_oct<NITER, DT, true, false, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
+        else quantize_oct<NITER, DT, false, false, true, PSRC>(fa.src, pbase, tok0, Tc, oct * 8, q1valid, oct == 0, a.C, maxf, so, scl + oct * 8, lane);
       }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -602,7 +408,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
       const CountsStream s = stream_of(j);
       u32 alloc;
       // (the counters are there; vq_base = the plane's first virtual quantising lane within the item)
-      if (HISTA && (LMC_FUSED_HIST_A_BYTE || hist_a)) alloc = counts_hist_stream<true, true>(a, s, hist, rtab_lds + RTAB_DWORDS, lane, cs);
+      if (HISTA) alloc = counts_hist_stream<true, true>(a, s, hist, rtab_lds + RTAB_DWORDS, lane, cs);
       else if (HISTN && hist_a) alloc = counts_hist_stream<true, true>(a, s, hist, rtab_lds + RTAB_DWORDS, lane, cs, (u32)(s.p - p0) * GL);
       else alloc = counts_hist_stream<true>(a, s, hist, rtab_lds + RTAB_DWORDS, lane, cs);
       if (lane == 0) st_alloc[j] = alloc;
@@ -618,10 +424,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
   for (int j = 0; j < NS; j++) wg_total += st_alloc[j];
   if (wave == 0) {
     unsigned long long* agg = a.agg + (long long)chunk * fa.ipc;
-    if (lane == 0 && it > 0) aggE_store(agg + it, AGG_A, fa.epoch, wg_total);
-    const u32 e = lookback_exclusive_epoch(agg, it, fa.epoch, lane, a.status);
+    if (lane == 0 && it > 0) agg_store(agg + it, AGG_A, wg_total, fa.epoch);
+    const u32 e = lookback_exclusive<true>(agg, it, lane, a.status, fa.epoch);
     if (lane == 0) {
-      aggE_store(agg + it, AGG_P, fa.epoch, e + wg_total);
+      agg_store(agg + it, AGG_P, e + wg_total, fa.epoch);
       wg_excl = e;
     }
   }

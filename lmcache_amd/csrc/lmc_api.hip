@@ -273,6 +273,26 @@ static bool bins_ok(const int32_t* bins_h, int P, BinsArg* out) {
   return true;
 }
 
+// f(IntTag<DT>) for the KV dtype code `dtype` (one that layout_ok has passed): where a run-time dtype picks a kernel instance.
+template <typename F>
+static auto with_kv_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case LMC_DTYPE_BF16: return f(IntTag<LMC_DTYPE_BF16>{});
+    case LMC_DTYPE_FP16: return f(IntTag<LMC_DTYPE_FP16>{});
+    case LMC_DTYPE_FP8_E4M3: return f(IntTag<LMC_DTYPE_FP8_E4M3>{});
+    default: return f(IntTag<LMC_DTYPE_FP8_E5M2>{});
+  }
+}
+
+// What every encode job asks of its source and its token range (lmc_encode_chunks, and the stores in front of it before
+// they take a buffer).  *nchunks: the job's chunks -- at most 65535, they ride on gridDim.z of k_quantize.
+static bool encode_job_ok(const lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                          int* nchunks) {
+  if (!c || !layout_ok(src) || tok_begin < 0 || tok_end <= tok_begin || chunk_tokens < 1 || chunk_tokens > 65535) return false;
+  *nchunks = (tok_end - tok_begin + chunk_tokens - 1) / chunk_tokens;
+  return *nchunks <= 65535;
+}
+
 template <int DT, bool QUAD>
 static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
   const int C = a.C;
@@ -306,12 +326,7 @@ static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
 
 template <bool QUAD>
 static int launch_quant(const QuantArgs& a, hipStream_t s) {
-  switch (a.src.dtype) {
-    case LMC_DTYPE_BF16: return launch_quant_dt<LMC_DTYPE_BF16, QUAD>(a, s);
-    case LMC_DTYPE_FP16: return launch_quant_dt<LMC_DTYPE_FP16, QUAD>(a, s);
-    case LMC_DTYPE_FP8_E4M3: return launch_quant_dt<LMC_DTYPE_FP8_E4M3, QUAD>(a, s);
-    default: return launch_quant_dt<LMC_DTYPE_FP8_E5M2, QUAD>(a, s);
-  }
+  return with_kv_dtype(a.src.dtype, [&](auto dt) { return launch_quant_dt<decltype(dt)::value, QUAD>(a, s); });
 }
 
 // The slot of a blob in the arenas and slots of this file: lmc_blob_bound rounded up to 16 bytes.
@@ -431,14 +446,12 @@ int lmc_encode_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, i
 static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
                                const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
                                lmc_stream_t stream, int nparts, const AfterPart* after_part) {
-  if (!c || !layout_ok(src) || tok_begin < 0 || tok_end <= tok_begin || chunk_tokens < 1 || chunk_tokens > 65535 ||
-      !blobs || !sizes || ((uintptr_t)blobs & 15) || (blob_stride & 15))
+  int nchunks;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks) || !blobs || !sizes || ((uintptr_t)blobs & 15) ||
+      (blob_stride & 15))
     return LMC_ERR_INVALID;
   const int L = src->num_layers, H = src->num_heads, D = src->head_size;
-  const int P = 2 * L, C = H * D, G = (C + 63) / 64;
-  if (C > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
-  const int nchunks = (tok_end - tok_begin + chunk_tokens - 1) / chunk_tokens;
-  if (nchunks > 65535) return LMC_ERR_INVALID;  // chunks ride on gridDim.z of k_quantize
+  const int P = 2 * L, C = H * D, G = (C + 63) / 64;  // (C <= LMC_MAX_CHANNELS: layout_ok)
   if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
   BinsArg bins;
   if (!bins_ok(bins_h, P, &bins)) return LMC_ERR_INVALID;
@@ -448,7 +461,7 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   std::lock_guard<std::mutex> lk(c->mu);
   bool split_done = false;  // the fused launch went out in plane ranges and after_part ran behind each
   // k_fused.h codes the 256-token chunks (the counts model) of every plane width: a work item is a run of whole planes
-  // of one chunk -- 8 planes of <= 128 channels, 4 of <= 256, else one
+  // of one chunk -- 8 planes of <= 64 channels, 4 of <= 128, 2 of <= 256, else one
   const int nfull = (tok_end - tok_begin) / chunk_tokens;  // chunks of exactly chunk_tokens tokens; a ragged one may follow
   // (planes of more than 1024 channels: two kernels -- the fused form built for them in round 4 never won below eight
   // generations of workgroups and was removed, k_fused.h)
@@ -593,10 +606,7 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
       const dim3 grid((unsigned)((long long)nfull * (it1 - it0)));
       fa.item_base = (u32)((long long)it0 * nfull);
       fa.e.ticket_base = w->tickets_drawn;
-      if (src->dtype == LMC_DTYPE_BF16) launch_fused<LMC_DTYPE_BF16>(C, grid, block, s, fa);
-      else if (src->dtype == LMC_DTYPE_FP16) launch_fused<LMC_DTYPE_FP16>(C, grid, block, s, fa);
-      else if (src->dtype == LMC_DTYPE_FP8_E4M3) launch_fused<LMC_DTYPE_FP8_E4M3>(C, grid, block, s, fa);
-      else launch_fused<LMC_DTYPE_FP8_E5M2>(C, grid, block, s, fa);
+      with_kv_dtype(src->dtype, [&](auto dt) { launch_fused<decltype(dt)::value>(C, grid, block, s, fa); });
       const hipError_t le = hipGetLastError();
       if (le != hipSuccess) { g_last_hip = (int)le; tickets_reset(); return LMC_ERR_HIP; }
       w->tickets_drawn += grid.x;
@@ -618,31 +628,43 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   return LMC_OK;
 }
 
-static int decode_common(lmc_ctx* c, const void* blobs, uint64_t blob_stride, int nchunks, int L, int H, int D,
-                         uint32_t* job_status, DecodeArgs& a) {
-  if (!c || !blobs || nchunks < 1 || ((uintptr_t)blobs & 15) || (blob_stride & 15)) return LMC_ERR_INVALID;
-  a.blobs = (const u8*)blobs; a.blob_stride = (long long)blob_stride; a.nchunks = nchunks;
-  a.blob_ptrs = nullptr; a.layer_begin = 0; a.layer_count = L;
-  a.seg_off = nullptr; a.seg_streams = nullptr; a.seg_n = 0;
+// A decode job's arguments in three steps, every refusal LMC_ERR_INVALID and none of them queues anything:
+// decode_geometry -- `nchunks` blobs of L layers x H heads x D, every layer (the ranged launches narrow that);
+static int decode_geometry(lmc_ctx* c, int nchunks, int L, int H, int D, uint32_t* job_status, DecodeArgs& a) {
+  memset(&a, 0, sizeof a);
+  if (!c || nchunks < 1) return LMC_ERR_INVALID;
+  a.nchunks = nchunks; a.layer_count = L;
   a.P = 2 * L; a.C = H * D; a.G = (a.C + 63) / 64;
   // k_decode numbers its streams (chunk, plane, group) in 32 bits: 2^31 of them would be > 10^11 tokens in one call
   if ((long long)nchunks * a.P * a.G >= (1ll << 31)) return LMC_ERR_INVALID;
   a.status = job_status ? job_status : c->status_h;
   return LMC_OK;
 }
+// decode_common -- ... of the geometry of `dst`, into it from token dst_tok0 on: what every entry point with a
+// destination asks of it (lmc_decode_symbols has none) before it looks at anything else of `dst`;
+static int decode_common(lmc_ctx* c, int nchunks, const lmc_kv_layout* dst, int dst_tok0, long long chunk_tokens,
+                         uint32_t* job_status, DecodeArgs& a) {
+  if (!layout_ok(dst, false) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens)) return LMC_ERR_INVALID;
+  const int rc = decode_geometry(c, nchunks, dst->num_layers, dst->num_heads, dst->head_size, job_status, a);
+  if (rc) return rc;
+  a.dst = to_addr(dst); a.dst_tok0 = dst_tok0; a.chunk_tokens = (int)chunk_tokens;
+  return LMC_OK;
+}
+// decode_blobs -- the caller's blobs, `stride` bytes apart from `blobs` on or, with blob_ptrs, each at its own address
+// (`blobs` is only a non-null placeholder then).  The load paths decode from their own staging and set the two fields.
+static bool decode_blobs(DecodeArgs& a, const void* blobs, uint64_t stride, const void* const* blob_ptrs = nullptr) {
+  if (!blobs || ((uintptr_t)blobs & 15) || (stride & 15)) return false;
+  a.blobs = (const u8*)blobs; a.blob_stride = (long long)stride; a.blob_ptrs = (const u8* const*)blob_ptrs;
+  return true;
+}
 
 // k_decode for a destination dtype: the destination's dtype decides what a blob decodes to (any blob, any of the four)
 static void launch_decode(int dtype, bool paged, dim3 grid, hipStream_t s, const DecodeArgs& a) {
-#define LD(DT)                                                                                       \
-  do {                                                                                               \
-    if (paged) hipLaunchKernelGGL((k_decode<false, DT, true>), grid, dim3(64 * DEC_WAVES), 0, s, a); \
-    else hipLaunchKernelGGL((k_decode<false, DT, false>), grid, dim3(64 * DEC_WAVES), 0, s, a);      \
-  } while (0)
-  if (dtype == LMC_DTYPE_BF16) LD(LMC_DTYPE_BF16);
-  else if (dtype == LMC_DTYPE_FP16) LD(LMC_DTYPE_FP16);
-  else if (dtype == LMC_DTYPE_FP8_E4M3) LD(LMC_DTYPE_FP8_E4M3);
-  else LD(LMC_DTYPE_FP8_E5M2);
-#undef LD
+  with_kv_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (paged) hipLaunchKernelGGL((k_decode<false, DT, true>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+    else hipLaunchKernelGGL((k_decode<false, DT, false>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+  });
 }
 
 // One range of layers of a decode: k_decode over the streams of layers [l0, l0 + nl) of the job's chunks, then `ev`
@@ -674,12 +696,10 @@ static int decode_range(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, int
 
 int lmc_decode_chunks(lmc_ctx* c, const void* blobs, uint64_t blob_stride, int32_t nchunks, const lmc_kv_layout* dst,
                       int32_t dst_tok0, int32_t chunk_tokens, uint32_t* job_status, lmc_stream_t stream) {
-  if (!layout_ok(dst, false) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens)) return LMC_ERR_INVALID;
   DecodeArgs a;
-  memset(&a, 0, sizeof a);
-  int rc = decode_common(c, blobs, blob_stride, nchunks, dst->num_layers, dst->num_heads, dst->head_size, job_status, a);
+  const int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a);
   if (rc) return rc;
-  a.dst = to_addr(dst); a.dst_tok0 = dst_tok0; a.chunk_tokens = chunk_tokens;
+  if (!decode_blobs(a, blobs, blob_stride)) return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   return decode_range(c, a, dst, 0, dst->num_layers, (hipStream_t)stream, nullptr);
 }
@@ -687,17 +707,12 @@ int lmc_decode_chunks(lmc_ctx* c, const void* blobs, uint64_t blob_stride, int32
 int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
                              const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t layer_begin,
                              int32_t layer_count, uint32_t* job_status, lmc_stream_t stream) {
-  if (!layout_ok(dst, false) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens) || !blob_ptrs || layer_begin < 0 ||
-      layer_count < 1 || layer_begin + layer_count > dst->num_layers)
-    return LMC_ERR_INVALID;
   DecodeArgs a;
-  memset(&a, 0, sizeof a);
-  // `blobs` is only a non-null placeholder here: the kernel takes every blob's address from the table
-  int rc = decode_common(c, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, nchunks, dst->num_layers, dst->num_heads,
-                         dst->head_size, job_status, a);
+  const int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a);
   if (rc) return rc;
-  a.blob_ptrs = (const u8* const*)blob_ptrs;
-  a.dst = to_addr(dst); a.dst_tok0 = dst_tok0; a.chunk_tokens = chunk_tokens;
+  if (!decode_blobs(a, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, blob_ptrs) || layer_begin < 0 || layer_count < 1 ||
+      layer_begin + layer_count > dst->num_layers)
+    return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   return decode_range(c, a, dst, layer_begin, layer_count, (hipStream_t)stream, nullptr);
 }
@@ -706,18 +721,14 @@ int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_
                                const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
                                const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
                                lmc_stream_t stream) {
-  if (!layout_ok(dst, false) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens) || !blob_ptrs || nranges < 1 || !layer_ends_h)
+  DecodeArgs a;
+  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a);
+  if (rc) return rc;
+  if (!decode_blobs(a, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, blob_ptrs) || nranges < 1 || !layer_ends_h)
     return LMC_ERR_INVALID;
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)  // the whole schedule is checked before anything is launched
     if (layer_ends_h[i] <= prev || layer_ends_h[i] > dst->num_layers) return LMC_ERR_INVALID;
   if (layer_ends_h[nranges - 1] != dst->num_layers) return LMC_ERR_INVALID;
-  DecodeArgs a;
-  memset(&a, 0, sizeof a);
-  int rc = decode_common(c, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, nchunks, dst->num_layers, dst->num_heads,
-                         dst->head_size, job_status, a);
-  if (rc) return rc;
-  a.blob_ptrs = (const u8* const*)blob_ptrs;
-  a.dst = to_addr(dst); a.dst_tok0 = dst_tok0; a.chunk_tokens = chunk_tokens;
   HIP_TRY(hipSetDevice(c->device));
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)
     if ((rc = decode_range(c, a, dst, prev, layer_ends_h[i] - prev, (hipStream_t)stream, events_h ? events_h[i] : nullptr)))
@@ -729,12 +740,12 @@ int lmc_decode_symbols(lmc_ctx* c, const void* blob, int32_t L, int32_t H, int32
                        lmc_stream_t stream) {
   if (!sym_out || L < 1 || H < 1 || D < 1 || (H * (long long)D) % 8) return LMC_ERR_INVALID;
   DecodeArgs a;
-  memset(&a, 0, sizeof a);
-  int rc = decode_common(c, blob, 0, 1, L, H, D, nullptr, a);
+  const int rc = decode_geometry(c, 1, L, H, D, nullptr, a);
   if (rc) return rc;
+  if (!decode_blobs(a, blob, 0)) return LMC_ERR_INVALID;
   a.sym_out = sym_out;
   HIP_TRY(hipSetDevice(c->device));
-  const long long n = (long long)a.P * a.G;  // every layer (decode_common set the full range)
+  const long long n = (long long)a.P * a.G;  // every layer (decode_geometry set the full range)
   hipLaunchKernelGGL((k_decode<true, LMC_DTYPE_BF16, false>), dim3((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return LMC_OK;
@@ -951,11 +962,10 @@ static int store_acquire(lmc_ctx* c, hipStream_t s, size_t arena_bytes, size_t t
 int lmc_store_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
                      const int32_t* bins_h, void* host_arena_h, uint64_t host_cap, uint64_t* offsets_h,
                      uint32_t* sizes_h, uint32_t* job_status, lmc_stream_t stream) {
-  if (!c || !layout_ok(src) || tok_begin < 0 || tok_end <= tok_begin || chunk_tokens < 1 || chunk_tokens > 65535 ||
-      !host_arena_h || ((uintptr_t)host_arena_h & 15) || !offsets_h || !sizes_h)
+  int nchunks;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks) || !host_arena_h || ((uintptr_t)host_arena_h & 15) ||
+      !offsets_h || !sizes_h)
     return LMC_ERR_INVALID;
-  const int nchunks = (tok_end - tok_begin + chunk_tokens - 1) / chunk_tokens;
-  if (nchunks > 65535) return LMC_ERR_INVALID;
   const uint64_t stride = blob_stride(src->num_layers, chunk_tokens, src->num_heads, src->head_size);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
@@ -1000,15 +1010,14 @@ static bool host_blob_ok(const u8* b, uint32_t size, int L, int H, int D, uint32
 int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint32_t* sizes_h, int32_t nchunks,
                     const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t layers_per_range,
                     lmc_event_t* range_events, uint32_t* job_status, lmc_stream_t stream) {
-  if (!c || !host_blob_ptrs_h || !sizes_h || nchunks < 1 || !layout_ok(dst, false) || chunk_tokens < 1 || layers_per_range < 0 ||
-      !decode_dst_ok(dst, chunk_tokens))
-    return LMC_ERR_INVALID;
+  if (!host_blob_ptrs_h || !sizes_h || layers_per_range < 0) return LMC_ERR_INVALID;
+  DecodeArgs da;
+  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, da);
+  if (rc) return rc;
   const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
-  if (H * D > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
   const uint64_t stride = blob_stride(L, chunk_tokens, H, D);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
-  int rc;
   const int step = layers_per_range > 0 && layers_per_range < L ? layers_per_range : L;
   std::lock_guard<std::mutex> lk(c->mu);
   if ((rc = legs_init(c))) return rc;
@@ -1041,10 +1050,7 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
                            hipMemcpyHostToDevice, cs[i & 1]));
   for (int q = 0; q < 2; q++)  // the decodes wait for both queues
     if ((rc = stream_follows(c, s, cs[q]))) return rc;
-  DecodeArgs da;
-  memset(&da, 0, sizeof da);
-  if ((rc = decode_common(c, c->load_slots, stride, nchunks, L, H, D, job_status, da))) return rc;
-  da.dst = to_addr(dst); da.dst_tok0 = dst_tok0; da.chunk_tokens = chunk_tokens;
+  da.blobs = c->load_slots; da.blob_stride = (long long)stride;
   int r = 0;
   for (int l0 = 0; l0 < L; l0 += step, r++) {
     const int n = l0 + step <= L ? step : L - l0;
@@ -1062,14 +1068,13 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
 static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
                            const int32_t* bins_h, void* pack_h, uint64_t pack_cap, uint32_t* sizes_h, int32_t nparts,
                            uint64_t* part_info_h, const lmc_event_t* part_events, uint32_t* job_status, lmc_stream_t stream) {
-  if (!c || !layout_ok(src) || tok_begin < 0 || tok_end <= tok_begin || chunk_tokens < 1 || chunk_tokens > 65535 || !bins_h ||
-      !pack_h || ((uintptr_t)pack_h & 15) || !sizes_h || nparts < 0 || nparts > 16 || (nparts > 0 && !part_info_h))
+  int nchunks;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks) || !pack_h || ((uintptr_t)pack_h & 15) || !sizes_h ||
+      nparts < 0 || nparts > 16 || (nparts > 0 && !part_info_h))
     return LMC_ERR_INVALID;
-  const int nchunks = (tok_end - tok_begin + chunk_tokens - 1) / chunk_tokens;
   const int L = src->num_layers, P = 2 * L;
-  if (nchunks > 65535 || (long long)P * nchunks > (1ll << 22)) return LMC_ERR_INVALID;
-  for (int p = 0; p < P; p++)
-    if (bins_h[p] < 4 || bins_h[p] > LMC_MAX_BINS) return LMC_ERR_INVALID;
+  BinsArg bins;  // (checked here, before the arena is taken; the encode makes its own copy)
+  if ((long long)P * nchunks > (1ll << 22) || !bins_ok(bins_h, P, &bins)) return LMC_ERR_INVALID;
   PackArgs pa;
   memset(&pa, 0, sizeof pa);
   lmc_pack_layout((uint32_t)nchunks, (uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)src->num_heads, (uint32_t)src->head_size, &pa.hdr);
@@ -1177,30 +1182,37 @@ int lmc_pack_info(const void* pack_h, uint64_t nbytes, lmc_pack_header* out) {
   return LMC_OK;
 }
 
+// Chunk `chunk` of a checked pack as the blob it was packed from: the checks of its static slot (the head of the blob:
+// its header says how long the head and the whole blob are) and the walk over its segments, which must add up to the
+// blob.  blob_out, if given, receives the blob (`cap` bytes of room).  Returns the blob's size, or 0: the pack holds no
+// such blob (or it does not fit).
+static uint32_t pack_chunk_walk(const u8* b, const lmc_pack_header& h, uint32_t chunk, u8* blob_out, uint64_t cap) {
+  const u8* st = b + h.off_static + (uint64_t)chunk * h.static_stride;
+  lmc_blob_header bh;
+  memcpy(&bh, st, sizeof bh);
+  if (bh.magic != LMC_BLOB_MAGIC || bh.off_streams > h.static_stride || bh.off_streams < sizeof bh ||
+      bh.total_bytes != bh.off_streams + bh.stream_bytes || (blob_out && bh.total_bytes > cap) || bh.num_layers != h.num_layers)
+    return 0;
+  if (blob_out) memcpy(blob_out, st, bh.off_streams);
+  const uint64_t* t = (const uint64_t*)(b + h.off_table);
+  uint64_t at = bh.off_streams;
+  for (uint32_t p = 0; p < 2 * h.num_layers; p++) {  // plane order of the blob and of the pack: K planes of every layer, then V planes
+    const uint64_t i = (uint64_t)p * h.nchunks + chunk;
+    const uint64_t len = t[i + 1] - t[i];
+    if (at + len > bh.total_bytes) return 0;
+    if (blob_out) memcpy(blob_out + at, b + h.off_streams + t[i], len);
+    at += len;
+  }
+  return at == bh.total_bytes ? bh.total_bytes : 0;
+}
+
 int lmc_pack_extract(const void* pack_h, uint64_t nbytes, int32_t chunk, void* blob_out, uint64_t cap, uint32_t* size_out) {
   lmc_pack_header h;
   const u8* b = (const u8*)pack_h;
   if (!pack_ok(b, nbytes, &h) || chunk < 0 || (uint32_t)chunk >= h.nchunks || !blob_out || !size_out) return LMC_ERR_INVALID;
-  const u8* st = b + h.off_static + (uint64_t)chunk * h.static_stride;
-  lmc_blob_header bh;
-  memcpy(&bh, st, sizeof bh);
-  // the static slot is the head of the blob: its header says how long the head and the whole blob are
-  if (bh.magic != LMC_BLOB_MAGIC || bh.off_streams > h.static_stride || bh.off_streams < sizeof bh ||
-      bh.total_bytes != bh.off_streams + bh.stream_bytes || bh.total_bytes > cap || bh.num_layers != h.num_layers)
-    return LMC_ERR_INVALID;
-  memcpy(blob_out, st, bh.off_streams);
-  const uint64_t* t = (const uint64_t*)(b + h.off_table);
-  const uint32_t L = h.num_layers, n = h.nchunks;
-  uint64_t at = bh.off_streams;
-  for (uint32_t p = 0; p < 2 * L; p++) {  // plane order of the blob and of the pack: K planes of every layer, then V planes
-    const uint64_t i = (uint64_t)p * n + (uint32_t)chunk;
-    const uint64_t len = t[i + 1] - t[i];
-    if (at + len > bh.total_bytes) return LMC_ERR_INVALID;
-    memcpy((u8*)blob_out + at, b + h.off_streams + t[i], len);
-    at += len;
-  }
-  if (at != bh.total_bytes) return LMC_ERR_INVALID;
-  *size_out = bh.total_bytes;
+  const uint32_t size = pack_chunk_walk(b, h, (uint32_t)chunk, (u8*)blob_out, cap);
+  if (!size) return LMC_ERR_INVALID;
+  *size_out = size;
   return LMC_OK;
 }
 
@@ -1208,19 +1220,19 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
                   const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
                   uint32_t* job_status, lmc_stream_t stream) {
   lmc_pack_header h;
-  if (!c || !layout_ok(dst, false) || layers_per_range < 0 || nchunks < 0 || chunk_begin < 0 ||
-      !pack_ok((const u8*)pack_h, pack_bytes, &h) || !decode_dst_ok(dst, (long long)h.chunk_tokens))
-    return LMC_ERR_INVALID;
-  const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
-  if ((uint32_t)L != h.num_layers || (uint32_t)H != h.num_heads || (uint32_t)D != h.head_size || H * D > LMC_MAX_CHANNELS ||
+  if (layers_per_range < 0 || nchunks < 0 || chunk_begin < 0 || !pack_ok((const u8*)pack_h, pack_bytes, &h) ||
       (uint32_t)chunk_begin >= h.nchunks || (uint32_t)nchunks > h.nchunks - (uint32_t)chunk_begin)
     return LMC_ERR_INVALID;
   const int n = (int)h.nchunks, c0 = chunk_begin, m = nchunks ? nchunks : n - c0;  // chunks c0 .. c0 + m of the pack
+  DecodeArgs da;
+  int rc = decode_common(c, m, dst, dst_tok0, (long long)h.chunk_tokens, job_status, da);
+  if (rc) return rc;
+  const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
+  if ((uint32_t)L != h.num_layers || (uint32_t)H != h.num_heads || (uint32_t)D != h.head_size) return LMC_ERR_INVALID;
   const u8* b = (const u8*)pack_h;
   const uint64_t* t = (const uint64_t*)(b + h.off_table);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
-  int rc;
   const int step = layers_per_range > 0 && layers_per_range < L ? layers_per_range : L;
   std::lock_guard<std::mutex> lk(c->mu);
   if ((rc = legs_init(c))) return rc;
@@ -1235,11 +1247,7 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
   HIP_TRY(hipMemcpyAsync(dev + h.off_table, b + h.off_table, 8 * (2 * (size_t)L * n + 1), hipMemcpyHostToDevice, cs));
   HIP_TRY(hipMemcpyAsync(dev + h.off_static + (size_t)c0 * h.static_stride, b + h.off_static + (size_t)c0 * h.static_stride,
                          (size_t)m * h.static_stride, hipMemcpyHostToDevice, cs));
-  DecodeArgs da;
-  memset(&da, 0, sizeof da);
-  if ((rc = decode_common(c, dev + h.off_static + (size_t)c0 * h.static_stride, h.static_stride, m, L, H, D, job_status, da)))
-    return rc;
-  da.dst = to_addr(dst); da.dst_tok0 = dst_tok0; da.chunk_tokens = (int)h.chunk_tokens;
+  da.blobs = dev + h.off_static + (size_t)c0 * h.static_stride; da.blob_stride = (long long)h.static_stride;  // (the static slots)
   da.seg_off = (const unsigned long long*)(dev + h.off_table) + c0; da.seg_streams = dev + h.off_streams; da.seg_n = n;
   int r = 0;
   for (int l0 = 0; l0 < L; l0 += step, r++) {
@@ -1315,21 +1323,9 @@ int lmc_pack_chunk_bytes(const void* pack_h, uint64_t nbytes, int32_t chunk, uin
   lmc_pack_header h;
   const u8* b = (const u8*)pack_h;
   if (!pack_ok(b, nbytes, &h) || chunk < 0 || (uint32_t)chunk >= h.nchunks || !size_out) return LMC_ERR_INVALID;
-  lmc_blob_header bh;
-  memcpy(&bh, b + h.off_static + (uint64_t)chunk * h.static_stride, sizeof bh);
-  // lmc_pack_extract's checks, and its walk over the chunk's segments, without the copies
-  if (bh.magic != LMC_BLOB_MAGIC || bh.off_streams > h.static_stride || bh.off_streams < sizeof bh ||
-      bh.total_bytes != bh.off_streams + bh.stream_bytes || bh.num_layers != h.num_layers)
-    return LMC_ERR_INVALID;
-  const uint64_t* t = (const uint64_t*)(b + h.off_table);
-  uint64_t at = bh.off_streams;
-  for (uint32_t p = 0; p < 2 * h.num_layers; p++) {
-    const uint64_t i = (uint64_t)p * h.nchunks + (uint32_t)chunk;
-    at += t[i + 1] - t[i];
-    if (at > bh.total_bytes) return LMC_ERR_INVALID;
-  }
-  if (at != bh.total_bytes) return LMC_ERR_INVALID;
-  *size_out = bh.total_bytes;
+  const uint32_t size = pack_chunk_walk(b, h, (uint32_t)chunk, nullptr, 0);  // lmc_pack_extract's checks and walk, without the copies
+  if (!size) return LMC_ERR_INVALID;
+  *size_out = size;
   return LMC_OK;
 }
 

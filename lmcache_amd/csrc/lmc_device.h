@@ -242,9 +242,6 @@ __device__ __forceinline__ u32 f2fp16(float f) {  // v_cvt_f16_f32, RNE
 // (profiles/r03_row_div.log; outside it -- bf16 maxes that are fp32 denormals or whose reciprocal is -- 4014 of
 // 491 520 differ, which is why the range test exists).  The test is on the row max, wave-uniform: a scalar branch;
 // zero / inf / NaN maxes fail it and keep the division.
-#ifndef LMC_SHORT_ROW_DIV
-#define LMC_SHORT_ROW_DIV 1
-#endif
 __device__ __forceinline__ bool row_div_in_range(u32 max_bits, int dtype) {
   if (dtype == LMC_DTYPE_BF16) {
     const u32 e = (max_bits >> 7) & 0xffu;  // bf16 carries fp32's exponent field

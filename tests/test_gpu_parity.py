@@ -758,9 +758,9 @@ FUSED_SHAPES = [
     (3, 768, 256, 4, 128, torch.float16, "randn"),    # C = 512: one channel run per lane
     (2, 256, 256, 3, 128, torch.bfloat16, "randn"),   # C = 384
     # narrow planes: several planes per work item, 16 / 32 lanes per quantise task
-    (10, 512, 256, 1, 128, torch.bfloat16, "randn"),  # C = 128 (Llama-3-70B TP=8 rank): 20 planes = items of 8, 8 and 4 planes
+    (10, 512, 256, 1, 128, torch.bfloat16, "randn"),  # C = 128 (Llama-3-70B TP=8 rank): 20 planes = five items of 4 planes
     (3, 256, 256, 1, 64, torch.float16, "outlier"),   # C = 64: one group stream per plane, 6 planes in one item
-    (5, 512, 256, 2, 128, torch.bfloat16, "rand"),    # C = 256: items of 4, 4 and 2 planes
+    (5, 512, 256, 2, 128, torch.bfloat16, "rand"),    # C = 256: 10 planes = five items of 2 planes
     (2, 256, 256, 1, 200, torch.bfloat16, "randn"),   # C = 200: the 32-lane task with a partial last group
     # planes of more than LMC_FUSED_MAX_CHANNELS = 1024 channels: two kernels whatever the setting (the fused form built
     # for them in round 4 was removed in round 5) -- the wide k_quantize variants (2 / 4 waves per row oct) run here
@@ -963,7 +963,7 @@ def test_fused_setting_is_a_preference_for_other_chunk_lengths(nat, ctx, oracle)
 def test_fused_encode_of_the_70b_tp8_rank_shape_at_32k(nat, ctx, oracle):
     """BASELINE configs[3]: Llama-3-70B, TP = 8 -- a rank holds 80 layers x 1 KV head x 128 = planes of 128 channels --
     32 768 tokens = 128 chunks.  The whole job through lmc_encode_chunks' default path (AUTO picks the fused kernel:
-    20 work items of 8 planes per chunk x 128 chunks), decoded again and held against the quantisation bound, and three
+    40 work items of 4 planes per chunk x 128 chunks), decoded again and held against the quantisation bound, and three
     chunks byte for byte against the oracle."""
     L, T, H, D, cs = 80, 32768, 1, 128, 256
     bins = [32] * 10 + [16] * 70 + [32] * 2 + [16] * 78

@@ -11,7 +11,7 @@ import sys
 
 BYTES = 1 << 30
 PATTERNS = {
-    "rd16_nt": ("FETCH_SIZE", "16 B / lane non-temporal loads (raw KV in quantize_oct_fused)"),
+    "rd16_nt": ("FETCH_SIZE", "16 B / lane non-temporal loads (raw KV in quantize_oct)"),
     "rd16": ("FETCH_SIZE", "16 B / lane loads (k_quantize)"),
     "rd4": ("FETCH_SIZE", "4 B / lane loads, 256 B per wave (symbol workspace, decoder stream words)"),
     "rd4_nt": ("FETCH_SIZE", "4 B / lane non-temporal loads (last-use symbol loads)"),

@@ -8,7 +8,7 @@
 // access widths and WRITE_SIZE are uncalibrated: calibrate on a known byte count in your own access pattern".  Every
 // kernel below moves exactly BYTES (1 GiB, four times the Infinity Cache: nothing is served on-die) with ONE pattern
 // of the encoder / decoder:
-//   rd16_nt     16 B / lane non-temporal loads       the raw KV (quantize_oct_fused)
+//   rd16_nt     16 B / lane non-temporal loads       the raw KV (quantize_oct)
 //   rd16        16 B / lane plain loads              k_quantize
 //   rd4         4 B / lane loads, 256 B per wave     the symbol workspace (passes 1 and 2), the decoder's stream words
 //   rd4_nt      ... non-temporal                     LMC_SYM_LAST_LOAD

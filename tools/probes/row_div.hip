@@ -9,7 +9,8 @@
 // and every MAX = 1 .. 15 (bins 4 .. 32).  Rows whose factor is inf / NaN or whose max is inf / NaN take the
 // quantiser's special path and need the SAME classification from both forms, so those are compared too.
 // Prints the mismatch count per dtype and how many of them lie inside the range test the product applies
-// (lmc_device.h: row_div_in_range): that second count has to be 0 before LMC_SHORT_ROW_DIV is switched on.
+// (lmc_device.h: row_div_in_range): that second count has to be 0 for the short form to stand in for the division
+// (it is: profiles/r03_row_div.log, and the quantisers take it).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 

@@ -1,6 +1,6 @@
 // tail_split.hip -- ONE 16 k request encoded as two concurrent launches: the first chunks by the shipped library on the
-// caller's stream, the last `ntail` chunks by a second library (e.g. a -DFUSED_WAVES=16 build: items of half the
-// duration) on a second, low-priority stream, joined by events.  Question: does a finer-grained last generation shorten
+// caller's stream, the last `ntail` chunks by a second library (e.g. a build whose work items take half the
+// time) on a second, low-priority stream, joined by events.  Question: does a finer-grained last generation shorten
 // the launch's drain (profiles/r06_decoder_and_timelines.md: ~0.1 ms per launch for the first and last generation)?
 //
 //   hipcc --offload-arch=gfx950 -O2 -o tools/probes/tail_split tools/probes/tail_split.hip -Iinclude -ldl
