@@ -92,9 +92,17 @@ int lmc_abi_version(void);
  *   K addr = plane_base(l,0) + b*stride_block + h*stride_head + (d / x)*(block_size*x) + w*x + d % x      [elements]
  *   V addr = plane_base(l,1) + b*stride_block + h*stride_head + d*block_size + w
  * (a dense cache: stride_head = D*block_size, stride_block = H*D*block_size).  A token's channels are not contiguous
- * there, so ONLY lmc_copy_kv takes such a layout, as its source or as its destination (not both; the other side is
- * any LMC_PAGED_ROWS layout): k_copy_split.h.  Every other entry point reads and writes rows and returns
- * LMC_ERR_INVALID for it -- bring the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot
+ * there.  Who takes such a layout:
+ *   - lmc_copy_kv, as its source or as its destination (not both; the other side is any LMC_PAGED_ROWS layout):
+ *     k_copy_split.h;
+ *   - as a DECODE DESTINATION, the four entry points behind a serving engine's retrieve: lmc_decode_chunks_layers,
+ *     lmc_decode_chunks_schedule, lmc_load_chunks and lmc_load_pack (k_decode.h stores into the split blocks: a lane's
+ *     head / granule / element is its 32-bit offset, a token its block, 64-bit, plus its slot's step).  Its 32-bit
+ *     offsets end at   stride_head >= 0  and  ((H-1)*stride_head + D*block_size)*E + 7*16 <= 0xfffffff0;
+ *     beyond that LMC_ERR_INVALID before anything is queued (blocks and planes may lie any distance apart).
+ *   - NOT lmc_decode_chunks: it is the replacement of the reference's from_bytes, whose caller wants a tensor of rows.
+ * Every other entry point -- the encoders and stores, lmc_quantize, lmc_rope_shift -- reads and writes rows and returns
+ * LMC_ERR_INVALID for it: bring the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot
  * read.  Any other paged_kind is LMC_ERR_INVALID; a caller that zeroes the struct gets LMC_PAGED_ROWS.
  */
 #define LMC_PAGED_ROWS 0
@@ -235,6 +243,9 @@ int lmc_encode_chunks(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin,
  *   chunk" rule of retrieve(), cache_engine.py:360-365: pass dst_tok0 = -skip)
  *   dst->dtype selects the output type (bf16 for "vllm", fp16 for
  *   "huggingface": cachegen_decoder.py:190-200)
+ * dst is a LMC_PAGED_ROWS layout.  This call alone among the decode entry points returns LMC_ERR_INVALID for an
+ * LMC_PAGED_SPLIT destination: it stands for from_bytes, which returns a tensor; a paged-attention cache is filled through
+ * lmc_decode_chunks_layers / _schedule, lmc_load_chunks or lmc_load_pack (see lmc_kv_layout).
  */
 int lmc_decode_chunks(lmc_ctx* ctx, const void* blobs, uint64_t blob_stride, int32_t nchunks,
                       const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, uint32_t* job_status,
@@ -306,7 +317,7 @@ int lmc_copy_kv(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32
  * With c = row |d| cos and s = sign(d) * row |d| sin:  o1 = x1 c - x2 s,  o2 = x2 c + x1 s, every product and sum rounded
  * to fp32 by itself, then one round-to-nearest-even cast to the layout's dtype.  (The shifted key has then been rounded
  * to 16 bits twice: when it was stored and now.)
- * LMC_ERR_INVALID, with nothing launched: a layout the decoders would refuse; LMC_PAGED_SPLIT (only lmc_copy_kv takes
+ * LMC_ERR_INVALID, with nothing launched: a layout the decoders would refuse; LMC_PAGED_SPLIT (no split addressing here: lmc_copy_kv takes
  * it: shift the chunk before it is scattered); an fp8 dtype (rotating fp8 would round the key to 3 or 2 mantissa bits a
  * second time: not offered); rot_dim odd, < 2 or > head_size; table_rows < 1; a uniform |delta| >= table_rows; ntok < 1,
  * tok_begin < 0, a NULL table; ntok * num_heads * rot_dim / 2 >= 2^31 (split the range).

@@ -246,20 +246,27 @@ class LMCacheEngine:
     @torch.no_grad()
     def retrieve_into_paged(self, tokens: torch.Tensor, kv_caches, slot_mapping: torch.Tensor, block_size: int,
                             layout: str = "NBHD", mask: Optional[torch.Tensor] = None,
-                            rope: Optional[RopeShift] = None) -> torch.Tensor:
+                            rope: Optional[RopeShift] = None, direct: bool = False) -> torch.Tensor:
         """retrieve() straight into a serving engine's PAGED KV cache: the decoded (or copied) KV of token t is
         written to slot slot_mapping[t] of every layer's cache -- the connector's `lmcache_retrieve_kv` +
         reshape_and_cache_flash scatter (LLM_Engine.rst:101-122) fused into the decode kernel's store.  Slots
         need not be contiguous or ordered (CacheBlend-style placement of a non-prefix segment, BASELINE
         configs[4]).  Returns ret_mask (True where KV was written); the caches of tokens outside it are untouched.
           slot_mapping  int64 [len(tokens)] (entries of tokens the mask skips are ignored)
-        layout "NHDB" (the cache of vLLM's ROCm paged-attention kernels, see store_paged) is STAGED, the same way for
-        every tier: the decoders write rows, and such a cache has none.  The hit chunks are decoded (or copied) into a
+        layout "NHDB" (the cache of vLLM's ROCm paged-attention kernels, see store_paged) is by default STAGED, the same
+        way for every tier.  The hit chunks are decoded (or copied) into a
         contiguous [L,2,nret,H,D] chunk on the current stream, as retrieve() fills its own blob, and one lmc_copy_kv on
         that stream scatters tokens 0 .. got-1 into the cache (k_copy_split.h); nothing is launched when nothing was
         retrieved.  Costs: device memory the size of the retrieved KV for the duration of the call, and one more pass
         over it.  A side effect: a stored chunk that fails to decode never touches the live
         cache, because the miss is decided before the scatter.
+          direct  True: an "NHDB" cache is written the way "NBHD" / "NHBD" are -- the decoder stores into the split blocks
+                  themselves (k_decode.h, DEC_PAGED_SPLIT; the raw tiers scatter each stored chunk with lmc_copy_kv): no
+                  staged chunk, no second pass, no device memory for the duration of the call.  The price is the side
+                  effect above: a stored chunk that fails to decode is a miss in ret_mask, but the slots of the call's
+                  tokens may hold garbage by then, as for the row layouts.  With a row layout the keyword changes
+                  nothing.  Not with `rope` (ValueError before anything is queued): lmc_rope_shift has no split
+                  addressing, and the staged chunk is where the keys are rotated.
           rope  a lmcache_amd.rope.RopeShift: the keys of the retrieved tokens are re-rotated to new positions on the way
                 (a segment that was prefilled on its own and is placed at offset p: delta = p; a per-token delta tensor
                 has one entry per token of `tokens`).  One lmc_rope_shift (k_rope.h) on the current stream behind the
@@ -272,13 +279,17 @@ class LMCacheEngine:
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
         if rope is not None:
+            if direct and layout == "NHDB":
+                raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
+                                 "not address an \"NHDB\" cache); use the staged retrieve")
             self._check_rope(rope, kv_caches, layout, len(tokens))
         staged, made = {}, {}
 
         def make_dst(nret, L, H, D, dtype, dev):
             dst = native.KVLayout.paged(kv_caches, slot_mapping[num_skip_tok:num_skip_tok + nret], block_size, layout)
             assert dst.L == L and native.torch_dtype(dst.dtype) == dtype, "cache geometry / dtype differs from the stored chunks"
-            if layout != "NHDB":
+            if layout != "NHDB" or direct:
+                assert layout != "NHDB" or (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
                 made["dst"] = dst
                 return dst
             assert (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"

@@ -44,6 +44,21 @@ __device__ __forceinline__ long long dec_tok_off(const KvAddr& a, int t) {
   }
   return (long long)b * a.stride_block + (long long)w * a.stride_token;
 }
+// The same for LMC_PAGED_SPLIT (include/lmc_hip.h): the token's part of an element's offset is its block and `wstep`
+// elements per slot of the block -- x for a key plane (a slot is one x-element granule of every d / x), 1 for a value plane
+// (tokens innermost).  The lane's part -- head, granule, element -- is in its voffset.
+__device__ __forceinline__ long long dec_tok_off_split(const KvAddr& a, int t, u32 wstep) {
+  const u32 s = (u32)a.slot_mapping[t], bs = (u32)a.block_size;
+  u32 b, w;
+  if ((bs & (bs - 1u)) == 0u) {
+    b = s >> (u32)__builtin_ctz(bs);
+    w = s & (bs - 1u);
+  } else {
+    b = s / bs;
+    w = s - b * bs;
+  }
+  return (long long)b * a.stride_block + (long long)(w * wstep);
+}
 
 struct DecodeArgs {
   const u8* blobs;
@@ -81,6 +96,17 @@ struct DecodeArgs {
 // wave's allocation and never touched by compiled code.  native.build() refuses a library whose k_decode kernels do not
 // report 60 VGPRs and 0 AGPRs (with 61..64 VGPRs a0 would lie OUTSIDE the allocation).
 #define LMC_DEC_A0_CLOBBER "v59"
+#ifndef LMC_DEC_SPLIT_NT
+#define LMC_DEC_SPLIT_NT 0  // the block path's stores into an LMC_PAGED_SPLIT cache WITHOUT the rows' non-temporal hint: a store
+                            // instruction writes 16-byte pieces there (K: eight per wave, V: one per lane), less than a sector,
+                            // and the neighbours arrive a token or a block later -- L2 has to hold the line to merge them.
+                            // 16 k context, same process: 1.47 ms without the hint, 3.11 with it (profiles/paged_split_decode.md)
+#endif
+#if LMC_DEC_SPLIT_NT
+#define LMC_SPLIT_NT " nt"
+#else
+#define LMC_SPLIT_NT ""
+#endif
 #define DEC_CDF_BYTES 4224
 #define DEC_RING_WORDS 256
 #define DEC_RING_BYTES (2 * (DEC_RING_WORDS + 64))
@@ -101,13 +127,24 @@ __device__ unsigned long long g_decode_timeline[65536 * 4];
 #else
 #define LMC_DTL(k, v) do { } while (0)
 #endif
-template <bool SYMOUT, int DT_OUT, bool PAGED>
+// KIND: how the destination's tokens are found.  DEC_ROWS: token t is row t (stride_token apart).  DEC_PAGED_ROWS: a slot
+// mapping names the row (LMC_PAGED_ROWS with slot_mapping).  DEC_PAGED_SPLIT: LMC_PAGED_SPLIT, the cache of vLLM's ROCm
+// paged-attention kernels -- no rows: a key plane is [block][h][d / x][slot][x], a value plane [block][h][d][slot].  The
+// split kind is the paged-rows path with other numbers: the lane's voffset holds head, granule and element, a token is a
+// 64-bit block base plus a scalar offset that grows by a fixed `step` per slot (16 bytes in a key plane, one element in a
+// value plane), and the eight tokens of a block of the block path are, in a value plane, 16 (fp8: 8) CONTIGUOUS bytes of
+// the lane: one wide store where the rows take eight narrow ones.
+enum { DEC_ROWS = 0, DEC_PAGED_ROWS = 1, DEC_PAGED_SPLIT = 2 };
+template <bool SYMOUT, int DT_OUT, int KIND>
 __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(8))) void k_decode(DecodeArgs a) {
   __shared__ __attribute__((aligned(16))) u8 lds_all[DEC_WAVES * (DEC_LUT_BYTES + DEC_WAVE_BYTES)];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform -> SGPRs
   constexpr bool OUT8 = lmc_dtype_fp8(DT_OUT);  // fp8 destination: one byte per element
   constexpr int ESZ = OUT8 ? 1 : 2;
+  constexpr bool PAGED = KIND != DEC_ROWS;
+  constexpr bool SPLIT = KIND == DEC_PAGED_SPLIT;
+  static_assert(!(SPLIT && SYMOUT), "symbols have no destination layout");
   // (32-bit work-item arithmetic: lmc_api.hip rejects a launch of 2^31 streams or more, and a 64-bit division costs
   // more than a hundred instructions per stream)
   u32 gid = blockIdx.x * (u32)DEC_WAVES + (u32)wave;
@@ -451,7 +488,14 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     lane_off = (u32)c;
   } else {
     const int h = c / a.dst.D, d = c - h * a.dst.D;
-    lane_off = (u32)(((long long)h * a.dst.stride_head + d) * ESZ);
+    if constexpr (SPLIT) {  // K: granule d / x of the head, element d % x of the granule; V: column d of the head
+      constexpr u32 X = 16u / (u32)ESZ;
+      const u32 bs = (u32)a.dst.block_size;
+      const u32 in_head = p >= (a.P >> 1) ? (u32)d * bs : ((u32)d / X) * (bs * X) + (u32)d % X;
+      lane_off = (u32)(((long long)h * a.dst.stride_head + (long long)in_head) * ESZ);
+    } else {
+      lane_off = (u32)(((long long)h * a.dst.stride_head + d) * ESZ);
+    }
     ubase = uniform_ptr(lmc_plane_base<typename KvElem<DT_OUT>::T>(a.dst, p));
   }
   const int tdst0 = a.dst_tok0 + chunk * a.chunk_tokens;
@@ -711,7 +755,9 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     // !PAGED: the rows of this stream through a raw buffer descriptor: base = row of the first stored token,
     // soffset (scalar) = one stride_token further each token, voffset = the lane's channel.  The descriptor's range
     // check (on voffset only) drops the stores of idle lanes, whose voffset is out of range: no exec masking.
-    const long long row_step = a.dst.stride_token * ESZ;
+    // SPLIT: `row_step` is the plane's step from one slot of a block to the next -- a 16-byte granule (K), an element (V)
+    const bool kv_v = SPLIT && p >= (a.P >> 1);  // (wave-uniform: a workgroup is one plane)
+    const long long row_step = SPLIT ? (kv_v ? (long long)ESZ : 16ll) : a.dst.stride_token * ESZ;
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(ubase + (u64)((long long)(tdst0 + (int)nskip) * row_step)), (short)0, (int)0xfffffff0u, 0x00020000);
     const u32 voff = active ? lane_off : 0xfffffff8u;
@@ -743,6 +789,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
       if ((sc_addr & 2ull) == 0ull && nskip + 8u <= T) {
         const u32 nblk = (u32)__builtin_amdgcn_readfirstlane((int)((T - nskip) >> 3));
         bool all_runs = true;
+        // SPLIT, V plane: every lane's offset in a block is a multiple of 4 bytes (head stride and block size are)
+        const bool v_wide = SPLIT && kv_v && ((a.dst.stride_head * ESZ) & 3ll) == 0ll && (((u32)a.dst.block_size * (u32)ESZ) & 3u) == 0u;
         u32 glo = 0, ghi = 0;  // PAGED: lane b = byte offset of block b's first row from the plane's base
         if constexpr (PAGED) {
           all_runs = row_step > 0 && row_step < (1ll << 28) && nblk <= 32u;
@@ -761,12 +809,20 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
             if (all_runs && 64u * r < 8u * nblk) {  // (a mapping that fails in its first 64 tokens costs one round)
               const u32 sl = slot[r];
               const u32 blk = pow2 ? sl >> bsh : sl / bs, w = sl - blk * bs;
-              const long long off = a.dst.slot_mapping ? ((long long)blk * a.dst.stride_block + (long long)w * a.dst.stride_token) * ESZ
-                                                       : (long long)(tfirst + (int)(64u * r) + lane) * row_step;
+              long long off;
+              if constexpr (SPLIT) off = (long long)blk * a.dst.stride_block * ESZ + (long long)w * row_step;
+              else off = a.dst.slot_mapping ? ((long long)blk * a.dst.stride_block + (long long)w * a.dst.stride_token) * ESZ
+                                            : (long long)(tfirst + (int)(64u * r) + lane) * row_step;
               const u32 olo = (u32)(unsigned long long)off, ohi = (u32)((unsigned long long)off >> 32);
               const u32 blo = (u32)__builtin_amdgcn_ds_bpermute(first, (int)olo), bhi = (u32)__builtin_amdgcn_ds_bpermute(first, (int)ohi);
               const long long rel = off - (long long)(((u64)bhi << 32) | (u64)blo);
-              all_runs = all_runs && __ballot(64u * r + (u32)lane >= 8u * nblk || rel == (long long)(lane & 7) * row_step) == ~0ull;
+              bool is_run = rel == (long long)(lane & 7) * row_step;
+              // SPLIT: the eight slots in ONE block (with a step this small, equal offsets alone would not say so)
+              if constexpr (SPLIT) {
+                const u32 blk0 = (u32)__builtin_amdgcn_ds_bpermute(first, (int)blk);  // (every lane takes part)
+                is_run = is_run && blk == blk0;
+              }
+              all_runs = all_runs && __ballot(64u * r + (u32)lane >= 8u * nblk || is_run) == ~0ull;
               const u32 tlo = (u32)__builtin_amdgcn_ds_bpermute(mine, (int)olo), thi = (u32)__builtin_amdgcn_ds_bpermute(mine, (int)ohi);
               if ((u32)(lane >> 3) == r) { glo = tlo; ghi = thi; }
             }
@@ -777,7 +833,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
           u32x4_t cur = sp[0];
           const u64 rbase = ubase + (PAGED ? 0ull : (u64)((long long)(tdst0 + (int)nskip) * row_step));
           u32x4_t desc = {(u32)rbase, (u32)(rbase >> 32) & 0xffffu, 0xfffffff0u, 0x00020000u};
-          auto pair = [&](u32 s2) {
+          auto pair_words = [&](u32 s2) -> u32 {  // two tokens decoded: their elements at bits 0 .. and 16 .. of a dword
             float lva = 0.0f, lvb = 0.0f;
             (void)decode_token(top_tag, model_tag, lva, BoolTag<false>{});
             (void)decode_token(top_tag, model_tag, lvb, BoolTag<true>{});
@@ -794,6 +850,10 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
             } else {
               asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(va), "v"(vb));
             }
+            return w;
+          };
+          auto pair = [&](u32 s2) {
+            const u32 w = pair_words(s2);
 #ifdef LMC_EXP_NO_STORE  // (timing experiment: what the stores and the waits behind them cost; output is wrong)
             asm volatile("" :: "v"(w), "v"(voff), "s"(desc), "s"(soff));
 #elif defined(LMC_EXP_ONE_STORE)
@@ -804,7 +864,28 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
               asm volatile("buffer_store_short %0, %1, %2, %3 offen nt"
                            :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
 #else
-            if constexpr (OUT8)
+            // SPLIT: `s_nop 4` in front of the stores.  On gfx9 a VALU write of an SGPR (v_readlane: how the compiler
+            // reloads a spilled SGPR) needs five wait states before a VMEM instruction reads that SGPR, and the compiler
+            // inserts none in front of inline asm.  Here the slots' steps are compile-time numbers (16 or the element
+            // size, from 0 every block), so the compiler keeps the eight offsets in SGPRs, spills them to VGPR lanes and
+            // reloads one directly in front of the asm block; the s_nop supplies the wait states for every SGPR operand
+            // (both offsets and the descriptor), wherever the compiler places its reloads.  (Two bodies with the steps as
+            // `offset:` immediates, one for K and one for V, do not compile beside the wide V body: the wave-uniform
+            // state of the token step then reaches its "s" operands through VGPRs.)
+            // The fp8 paged-ROWS instances carry the same pattern in front of their SECOND store of a pair
+            // (v_readlane s58 / buffer_store_byte .. s12 / buffer_store_byte_d16_hi .. s58), as they did before the split
+            // kind existed; they are left as they compile: a follow-up of its own.
+            if constexpr (SPLIT && OUT8)
+              asm volatile("s_nop 4\n\t"
+                           "buffer_store_byte %0, %1, %2, %3 offen" LMC_SPLIT_NT "\n\t"
+                           "buffer_store_byte_d16_hi %0, %1, %2, %4 offen" LMC_SPLIT_NT
+                           :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
+            else if constexpr (SPLIT)
+              asm volatile("s_nop 4\n\t"
+                           "buffer_store_short %0, %1, %2, %3 offen" LMC_SPLIT_NT "\n\t"
+                           "buffer_store_short_d16_hi %0, %1, %2, %4 offen" LMC_SPLIT_NT
+                           :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
+            else if constexpr (OUT8)
               asm volatile("buffer_store_byte %0, %1, %2, %3 offen nt\n\t"
                            "buffer_store_byte_d16_hi %0, %1, %2, %4 offen nt"
                            :: "v"(w), "v"(voff), "s"(desc), "s"(soff), "s"(soff + (u32)row_step) : "memory");
@@ -828,6 +909,27 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
               desc.y = (u32)(rb >> 32) & 0xffffu;
               soff = 0;
             }
+            if constexpr (SPLIT) {
+              // V: the block's eight elements of a lane are 16 (fp8: 8) contiguous bytes -- one store, where every lane's
+              // run starts on a dword boundary (wave-uniform: the lanes' offsets are all multiples of 4 bytes -- v_wide --
+              // and the block's first slot is)
+              if (v_wide && (desc.x & 3u) == 0u) {
+                const u32 w0 = pair_words(cur.x), w1 = pair_words(cur.y), w2 = pair_words(cur.z), w3 = pair_words(cur.w);
+                if constexpr (OUT8) {
+                  // a pair's bytes are at bits 0..7 and 16..23: v_perm_b32 packs two pairs into a dword
+                  const u32x2_t v2 = {__builtin_amdgcn_perm(w1, w0, 0x06040200u), __builtin_amdgcn_perm(w3, w2, 0x06040200u)};
+                  asm volatile("s_nop 4\n\tbuffer_store_dwordx2 %0, %1, %2, 0 offen" LMC_SPLIT_NT :: "v"(v2), "v"(voff), "s"(desc) : "memory");
+                } else {
+                  const u32x4_t v4 = {w0, w1, w2, w3};
+                  asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, 0 offen" LMC_SPLIT_NT :: "v"(v4), "v"(voff), "s"(desc) : "memory");
+                }
+#if LMC_DEC_RING_AGPR
+                nst += 1u;  // (ONE vector memory operation: block_take's vmcnt(N) counts on it)
+#endif
+                cur = nxt;
+                continue;
+              }
+            }
             pair(cur.x);
             pair(cur.y);
             pair(cur.z);
@@ -846,7 +948,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
       // PAGED: lane i works out the block row of token t0 + i once (slot_mapping load + division); every token
       // then takes its row with two v_readlane and the store goes through a descriptor based at that row
       long long tok_off2 = 0;
-      if (PAGED && !SYMOUT) tok_off2 = (t0 + (u32)lane < T) ? dec_tok_off(a.dst, tdst0 + (int)(t0 + (u32)lane)) * ESZ : 0ll;
+      if constexpr (SPLIT) {
+        tok_off2 = (t0 + (u32)lane < T) ? dec_tok_off_split(a.dst, tdst0 + (int)(t0 + (u32)lane), kv_v ? 1u : 16u / (u32)ESZ) * ESZ : 0ll;
+      } else {
+        if (PAGED && !SYMOUT) tok_off2 = (t0 + (u32)lane < T) ? dec_tok_off(a.dst, tdst0 + (int)(t0 + (u32)lane)) * ESZ : 0ll;
+      }
       auto one_token = [&](u32 i) {
         float lv = 0.0f;
         const u32 sa = decode_token(top_tag, model_tag, lv, BoolTag<true>{});

@@ -194,8 +194,8 @@ int lmc_device_status(lmc_ctx* c, int clear) {
 // (stride_head == head_size: the vllm chunk, the per-layer [T,H,D] tensors, NBHD paged blocks), where a vector that
 // crosses a head boundary is still 8 consecutive elements.  !vec: element-wise access (the decoder's scatter, the
 // element-wise copy): any strides.  Either way a plane has a multiple of 8 channels (the blob's geometry).
-// `split`: the caller addresses LMC_PAGED_SPLIT itself (lmc_copy_kv alone); everybody else reads and writes rows and must
-// refuse such a layout rather than address it as rows.
+// `split`: the caller addresses LMC_PAGED_SPLIT itself (lmc_copy_kv, and the decode entry points that decode_common lets);
+// everybody else reads and writes rows and must refuse such a layout rather than address it as rows.
 static bool layout_ok(const lmc_kv_layout* l, bool vec = true, bool split = false) {
   if (!l) return false;
   if (l->paged_kind != LMC_PAGED_ROWS && l->paged_kind != LMC_PAGED_SPLIT) return false;
@@ -239,10 +239,19 @@ static bool layout_ok(const lmc_kv_layout* l, bool vec = true, bool split = fals
 //       reach = slot_mapping ? (row_step < 2^28 ? 7 * row_step : 0) : (chunk_tokens - 1) * row_step
 //       admitted:  stride_head >= 0,  stride_token >= 0,  reach + row <= 0xfffffff0
 // (so a row always fits the range, and without a slot mapping a chunk's rows end within 4 GiB of its first row).
+// LMC_PAGED_SPLIT (k_decode's DEC_PAGED_SPLIT): the descriptor stands at a block (64-bit: blocks and planes may lie any
+// distance apart), voffset is the lane's head, granule / column and element, below
+//       head = ((H - 1) * stride_head + D * block_size) * E,
+// and soffset the slot's step within a run of eight: at most 7 * 16 bytes (a key plane; a value plane 7 * E).
+//       admitted:  stride_head >= 0,  head + 7 * 16 <= 0xfffffff0
 // Every entry point that launches k_decode with a destination asks this before anything is queued.
 static bool decode_dst_ok(const lmc_kv_layout* d, long long chunk_tokens) {
   typedef __int128 wide;  // (the products of two 64-bit strides and counts)
   const wide E = lmc_dtype_fp8(d->dtype) ? 1 : 2;
+  if (d->paged_kind == LMC_PAGED_SPLIT) {
+    if (d->stride_head < 0) return false;
+    return ((wide)(d->num_heads - 1) * d->stride_head + (wide)d->head_size * d->block_size) * E + 7 * 16 <= (wide)0xfffffff0ll;
+  }
   if (d->stride_head < 0 || d->stride_token < 0) return false;
   const wide row = ((wide)(d->num_heads - 1) * d->stride_head + d->head_size) * E;
   const wide row_step = (wide)d->stride_token * E;
@@ -641,10 +650,11 @@ static int decode_geometry(lmc_ctx* c, int nchunks, int L, int H, int D, uint32_
   return LMC_OK;
 }
 // decode_common -- ... of the geometry of `dst`, into it from token dst_tok0 on: what every entry point with a
-// destination asks of it (lmc_decode_symbols has none) before it looks at anything else of `dst`;
+// destination asks of it (lmc_decode_symbols has none) before it looks at anything else of `dst`.  `split_ok`: the entry
+// point takes an LMC_PAGED_SPLIT destination -- the four the engine's retrieve paths use; lmc_decode_chunks does not;
 static int decode_common(lmc_ctx* c, int nchunks, const lmc_kv_layout* dst, int dst_tok0, long long chunk_tokens,
-                         uint32_t* job_status, DecodeArgs& a) {
-  if (!layout_ok(dst, false) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens)) return LMC_ERR_INVALID;
+                         uint32_t* job_status, DecodeArgs& a, bool split_ok = false) {
+  if (!layout_ok(dst, false, split_ok) || chunk_tokens < 1 || !decode_dst_ok(dst, chunk_tokens)) return LMC_ERR_INVALID;
   const int rc = decode_geometry(c, nchunks, dst->num_layers, dst->num_heads, dst->head_size, job_status, a);
   if (rc) return rc;
   a.dst = to_addr(dst); a.dst_tok0 = dst_tok0; a.chunk_tokens = (int)chunk_tokens;
@@ -659,11 +669,12 @@ static bool decode_blobs(DecodeArgs& a, const void* blobs, uint64_t stride, cons
 }
 
 // k_decode for a destination dtype: the destination's dtype decides what a blob decodes to (any blob, any of the four)
-static void launch_decode(int dtype, bool paged, dim3 grid, hipStream_t s, const DecodeArgs& a) {
+static void launch_decode(int dtype, int kind, dim3 grid, hipStream_t s, const DecodeArgs& a) {
   with_kv_dtype(dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
-    if (paged) hipLaunchKernelGGL((k_decode<false, DT, true>), grid, dim3(64 * DEC_WAVES), 0, s, a);
-    else hipLaunchKernelGGL((k_decode<false, DT, false>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+    if (kind == DEC_PAGED_SPLIT) hipLaunchKernelGGL((k_decode<false, DT, DEC_PAGED_SPLIT>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+    else if (kind == DEC_PAGED_ROWS) hipLaunchKernelGGL((k_decode<false, DT, DEC_PAGED_ROWS>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+    else hipLaunchKernelGGL((k_decode<false, DT, DEC_ROWS>), grid, dim3(64 * DEC_WAVES), 0, s, a);
   });
 }
 
@@ -673,7 +684,8 @@ static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, 
   a.layer_begin = l0; a.layer_count = nl;
   const long long n = (long long)a.nchunks * 2 * nl * a.G;
   const dim3 grid((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES));
-  launch_decode(dst->dtype, dst->slot_mapping != nullptr, grid, s, a);
+  const int kind = dst->paged_kind == LMC_PAGED_SPLIT ? DEC_PAGED_SPLIT : dst->slot_mapping ? DEC_PAGED_ROWS : DEC_ROWS;
+  launch_decode(dst->dtype, kind, grid, s, a);
   HIP_TRY(hipGetLastError());
   if (ev) HIP_TRY(hipEventRecord((hipEvent_t)ev, s));
   return LMC_OK;
@@ -708,7 +720,7 @@ int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t 
                              const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t layer_begin,
                              int32_t layer_count, uint32_t* job_status, lmc_stream_t stream) {
   DecodeArgs a;
-  const int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a);
+  const int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, true);
   if (rc) return rc;
   if (!decode_blobs(a, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, blob_ptrs) || layer_begin < 0 || layer_count < 1 ||
       layer_begin + layer_count > dst->num_layers)
@@ -722,7 +734,7 @@ int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_
                                const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
                                lmc_stream_t stream) {
   DecodeArgs a;
-  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a);
+  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, true);
   if (rc) return rc;
   if (!decode_blobs(a, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, blob_ptrs) || nranges < 1 || !layer_ends_h)
     return LMC_ERR_INVALID;
@@ -746,7 +758,7 @@ int lmc_decode_symbols(lmc_ctx* c, const void* blob, int32_t L, int32_t H, int32
   a.sym_out = sym_out;
   HIP_TRY(hipSetDevice(c->device));
   const long long n = (long long)a.P * a.G;  // every layer (decode_geometry set the full range)
-  hipLaunchKernelGGL((k_decode<true, LMC_DTYPE_BF16, false>), dim3((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((k_decode<true, LMC_DTYPE_BF16, DEC_ROWS>), dim3((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return LMC_OK;
 }
@@ -1012,7 +1024,7 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
                     lmc_event_t* range_events, uint32_t* job_status, lmc_stream_t stream) {
   if (!host_blob_ptrs_h || !sizes_h || layers_per_range < 0) return LMC_ERR_INVALID;
   DecodeArgs da;
-  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, da);
+  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, da, true);
   if (rc) return rc;
   const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
   const uint64_t stride = blob_stride(L, chunk_tokens, H, D);
@@ -1225,7 +1237,7 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
     return LMC_ERR_INVALID;
   const int n = (int)h.nchunks, c0 = chunk_begin, m = nchunks ? nchunks : n - c0;  // chunks c0 .. c0 + m of the pack
   DecodeArgs da;
-  int rc = decode_common(c, m, dst, dst_tok0, (long long)h.chunk_tokens, job_status, da);
+  int rc = decode_common(c, m, dst, dst_tok0, (long long)h.chunk_tokens, job_status, da, true);
   if (rc) return rc;
   const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
   if ((uint32_t)L != h.num_layers || (uint32_t)H != h.num_heads || (uint32_t)D != h.head_size) return LMC_ERR_INVALID;

@@ -414,7 +414,8 @@ class KVLayout:
         """Whether the encoders can read this layout with their 16-byte vectors of 8 channels (the rule of layout_ok in
         lmc_api.hip / include/lmc_hip.h): rows on 16-byte boundaries, strides multiples of 8 elements, and head_size a
         multiple of 8 unless the heads of a token row lie back to back.  The decoders and lmc_copy_kv take any layout.
-        A PAGED_SPLIT layout ("NHDB") has no rows at all: only lmc_copy_kv reads or writes it."""
+        A PAGED_SPLIT layout ("NHDB") has no rows at all: lmc_copy_kv reads and writes it, the decoders behind the
+        engine's retrieve paths (decode_chunks_layers / _schedule, load_chunks, load_pack) write it, nobody else takes it."""
         s = self.struct
         if s.paged_kind != PAGED_ROWS:
             return False
@@ -520,7 +521,9 @@ class KVLayout:
             index 1 IS the value cache, index 0 holds the keys in the x-split order of the next form, or
           - the pair (key_cache [num_blocks, H, D / x, block_size, x], value_cache [num_blocks, H, D, block_size]).
         A token's channels are not contiguous there (K: x-element granules block_size * x apart, V: every element
-        block_size apart), so the layout is not vector_readable() and only lmc_copy_kv takes it (k_copy_split.h)."""
+        block_size apart), so the layout is not vector_readable(): the encoders cannot read it.  lmc_copy_kv gathers from and
+        scatters into it (k_copy_split.h), and the decoders store into it (k_decode.h, DEC_PAGED_SPLIT) -- all of them but
+        decode_chunks, whose callers want a tensor."""
         first = kv_caches[0]
         pair = isinstance(first, (tuple, list))
         v0 = first[1] if pair else first

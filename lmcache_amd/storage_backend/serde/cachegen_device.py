@@ -1118,6 +1118,19 @@ class CacheGenDeviceCodec:
                     # decodes batch b as soon as its blobs have landed (one event per batch)
                     B = batch_chunks or self.decode_batch_chunks
                     last = None
+                    table, table_at = None, {}
+                    if dst.struct.paged_kind == native.PAGED_SPLIT:
+                        # lmc_decode_chunks stands for from_bytes and writes rows only (include/lmc_hip.h): an "NHDB"
+                        # cache takes the same slots through a pointer table -- ONE for all n slots, made before the
+                        # first batch and uploaded stream-ordered from pinned memory (no host wait, as decode_device's table);
+                        # batch b reads its part of it; the job keeps it until it is finished
+                        # (a batch's part starts on a 16-byte boundary, as the call asks of its table: an odd batch is padded)
+                        ptrs = []
+                        for b0 in range(0, n, B):
+                            table_at[b0] = len(ptrs)
+                            ptrs += [arena.data_ptr() + i * stride for i in range(b0, min(n, b0 + B))]
+                            ptrs += [0] * (len(ptrs) & 1)
+                        table = torch.tensor(ptrs, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
                     for b0 in range(0, n, B):
                         b1 = min(n, b0 + B)
                         for i in range(b0, b1):
@@ -1139,13 +1152,18 @@ class CacheGenDeviceCodec:
                         ready = torch.cuda.Event()
                         ready.record(self.copy_stream)
                         cur.wait_event(ready)
-                        self.ctx.decode_chunks(arena.data_ptr() + b0 * stride, stride, b1 - b0, dst,
-                                               dst_tok0 + b0 * chunk_tokens, chunk_tokens, stream=cur.cuda_stream,
-                                               status_ptr=st_ptr)
+                        if table is not None:
+                            self.ctx.decode_chunks_layers(table.data_ptr() + 8 * table_at[b0], stride, b1 - b0, dst,
+                                                          dst_tok0 + b0 * chunk_tokens, chunk_tokens, 0, dst.L,
+                                                          stream=cur.cuda_stream, status_ptr=st_ptr)
+                        else:
+                            self.ctx.decode_chunks(arena.data_ptr() + b0 * stride, stride, b1 - b0, dst,
+                                                   dst_tok0 + b0 * chunk_tokens, chunk_tokens, stream=cur.cuda_stream,
+                                                   status_ptr=st_ptr)
                         last = torch.cuda.Event()
                         last.record(cur)
                     self._dec_free = last
-                return DecodeJob(last, status_idx=st, pool=self._status)
+                return DecodeJob(last, table=table, status_idx=st, pool=self._status)
 
     def finish_decode(self, job: Optional[DecodeJob], what: str = "CacheGen decode") -> None:
         """Wait for THIS decode (its event, not the device) and raise NativeError if a kernel flagged its blobs
