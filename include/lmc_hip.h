@@ -94,7 +94,7 @@ int lmc_abi_version(void);
  * (a dense cache: stride_head = D*block_size, stride_block = H*D*block_size).  A token's channels are not contiguous
  * there.  Who takes such a layout:
  *   - lmc_copy_kv, as its source or as its destination (not both; the other side is any LMC_PAGED_ROWS layout):
- *     k_copy_split.h;
+ *     k_copy_split.h; the scatter_dst of an lmc_range_post, as a destination;
  *   - as a DECODE DESTINATION, the four entry points behind a serving engine's retrieve: lmc_decode_chunks_layers,
  *     lmc_decode_chunks_schedule, lmc_load_chunks and lmc_load_pack (k_decode.h stores into the split blocks: a lane's
  *     head / granule / element is its 32-bit offset, a token its block, 64-bit, plus its slot's step).  Its 32-bit
@@ -277,6 +277,40 @@ int lmc_decode_chunks_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint6
                                const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
                                lmc_stream_t stream);
 
+/*
+ * What is done to each layer range of a decode job AFTER its decode launch and BEFORE its event (lmc_decode_chunks_schedule_post,
+ * lmc_load_pack_post): the event of a range then says "decoded, re-rotated and in its final place".  Stands where
+ * engine.retrieve_into_paged() queues one lmc_rope_shift and, for a staged "NHDB" retrieve, one lmc_copy_kv over ALL
+ * layers behind the whole decode, so that the model waits for the last layer: here the same work is cut by the job's
+ * ranges and the attention of layer l waits for its own range only (a vLLM v1 connector's wait_for_layer_load(l)).
+ *   `dst` below is the job's decode destination; the post-op works on the layer window [l0, l0 + nl) of the layouts
+ *   cos_sin .. deltas  a rotation as lmc_rope_shift takes it (cos_sin NULL: none); deltas[i] belongs to token tok_begin + i
+ *   tok_begin, ntok    the tokens of `dst` this job filled (the caller knows: dst_tok0, the chunks, the first-chunk trim)
+ *   scatter_dst        NULL, or an LMC_PAGED_SPLIT cache: `dst` is a staged chunk of rows, and token tok_begin + i of the
+ *                      range's layers is scattered to token scatter_tok0 + i of scatter_dst (lmc_copy_kv's scatter)
+ * Per range:  rotation -- lmc_rope_shift's kernels in place on the window of `dst` (rows);  scatter -- lmc_copy_kv's
+ * scatter of the window;  both -- the rotation of the staged window, then its scatter, two launches (a scatter that
+ * rotates the keys on their way was built and measured: slower than the two, profiles/paged_layerwise.md).  Neither: nothing.
+ * The whole post-op is held against lmc_rope_shift's and lmc_copy_kv's rules before anything of the job is queued
+ * (LMC_ERR_INVALID): a rotation of an LMC_PAGED_SPLIT `dst`, of fp8, a scatter_dst that is not LMC_PAGED_SPLIT or differs
+ * from `dst` in geometry or dtype, ntok < 1, ...  A per-token |delta| outside the table is reported as lmc_rope_shift
+ * reports it with job_status NULL: LMC_STATUS_BAD_POSITION in the context's sticky word, that token copied unrotated (the
+ * job's own word stays the verdict on its blobs).
+ * The struct and everything it points to on the host is read during the call only.
+ */
+typedef struct lmc_range_post {
+  const float* cos_sin; int32_t table_rows, rot_dim, is_neox, delta; const int32_t* deltas;
+  int32_t tok_begin, ntok;
+  const lmc_kv_layout* scatter_dst;
+  int32_t scatter_tok0;
+} lmc_range_post;
+/* lmc_decode_chunks_schedule with `post` done to every range between its launch and its event; post NULL IS
+ * lmc_decode_chunks_schedule (one body). */
+int lmc_decode_chunks_schedule_post(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                    const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                    const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
+                                    lmc_stream_t stream, const lmc_range_post* post);
+
 /* Entropy-decode only (debug / parity): blob -> sym_out int8 [P][T][C].
  * Stands where torchac_cuda.decode_fast_prefsum stands (cachegen_decoder.py:65-66). */
 int lmc_decode_symbols(lmc_ctx* ctx, const void* blob, int32_t L, int32_t H, int32_t D, int8_t* sym_out,
@@ -438,6 +472,12 @@ int lmc_pack_extract(const void* pack_h, uint64_t nbytes, int32_t chunk, void* b
 int lmc_load_pack(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
                   const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
                   uint32_t* job_status, lmc_stream_t stream);
+/* lmc_load_pack with `post` (lmc_range_post, above) done to every range between its decode and range_events[r]: the
+ * pinned tier's layer-by-layer retrieve into a paged cache.  post NULL IS lmc_load_pack (one body); a post-op that does
+ * not check out is LMC_ERR_INVALID with nothing queued, like a pack that does not. */
+int lmc_load_pack_post(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
+                       const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
+                       uint32_t* job_status, lmc_stream_t stream, const lmc_range_post* post);
 
 /*
  * Moving encoded chunks BETWEEN the two local tiers without re-encoding them (bounded tiers: the HBM tier demotes its

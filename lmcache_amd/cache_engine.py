@@ -374,11 +374,85 @@ class LMCacheEngine:
         # launches above and the caller's first wait_layer)
         return LayerwiseRetrieval(lambda: self._blob_to_tuple_kv(blob), ret_mask, event_sets[-1], jobs, event_sets)
 
+    @_lmcache_nvtx_annotate
+    @torch.no_grad()
+    def retrieve_into_paged_layerwise(self, tokens: torch.Tensor, kv_caches, slot_mapping: torch.Tensor, block_size: int,
+                                      layout: str = "NBHD", mask: Optional[torch.Tensor] = None,
+                                      rope: Optional[RopeShift] = None, direct: bool = False,
+                                      layers_per_launch=1) -> "LayerwiseRetrieval":
+        """retrieve_into_paged() that does not make the model wait for the last layer -- the two halves of a warm prefix's
+        TTFT together: the KV goes straight into the serving engine's paged cache, as retrieve_into_paged writes it, and
+        the call returns at once with an event per range of layers, as retrieve_layerwise does.  The shape of a vLLM v1
+        connector: start_load_kv() calls this once, wait_for_layer_load(l) is `r.wait_layer(l)` in front of every
+        attention layer.  Arguments, layouts and refusals are retrieve_into_paged's (`direct`
+        with `rope` on "NHDB": ValueError before anything is queued); layers_per_launch is retrieve_layerwise's.
+        Returns a LayerwiseRetrieval whose `kv` is () -- the KV is in the cache -- and whose ret_mask is
+        retrieve_into_paged's.  A miss launches nothing: an all-False mask, no events.
+        The events: after wait_layer(l, s), work on stream s sees layer l's K and V in the cache in their FINAL state --
+        decoded, re-rotated (`rope`), and for a staged "NHDB" retrieve scattered into the split blocks.  What
+        retrieve_into_paged queues behind the whole decode (one lmc_rope_shift, one lmc_copy_kv, over all layers) is done
+        here per range, between the range's decode and its event, by the C call that launches the range (include/lmc_hip.h,
+        lmc_range_post); for "NHDB" with `rope` that is the rotation of the range's staged keys, then their scatter.
+        When everything has completed, every cache
+        tensor holds, bit for bit, what retrieve_into_paged with the same arguments leaves.
+        Staged "NHDB" (direct=False) keeps ONE staged chunk of the retrieved size; the returned object holds it until
+        finish().  direct=True sets no scatter: the decoder writes the split blocks.
+        Tiers: the HBM-resident CacheGen tier and the pinned tier's packs are cut by layers as above.  Pinned blobs that
+        are no pack (a store of one chunk, LMCACHE_AMD_PINNED_PACKS=0) cross PCIe whole, then decode range by range with
+        the post-ops in front of the events: layer 0 waits for that transfer.  The raw tiers and remote backends queue
+        everything, then the post-ops for all layers behind it, and ONE event covers every layer: correct, not layer-wise.
+        Call finish() before trusting the cache for good: it waits for the decode and raises NativeError if a stored
+        blob was corrupt -- the slots of the call's tokens may hold garbage then, as for retrieve_into_paged(direct=True)."""
+        assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
+        assert len(tokens) == slot_mapping.numel(), "one slot per token"
+        num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
+        if rope is not None:
+            if direct and layout == "NHDB":
+                raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
+                                 "not address an \"NHDB\" cache); use the staged retrieve")
+            self._check_rope(rope, kv_caches, layout, len(tokens))
+        box, jobs = {}, []
+
+        def make_dst(nret, L, H, D, dtype, dev):
+            dst = native.KVLayout.paged(kv_caches, slot_mapping[num_skip_tok:num_skip_tok + nret], block_size, layout)
+            assert dst.L == L and native.torch_dtype(dst.dtype) == dtype, "cache geometry / dtype differs from the stored chunks"
+            staged = layout == "NHDB" and not direct
+            assert layout != "NHDB" or (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
+            rows = dst
+            if staged:
+                box["chunk"] = torch.empty((L, 2, nret, H, D), dtype=dtype, device=dst.device)
+                rows = native.KVLayout.from_chunk(box["chunk"], "vllm")
+            box["L"], box["dev"] = L, dst.device
+            if staged or rope is not None:
+                box["post"] = native.RangePost(
+                    cos_sin=None if rope is None else rope.cos_sin.to(dst.device),
+                    rot_dim=0 if rope is None else rope.rot_dim, is_neox=rope is None or rope.is_neox,
+                    delta=0 if rope is None or isinstance(rope.delta, torch.Tensor) else rope.delta,
+                    deltas=None if rope is None else rope.deltas_for(num_skip_tok, nret, len(tokens), dst.device),
+                    scatter_dst=dst if staged else None)
+            return rows
+
+        got, ret_mask = self._retrieve_into(tokens, mask, make_dst, layers_per_launch=layers_per_launch, jobs_out=jobs,
+                                            post=lambda: box.get("post"))
+        if got == 0:
+            return LayerwiseRetrieval((), ret_mask, [], [])
+        # (the events of every decode job, or one event behind everything: as retrieve_layerwise)
+        event_sets = [list(job.layer_events) for _, job in jobs if job is not None and job.layer_events]
+        if not event_sets or len(event_sets) < len(jobs):
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(box["dev"]))
+            event_sets.append([(box["L"], ev)])
+        return LayerwiseRetrieval((), ret_mask, event_sets[-1], jobs, event_sets, hold=(box.get("chunk"), box.get("post")))
+
     def _retrieve_into(self, tokens: torch.Tensor, mask: Optional[torch.Tensor], make_dst,
-                       layers_per_launch: Optional[int] = None, jobs_out: Optional[list] = None) -> Tuple[int, torch.Tensor]:
+                       layers_per_launch: Optional[int] = None, jobs_out: Optional[list] = None,
+                       post=None) -> Tuple[int, torch.Tensor]:
         """The body of retrieve(): prefix probe, the first-chunk trim of a suffix mask, then every hit chunk
         written to destination tokens 0 .. got-1 of the layout make_dst(nret, L, H, D, dtype, device) returns.
-        -> (got = tokens written, ret_mask)."""
+        -> (got = tokens written, ret_mask).
+        post: a callable, asked after make_dst, for the native.RangePost of this retrieve (or None).  The CacheGen tiers
+        take it into their decode jobs (get_kv_range(post=...)); behind any other backend it is queued here (`pending`),
+        for all layers, once everything has been written."""
         t_start = time.perf_counter()
         fmt = self.metadata.fmt
         cs = self.chunk_size
@@ -404,6 +478,7 @@ class LMCacheEngine:
                     memo.pop(next(iter(memo)))
                 memo[mk] = keys
         dev = torch.device("cuda", torch.cuda.current_device())
+        pending = None  # the RangePost this function itself still has to queue, behind everything else
 
         def miss():
             ret_mask[:] = False
@@ -429,10 +504,13 @@ class LMCacheEngine:
             L = shape0[0]
             H, D = (shape0[3], shape0[4]) if fmt == "vllm" else (shape0[2], shape0[4])
             dst = make_dst(nret, L, H, D, dtype, dev)
+            pending = post() if post is not None else None
             try:
                 if jobs_out is not None and getattr(self.engine_, "mode", None) in ("hbm-cachegen", "cachegen"):
+                    kw = {} if pending is None else {"post": pending}
+                    pending = None  # (the decode jobs do it, range by range)
                     got = self.engine_.get_kv_range(keys if hits == len(keys) else keys[:hits], dst, fmt, -extra, cs,
-                                                    layers_per_launch=layers_per_launch, jobs_out=jobs_out)
+                                                    layers_per_launch=layers_per_launch, jobs_out=jobs_out, **kw)
                 else:
                     got = self.engine_.get_kv_range(keys if hits == len(keys) else keys[:hits], dst, fmt, -extra, cs)
             except native.NativeError:
@@ -459,6 +537,7 @@ class LMCacheEngine:
             L = c0.shape[0]
             H, D = (c0.shape[3], c0.shape[4]) if fmt == "vllm" else (c0.shape[2], c0.shape[4])
             dst = make_dst(nret, L, H, D, c0.dtype, c0.device)
+            pending = post() if post is not None else None
             ctx = native.get_context(c0.device.index)
             pos = -extra
             for c in chunks:  # scatter every chunk into its slice (replaces slice + torch.cat, :360-368)
@@ -467,6 +546,9 @@ class LMCacheEngine:
                 if skip < T:
                     ctx.copy_kv(native.KVLayout.from_chunk(c, fmt), skip, T - skip, dst, pos + skip)
                 pos += T
+        if pending is not None:  # (only reached behind a retrieve that wrote its nret tokens: every miss has returned)
+            with torch.cuda.device(dst.device):
+                pending.apply(native.get_context(dst.device.index), dst, 0, nret)
         if num_skip_tok + nret < len(ret_mask):
             ret_mask[num_skip_tok + nret:] = False
         logger.info("Retrieved %d chunks (%d tokens in total) -- elapsed time %.4f", hits, nret,
@@ -478,13 +560,15 @@ class LMCacheEngine:
 
 
 class LayerwiseRetrieval:
-    """What retrieve_layerwise returns: the KV tuple (being filled layer by layer), ret_mask, and the events."""
+    """What retrieve_layerwise and retrieve_into_paged_layerwise return: the KV tuple (being filled layer by layer; () when
+    the KV goes into a paged cache), ret_mask, and the events."""
 
-    def __init__(self, kv, ret_mask, layer_events, jobs, event_sets=None):
+    def __init__(self, kv, ret_mask, layer_events, jobs, event_sets=None, hold=None):
         # `layer_events` is the LAST run's list only (kept for callers of rounds 2-4): a retrieve that spans several
         # stores has one list per run, and layer l is complete when every run's range that holds l is -- use wait_layer()
         self._kv, self.ret_mask, self.layer_events, self._jobs = kv, ret_mask, layer_events, jobs
         self._event_sets = event_sets if event_sets is not None else ([layer_events] if layer_events else [])
+        self._hold = hold  # retrieve_into_paged_layerwise: the staged chunk and what the post-ops read, until finish()
 
     @property
     def kv(self):
@@ -516,8 +600,13 @@ class LayerwiseRetrieval:
     def finish(self) -> None:
         """Host-side completion: waits for the decode and raises NativeError if a blob did not check out."""
         jobs, self._jobs = self._jobs, []
-        for codec, job in jobs:
-            codec.finish_decode(job)
+        try:
+            for codec, job in jobs:
+                codec.finish_decode(job)
+            if self._hold is not None and not jobs and self.layer_events:
+                self.layer_events[-1][1].synchronize()  # a backend without jobs: its one event
+        finally:
+            self._hold = None
 
 
 class LMCacheEngineBuilder:

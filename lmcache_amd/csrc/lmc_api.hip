@@ -680,20 +680,27 @@ static void launch_decode(int dtype, int kind, dim3 grid, hipStream_t s, const D
 
 // One range of layers of a decode: k_decode over the streams of layers [l0, l0 + nl) of the job's chunks, then `ev`
 // (if any) recorded behind it.  The lock is not needed for the launch itself: the load paths call this with c->mu held.
-static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev) {
+static int range_post(lmc_ctx* c, const lmc_kv_layout* dst, const lmc_range_post* post, int l0, int nl, hipStream_t s);
+static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev,
+                               lmc_ctx* c = nullptr, const lmc_range_post* post = nullptr) {
   a.layer_begin = l0; a.layer_count = nl;
   const long long n = (long long)a.nchunks * 2 * nl * a.G;
   const dim3 grid((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES));
   const int kind = dst->paged_kind == LMC_PAGED_SPLIT ? DEC_PAGED_SPLIT : dst->slot_mapping ? DEC_PAGED_ROWS : DEC_ROWS;
   launch_decode(dst->dtype, kind, grid, s, a);
   HIP_TRY(hipGetLastError());
+  if (post) {  // (none of its launches needs the lock)
+    const int rc = range_post(c, dst, post, l0, nl, s);
+    if (rc) return rc;
+  }
   if (ev) HIP_TRY(hipEventRecord((hipEvent_t)ev, s));
   return LMC_OK;
 }
 
 // The same for the decode entry points, which do not hold the lock: taken here, and the launch bracketed by the
 // profiling marks (the range's event follows the second mark).
-static int decode_range(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev) {
+static int decode_range(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev,
+                        const lmc_range_post* post = nullptr) {
   int rc;
   {
     std::lock_guard<std::mutex> lk(c->mu);
@@ -702,6 +709,7 @@ static int decode_range(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, int
     if ((rc = decode_range_locked(a, dst, l0, nl, s, nullptr))) return rc;
     if ((rc = prof_mark(c, s))) return rc;
   }
+  if (post && (rc = range_post(c, dst, post, l0, nl, s))) return rc;
   if (ev) HIP_TRY(hipEventRecord((hipEvent_t)ev, s));
   return LMC_OK;
 }
@@ -729,10 +737,12 @@ int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t 
   return decode_range(c, a, dst, layer_begin, layer_count, (hipStream_t)stream, nullptr);
 }
 
-int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
-                               const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
-                               const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
-                               lmc_stream_t stream) {
+static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* post);
+
+int lmc_decode_chunks_schedule_post(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                    const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                    const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
+                                    lmc_stream_t stream, const lmc_range_post* post) {
   DecodeArgs a;
   int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, true);
   if (rc) return rc;
@@ -740,12 +750,20 @@ int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_
     return LMC_ERR_INVALID;
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)  // the whole schedule is checked before anything is launched
     if (layer_ends_h[i] <= prev || layer_ends_h[i] > dst->num_layers) return LMC_ERR_INVALID;
-  if (layer_ends_h[nranges - 1] != dst->num_layers) return LMC_ERR_INVALID;
+  if (layer_ends_h[nranges - 1] != dst->num_layers || !post_ok(dst, post)) return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)
-    if ((rc = decode_range(c, a, dst, prev, layer_ends_h[i] - prev, (hipStream_t)stream, events_h ? events_h[i] : nullptr)))
+    if ((rc = decode_range(c, a, dst, prev, layer_ends_h[i] - prev, (hipStream_t)stream, events_h ? events_h[i] : nullptr, post)))
       return rc;
   return LMC_OK;
+}
+
+int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                               const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                               const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
+                               lmc_stream_t stream) {
+  return lmc_decode_chunks_schedule_post(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h,
+                                         events_h, job_status, stream, nullptr);
 }
 
 int lmc_decode_symbols(lmc_ctx* c, const void* blob, int32_t L, int32_t H, int32_t D, int8_t* sym_out,
@@ -808,6 +826,39 @@ static int copy_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, i
   return LMC_OK;
 }
 
+// What lmc_copy_kv asks of its two layouts and its range (every refusal LMC_ERR_INVALID, nothing launched).
+static bool copy_kv_ok(const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst, int32_t dst_tok0) {
+  if (!layout_ok(src, false, true) || !layout_ok(dst, false, true) || ntok < 1 || tok_begin < 0 || dst_tok0 < 0) return false;
+  if (src->num_layers != dst->num_layers || src->num_heads != dst->num_heads || src->head_size != dst->head_size ||
+      src->dtype != dst->dtype)
+    return false;
+  return !(src->paged_kind == LMC_PAGED_SPLIT && dst->paged_kind == LMC_PAGED_SPLIT);  // one side is rows
+}
+
+// A rotation as lmc_rope_shift takes it.
+struct RopeSpec {
+  const float* cos_sin;
+  int32_t table_rows, rot_dim, is_neox, delta;
+  const int32_t* deltas;
+};
+// 16-byte accesses to the table and whole 8-channel vectors per pair half (k_rope_vec)
+static bool rope_vec_ok(const RopeSpec& r) {
+  return r.rot_dim % (r.is_neox ? 16 : 8) == 0 && ((uintptr_t)r.cos_sin & 15) == 0;
+}
+// The access form is chosen as lmc_copy_kv chooses `vec`; -> the work items of one head
+static bool rope_vec(const lmc_kv_layout* kv, const RopeSpec& r) { return layout_ok(kv) && kv->head_size % 8 == 0 && rope_vec_ok(r); }
+static int rope_per_head(const lmc_kv_layout* kv, const RopeSpec& r) {
+  return rope_vec(kv, r) ? r.rot_dim / (r.is_neox ? 16 : 8) : r.rot_dim / 2;
+}
+// ... and what lmc_rope_shift asks of it, of the rows it rotates and of their range.
+static bool rope_ok(const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const RopeSpec& r) {
+  if (!layout_ok(kv, false) || lmc_dtype_fp8(kv->dtype) || ntok < 1 || tok_begin < 0 || !r.cos_sin || r.table_rows < 1) return false;
+  if (r.rot_dim < 2 || (r.rot_dim & 1) || r.rot_dim > kv->head_size) return false;
+  if (!r.deltas && (r.delta <= -r.table_rows || r.delta >= r.table_rows)) return false;
+  // the work items of one layer: the kernels index them with 32 bits
+  return (long long)ntok * kv->num_heads * rope_per_head(kv, r) < (1ll << 31);
+}
+
 // Re-rotate the keys of tokens [tok_begin, +ntok) by a position difference, in place (k_rope.h).  The access form is
 // chosen as lmc_copy_kv chooses `vec`: 16-byte vectors where the rows, the head and the pair halves are whole vectors
 // (and the table's rows are), one pair per thread for everything else.
@@ -818,19 +869,77 @@ static void launch_rope(bool vec, bool neox, dim3 grid, size_t lds, hipStream_t 
   else hipLaunchKernelGGL((k_rope_vec<DT, false>), grid, dim3(256), lds, s, a);
 }
 
+// lmc_rope_shift behind its checks (rope_ok).
+static int rope_launch(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const RopeSpec& r,
+                       uint32_t* job_status, hipStream_t stream) {
+  const bool neox = r.is_neox != 0;
+  const int rot_dim = r.rot_dim;
+  const bool vec = rope_vec(kv, r);
+  RopeArgs a;
+  memset(&a, 0, sizeof a);
+  a.kv = to_addr(kv);
+  a.cos_sin = r.cos_sin; a.deltas = r.deltas; a.status = job_status ? job_status : c->status_h;
+  a.tok_begin = tok_begin; a.ntok = ntok; a.rot = rot_dim; a.table_rows = r.table_rows; a.delta = r.delta; a.neox = neox;
+  a.per_head = (u32)rope_per_head(kv, r);
+  const long long nitems = (long long)ntok * kv->num_heads * a.per_head;  // of one layer (< 2^31: rope_ok)
+  a.nitems = (u32)nitems;
+  HIP_TRY(hipSetDevice(c->device));
+  long long blocks = (nitems + 255) / 256;
+  const long long cap = std::max(1ll, 64ll * c->num_cus / kv->num_layers);  // grid-stride beyond 64 blocks per CU
+  if (blocks > cap) blocks = cap;
+  const dim3 grid((unsigned)blocks, (unsigned)kv->num_layers);
+  const size_t lds = vec && !r.deltas ? (size_t)rot_dim * sizeof(float) : 0;  // the one table row of a uniform delta
+  if (kv->dtype == LMC_DTYPE_BF16) launch_rope<LMC_DTYPE_BF16>(vec, neox, grid, lds, stream, a);
+  else launch_rope<LMC_DTYPE_FP16>(vec, neox, grid, lds, stream, a);
+  HIP_TRY(hipGetLastError());
+  return LMC_OK;
+}
+
+// ---- the post-op of a layer range (lmc_range_post): between a range's decode and its event --------------------------
+// Layers [l0, l0 + nl) of a layout as a layout of nl layers: the plane table is layer-major (lmc_plane_base), so the
+// window is a pointer into it, or the base moved by l0 layer strides.  The rope and copy kernels need nothing else.
+static lmc_kv_layout layer_window(const lmc_kv_layout* l, int l0, int nl) {
+  lmc_kv_layout w = *l;
+  if (w.plane_ptrs) w.plane_ptrs += 2 * l0;
+  else w.base = (const u8*)w.base + (long long)l0 * w.stride_layer * (lmc_dtype_fp8(w.dtype) ? 1 : 2);
+  w.num_layers = nl;
+  return w;
+}
+static RopeSpec post_rope(const lmc_range_post* p) {
+  const RopeSpec r = {p->cos_sin, p->table_rows, p->rot_dim, p->is_neox, p->delta, p->deltas};
+  return r;
+}
+// The whole post-op against lmc_copy_kv's and lmc_rope_shift's rules, before anything of the job is queued.
+static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* p) {
+  if (!p || (!p->cos_sin && !p->scatter_dst)) return true;
+  if (p->scatter_dst && (p->scatter_dst->paged_kind != LMC_PAGED_SPLIT ||
+                         !copy_kv_ok(dst, p->tok_begin, p->ntok, p->scatter_dst, p->scatter_tok0)))
+    return false;
+  return !p->cos_sin || rope_ok(dst, p->tok_begin, p->ntok, post_rope(p));  // (a split `dst` has no rows to rotate: refused)
+}
+// A bad position is reported where lmc_rope_shift reports it for the one-shot retrieve: the context's sticky word (the
+// job's own word says whether its blobs decoded).
+static int range_post(lmc_ctx* c, const lmc_kv_layout* dst, const lmc_range_post* p, int l0, int nl, hipStream_t s) {
+  if (!p->cos_sin && !p->scatter_dst) return LMC_OK;
+  const lmc_kv_layout rows = layer_window(dst, l0, nl);
+  if (!p->scatter_dst) return rope_launch(c, &rows, p->tok_begin, p->ntok, post_rope(p), nullptr, s);
+  // rotation and scatter: the staged rows are rotated in place, then scattered (a scatter that rotates on the way was built
+  // and measured slower than these two launches: profiles/paged_layerwise.md)
+  if (p->cos_sin) {
+    const int rc = rope_launch(c, &rows, p->tok_begin, p->ntok, post_rope(p), nullptr, s);
+    if (rc) return rc;
+  }
+  const lmc_kv_layout split = layer_window(p->scatter_dst, l0, nl);
+  return copy_split(c, &rows, p->tok_begin, p->ntok, &split, p->scatter_tok0, s);
+}
+
 extern "C" {
 
 int lmc_copy_kv(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst,
                 int32_t dst_tok0, lmc_stream_t stream) {
-  if (!c || !layout_ok(src, false, true) || !layout_ok(dst, false, true) || ntok < 1 || tok_begin < 0 || dst_tok0 < 0)
-    return LMC_ERR_INVALID;
-  if (src->num_layers != dst->num_layers || src->num_heads != dst->num_heads || src->head_size != dst->head_size ||
-      src->dtype != dst->dtype)
-    return LMC_ERR_INVALID;
-  if (src->paged_kind == LMC_PAGED_SPLIT || dst->paged_kind == LMC_PAGED_SPLIT) {
-    if (src->paged_kind == dst->paged_kind) return LMC_ERR_INVALID;  // one side is rows
+  if (!c || !copy_kv_ok(src, tok_begin, ntok, dst, dst_tok0)) return LMC_ERR_INVALID;
+  if (src->paged_kind == LMC_PAGED_SPLIT || dst->paged_kind == LMC_PAGED_SPLIT)
     return copy_split(c, src, tok_begin, ntok, dst, dst_tok0, (hipStream_t)stream);
-  }
   const bool vec = layout_ok(src) && layout_ok(dst);  // else one element per thread (any strides, any head_size)
   CopyArgs a;
   memset(&a, 0, sizeof a);
@@ -853,31 +962,9 @@ int lmc_copy_kv(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t
 int lmc_rope_shift(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const float* cos_sin,
                    int32_t table_rows, int32_t rot_dim, int32_t is_neox, int32_t delta, const int32_t* deltas,
                    uint32_t* job_status, lmc_stream_t stream) {
-  if (!c || !layout_ok(kv, false) || lmc_dtype_fp8(kv->dtype) || ntok < 1 || tok_begin < 0 || !cos_sin || table_rows < 1)
-    return LMC_ERR_INVALID;
-  if (rot_dim < 2 || (rot_dim & 1) || rot_dim > kv->head_size) return LMC_ERR_INVALID;
-  if (!deltas && (delta <= -table_rows || delta >= table_rows)) return LMC_ERR_INVALID;
-  const bool neox = is_neox != 0;
-  const bool vec = layout_ok(kv) && kv->head_size % 8 == 0 && rot_dim % (neox ? 16 : 8) == 0 && ((uintptr_t)cos_sin & 15) == 0;
-  RopeArgs a;
-  memset(&a, 0, sizeof a);
-  a.kv = to_addr(kv);
-  a.cos_sin = cos_sin; a.deltas = deltas; a.status = job_status ? job_status : c->status_h;
-  a.tok_begin = tok_begin; a.ntok = ntok; a.rot = rot_dim; a.table_rows = table_rows; a.delta = delta; a.neox = neox;
-  a.per_head = (u32)(vec ? rot_dim / (neox ? 16 : 8) : rot_dim / 2);
-  const long long nitems = (long long)ntok * kv->num_heads * a.per_head;  // of one layer: the kernels index it with 32 bits
-  if (nitems >= (1ll << 31)) return LMC_ERR_INVALID;
-  a.nitems = (u32)nitems;
-  HIP_TRY(hipSetDevice(c->device));
-  long long blocks = (nitems + 255) / 256;
-  const long long cap = std::max(1ll, 64ll * c->num_cus / kv->num_layers);  // grid-stride beyond 64 blocks per CU
-  if (blocks > cap) blocks = cap;
-  const dim3 grid((unsigned)blocks, (unsigned)kv->num_layers);
-  const size_t lds = vec && !deltas ? (size_t)rot_dim * sizeof(float) : 0;  // the one table row of a uniform delta
-  if (kv->dtype == LMC_DTYPE_BF16) launch_rope<LMC_DTYPE_BF16>(vec, neox, grid, lds, (hipStream_t)stream, a);
-  else launch_rope<LMC_DTYPE_FP16>(vec, neox, grid, lds, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return LMC_OK;
+  const RopeSpec r = {cos_sin, table_rows, rot_dim, is_neox, delta, deltas};
+  if (!c || !rope_ok(kv, tok_begin, ntok, r)) return LMC_ERR_INVALID;
+  return rope_launch(c, kv, tok_begin, ntok, r, job_status, (hipStream_t)stream);
 }
 
 // ---- host DRAM offload plumbing ---------------------------------------------
@@ -1228,9 +1315,9 @@ int lmc_pack_extract(const void* pack_h, uint64_t nbytes, int32_t chunk, void* b
   return LMC_OK;
 }
 
-int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
-                  const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
-                  uint32_t* job_status, lmc_stream_t stream) {
+int lmc_load_pack_post(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
+                       const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
+                       uint32_t* job_status, lmc_stream_t stream, const lmc_range_post* post) {
   lmc_pack_header h;
   if (layers_per_range < 0 || nchunks < 0 || chunk_begin < 0 || !pack_ok((const u8*)pack_h, pack_bytes, &h) ||
       (uint32_t)chunk_begin >= h.nchunks || (uint32_t)nchunks > h.nchunks - (uint32_t)chunk_begin)
@@ -1240,7 +1327,8 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
   int rc = decode_common(c, m, dst, dst_tok0, (long long)h.chunk_tokens, job_status, da, true);
   if (rc) return rc;
   const int L = dst->num_layers, H = dst->num_heads, D = dst->head_size;
-  if ((uint32_t)L != h.num_layers || (uint32_t)H != h.num_heads || (uint32_t)D != h.head_size) return LMC_ERR_INVALID;
+  if ((uint32_t)L != h.num_layers || (uint32_t)H != h.num_heads || (uint32_t)D != h.head_size || !post_ok(dst, post))
+    return LMC_ERR_INVALID;
   const u8* b = (const u8*)pack_h;
   const uint64_t* t = (const uint64_t*)(b + h.off_table);
   HIP_TRY(hipSetDevice(c->device));
@@ -1280,11 +1368,18 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
       }
     }
     if ((rc = stream_follows(c, s, cs))) return rc;
-    if ((rc = decode_range_locked(da, dst, l0, nl, s, range_events ? range_events[r] : nullptr))) return rc;
+    if ((rc = decode_range_locked(da, dst, l0, nl, s, range_events ? range_events[r] : nullptr, c, post))) return rc;
   }
   HIP_TRY(hipEventRecord(c->load_free, s));
   c->load_used = true;
   return LMC_OK;
+}
+
+int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
+                  const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
+                  uint32_t* job_status, lmc_stream_t stream) {
+  return lmc_load_pack_post(c, pack_h, pack_bytes, chunk_begin, nchunks, dst, dst_tok0, layers_per_range, range_events, job_status,
+                            stream, nullptr);
 }
 
 // ---- bounded tiers: blobs of earlier stores -> a pack (demotion), a pack -> blobs (promotion) ------------------------

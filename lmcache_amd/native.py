@@ -111,6 +111,14 @@ class KvLayoutStruct(ctypes.Structure):
 PAGED_ROWS, PAGED_SPLIT = 0, 1  # LMC_PAGED_*: lmc_kv_layout.paged_kind
 
 
+class RangePostStruct(ctypes.Structure):
+    """lmc_range_post (include/lmc_hip.h): what is done to each layer range of a decode job before its event."""
+    _fields_ = [("cos_sin", ctypes.c_void_p), ("table_rows", ctypes.c_int32), ("rot_dim", ctypes.c_int32),
+                ("is_neox", ctypes.c_int32), ("delta", ctypes.c_int32), ("deltas", ctypes.c_void_p),
+                ("tok_begin", ctypes.c_int32), ("ntok", ctypes.c_int32), ("scatter_dst", ctypes.POINTER(KvLayoutStruct)),
+                ("scatter_tok0", ctypes.c_int32)]
+
+
 class BlobHeader(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint16), ("header_bytes", ctypes.c_uint16),
                 ("dtype", ctypes.c_uint32), ("num_layers", ctypes.c_uint32), ("ntokens", ctypes.c_uint32),
@@ -152,6 +160,8 @@ SYMBOLS = {
     "lmc_decode_chunks": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _vp, _vp]),
     "lmc_decode_chunks_layers": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lmc_decode_chunks_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "lmc_decode_chunks_schedule_post": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                                       ctypes.POINTER(RangePostStruct)]),
     "lmc_decode_symbols": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "lmc_store_chunks": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "lmc_load_chunks": (ctypes.c_int, [_vp, _vp, _vp, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -160,6 +170,8 @@ SYMBOLS = {
     "lmc_pack_info": (ctypes.c_int, [_vp, _u64, ctypes.POINTER(PackHeader)]),
     "lmc_pack_extract": (ctypes.c_int, [_vp, _u64, _i32, _vp, _u64, _vp]),
     "lmc_load_pack": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _PL, _i32, _i32, _vp, _vp, _vp]),
+    "lmc_load_pack_post": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _PL, _i32, _i32, _vp, _vp, _vp,
+                                          ctypes.POINTER(RangePostStruct)]),
     "lmc_pack_blobs": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _u64, _vp, _vp]),
     "lmc_unpack_blobs": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "lmc_pack_chunk_bytes": (ctypes.c_int, [_vp, _u64, _i32, ctypes.POINTER(ctypes.c_uint32)]),
@@ -410,6 +422,21 @@ class KVLayout:
     def dtype(self):
         return self.struct.dtype
 
+    def layers(self, l0: int, nl: int) -> "KVLayout":
+        """Layers [l0, l0 + nl) of this layout as a layout of nl layers (the window the C side cuts for the post-op of a
+        layer range -- layer_window() in lmc_api.hip is the same arithmetic, and tests/test_gpu_range_post.py holds
+        a rotation of this window against the C side's): the plane table is layer-major, so the window is a pointer into
+        it, or the base moved by l0 layer strides.  Shares everything this layout keeps alive."""
+        if not (0 <= l0 and nl >= 1 and l0 + nl <= self.L):
+            raise ValueError(f"layers [{l0}, {l0 + nl}) of a layout of {self.L}")
+        s = KvLayoutStruct.from_buffer_copy(self.struct)
+        if s.plane_ptrs:
+            s.plane_ptrs += 16 * l0  # two 8-byte pointers per layer
+        else:
+            s.base += l0 * s.stride_layer * elem_bytes(s.dtype)
+        s.num_layers = nl
+        return KVLayout(s, self._keep, self.ntokens, self.device)
+
     def vector_readable(self) -> bool:
         """Whether the encoders can read this layout with their 16-byte vectors of 8 channels (the rule of layout_ok in
         lmc_api.hip / include/lmc_hip.h): rows on 16-byte boundaries, strides multiples of 8 elements, and head_size a
@@ -577,6 +604,51 @@ class KVLayout:
         s = _layout_struct(v0.dtype, len(planes), H, D, 0, stride_head, plane_ptrs=table.data_ptr(), slot_mapping=sm.data_ptr(),
                            block_size=block_size, stride_block=stride_block, paged_kind=PAGED_SPLIT)
         return KVLayout(s, keep + [table, sm], sm.numel(), v0.device)
+
+
+class RangePost:
+    """Python owner of what becomes one lmc_range_post per decode job: a rotation as Context.rope_shift takes it and / or
+    the LMC_PAGED_SPLIT cache the decode destination (then a staged chunk of rows) is scattered into.  Written in the
+    decode destination's tokens: deltas[t] belongs to destination token t, and destination token t goes to token
+    scatter_tok0 + t of scatter_dst.  Keeps the tensors the kernels read alive."""
+
+    def __init__(self, cos_sin: Optional[torch.Tensor] = None, rot_dim: int = 0, is_neox: bool = True, delta: int = 0,
+                 deltas: Optional[torch.Tensor] = None, scatter_dst: Optional["KVLayout"] = None, scatter_tok0: int = 0):
+        if cos_sin is not None:
+            Context._check_rope_args(cos_sin, rot_dim, deltas, None)
+        self.cos_sin, self.rot_dim, self.is_neox, self.delta, self.deltas = cos_sin, int(rot_dim), bool(is_neox), int(delta), deltas
+        self.scatter_dst, self.scatter_tok0 = scatter_dst, int(scatter_tok0)
+
+    @staticmethod
+    def window(dst: "KVLayout", dst_tok0: int, nchunks: int, chunk_tokens: int) -> Tuple[int, int]:
+        """(first token, tokens) of `dst` that a decode job of nchunks chunks from dst_tok0 on fills: tokens below 0 are
+        dropped, and the last chunk ends with the destination."""
+        t0 = max(0, dst_tok0)
+        return t0, min(dst.ntokens, dst_tok0 + nchunks * chunk_tokens) - t0
+
+    def struct(self, tok_begin: int, ntok: int) -> RangePostStruct:
+        """The lmc_range_post of the job that fills destination tokens [tok_begin, +ntok): filled per call, nothing kept."""
+        p = RangePostStruct()
+        if self.cos_sin is not None:
+            p.cos_sin, p.table_rows, p.rot_dim = self.cos_sin.data_ptr(), self.cos_sin.shape[0], self.rot_dim
+            p.is_neox, p.delta = 1 if self.is_neox else 0, self.delta
+            if self.deltas is not None:
+                p.deltas = self.deltas.data_ptr() + 4 * tok_begin
+        p.tok_begin, p.ntok = tok_begin, ntok
+        if self.scatter_dst is not None:
+            p.scatter_dst = ctypes.pointer(self.scatter_dst.struct)
+            p.scatter_tok0 = self.scatter_tok0 + tok_begin
+        return p
+
+    def apply(self, ctx: "Context", dst: "KVLayout", tok_begin: int, ntok: int) -> None:
+        """The same work from Python, for ALL layers of destination tokens [tok_begin, +ntok), on the current stream:
+        lmc_rope_shift on the rows, then lmc_copy_kv into scatter_dst -- what retrieve_into_paged queues.  For the
+        tiers whose decode is not cut by the C side."""
+        if self.cos_sin is not None:
+            ctx.rope_shift(dst, tok_begin, ntok, self.cos_sin, self.rot_dim, self.is_neox, delta=self.delta,
+                           deltas=None if self.deltas is None else self.deltas[tok_begin:tok_begin + ntok])
+        if self.scatter_dst is not None:
+            ctx.copy_kv(dst, tok_begin, ntok, self.scatter_dst, self.scatter_tok0 + tok_begin)
 
 
 class PinnedBuffer:
@@ -752,6 +824,20 @@ class Context:
         self._call("lmc_decode_chunks_schedule", dst.device, stream, blob_ptrs, max_blob_bytes, nchunks,
                    ctypes.byref(dst.struct), dst_tok0, chunk_tokens, n, ends, evs, status_ptr)
 
+    def decode_chunks_schedule_post(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
+                                    chunk_tokens: int, layer_ends, events, post: Optional[RangePostStruct],
+                                    stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
+        """lmc_decode_chunks_schedule_post: decode_chunks_schedule with `post` (RangePost.struct) done to every range
+        between its launch and its event, still ONE call.  post None is decode_chunks_schedule."""
+        n = len(layer_ends)
+        ends = layer_ends if isinstance(layer_ends, ctypes.Array) else (ctypes.c_int32 * n)(*layer_ends)
+        evs = events if events is None or isinstance(events, ctypes.Array) else (ctypes.c_void_p * n)(*[e.handle for e in events])
+        st = current_stream_ptr(dst.device) if stream is None else stream
+        check(lib().lmc_decode_chunks_schedule_post(self.handle, blob_ptrs, max_blob_bytes, nchunks, ctypes.byref(dst.struct),
+                                                    dst_tok0, chunk_tokens, n, ends, evs, status_ptr, st,
+                                                    None if post is None else ctypes.byref(post)),
+              "lmc_decode_chunks_schedule_post")
+
     def store_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, host_arena_ptr: int,
                      host_cap: int, offsets_ptr: int, sizes_ptr: int, stream: Optional[int] = None,
                      status_ptr: Optional[int] = None) -> int:
@@ -794,6 +880,15 @@ class Context:
         self._call("lmc_load_pack", dst.device, stream, pack_ptr, pack_bytes, chunk_begin, nchunks, ctypes.byref(dst.struct),
                    dst_tok0, layers_per_range, range_events_ptr, status_ptr)
 
+    def load_pack_post(self, pack_ptr: int, pack_bytes: int, chunk_begin: int, nchunks: int, dst: KVLayout, dst_tok0: int,
+                       layers_per_range: int, range_events_ptr: Optional[int], post: Optional[RangePostStruct],
+                       stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
+        """lmc_load_pack_post: load_pack with `post` (RangePost.struct) done to every range between its decode and its event."""
+        st = current_stream_ptr(dst.device) if stream is None else stream
+        check(lib().lmc_load_pack_post(self.handle, pack_ptr, pack_bytes, chunk_begin, nchunks, ctypes.byref(dst.struct), dst_tok0,
+                                       layers_per_range, range_events_ptr, status_ptr, st,
+                                       None if post is None else ctypes.byref(post)), "lmc_load_pack_post")
+
     def pack_blobs(self, blob_ptrs: int, blob_bytes_ptr: int, nchunks: int, L: int, H: int, D: int, chunk_tokens: int,
                    ntokens: int, pack_ptr: int, pack_cap: int, device, stream: Optional[int] = None,
                    status_ptr: Optional[int] = None) -> None:
@@ -829,15 +924,19 @@ class Context:
         by deltas[i] for token tok_begin + i: device int32 [ntok]).  cos_sin: device fp32 [table_rows, rot_dim], the
         model's cos_sin_cache (lmcache_amd.rope.RopeShift builds or widens one).  job_status: pinned word that receives
         LMC_STATUS_BAD_POSITION for a per-token delta outside the table (None: the context's sticky word)."""
+        self._check_rope_args(cos_sin, rot_dim, deltas, ntok)
+        self._call("lmc_rope_shift", layout.device, stream, ctypes.byref(layout.struct), tok_begin, ntok, cos_sin.data_ptr(),
+                   cos_sin.shape[0], rot_dim, 1 if is_neox else 0, int(delta), None if deltas is None else deltas.data_ptr(),
+                   job_status)
+
+    @staticmethod
+    def _check_rope_args(cos_sin: torch.Tensor, rot_dim: int, deltas: Optional[torch.Tensor], ntok: Optional[int]) -> None:
         if not (cos_sin.is_cuda and cos_sin.dtype == torch.float32 and cos_sin.dim() == 2 and cos_sin.is_contiguous()
                 and cos_sin.shape[1] == rot_dim):
             raise ValueError(f"cos_sin must be a contiguous device float32 [table_rows, rot_dim = {rot_dim}] tensor")
         if deltas is not None and not (deltas.is_cuda and deltas.dtype == torch.int32 and deltas.is_contiguous()
-                                       and deltas.numel() == ntok):
+                                       and (ntok is None or deltas.numel() == ntok)):
             raise ValueError(f"deltas must be a contiguous device int32 tensor of ntok = {ntok} entries")
-        self._call("lmc_rope_shift", layout.device, stream, ctypes.byref(layout.struct), tok_begin, ntok, cos_sin.data_ptr(),
-                   cos_sin.shape[0], rot_dim, 1 if is_neox else 0, int(delta), None if deltas is None else deltas.data_ptr(),
-                   job_status)
 
 
 def describe_status(st: int) -> str:

@@ -858,17 +858,27 @@ class LMCLocalBackend(LMCBackendInterface):
         return n
 
     def get_kv_range(self, keys: Sequence[CacheEngineKey], dst: native.KVLayout, fmt: str, dst_tok0: int,
-                     chunk_tokens: int, layers_per_launch: Optional[int] = None, jobs_out: Optional[list] = None) -> int:
+                     chunk_tokens: int, layers_per_launch: Optional[int] = None, jobs_out: Optional[list] = None,
+                     post: Optional[native.RangePost] = None) -> int:
         """Write chunk i (stored under keys[i]) to dst tokens dst_tok0 + i*chunk_tokens ...; tokens that land
         below 0 are dropped (retrieve()'s first-chunk trim, cache_engine.py:360-365).  Returns the number of
         leading chunks written (a key that has gone since `contains` ends the run, like the reference's break on
-        the first None chunk, cache_engine.py:339-345); raises NativeError if a stored blob does not decode."""
+        the first None chunk, cache_engine.py:339-345); raises NativeError if a stored blob does not decode.
+        post (CacheGen tiers, with jobs_out): a native.RangePost -- re-rotate the keys, scatter a staged chunk into an
+        "NHDB" cache -- done to every layer range of every decode job before the range's event, by the C call that
+        launches the range (HBM blobs: lmc_decode_chunks_schedule_post, packs: lmc_load_pack_post).  One lmc_range_post
+        per job: a retrieve that spans several stores is several jobs, each with its own token window.  A run of pinned
+        blobs that are no pack (a store of one chunk, LMCACHE_AMD_PINNED_PACKS=0) crosses PCIe whole before its first
+        range is decoded (CacheGenDeviceCodec.decode_host_post): its events mean what the others' mean, but layer 0 waits
+        for the run's whole transfer."""
         # the tier lock is held from taking the entries to the last launch: an eviction either happens before (the keys
         # are gone: a shorter run) or after (the jobs launched here are among the events its release is fenced by)
         with self._tier_lock:
-            return self._get_kv_range_locked(keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out)
+            return self._get_kv_range_locked(keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out, post)
 
-    def _get_kv_range_locked(self, keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out) -> int:
+    def _get_kv_range_locked(self, keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out, post=None) -> int:
+        assert post is None or (jobs_out is not None and layers_per_launch and self.mode in ("cachegen", "hbm-cachegen")), \
+            "a post-op rides on the layer ranges of the CacheGen tiers' decode jobs: it needs layers_per_launch and jobs_out"
         entries = self._prefix_entries(keys)
         if not entries:
             return 0
@@ -882,7 +892,7 @@ class LMCLocalBackend(LMCBackendInterface):
                 # (`entries` is the SAME list object for a repeated lookup of one prefix -- _prefix_entries -- and the codec
                 # keeps the uploaded address table of the last few lists it has seen)
                 job = codec.decode_device([e.blob for e in entries], dst, dst_tok0, chunk_tokens, layers_per_launch,
-                                          same_blobs_as=entries)
+                                          same_blobs_as=entries, post=post)
             self._touch(keys[:len(entries)], [job.done])
             if jobs_out is not None:
                 jobs_out.append((codec, job))
@@ -924,13 +934,17 @@ class LMCLocalBackend(LMCBackendInterface):
                 tok0 = dst_tok0 + i * chunk_tokens
                 with torch.cuda.device(dev):
                     if kind == "dev":
-                        job = codec.decode_device([e.blob for e in entries[i:j]], dst, tok0, chunk_tokens, layers_per_launch)
+                        job = codec.decode_device([e.blob for e in entries[i:j]], dst, tok0, chunk_tokens, layers_per_launch,
+                                                  post=post)
                     elif kind == "pack":
-                        job = codec.load_pack(entries[i].pack, entries[i].index, j - i, dst, tok0, layers_per_launch)
+                        job = codec.load_pack(entries[i].pack, entries[i].index, j - i, dst, tok0, layers_per_launch, post=post)
                     else:
                         # (a pack chunk of another chunk length -- never stored by this engine -- takes its blob from the pack)
                         blobs = [self._own_blob(e) if isinstance(e, _PackChunk) else e.blob for e in entries[i:j]]
-                        if layerwise:
+                        if post is not None:
+                            # (whole blobs over PCIe, then the ranges' decodes with the post-op in front of every event)
+                            job = codec.decode_host_post(blobs, dst, tok0, chunk_tokens, layers_per_launch, post)
+                        elif layerwise:
                             # pinned tier cut by layers (engine.retrieve_layerwise): one lmc_load_chunks call gathers and
                             # decodes range after range; the caller's layers wait for their range's event only
                             job = codec.decode_host_layerwise(blobs, dst, tok0, chunk_tokens, layers_per_launch)

@@ -753,13 +753,16 @@ class CacheGenDeviceCodec:
 
     # ---- decode ------------------------------------------------------------------
     def decode_device(self, blobs: Sequence[torch.Tensor], dst: native.KVLayout, dst_tok0: int, chunk_tokens: int,
-                      layers_per_launch: Optional[int] = None, same_blobs_as=None) -> Optional[DecodeJob]:
+                      layers_per_launch: Optional[int] = None, same_blobs_as=None,
+                      post: Optional[native.RangePost] = None) -> Optional[DecodeJob]:
         """Decode blobs that live in HBM (uint8 CUDA tensors, anywhere) straight into `dst` on the current stream,
         no staging copy: the kernel takes the blob addresses from a pointer table.  With layers_per_launch the
         retrieve is cut into one launch per range of layers with an event after each (DecodeJob.layer_events): the
         model can start on layer 0 after 1/L of the decode.  layers_per_launch is a range size or a schedule of
         range sizes whose last entry repeats, e.g. (2, 2, 4, 8, 16): small ranges first so that the model starts
-        early, large ones later (a launch of few layers does not fill the GPU, and every launch costs an event)."""
+        early, large ones later (a launch of few layers does not fill the GPU, and every launch costs an event).
+        post: a native.RangePost done to every range between its launch and its event, by the same C call
+        (lmc_decode_chunks_schedule_post); its struct is filled here, per call -- the kept tables are not touched."""
         n = len(blobs)
         if n == 0:
             return None
@@ -808,8 +811,13 @@ class CacheGenDeviceCodec:
                 # ranges used to be one ctypes call + one torch event each
                 ends = [l1 for _, l1 in ranges]
                 evs = [native.NativeEvent() for _ in ranges]
-                self.ctx.decode_chunks_schedule(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
-                                                stream=cur.cuda_stream, status_ptr=st_ptr)
+                if post is None:
+                    self.ctx.decode_chunks_schedule(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
+                                                    stream=cur.cuda_stream, status_ptr=st_ptr)
+                else:
+                    self.ctx.decode_chunks_schedule_post(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
+                                                         post.struct(*post.window(dst, dst_tok0, n, chunk_tokens)),
+                                                         stream=cur.cuda_stream, status_ptr=st_ptr)
                 events = list(zip(ends, evs))
             return DecodeJob(evs[-1], events if layers_per_launch else None, table, status_idx=st, pool=self._status)
 
@@ -843,6 +851,40 @@ class CacheGenDeviceCodec:
                 self.ctx.load_chunks(meta.ptr, meta.ptr + 8 * n, n, dst, dst_tok0, chunk_tokens, step,
                                      ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream, status_ptr=st_ptr)
             return DecodeJob(events[-1][1], events, status_idx=st, pool=self._status, loans=loans)
+
+    def decode_host_post(self, host_blobs: Sequence["HostBlob"], dst: native.KVLayout, dst_tok0: int, chunk_tokens: int,
+                         layers_per_launch, post: native.RangePost) -> Optional[DecodeJob]:
+        """Blobs in pinned host DRAM that are no pack (a store of a single chunk, LMCACHE_AMD_PINNED_PACKS=0) with a
+        post-op: lmc_load_chunks has no post-op, so the blobs cross PCIe whole into the decode slots, as decode() moves
+        them, and ONE lmc_decode_chunks_schedule_post over the slots decodes them range by range with `post` in front
+        of every range's event, as decode_device does for blobs that live in HBM."""
+        n = len(host_blobs)
+        if n == 0:
+            return None
+        stride = native.r16(max(hb.nbytes for hb in host_blobs))
+        ranges = layer_ranges(dst.L, layers_per_launch)
+        with self._lock, torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            arena = self._dec_slots(n, stride, cur)
+            with self._launch(cur) as (st, st_ptr):
+                if self._dec_free is not None:
+                    self.copy_stream.wait_event(self._dec_free)  # previous decode has read the slots
+                for i, hb in enumerate(host_blobs):
+                    native.memcpy_async(arena.data_ptr() + i * stride, hb.ptr, hb.nbytes, "h2d", self.copy_stream.cuda_stream)
+                ready = torch.cuda.Event()
+                ready.record(self.copy_stream)
+                cur.wait_event(ready)
+                table = torch.tensor([arena.data_ptr() + i * stride for i in range(n)],
+                                     dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+                ends = [l1 for _, l1 in ranges]
+                evs = [native.NativeEvent() for _ in ranges]
+                self.ctx.decode_chunks_schedule_post(table.data_ptr(), stride, n, dst, dst_tok0, chunk_tokens, ends, evs,
+                                                     post.struct(*post.window(dst, dst_tok0, n, chunk_tokens)),
+                                                     stream=cur.cuda_stream, status_ptr=st_ptr)
+                last = torch.cuda.Event()
+                last.record(cur)
+                self._dec_free = last
+            return DecodeJob(evs[-1], list(zip(ends, evs)), table, status_idx=st, pool=self._status)
 
     # ---- packs: the plane-major pinned tier ---------------------------------------------------------------
     def store_pack(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins: Sequence[int],
@@ -961,18 +1003,26 @@ class CacheGenDeviceCodec:
         return HostPack(arena.shrink(region, total), job.nchunks, job.chunk_tokens)
 
     def load_pack(self, pack: HostPack, chunk_begin: int, nchunks: int, dst: native.KVLayout, dst_tok0: int,
-                  layers_per_range) -> DecodeJob:
+                  layers_per_range, post: Optional[native.RangePost] = None) -> DecodeJob:
         """Chunks [chunk_begin, chunk_begin + nchunks) of a pack -> decoded KV through ONE C-ABI call (lmc_load_pack): the streams of a
         range of layers are one contiguous transfer, the range's decode follows it, an event per range
         (DecodeJob.layer_events) lets the model run layer 0 while the later ranges are still crossing PCIe.
-        layers_per_range: see range_step."""
+        layers_per_range: see range_step.  post: a native.RangePost done to every range between its decode and its event
+        (lmc_load_pack_post)."""
         step = range_step(dst.L, layers_per_range)
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             with self._launch(cur) as (st, st_ptr):
                 events, handles = self._range_events(dst.L, step)
-                self.ctx.load_pack(pack.blob.ptr, pack.blob.nbytes, chunk_begin, nchunks, dst, dst_tok0, step,
-                                   ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream, status_ptr=st_ptr)
+                if post is None:
+                    self.ctx.load_pack(pack.blob.ptr, pack.blob.nbytes, chunk_begin, nchunks, dst, dst_tok0, step,
+                                       ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream, status_ptr=st_ptr)
+                else:
+                    n = nchunks or pack.nchunks - chunk_begin
+                    self.ctx.load_pack_post(pack.blob.ptr, pack.blob.nbytes, chunk_begin, nchunks, dst, dst_tok0, step,
+                                            ctypes.cast(handles, ctypes.c_void_p).value,
+                                            post.struct(*post.window(dst, dst_tok0, n, pack.chunk_tokens)),
+                                            stream=cur.cuda_stream, status_ptr=st_ptr)
             return DecodeJob(events[-1][1], events, status_idx=st, pool=self._status)
 
     # ---- bounded tiers: HBM blobs <-> pinned pack, no re-encode ---------------------------------------------------------
