@@ -101,9 +101,17 @@ int lmc_abi_version(void);
  *     offsets end at   stride_head >= 0  and  ((H-1)*stride_head + D*block_size)*E + 7*16 <= 0xfffffff0;
  *     beyond that LMC_ERR_INVALID before anything is queued (blocks and planes may lie any distance apart).
  *   - NOT lmc_decode_chunks: it is the replacement of the reference's from_bytes, whose caller wants a tensor of rows.
- * Every other entry point -- the encoders and stores, lmc_quantize, lmc_rope_shift -- reads and writes rows and returns
- * LMC_ERR_INVALID for it: bring the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot
- * read.  Any other paged_kind is LMC_ERR_INVALID; a caller that zeroes the struct gets LMC_PAGED_ROWS.
+ *   - as an ENCODE SOURCE, lmc_encode_chunks_split and the stores (lmc_store_chunks, lmc_store_pack,
+ *     lmc_store_pack_parts): k_quantize.h reads the split blocks in place (a V oct whose tokens are eight consecutive
+ *     slots of a block, from slot % 8 == 0 on, as 16-byte runs of one channel; a K token's granules where they lie;
+ *     anything else element by element), then k_cdf_encode -- never the fused kernel, so a pack store is one part.
+ *     Planes of at most 1024 channels (H * D), stride_head >= 0 and ((H-1)*stride_head + D*block_size)*E <= 0xfffffff0;
+ *     beyond that LMC_ERR_INVALID before anything is queued.
+ *   - NOT lmc_encode_chunks and lmc_quantize: they stand for the reference's to_bytes / torch_quant_vectorized, whose
+ *     caller holds a tensor of rows.
+ * Every other entry point -- lmc_rope_shift among them -- reads and writes rows and returns LMC_ERR_INVALID for it: bring
+ * the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot read.  Any other paged_kind is
+ * LMC_ERR_INVALID; a caller that zeroes the struct gets LMC_PAGED_ROWS.
  */
 #define LMC_PAGED_ROWS 0
 #define LMC_PAGED_SPLIT 1
@@ -226,6 +234,17 @@ int lmc_calculate_cdf(lmc_ctx* ctx, const int8_t* sym, int32_t P, int32_t T, int
 int lmc_encode_chunks(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
                       int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
                       uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
+
+/*
+ * lmc_encode_chunks for any source lmc_encode_chunks takes AND an LMC_PAGED_SPLIT one (see lmc_kv_layout): the cache of
+ * vLLM's ROCm paged-attention kernels is read in place, no staged chunk and no lmc_copy_kv in front.  The blobs are
+ * byte for byte those lmc_encode_chunks writes from the gathered chunk.  A split source always takes k_quantize +
+ * k_cdf_encode, whatever lmc_ctx_set_encode_path says; with more than 1024 channels per plane it is LMC_ERR_INVALID and
+ * nothing is launched.  Any other source: exactly lmc_encode_chunks.
+ */
+int lmc_encode_chunks_split(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
+                            int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
+                            uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
 
 /* ------------------------------------------------------------------ */
 /* decode side                                                         */

@@ -162,7 +162,7 @@ class LMCacheEngine:
     @_lmcache_nvtx_annotate
     @torch.no_grad()
     def store_paged(self, tokens: torch.Tensor, kv_caches, slot_mapping: torch.Tensor, block_size: int,
-                    layout: str = "NBHD", skip_existing=True, blocking=True) -> None:
+                    layout: str = "NBHD", skip_existing=True, blocking=True, direct: bool = False) -> None:
         """store() for a serving engine's PAGED KV cache -- what the external vLLM connector does around
         store() (`lmcache_store_kv`: gather the rows of every layer's cache by slot_mapping into [T,H,D], then
         store; docs/source/developer_tutorial/LLM_Engine.rst:91-122), without the gather copy: the kernels
@@ -174,17 +174,25 @@ class LMCacheEngine:
                         value_cache) pair of PagedAttention.split_kv_cache (native.KVLayout.paged); bf16 / fp16 / fp8
           slot_mapping  int64 [len(tokens)]: token t lives in slot slot_mapping[t] = block * block_size + offset
         The engine's fmt must be "vllm" (chunks are keyed and laid out [L,2,T,H,D]).
-        An "NHDB" cache has no token rows for the encoders to read: every tier first brings the range into a vllm chunk
-        on the device with one lmc_copy_kv (k_copy_split.h) -- the codec's staging of any layout it cannot read, the
-        raw tiers' own gather -- instead of the connector's torch gather of every layer."""
+        An "NHDB" cache has no token rows: by default every tier first brings the range into a vllm chunk on the device
+        with one lmc_copy_kv (k_copy_split.h) -- the codec's staging of any layout the row encoders cannot read, the raw
+        tiers' own gather -- instead of the connector's torch gather of every layer.
+          direct  True: the CacheGen tiers hand an "NHDB" cache to the encoder as it is -- k_quantize reads the split
+                  blocks (lmc_encode_chunks_split, lmc_store_pack_parts; k_quantize.h), no staging chunk of the size of
+                  the raw KV is allocated and no lmc_copy_kv is launched.  Such a job is coded by k_quantize +
+                  k_cdf_encode, never by the fused kernel, and on the pinned tier its pack leaves as one part, without the
+                  overlap of the part copies with the encode: it buys memory first, time only
+                  where profiles/paged_split_encode.md says so.  Planes of more than 1024 channels (H * D) are staged all
+                  the same.  It means nothing for "NBHD" / "NHBD", which are read in place anyway, and nothing for the raw
+                  tiers and the chunk-tensor backends, whose gather IS the store.  The stored bytes are the same."""
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens.shape) == 1, f"Invalid shape of tokens: {tokens.shape}"
         assert len(kv_caches) > 0, "Empty kv_caches"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         self._store_from(tokens, lambda: native.KVLayout.paged(kv_caches, slot_mapping, block_size, layout),
-                         skip_existing, blocking)
+                         skip_existing, blocking, direct=direct and layout == "NHDB")
 
-    def _store_from(self, tokens: torch.Tensor, make_src, skip_existing: bool, blocking: bool) -> None:
+    def _store_from(self, tokens: torch.Tensor, make_src, skip_existing: bool, blocking: bool, direct: bool = False) -> None:
         t_start = time.perf_counter()
         fmt = self.metadata.fmt
         ntok = len(tokens)
@@ -200,7 +208,7 @@ class LMCacheEngine:
         src = make_src()
         t_plan = time.perf_counter()
         if getattr(self.engine_, "supports_kv_layout", False):
-            n = self.engine_.put_kv_range(keys, src, fmt, first * cs, ntok, cs, blocking=blocking)
+            n = self.engine_.put_kv_range(keys, src, fmt, first * cs, ntok, cs, blocking=blocking, **({"direct": True} if direct else {}))
         else:
             n = self.engine_.batched_put(self._gather_chunks(keys, src, fmt, first * cs, ntok), blocking=blocking)
         logger.info("Stored/updated %d chunks, total time %.4fs, planning %.4fs", n,

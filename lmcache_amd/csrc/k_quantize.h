@@ -64,6 +64,115 @@ __device__ __forceinline__ u32 quant_special(float x, float factor, float maxf) 
   return (__builtin_fabsf(r) < 2147483648.0f) ? ((u32)(int)r & 0xffu) : 0u;
 }
 
+// ---- an LMC_PAGED_SPLIT source (include/lmc_hip.h: the cache of vLLM's ROCm paged-attention kernels) -----------------
+// The cache keeps, per block b and head h, one dense run of D * block_size elements (k_copy_split.h):
+//   K(b, h, d, w) = b * stride_block + h * stride_head + ((d / X) * block_size + w) * X + d % X     X = 16 / element bytes
+//   V(b, h, d, w) = b * stride_block + h * stride_head + d * block_size + w
+// The block offset is 64-bit; everything inside a block fits 32 bits (lmc_api.hip: split_range_ok).
+// K: a lane's 8 channels of a token are still one x-granule (fp8: half of one), only at another address -- the task
+// keeps quantize_task's token-major registers, v[r][it] = token r.  V: 16 bytes (fp8: 8) are eight consecutive slots of
+// ONE channel, which is what a workspace dword holds anyway, so the task loads channel-major, v[e][it] = the 8 tokens of
+// channel c0[it] + e, and quantises without a transpose (the V form of quantize_task).  That needs the oct's tokens at
+// slots s, s + 1, ... of one block with s % 8 == 0 and block_size % 8 == 0 (of a ragged oct: its tokens below Tc; the
+// load still lies inside the block that the oct's first slot names), and both forms need the plane base and the block
+// and head strides to keep the vector on its 16-byte (8-byte) boundary.  Anything else -- single tokens at random slots,
+// a run that enters a block at offset 5 or breaks inside the oct, a base 2 bytes off -- is loaded element by element
+// into the token-major registers.  Decided per task; a ballot sends the whole wave (G < 64: several octs) one way.
+// Only slots of the job's own tokens are turned into addresses, and a token at or past Tc is zero in the registers.
+
+// 8 elements p[0], p[step], ..., p[7 * step] as kv_ld8 would hold them
+template <int DT>
+__device__ __forceinline__ uint4 split_ld_elems(const typename KvElem<DT>::T* p, u32 step) {
+  const LMC_GLOBAL typename KvElem<DT>::T* q = (const LMC_GLOBAL typename KvElem<DT>::T*)p;
+  u32 e[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) e[k] = (u32)q[(u32)k * step];
+  if constexpr (!lmc_dtype_fp8(DT)) return make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
+  else return make_uint4(e[0] | (e[1] << 8) | (e[2] << 16) | (e[3] << 24), e[4] | (e[5] << 8) | (e[6] << 16) | (e[7] << 24), 0u, 0u);
+}
+
+// The loads of one row oct from a split source.  -> true: the V form (v[e][it]), false: token-major (v[r][it]).
+template <int NITER, int DT>
+__device__ __forceinline__ bool split_load_oct(const KvAddr& src, int p, int tok0, int Tc, int t_first, bool qvalid,
+                                               const int (&c0)[NITER], const bool (&cval)[NITER], uint4 (&v)[8][NITER],
+                                               bool (&tv)[8]) {
+  typedef typename KvElem<DT>::T E;
+  constexpr u32 X = 16 / (u32)sizeof(E);
+  const bool is_v = p >= src.L;  // (wave-uniform, like everything of the plane)
+  const E* const pbase = lmc_plane_base<E>(src, p);
+  const u32 bs = (u32)src.block_size;
+  const bool aligned = ((((uintptr_t)pbase) & (lmc_dtype_fp8(DT) ? 7u : 15u)) | (uintptr_t)((src.stride_block | src.stride_head) & 7)) == 0;
+  u32 s[8];
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    tv[r] = qvalid && t_first + r < Tc;
+    s[r] = tv[r] ? (u32)src.slot_mapping[tok0 + t_first + r] : 0u;
+  }
+  const u32 b0 = s[0] / bs, w0 = s[0] - b0 * bs;  // (the valid tokens of an oct are its first: tv[0] or none)
+  // the lane's channel runs inside a block
+  u32 in_k[NITER], in_v[NITER];
+#pragma unroll
+  for (int it = 0; it < NITER; it++) {
+    const u32 h = (u32)c0[it] / (u32)src.D, d = (u32)c0[it] - h * (u32)src.D;
+    const u32 hoff = h * (u32)src.stride_head;
+    in_k[it] = hoff + (d / X) * (bs * X) + d % X;
+    in_v[it] = hoff + d * bs;
+  }
+  if (is_v) {
+    bool run = aligned && (w0 & 7u) == 0u && (bs & 7u) == 0u;
+#pragma unroll
+    for (int r = 1; r < 8; r++) run = run && (!tv[r] || s[r] == s[0] + (u32)r);
+    if (__ballot(tv[0] && !run) == 0ull) {
+      // tokens at or past Tc share the vector with the oct's own: cleared
+      u32 msk[4];
+      if constexpr (!lmc_dtype_fp8(DT)) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) msk[j] = (tv[2 * j] ? 0xffffu : 0u) | (tv[2 * j + 1] ? 0xffff0000u : 0u);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+          msk[j] = (tv[4 * j] ? 0xffu : 0u) | (tv[4 * j + 1] ? 0xff00u : 0u) | (tv[4 * j + 2] ? 0xff0000u : 0u) | (tv[4 * j + 3] ? 0xff000000u : 0u);
+        msk[2] = msk[3] = 0u;
+      }
+      const E* const blk = pbase + (long long)b0 * src.stride_block + w0;
+#pragma unroll
+      for (int it = 0; it < NITER; it++) {
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          if (tv[0] && cval[it]) {
+            const uint4 u = kv_ld8<DT>(blk + (in_v[it] + (u32)e * bs));
+            v[e][it] = make_uint4(u.x & msk[0], u.y & msk[1], u.z & msk[2], u.w & msk[3]);
+          } else v[e][it] = make_uint4(0, 0, 0, 0);
+        }
+      }
+      return true;
+    }
+  }
+  // token-major: every token's own block and column -- without a division where the oct stays in the block of its first
+  // token (wave-uniform: a ballot)
+  bool same = true;
+#pragma unroll
+  for (int r = 1; r < 8; r++) same = same && (!tv[r] || s[r] - (s[0] - w0) < bs);
+  auto load_tokens = [&](auto same_tag) {
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      const u32 br = decltype(same_tag)::value ? b0 : s[r] / bs;
+      const u32 wr = decltype(same_tag)::value ? s[r] - (s[0] - w0) : s[r] - br * bs;
+      const E* const tp = pbase + (long long)br * src.stride_block;
+#pragma unroll
+      for (int it = 0; it < NITER; it++) {
+        if (!(tv[r] && cval[it])) v[r][it] = make_uint4(0, 0, 0, 0);
+        else if (is_v) v[r][it] = split_ld_elems<DT>(tp + (in_v[it] + wr), bs);
+        else if (aligned) v[r][it] = kv_ld8<DT>(tp + (in_k[it] + wr * X));
+        else v[r][it] = split_ld_elems<DT>(tp + (in_k[it] + wr * X), 1u);
+      }
+    }
+  };
+  if (__ballot(!same) == 0ull) load_tokens(BoolTag<true>{});
+  else load_tokens(BoolTag<false>{});
+  return false;
+}
+
 // One task = 4 (row quad) or, NIB, 8 consecutive tokens starting at token t_first of plane p of one chunk,
 // by the G lanes sl = 0..G-1.
 //   sym_out     QUAD: the task's dwords, [channel]      sym8_plane  !QUAD: &sym8[p][0][0]
@@ -80,7 +189,10 @@ __device__ __forceinline__ u32 quant_special(float x, float factor, float maxf) 
 // HIST (the fused encode's narrow planes, round 6): the task's symbols also go into the work item's histogram (k_hist.h)
 // -- hist_lane4 = 4 * the task's virtual quantising lane, hist_it its virtual channel run (wave-uniform: a wave pass
 // quantises row octs of ONE plane).
-template <int G, int NITER, int DT, bool QUAD, bool NIB, int ROWS = 4, int NQ = NIB ? 2 : 1, int SPLIT = 1, bool HIST = false>
+// NHDB: the source is an LMC_PAGED_SPLIT cache (split_load_oct above): the loads, and for a V oct on its fast path the
+// max and the conversion in their channel-major form; from o[][][] on the task is the same.
+template <int G, int NITER, int DT, bool QUAD, bool NIB, int ROWS = 4, int NQ = NIB ? 2 : 1, int SPLIT = 1, bool HIST = false,
+          bool NHDB = false>
 __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0, int Tc, int t_first, bool qvalid,
                                               bool q1valid, int C, float maxf, u32* sym_out, int8_t* sym8_plane,
                                               u16* scale_out, int sl, int slice = 0, u32* xmax = nullptr,
@@ -90,6 +202,7 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
   static_assert(ROWS == 2 || ROWS == 4 || (ROWS == 8 && NQ == 2), "rows in flight: a power of two within the task");
   static_assert(QUAD || (!NIB && NQ == 1), "nibble packing and two-quad tasks are workspace formats");
   static_assert(!NIB || NQ == 2, "a nibble dword holds two row quads");
+  static_assert(!NHDB || (QUAD && ROWS == 8 && SPLIT == 1 && !HIST), "a split source: whole octs into the workspace");
   // per-lane channel runs (row independent)
   long long coff[NITER];
   int c0[NITER];
@@ -117,36 +230,73 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
   for (int r0 = 0; r0 < 4 * NQ; r0 += ROWS) {
     uint4 v[ROWS][NITER];
     bool tv[ROWS];
+    bool vform = false;  // NHDB, a V oct on its fast path: v[e][it] = the 8 tokens of channel c0[it] + e
+    if constexpr (NHDB) {
+      vform = split_load_oct<NITER, DT>(src, p, tok0, Tc, t_first, qvalid, c0, cval, v, tv);
+    } else {
 #pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-      int t = t_first + r0 + r;
-      tv[r] = qvalid && t < Tc;
-      const typename KvElem<DT>::T* rowp = pbase + (tv[r] ? lmc_tok_off(src, tok0 + t) : 0);
+      for (int r = 0; r < ROWS; r++) {
+        int t = t_first + r0 + r;
+        tv[r] = qvalid && t < Tc;
+        const typename KvElem<DT>::T* rowp = pbase + (tv[r] ? lmc_tok_off(src, tok0 + t) : 0);
 #pragma unroll
-      for (int it = 0; it < NITER; it++) {
-        if (tv[r] && cval[it]) v[r][it] = kv_ld8<DT>(rowp + coff[it]);  // (non-temporal here: two-kernel path +0.5 %)
-        else v[r][it] = make_uint4(0, 0, 0, 0);
+        for (int it = 0; it < NITER; it++) {
+          if (tv[r] && cval[it]) v[r][it] = kv_ld8<DT>(rowp + coff[it]);  // (non-temporal here: two-kernel path +0.5 %)
+          else v[r][it] = make_uint4(0, 0, 0, 0);
+        }
       }
     }
 
     // row |x| max on bit patterns, two rows per register through the xor-shuffle reduction
     u32 mrow[ROWS];
+    if (!NHDB || !vform) {
 #pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-      u32 m = 0;
+      for (int r = 0; r < ROWS; r++) {
+        u32 m = 0;
+#pragma unroll
+        for (int it = 0; it < NITER; it++) {
+          m = kv_absmax8<DT>(m, v[r][it]);
+        }
+        mrow[r] = max(m & 0xffffu, m >> 16);
+      }
+#pragma unroll
+      for (int r = 0; r < ROWS; r += 2) {
+        u32 m2 = mrow[r] | (mrow[r + 1] << 16);
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) m2 = pk_max_u16(m2, (u32)__shfl_xor((int)m2, off));
+        mrow[r] = m2 & 0xffffu;
+        mrow[r + 1] = m2 >> 16;
+      }
+    } else if constexpr (NHDB) {
+      // V form: the element-wise packed max over the lane's channels leaves the eight per-token maxima in 4 dwords --
+      // 16-bit: dword j = tokens 2j | 2j + 1; fp8 (a byte per token, widened to the u16 lanes): tokens 0|2, 1|3, 4|6, 5|7
+      u32 m4[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
       for (int it = 0; it < NITER; it++) {
-        m = kv_absmax8<DT>(m, v[r][it]);
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          const uint4& u = v[e][it];
+          if constexpr (!lmc_dtype_fp8(DT)) {
+            m4[0] = pk_max_u16(m4[0], u.x & 0x7fff7fffu);
+            m4[1] = pk_max_u16(m4[1], u.y & 0x7fff7fffu);
+            m4[2] = pk_max_u16(m4[2], u.z & 0x7fff7fffu);
+            m4[3] = pk_max_u16(m4[3], u.w & 0x7fff7fffu);
+          } else {
+            m4[0] = pk_max_u16(m4[0], u.x & 0x007f007fu);
+            m4[1] = pk_max_u16(m4[1], (u.x >> 8) & 0x007f007fu);
+            m4[2] = pk_max_u16(m4[2], u.y & 0x007f007fu);
+            m4[3] = pk_max_u16(m4[3], (u.y >> 8) & 0x007f007fu);
+          }
+        }
       }
-      mrow[r] = max(m & 0xffffu, m >> 16);
-    }
 #pragma unroll
-    for (int r = 0; r < ROWS; r += 2) {
-      u32 m2 = mrow[r] | (mrow[r + 1] << 16);
+      for (int j = 0; j < 4; j++) {
 #pragma unroll
-      for (int off = 1; off < G; off <<= 1) m2 = pk_max_u16(m2, (u32)__shfl_xor((int)m2, off));
-      mrow[r] = m2 & 0xffffu;
-      mrow[r + 1] = m2 >> 16;
+        for (int off = 1; off < G; off <<= 1) m4[j] = pk_max_u16(m4[j], (u32)__shfl_xor((int)m4[j], off));
+        constexpr bool B8 = lmc_dtype_fp8(DT);
+        mrow[B8 ? 4 * (j >> 1) + (j & 1) : 2 * j] = m4[j] & 0xffffu;
+        mrow[B8 ? 4 * (j >> 1) + (j & 1) + 2 : 2 * j + 1] = m4[j] >> 16;
+      }
     }
 
     if constexpr (SPLIT > 1) {  // the row maxima of the SPLIT channel slices meet in LDS
@@ -191,6 +341,29 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
 #pragma unroll
     for (int it = 0; it < NITER; it++) {
       if (!cval[it] || !qvalid) continue;
+      if constexpr (NHDB) {
+        if (vform) {
+          // V form: dword j of channel e holds tokens 2j and 2j + 1 (kv_lo / kv_hi: for fp8 the byte pairs, in the same
+          // order), each with its own row's factor, inserted at its token's byte of o[token / 4][it][e]
+#pragma unroll
+          for (int e = 0; e < 8; e++) {
+            const u32 w[4] = {v[e][it].x, v[e][it].y, v[e][it].z, v[e][it].w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+              const float xlo = kv_lo<DT>(w, j), xhi = kv_hi<DT>(w, j);
+              if (!slow) {
+                const f32x2_t f2 = {factor[2 * j], factor[2 * j + 1]};
+                const f32x2_t z = quant_z2(xlo, xhi, f2, maxf2);
+                o[j >> 1][it][e] = __builtin_amdgcn_cvt_pk_u8_f32(z.x, (2 * j) & 3, o[j >> 1][it][e]);
+                o[j >> 1][it][e] = __builtin_amdgcn_cvt_pk_u8_f32(z.y, (2 * j + 1) & 3, o[j >> 1][it][e]);
+              } else {
+                o[j >> 1][it][e] |= (sym_of(2 * j, xlo) << (8 * ((2 * j) & 3))) | (sym_of(2 * j + 1, xhi) << (8 * ((2 * j + 1) & 3)));
+              }
+            }
+          }
+          continue;
+        }
+      }
       if (QUAD) {
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
@@ -290,9 +463,12 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
 // get the nibble-packed workspace format (one dword per channel for the oct), the others two row quads.
 // grid = (ceil(TO / (4 * RPW)), P, chunks), TO = ceil(TQ / 2): plane and chunk come straight from the block
 // index, and with G = 64 everything but the channel offset is wave-uniform and lives in SGPRs.
-template <int G, int NITER, int DT, bool QUAD, int SPLIT = 1>
+// NHDB: the instances that read an LMC_PAGED_SPLIT source (workspace form, up to 1024 channels); every other instance is
+// what it was before they existed.
+template <int G, int NITER, int DT, bool QUAD, int SPLIT = 1, bool NHDB = false>
 __global__ __launch_bounds__(256) void k_quantize(QuantArgs a) {
   static_assert(SPLIT == 1 || (QUAD && G == LMC_WAVE && (SPLIT == 2 || SPLIT == 4)), "split tasks: whole waves, workspace output");
+  static_assert(!NHDB || (QUAD && SPLIT == 1 && NITER <= 2), "a split source: the workspace form, planes of up to 1024 channels");
   constexpr int RPW = LMC_WAVE / G;  // tasks per wave
   __shared__ u32 xmax[SPLIT > 1 ? (4 / SPLIT) * 8 * SPLIT : 1];  // row maxima of the split tasks of this workgroup
   const int lane = threadIdx.x & 63;
@@ -322,11 +498,11 @@ __global__ __launch_bounds__(256) void k_quantize(QuantArgs a) {
     const bool q1valid = 2 * oct + 1 < a.TQ;
     u32* const xm = xmax + (SPLIT > 1 ? (wave / SPLIT) * 8 * SPLIT : 0);  // this task's exchange slots
     if (lmc_sym_nibbles(bins))
-      quantize_task<G, NITER, DT, true, true, ROWS, 2, SPLIT>(a.src, p, tok0, Tc, oct * 8, ovalid, q1valid, a.C, maxf, sym_out,
-                                                              nullptr, scale_out, sl, slice, xm);
+      quantize_task<G, NITER, DT, true, true, ROWS, 2, SPLIT, false, NHDB>(a.src, p, tok0, Tc, oct * 8, ovalid, q1valid, a.C, maxf,
+                                                                           sym_out, nullptr, scale_out, sl, slice, xm);
     else
-      quantize_task<G, NITER, DT, true, false, ROWS, 2, SPLIT>(a.src, p, tok0, Tc, oct * 8, ovalid, q1valid, a.C, maxf, sym_out,
-                                                               nullptr, scale_out, sl, slice, xm);
+      quantize_task<G, NITER, DT, true, false, ROWS, 2, SPLIT, false, NHDB>(a.src, p, tok0, Tc, oct * 8, ovalid, q1valid, a.C, maxf,
+                                                                            sym_out, nullptr, scale_out, sl, slice, xm);
   } else {
 #pragma unroll 1
     for (int hq = 0; hq < 2; hq++) {

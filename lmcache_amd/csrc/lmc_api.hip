@@ -194,8 +194,9 @@ int lmc_device_status(lmc_ctx* c, int clear) {
 // (stride_head == head_size: the vllm chunk, the per-layer [T,H,D] tensors, NBHD paged blocks), where a vector that
 // crosses a head boundary is still 8 consecutive elements.  !vec: element-wise access (the decoder's scatter, the
 // element-wise copy): any strides.  Either way a plane has a multiple of 8 channels (the blob's geometry).
-// `split`: the caller addresses LMC_PAGED_SPLIT itself (lmc_copy_kv, and the decode entry points that decode_common lets);
-// everybody else reads and writes rows and must refuse such a layout rather than address it as rows.
+// `split`: the caller addresses LMC_PAGED_SPLIT itself (lmc_copy_kv, the decode entry points that decode_common lets and
+// the encode entry points that encode_job_ok lets); everybody else reads and writes rows and must refuse such a layout
+// rather than address it as rows.
 static bool layout_ok(const lmc_kv_layout* l, bool vec = true, bool split = false) {
   if (!l) return false;
   if (l->paged_kind != LMC_PAGED_ROWS && l->paged_kind != LMC_PAGED_SPLIT) return false;
@@ -293,16 +294,35 @@ static auto with_kv_dtype(int dtype, F&& f) {
   }
 }
 
+// What k_quantize's loads can address in an LMC_PAGED_SPLIT source that layout_ok(src, false, true) has passed
+// (k_quantize.h, split_load_oct): the block offset is 64-bit, everything inside a block -- head, granule or channel,
+// column, element -- is added up in 32 bits, in elements, and stays below
+//       head = (H - 1) * stride_head + D * block_size.
+//       admitted:  stride_head >= 0,  head * E <= 0xfffffff0     (E = element bytes; the bound decode_dst_ok sets the stores)
+static bool split_range_ok(const lmc_kv_layout* l) {
+  typedef __int128 wide;
+  if (l->stride_head < 0 || l->block_size < 1) return false;
+  const wide E = lmc_dtype_fp8(l->dtype) ? 1 : 2;
+  return ((wide)(l->num_heads - 1) * l->stride_head + (wide)l->head_size * l->block_size) * E <= (wide)0xfffffff0ll;
+}
+
 // What every encode job asks of its source and its token range (lmc_encode_chunks, and the stores in front of it before
 // they take a buffer).  *nchunks: the job's chunks -- at most 65535, they ride on gridDim.z of k_quantize.
+// `split_ok`: the entry point takes an LMC_PAGED_SPLIT source (lmc_encode_chunks_split and the stores; lmc_encode_chunks
+// does not) -- the twin of decode_common's flag.  Such a source is asked what lmc_copy_kv asks of a split side (a slot
+// mapping, block_size >= 1, whole x-granules), split_range_ok, and planes of at most 1024 channels.
 static bool encode_job_ok(const lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
-                          int* nchunks) {
-  if (!c || !layout_ok(src) || tok_begin < 0 || tok_end <= tok_begin || chunk_tokens < 1 || chunk_tokens > 65535) return false;
+                          int* nchunks, bool split_ok = false) {
+  const bool nhdb = src && src->paged_kind == LMC_PAGED_SPLIT;
+  if (nhdb ? !(split_ok && layout_ok(src, false, true) && split_range_ok(src)) : !layout_ok(src)) return false;
+  if (nhdb && (long long)src->num_heads * src->head_size > 1024) return false;  // k_quantize's split instances stop there
+  if (!c || tok_begin < 0 || tok_end <= tok_begin || chunk_tokens < 1 || chunk_tokens > 65535) return false;
   *nchunks = (tok_end - tok_begin + chunk_tokens - 1) / chunk_tokens;
   return *nchunks <= 65535;
 }
 
-template <int DT, bool QUAD>
+// NHDB: the source is an LMC_PAGED_SPLIT cache (k_quantize.h: instances of their own, planes of up to 1024 channels)
+template <int DT, bool QUAD, bool NHDB = false>
 static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
   const int C = a.C;
   if (a.pc_limit < 1) return LMC_OK;
@@ -311,7 +331,7 @@ static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
   do {                                                                                             \
     const int per_wg = 4 * (64 / (G)), TO = (a.TQ + 1) / 2; /* row octs per plane-chunk */         \
     dim3 grid((unsigned)((TO + per_wg - 1) / per_wg), (unsigned)a.P, nz);                        \
-    hipLaunchKernelGGL((k_quantize<G, N, DT, QUAD>), grid, dim3(256), 0, s, a);                    \
+    hipLaunchKernelGGL((k_quantize<G, N, DT, QUAD, 1, NHDB>), grid, dim3(256), 0, s, a);           \
   } while (0)
   // wide planes, workspace output: SPLIT waves share a row oct, 1024 channels each (k_quantize.h)
 #define LQS(SPLIT)                                                                                 \
@@ -324,6 +344,7 @@ static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
   else if (C <= 256) LQ(32, 1);
   else if (C <= 512) LQ(64, 1);
   else if (C <= 1024) LQ(64, 2);
+  else if constexpr (NHDB) return LMC_ERR_INVALID;
   else if (C <= 2048) { if (QUAD) LQS(2); else LQ(64, 4); }
   else if (C <= 4096) { if (QUAD) LQS(4); else LQ(64, 8); }
   else return LMC_ERR_INVALID;
@@ -334,8 +355,13 @@ static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
 }
 
 template <bool QUAD>
-static int launch_quant(const QuantArgs& a, hipStream_t s) {
-  return with_kv_dtype(a.src.dtype, [&](auto dt) { return launch_quant_dt<decltype(dt)::value, QUAD>(a, s); });
+static int launch_quant(const QuantArgs& a, hipStream_t s, bool nhdb = false) {
+  return with_kv_dtype(a.src.dtype, [&](auto dt) {
+    if constexpr (QUAD) {
+      if (nhdb) return launch_quant_dt<decltype(dt)::value, true, true>(a, s);
+    }
+    return launch_quant_dt<decltype(dt)::value, QUAD>(a, s);
+  });
 }
 
 // The slot of a blob in the arenas and slots of this file: lmc_blob_bound rounded up to 16 bytes.
@@ -443,25 +469,36 @@ int lmc_calculate_cdf(lmc_ctx* c, const int8_t* sym, int32_t P, int32_t T, int32
 typedef std::function<int(int, int, bool)> AfterPart;
 static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
                                const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
-                               lmc_stream_t stream, int nparts, const AfterPart* after_part);
+                               lmc_stream_t stream, int nparts, const AfterPart* after_part, bool split_ok);
 
 int lmc_encode_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
                       const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
                       lmc_stream_t stream) {
   return encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream, 1,
-                             nullptr);
+                             nullptr, false);
+}
+
+// ... and from any source: an LMC_PAGED_SPLIT cache is read in place by k_quantize's split instances (never fused)
+int lmc_encode_chunks_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                            lmc_stream_t stream) {
+  return encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream, 1,
+                             nullptr, true);
 }
 
 static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
                                const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
-                               lmc_stream_t stream, int nparts, const AfterPart* after_part) {
+                               lmc_stream_t stream, int nparts, const AfterPart* after_part, bool split_ok) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks) || !blobs || !sizes || ((uintptr_t)blobs & 15) ||
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok) || !blobs || !sizes || ((uintptr_t)blobs & 15) ||
       (blob_stride & 15))
     return LMC_ERR_INVALID;
   const int L = src->num_layers, H = src->num_heads, D = src->head_size;
   const int P = 2 * L, C = H * D, G = (C + 63) / 64;  // (C <= LMC_MAX_CHANNELS: layout_ok)
   if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
+  // an LMC_PAGED_SPLIT source (at most 1024 channels per plane: encode_job_ok): k_quantize's split instances, then
+  // k_cdf_encode -- never the fused kernel, so the job is one part
+  const bool nhdb = src->paged_kind == LMC_PAGED_SPLIT;
   BinsArg bins;
   if (!bins_ok(bins_h, P, &bins)) return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
@@ -486,7 +523,7 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   // 64 planes of 1024 channels, 4 / 8 / 12 / 16 / 32 / 64 chunks: fused / two-kernel time = 1.27 / 1.16 / 1.05 / 1.00 /
   // 0.91 / 0.90 (tools/probes/encode_ab.hip)
   const long long auto_min = 4ll * c->num_cus;
-  const bool fused = fused_fits && (c->enc_path == LMC_ENCODE_PATH_FUSED ||
+  const bool fused = !nhdb && fused_fits && (c->enc_path == LMC_ENCODE_PATH_FUSED ||
                                     (c->enc_path == LMC_ENCODE_PATH_AUTO && (long long)nfull * ipc >= auto_min));
   // chunks that go through the general coder launch (scratch slots): every chunk of a job whose chunks are longer than
   // 256 tokens or whose streams do not fill 8-wave workgroups, a ragged last chunk of a single token
@@ -570,7 +607,7 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
     qa.sizes = e2.sizes;
     int r;
     if ((r = prof_mark(c, s))) return r;
-    if ((r = launch_quant<true>(qa, s))) return r;
+    if ((r = launch_quant<true>(qa, s, nhdb))) return r;
     if ((r = prof_mark(c, s))) return r;
     const long long ngroups = (long long)n * PG;
     // launches whose chunks all have 2 .. 256 tokens (a ragged last chunk included) take the counts-only coder: 8 waves
@@ -1062,7 +1099,7 @@ int lmc_store_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, in
                      const int32_t* bins_h, void* host_arena_h, uint64_t host_cap, uint64_t* offsets_h,
                      uint32_t* sizes_h, uint32_t* job_status, lmc_stream_t stream) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks) || !host_arena_h || ((uintptr_t)host_arena_h & 15) ||
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true) || !host_arena_h || ((uintptr_t)host_arena_h & 15) ||
       !offsets_h || !sizes_h)
     return LMC_ERR_INVALID;
   const uint64_t stride = blob_stride(src->num_layers, chunk_tokens, src->num_heads, src->head_size);
@@ -1076,8 +1113,8 @@ int lmc_store_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, in
   for (int c0 = 0; c0 < nchunks; c0 += per) {
     const int c1 = c0 + per < nchunks ? c0 + per : nchunks;
     const int t1 = tok_begin + c1 * chunk_tokens < tok_end ? tok_begin + c1 * chunk_tokens : tok_end;
-    if ((rc = lmc_encode_chunks(c, src, tok_begin + c0 * chunk_tokens, t1, chunk_tokens, bins_h, c->store_arena + (size_t)c0 * stride,
-                                stride, sizes_h + c0, job_status, stream)))
+    if ((rc = encode_chunks_parts(c, src, tok_begin + c0 * chunk_tokens, t1, chunk_tokens, bins_h, c->store_arena + (size_t)c0 * stride,
+                                  stride, sizes_h + c0, job_status, stream, 1, nullptr, true)))
       return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = stream_follows(c, c->copy_stream, s))) return rc;
@@ -1168,7 +1205,7 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
                            const int32_t* bins_h, void* pack_h, uint64_t pack_cap, uint32_t* sizes_h, int32_t nparts,
                            uint64_t* part_info_h, const lmc_event_t* part_events, uint32_t* job_status, lmc_stream_t stream) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks) || !pack_h || ((uintptr_t)pack_h & 15) || !sizes_h ||
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true) || !pack_h || ((uintptr_t)pack_h & 15) || !sizes_h ||
       nparts < 0 || nparts > 16 || (nparts > 0 && !part_info_h))
     return LMC_ERR_INVALID;
   const int L = src->num_layers, P = 2 * L;
@@ -1191,7 +1228,8 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
   pa.status = job_status ? job_status : c->status_h;
   if (nparts == 0) {
     // the whole job is encoded (1 ms per 16 k tokens) before the first byte leaves: the pack kernels on the copy stream
-    if ((rc = lmc_encode_chunks(c, src, tok_begin, tok_end, chunk_tokens, bins_h, c->store_arena, stride, sizes_h, job_status, stream)))
+    if ((rc = encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, c->store_arena, stride, sizes_h, job_status, stream,
+                                  1, nullptr, true)))
       return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = stream_follows(c, c->copy_stream, s))) return rc;
@@ -1228,7 +1266,7 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
     return LMC_OK;
   };
   if ((rc = encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, c->store_arena, stride, sizes_h, job_status,
-                                stream, nparts, &after)))
+                                stream, nparts, &after, true)))
     return rc;
   std::lock_guard<std::mutex> lk(c->mu);
   for (; parts_out < nparts; parts_out++)  // a job that could not be split: the unused parts' events fire behind the only one

@@ -157,6 +157,7 @@ SYMBOLS = {
     "lmc_quantize": (ctypes.c_int, [_vp, _PL, _i32, _i32, _vp, _vp, _vp, _vp]),
     "lmc_calculate_cdf": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lmc_encode_chunks": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "lmc_encode_chunks_split": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_decode_chunks": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _vp, _vp]),
     "lmc_decode_chunks_layers": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lmc_decode_chunks_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -792,6 +793,14 @@ class Context:
         (None: the context's sticky word)."""
         self._call("lmc_encode_chunks", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
                    self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
+        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+
+    def encode_chunks_split(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
+                            blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
+                            status_ptr: Optional[int] = None) -> int:
+        """encode_chunks for any source it takes and a PAGED_SPLIT ("NHDB") one, read in place (lmc_encode_chunks_split)."""
+        self._call("lmc_encode_chunks_split", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end,
+                   chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
         return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
     def decode_chunks(self, blobs_ptr: int, blob_stride: int, nchunks: int, dst: KVLayout, dst_tok0: int,

@@ -748,8 +748,10 @@ class LMCLocalBackend(LMCBackendInterface):
         return self._stage
 
     def put_kv_range(self, keys: Sequence[CacheEngineKey], src: native.KVLayout, fmt: str, tok_begin: int,
-                     tok_end: int, chunk_tokens: int, blocking: bool = True) -> int:
-        """Store chunks [tok_begin + i*chunk_tokens, ...) of `src` under keys[i], reading KV where it lies."""
+                     tok_end: int, chunk_tokens: int, blocking: bool = True, direct: bool = False) -> int:
+        """Store chunks [tok_begin + i*chunk_tokens, ...) of `src` under keys[i], reading KV where it lies.
+        direct (store_paged(direct=True)): the CacheGen tiers hand an "NHDB" cache to the encoder instead of staging it;
+        the raw tiers gather every chunk themselves either way."""
         n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
         assert n == len(keys), "one key per chunk"
         if n == 0:
@@ -765,14 +767,14 @@ class LMCLocalBackend(LMCBackendInterface):
             if self.pack_stores and n >= 2:
                 with torch.cuda.device(dev):
                     pjob = self._codec().store_pack(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L),
-                                                    self.host_arena)
+                                                    self.host_arena, direct=direct)
                 if blocking:
                     self._finish_pack(keys, pjob, shapes, out_dt)
                 else:
                     self.put_queue.put(lambda: self._finish_pack(list(keys), pjob, shapes, out_dt))
                 return n
             with torch.cuda.device(dev):
-                job = self._codec().encode(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L))
+                job = self._codec().encode(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L), direct=direct)
             if blocking:
                 self._finish_encoded(keys, job, shapes, out_dt)
             else:

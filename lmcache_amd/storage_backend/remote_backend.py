@@ -192,7 +192,7 @@ class LMCPipelinedRemoteBackend(LMCRemoteBackend):
         return retrieve_spec(self.fmt, h)
 
     def put_kv_range(self, keys, src, fmt: str, tok_begin: int, tok_end: int, chunk_tokens: int,
-                     blocking: bool = True) -> int:
+                     blocking: bool = True, direct: bool = False) -> int:
         from lmcache_amd.storage_backend.serde.cachegen_device import PinnedArena, get_codec
         n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
         assert n == len(keys), "one key per chunk"
@@ -200,7 +200,7 @@ class LMCPipelinedRemoteBackend(LMCRemoteBackend):
             return 0
         codec = get_codec(src.device.index)
         with torch.cuda.device(src.device):
-            job = codec.encode(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(src.L))
+            job = codec.encode(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(src.L), direct=direct)
             if self._dev_conn:  # device to device: every blob straight into its owner's HBM arena
                 sizes = codec.sizes_of(job)
                 for i, key in enumerate(keys):

@@ -583,18 +583,28 @@ class CacheGenDeviceCodec:
         # plane ranges a pack's encode is launched in (store_pack): LMCACHE_AMD_PACK_PARTS=1 is the round-5 behaviour
         # (the whole encode, then the pack, then its copies), for A/B
         self.pack_parts = max(1, min(16, int(os.environ.get("LMCACHE_AMD_PACK_PARTS", "8"))))
+        self._warned_wide_split = False                      # direct store of an NHDB cache with planes the split quantiser does not read
         self._same_blobs: dict = {}                          # id(caller's list) -> (the list, its blobs' address tuple, largest blob)
         self._table_cache: dict = {}                         # blob-address tuple -> (device table, upload stream)
 
     # ---- encode ------------------------------------------------------------------
-    def _readable(self, src: native.KVLayout, tok_begin: int, tok_end: int):
+    def _readable(self, src: native.KVLayout, tok_begin: int, tok_end: int, direct: bool = False):
         """The encoders read 16-byte vectors (native.KVLayout.vector_readable).  The reference's serde takes any shape
         (torch_quant_vectorized, cachegen_encoder.py:40-61), so a range of a layout that is not -- a head_size that is no
-        multiple of 8 under a huggingface / NHBD layout, rows off a 16-byte boundary, or the "NHDB" cache of vLLM's ROCm
-        paged-attention kernels, which has no rows at all -- is first brought into a contiguous vllm chunk on the device
-        (lmc_copy_kv: element-wise for the former, k_copy_split.h's gather for the latter) and encoded from there."""
+        multiple of 8 under a huggingface / NHBD layout, rows off a 16-byte boundary, or by default the "NHDB" cache of
+        vLLM's ROCm paged-attention kernels, which has no rows at all -- is first brought into a contiguous vllm chunk on
+        the device (lmc_copy_kv: element-wise for the former, k_copy_split.h's gather for the latter) and encoded from
+        there.  direct: an "NHDB" cache with planes of at most 1024 channels goes to the encoder as it is
+        (lmc_encode_chunks_split and the stores read the split blocks: k_quantize.h); wider planes are staged all the same."""
         if src.vector_readable():
             return src, tok_begin, tok_end
+        if direct and src.struct.paged_kind == native.PAGED_SPLIT:
+            if src.H * src.D <= 1024:
+                return src, tok_begin, tok_end
+            if not self._warned_wide_split:
+                self._warned_wide_split = True
+                logger.warning("direct store from an NHDB cache: planes of %d channels are wider than the 1024 the split "
+                               "quantiser reads; staging through lmc_copy_kv", src.H * src.D)
         n = tok_end - tok_begin
         with torch.cuda.device(self.device):
             chunk = torch.empty((src.L, 2, n, src.H, src.D), dtype=native.torch_dtype(src.dtype), device=src.device)
@@ -602,10 +612,11 @@ class CacheGenDeviceCodec:
         return native.KVLayout.from_chunk(chunk, "vllm"), 0, n
 
     def encode(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int,
-               bins: Sequence[int]) -> EncodeJob:
+               bins: Sequence[int], direct: bool = False) -> EncodeJob:
         """Launch the fused encode of every chunk of [tok_begin, tok_end) on the CURRENT stream
-        (so it is ordered after whatever produced the KV).  Asynchronous."""
-        src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end)
+        (so it is ordered after whatever produced the KV).  Asynchronous.  direct: see _readable."""
+        src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end, direct)
+        encode_chunks = self.ctx.encode_chunks_split if src.struct.paged_kind == native.PAGED_SPLIT else self.ctx.encode_chunks
         L, H, D = src.L, src.H, src.D
         n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
         stride = native.r16(native.blob_bound(L, chunk_tokens, H, D))
@@ -635,9 +646,9 @@ class CacheGenDeviceCodec:
                     parts = []
                     for c0 in range(0, n, per):
                         c1 = min(n, c0 + per)
-                        self.ctx.encode_chunks(src, tok_begin + c0 * chunk_tokens, min(tok_end, tok_begin + c1 * chunk_tokens),
-                                               chunk_tokens, bins, arena.data_ptr() + c0 * stride, stride,
-                                               sizes.ptr + 4 * c0, stream=cur.cuda_stream, status_ptr=st_ptr)
+                        encode_chunks(src, tok_begin + c0 * chunk_tokens, min(tok_end, tok_begin + c1 * chunk_tokens),
+                                      chunk_tokens, bins, arena.data_ptr() + c0 * stride, stride,
+                                      sizes.ptr + 4 * c0, stream=cur.cuda_stream, status_ptr=st_ptr)
                         ev = torch.cuda.Event()
                         ev.record(cur)
                         parts.append((c0, c1, ev))
@@ -888,14 +899,15 @@ class CacheGenDeviceCodec:
 
     # ---- packs: the plane-major pinned tier ---------------------------------------------------------------
     def store_pack(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins: Sequence[int],
-                   arena: PinnedArena) -> PackJob:
+                   arena: PinnedArena, direct: bool = False) -> PackJob:
         """lmc_store_pack_parts on the CURRENT stream: encode every chunk of [tok_begin, tok_end), then a copy kernel writes
         the blobs transposed (static sections, then streams ordered layer / K,V / chunk) into one region.  No host
         wait here; finish_pack() returns the pack in pinned host DRAM (`arena` is taken there, not here).
         The region is in HBM and finish_pack() moves the pack with copies of its exact size -- the copy kernel then runs
         at HBM speed (0.3 ms) and the PCIe leg disturbs nobody (a copy kernel whose own stores crossed PCIe made the
-        kernels beside its 11 ms 4.3x slower: bench.py store_hidden)."""
-        src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end)
+        kernels beside its 11 ms 4.3x slower: bench.py store_hidden).
+        direct: see _readable; a split source is coded by the two kernels, so its pack leaves as ONE part."""
+        src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end, direct)
         L, H, D = src.L, src.H, src.D
         n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
         with self._lock, torch.cuda.device(self.device):
