@@ -246,6 +246,39 @@ int lmc_encode_chunks_split(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_
                             int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
                             uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
 
+/*
+ * The same encode issued LAYER BY LAYER (additive in ABI 6; csrc/k_layers.h).  Replaces the store of the reference, which
+ * serialises every chunk after the whole forward pass (cache_engine.py:268-282), and the per-layer gather of the paged
+ * cache that a connector runs in front of it (docs/source/developer_tutorial/LLM_Engine.rst:91-122): layer l's planes
+ * l and L + l are quantised and entropy-coded the moment layer l has written its KV, and one pass at HBM speed finishes
+ * the blobs.  After lmc_encode_layers_finish every blob and size word is byte for byte what lmc_encode_chunks (or, for an
+ * LMC_PAGED_SPLIT source, lmc_encode_chunks_split) writes for the same source, token range, chunk length and bins; a size
+ * word stays 0 until then.
+ *   lmc_encode_layers_begin   arguments and refusals of lmc_encode_chunks_split; `src` is the full layout, every layer's
+ *                             planes (only their contents arrive layer by layer) and must stay valid, with whatever it
+ *                             points to, until finish or abort.  Queues nothing.  Returns LMC_OK and the job, or
+ *                             LMC_NOT_LAYERWISE (positive, no job): the arguments are fine but the job is not eligible --
+ *                             eligible are jobs whose every chunk, a ragged last one included, has 2 .. 256 tokens and
+ *                             whose planes have at most 1024 channels; the caller encodes in one piece instead.
+ *                             The job owns its look-back granules, ticket counter, two-plane symbol workspace and V
+ *                             region: it takes neither of the context's encode workspaces nor its store arena, so a job
+ *                             that spans a forward pass makes no other store wait.
+ *   lmc_encode_layer          quantise and code layer `layer` on `stream`.  Layers come in ascending order from 0; a
+ *                             repeated, skipped or out-of-range layer is LMC_ERR_INVALID with nothing queued.  The
+ *                             calls of one job are ordered by the caller: one stream, or events between them.
+ *   lmc_encode_layers_finish  k_layers_finish on `stream` behind layer L - 1 (LMC_ERR_INVALID before that, nothing
+ *                             queued); the job handle is gone afterwards, its buffers are reused behind the launch.
+ *   lmc_encode_layers_abort   gives the job up at any point: its buffers are reused behind what it has queued.
+ */
+#define LMC_NOT_LAYERWISE 1
+typedef struct lmc_layer_job lmc_layer_job;
+int lmc_encode_layers_begin(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
+                            int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
+                            uint32_t* sizes, uint32_t* job_status, lmc_layer_job** job_out);
+int lmc_encode_layer(lmc_ctx* ctx, lmc_layer_job* job, int32_t layer, lmc_stream_t stream);
+int lmc_encode_layers_finish(lmc_ctx* ctx, lmc_layer_job* job, lmc_stream_t stream);
+int lmc_encode_layers_abort(lmc_ctx* ctx, lmc_layer_job* job);
+
 /* ------------------------------------------------------------------ */
 /* decode side                                                         */
 /* ------------------------------------------------------------------ */

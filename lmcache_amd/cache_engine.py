@@ -192,6 +192,55 @@ class LMCacheEngine:
         self._store_from(tokens, lambda: native.KVLayout.paged(kv_caches, slot_mapping, block_size, layout),
                          skip_existing, blocking, direct=direct and layout == "NHDB")
 
+    @_lmcache_nvtx_annotate
+    @torch.no_grad()
+    def store_paged_layerwise(self, tokens: torch.Tensor, kv_caches, slot_mapping: torch.Tensor, block_size: int,
+                              layout: str = "NBHD", skip_existing=True, direct: bool = False) -> "LayerwiseStore":
+        """store_paged() whose encode is issued layer by layer WHILE the forward pass fills the cache: call this before the
+        step (the cache tensors exist; only their contents arrive layer by layer), `save_layer(l)` on the model's stream
+        right behind layer l's cache write, `finish()` behind the last layer -- the `save_kv_layer` / `wait_for_save`
+        hooks of a vLLM v1 connector.  Replaces the reference's store behind the forward pass
+        (cache_engine.py:268-282) and the connector's per-layer gather in front of it
+        (docs/source/developer_tutorial/LLM_Engine.rst:91-122).  Arguments are store_paged's.
+        Hashing, skip_existing and the keys are resolved HERE, from the tokens alone: with everything present every
+        method of the returned LayerwiseStore is a no-op; with a stored prefix only the missing chunks' token range is
+        encoded and published.
+        Layer-wise (LayerwiseStore.layerwise): the two CacheGen tiers of the local backend, chunks of 2 .. 256 tokens
+        (the ragged last one included), planes of at most 1024 channels, layouts "NBHD" / "NHBD", and "NHDB" with
+        direct=True (the split blocks are read per layer).  save_layer(l) then quantises and entropy-codes layer l's two
+        planes on a side stream of the job -- never on the model's -- and layer_event(l) fires once layer l's KV has been
+        read; finish() is one pass at HBM speed plus the tier's copies, and leaves what store_paged leaves: the same keys,
+        byte for byte the same blobs (and the same pack on the pinned tier).
+        Everything else FALLS BACK: the raw tiers, remote, hybrid and chunk-tensor backends, a job the layer-wise encoder
+        does not take, and an "NHDB" cache without `direct` -- it has no token rows to read per layer, and its staging
+        gather needs every layer.  save_layer is then a no-op, layer_event(l) is None (nothing has been read: the cache
+        must keep every layer until finish), and finish() runs today's store_paged path for the keys resolved here.
+        That is correct, not layer-wise -- the rule retrieve_into_paged_layerwise states for its side; logged once."""
+        assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
+        assert len(tokens.shape) == 1, f"Invalid shape of tokens: {tokens.shape}"
+        assert len(kv_caches) > 0, "Empty kv_caches"
+        assert len(tokens) == slot_mapping.numel(), "one slot per token"
+        fmt, cs, ntok = self.metadata.fmt, self.chunk_size, len(tokens)
+        chunk_hashes = self._prefix_hashes_of(tokens)
+        first = 0
+        if skip_existing:
+            first = self._first_missing_chunk(chunk_hashes, fmt)
+            if first is None:
+                return LayerwiseStore(self, None, [], None, 0, 0, False)
+        keys = [self._make_key(h, fmt) for h in chunk_hashes[first:]]
+        direct = direct and layout == "NHDB"
+        src = native.KVLayout.paged(kv_caches, slot_mapping, block_size, layout)
+        put = None
+        if layout != "NHDB" or direct:
+            begin = getattr(self.engine_, "begin_put_kv_layers", None)
+            if begin is not None and getattr(self.engine_, "supports_kv_layout", False):
+                put = begin(keys, src, fmt, first * cs, ntok, cs)
+        if put is None and not getattr(self, "_layerwise_fallback_logged", False):
+            self._layerwise_fallback_logged = True
+            logger.info("store_paged_layerwise: no layer-wise path for this backend / job: storing in one piece at finish() "
+                        "(logged once)")
+        return LayerwiseStore(self, put, keys, src, first * cs, ntok, direct)
+
     def _store_from(self, tokens: torch.Tensor, make_src, skip_existing: bool, blocking: bool, direct: bool = False) -> None:
         t_start = time.perf_counter()
         fmt = self.metadata.fmt
@@ -565,6 +614,52 @@ class LMCacheEngine:
 
     def close(self):
         self.engine_.close()
+
+
+class LayerwiseStore:
+    """What store_paged_layerwise returns.  `layerwise`: the encode runs per layer (else: in one piece at finish, or --
+    nothing to store -- never); `nchunks`: chunks that will be stored."""
+
+    def __init__(self, engine: "LMCacheEngine", put, keys, src, tok_begin: int, tok_end: int, direct: bool):
+        self._engine, self._put, self._keys, self._src = engine, put, keys, src
+        self._range, self._direct = (tok_begin, tok_end), direct
+        self._done = False
+
+    @property
+    def layerwise(self) -> bool:
+        return self._put is not None
+
+    @property
+    def nchunks(self) -> int:
+        return len(self._keys)
+
+    def save_layer(self, layer: int) -> None:
+        """Layer `layer`'s K and V are in the cache as far as the CURRENT stream is concerned: encode them (on the job's
+        side stream, behind an event recorded here).  Layers in ascending order from 0."""
+        if self._put is not None:
+            self._put.encode_layer(layer)
+
+    def layer_event(self, layer: int):
+        """The event behind which layer `layer`'s KV has been read and its cache may be overwritten; None when the store is
+        not layer-wise (nothing is read before finish) or there is nothing to store."""
+        return self._put.layer_event(layer) if self._put is not None else None
+
+    def finish(self, blocking: bool = True) -> int:
+        """Behind the last layer: finish the blobs and hand them to the tier (blocking=False: the tier's copies and the
+        publishing run on the backend's worker thread; backend.drain() waits for them).  -> chunks stored."""
+        if self._done or not self._keys:
+            return 0
+        self._done = True
+        eng, (t0, t1) = self._engine, self._range
+        if self._put is not None:
+            n = self._put.finish(blocking=blocking)
+        elif getattr(eng.engine_, "supports_kv_layout", False):
+            n = eng.engine_.put_kv_range(self._keys, self._src, eng.metadata.fmt, t0, t1, eng.chunk_size, blocking=blocking,
+                                         **({"direct": True} if self._direct else {}))
+        else:
+            n = eng.engine_.batched_put(eng._gather_chunks(self._keys, self._src, eng.metadata.fmt, t0, t1), blocking=blocking)
+        self._src = None
+        return n
 
 
 class LayerwiseRetrieval:

@@ -52,6 +52,20 @@ struct EncodeArgs {
   // knows how many tickets earlier launches drew (ticket_base); launches sharing a context run on ordered streams.
   u32* ticket;
   u32 ticket_base;
+  // ---- a launch over a subset of the planes, of a layer-wise job (k_layers.h; the counts-only k_cdf_encode alone reads these) ----
+  // Stream (y, g) of a chunk is group g of plane plane0 + y * plane_step, y < nplanes; the symbol workspace holds the
+  // launch's planes, region (chunk, y).  bins, the scales' checksum and the directory entry stay addressed by the real plane.
+  // All zero: every plane, as every launch was before these fields existed.
+  int plane0, plane_step, nplanes;
+  // chain_gran != 0: the job's streams are placed by TWO chains per chunk, K planes and V planes, of L * chain_gran
+  // granules each (chain_gran = G / 8 workgroup granules, or G per-wave granules where G is no multiple of 8): agg is
+  // [nchunks][2][L * chain_gran], zeroed once per job, so a layer's look-back meets the final inclusive prefixes of the
+  // layers before it.  K streams go to their final place; V streams to vregion + chunk * vstride at V-relative offsets
+  // (their directory entries too) until k_layers_finish moves them behind the chunk's K streams.  Nobody writes the
+  // static sections or the size word before that kernel.
+  int chain_gran;
+  u8* vregion;
+  long long vstride;
 };
 
 // The calling workgroup's work index (see EncodeArgs::ticket); ends with a workgroup barrier.

@@ -704,7 +704,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
   const int lane = threadIdx.x & 63;
   // everything derived from the wave id is wave-uniform: keep it in SGPRs
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long ngroups_total = (long long)a.nchunks * a.P * a.G;
+  const int npl = (COUNTS_ONLY && a.nplanes) ? a.nplanes : a.P;  // planes of this launch (EncodeArgs::nplanes)
+  const long long ngroups_total = (long long)a.nchunks * npl * a.G;
   u32* hist = lds_all + wave * TAB_DWORDS;  // [32][64] u16 counters; lanes 2i, 2i+1 share a dword
 
   // Workgroup -> streams.  When the streams of a chunk fill whole workgroups, consecutive workgroups take the SAME
@@ -718,7 +719,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
   if constexpr (ENCODE) item = (u32)__builtin_amdgcn_readfirstlane((int)draw_ticket(a.ticket, a.ticket_base));
   // stream = (chunk_i, pg_i), pg_i = p * G + g; all 32-bit (nchunks <= 65535, P * G <= 2^14): a 64-bit division costs
   // more than a hundred instructions
-  const u32 npg = (u32)(a.P * a.G);
+  const u32 npg = (u32)(npl * a.G);
   u32 chunk_i, pg_i;
   if (ENCODE && npg % NW == 0) {
     chunk_i = item % (unsigned)a.nchunks;
@@ -745,52 +746,76 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
     if (lane == 0 && (t.exact > alloc || t.exact + 16 > a.cap)) atomicOr(a.status, LMC_ST_STREAM_OVERFLOW);
   };
   if constexpr (COUNTS_ONLY) {
-    // Launches of 256-token chunks only (lmc_api.hip: P * G is a multiple of NW): like the fused kernel, the streams are
+    // Launches whose chunks all take the counts model (lmc_api.hip: a one-piece job's P * G is a multiple of NW; a layer
+    // of a layer-wise job, two planes, need not be: see wave_gran below): like the fused kernel, the streams are
     // placed BETWEEN their two passes -- histogram, allocation, one look-back per workgroup, then the coder writes
     // straight into the blob.  No scratch slot, no copy.
     const int n = a.P * a.G;
-    const u32 p_i = pg_i / (u32)a.G;
-    const CountsStream s = counts_stream_of(a, (int)chunk_i, (int)p_i, (int)(pg_i - p_i * (u32)a.G), lane);
+    // the stream's plane: row y of the launch is plane plane0 + y * plane_step (all planes: y itself)
+    const u32 y_i = pg_i / (u32)a.G, g_i = pg_i - y_i * (u32)a.G;
+    const int p_i = a.plane0 + (int)y_i * (a.plane_step ? a.plane_step : 1);
+    CountsStream s = counts_stream_of(a, (int)chunk_i, p_i, (int)g_i, lane);
+    s.symq = a.sym4 + ((long long)chunk_i * npl + y_i) * a.sym_stride + s.c;  // the workspace holds the launch's planes
     CountsState cs;
     alloc = counts_hist_stream<true>(a, s, hist, rtab_lds + RTAB_DWORDS, lane, cs);
+    // Which granules place the stream.  One chain per chunk, a granule per workgroup; or, a layer-wise job (chain_gran),
+    // the chain of its K or its V planes -- whose granules of earlier layers are final prefixes left by earlier launches --
+    // with a granule per workgroup or, where a plane's streams do not fill workgroups, per wave.
+    const bool layered = a.chain_gran != 0;
+    const bool wave_gran = layered && (a.G % NW) != 0;  // (uniform over the launch)
+    const int kv = (layered && p_i >= a.L) ? 1 : 0;
+    unsigned long long* const agg = layered ? a.agg + ((long long)chunk_i * 2 + kv) * a.L * a.chain_gran : a.agg + (long long)chunk_i * n;
+    const int gi = layered ? (p_i - kv * a.L) * a.chain_gran + (int)(wave_gran ? g_i : g_i / NW) : (int)pg_i / NW;
     __shared__ u32 wg_alloc[NW];
     __shared__ u32 wg_excl;
-    if (lane == 0) wg_alloc[wave] = alloc;
-    __syncthreads();
-    u32 before = 0, wg_total = 0;
+    u32 beg, chain_end;  // the stream's offset in its chain; the chain's length up to and including this granule
+    if (!wave_gran) {
+      if (lane == 0) wg_alloc[wave] = alloc;
+      __syncthreads();
+      u32 before = 0, wg_total = 0;
 #pragma unroll
-    for (int w = 0; w < NW; w++) {
-      before += w < wave ? wg_alloc[w] : 0u;
-      wg_total += wg_alloc[w];
-    }
-    if (wave == 0) {
-      unsigned long long* agg = a.agg + (long long)chunk_i * n;
-      const int wgi = (int)pg_i / NW;
-      if (lane == 0 && wgi > 0) agg_store(agg + wgi, AGG_A, wg_total);
-      const u32 e = lookback_exclusive(agg, wgi, lane, a.status);
-      if (lane == 0) {
-        agg_store(agg + wgi, AGG_P, e + wg_total);
-        wg_excl = e;
+      for (int w = 0; w < NW; w++) {
+        before += w < wave ? wg_alloc[w] : 0u;
+        wg_total += wg_alloc[w];
       }
+      if (wave == 0) {
+        if (lane == 0 && gi > 0) agg_store(agg + gi, AGG_A, wg_total);
+        const u32 e = lookback_exclusive(agg, gi, lane, a.status);
+        if (lane == 0) {
+          agg_store(agg + gi, AGG_P, e + wg_total);
+          wg_excl = e;
+        }
+      }
+      __syncthreads();
+      beg = wg_excl + before;
+      chain_end = wg_excl + wg_total;
+    } else {  // every wave publishes and looks back for itself (the general launch's n % NW != 0 branch)
+      if (lane == 0 && gi > 0) agg_store(agg + gi, AGG_A, alloc);
+      beg = lookback_exclusive(agg, gi, lane, a.status);
+      if (lane == 0) agg_store(agg + gi, AGG_P, beg + alloc);
+      chain_end = beg + alloc;
     }
-    __syncthreads();
-    const u32 beg = wg_excl + before;
     const BlobOff bo = lmc_blob_off((u32)a.P, (u32)s.T, (u32)a.G);
     u8* const blob = a.blobs + (long long)chunk_i * a.blob_stride;
-    u8* const out = blob + bo.streams + beg;
+    // a layer-wise job's V streams wait in the job's V region (k_layers_finish moves them behind the K streams)
+    u8* const out = kv ? a.vregion + (long long)chunk_i * a.vstride + beg : blob + bo.streams + beg;
+    if (kv && (long long)beg + alloc > a.vstride) {  // the region is the bound of the chunk's V streams: never
+      if (lane == 0) atomicOr(a.status, LMC_ST_STREAM_OVERFLOW);
+      return;
+    }
     counts_open_stream(s, cs, out, hist, lane);
     const u32 exact = cs.head + counts_code_stream<true>(a, s, hist, wring, rtab_lds, lane, reinterpret_cast<u16*>(out + cs.head));
     const u32 padded = (exact + 15u) & ~15u;
     if (alloc > padded) zero_fill16(out + padded, alloc - padded, lane);
     if (lane == 0) {
-      u32* d = reinterpret_cast<u32*>(blob + bo.gdir) + 2 * pg_i;
+      u32* d = reinterpret_cast<u32*>(blob + bo.gdir) + 2 * (p_i * a.G + (int)g_i);
       d[0] = beg;
       d[1] = beg + exact;
       if (exact > alloc) atomicOr(a.status, LMC_ST_STREAM_OVERFLOW);  // the bound is a theorem: never
     }
-    if ((int)pg_i == n - 1) {  // the chunk's last stream knows the chunk's size: header, static sections, size word
-      write_blob_static(blob, bo, a, (u32)s.T, wg_excl + wg_total, lane);
-      if (lane == 0) a.sizes[chunk_i] = bo.streams + wg_excl + wg_total;
+    if (!layered && (int)pg_i == n - 1) {  // the chunk's last stream knows the chunk's size: header, static sections, size word
+      write_blob_static(blob, bo, a, (u32)s.T, chain_end, lane);
+      if (lane == 0) a.sizes[chunk_i] = bo.streams + chain_end;
     }
     return;
   } else if constexpr (ENCODE && QUADSYM) {

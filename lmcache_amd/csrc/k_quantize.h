@@ -37,6 +37,11 @@ struct QuantArgs {
   unsigned long long* agg;  // the coder's look-back granules, zeroed here (saves a memset dispatch), or NULL
   long long agg_n;
   u32* sizes;               // ... and the job's size words [nchunks] (0 = "this chunk's encode did not finish"), or NULL
+  // A launch over a SUBSET of the planes (k_layers.h: a layer of a layer-wise store is plane0 = l, plane_step = L, two
+  // planes): grid row y takes plane plane0 + y * plane_step of every chunk.  Source, bins and the scales' place in the blob
+  // stay addressed by that real plane; the symbol workspace holds the launch's planes only, region (chunk, y).  All zero:
+  // every plane, plane y in row y -- what every launch was before these fields existed.
+  int plane0, plane_step, nplanes;
 };
 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -474,10 +479,10 @@ __global__ __launch_bounds__(256) void k_quantize(QuantArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int sub = lane / G, sl = lane % G;
-  const int p = (int)blockIdx.y, chunk = (int)blockIdx.z;
-  if (QUAD && a.agg) {  // the launch has at least 256 threads per plane-chunk, a plane-chunk at most 64 granules
+  const int p = a.plane0 + (int)blockIdx.y * (a.plane_step ? a.plane_step : 1), chunk = (int)blockIdx.z;
+  if (QUAD && (a.agg || a.sizes)) {  // the launch has at least 256 threads per plane-chunk, a plane-chunk at most 64 granules
     const long long i = (((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-    if (i < a.agg_n) a.agg[i] = 0ull;
+    if (a.agg && i < a.agg_n) a.agg[i] = 0ull;  // (a layer-wise job's granules live across its launches: zeroed once, by the host)
     if (a.sizes && i < a.nchunks) a.sizes[i] = 0u;
   }
   const int TO = (a.TQ + 1) >> 1;
@@ -490,7 +495,7 @@ __global__ __launch_bounds__(256) void k_quantize(QuantArgs a) {
   const int bins = (int)a.bins.b[p];
   const float maxf = (float)(bins / 2 - 1);
   u16* scale_out = reinterpret_cast<u16*>(a.scale_base + (long long)chunk * a.scale_stride) + ((long long)p * Tc + oct * 8);
-  u32* sym_pc = QUAD ? a.sym4 + ((long long)chunk * a.P + p) * a.sym_stride : nullptr;  // this plane-chunk's workspace
+  u32* sym_pc = QUAD ? a.sym4 + ((long long)chunk * gridDim.y + blockIdx.y) * a.sym_stride : nullptr;  // this plane-chunk's workspace (gridDim.y: the launch's planes)
   int8_t* sym8_plane = QUAD ? nullptr : a.sym8 + (long long)p * Tc * a.C;
   if constexpr (QUAD) {
     constexpr int ROWS = NITER <= 2 ? 8 : 4;  // 16-byte loads in flight per lane: ROWS * NITER

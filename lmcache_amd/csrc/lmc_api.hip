@@ -12,6 +12,7 @@
 #include <new>
 #include <stdlib.h>
 #include <string.h>
+#include <vector>
 
 #include "../../include/lmc_hip.h"
 #include "k_copy.h"
@@ -19,6 +20,7 @@
 #include "k_decode.h"
 #include "k_encode_counts.h"
 #include "k_fused.h"
+#include "k_layers.h"
 #include "k_offload.h"
 #include "k_quantize.h"
 #include "k_repack.h"
@@ -35,9 +37,39 @@ static thread_local int g_last_hip = 0;
     }                                      \
   } while (0)
 
+// What a layer-wise encode job (lmc_encode_layers_*) owns from begin to finish: look-back granules that live across the
+// job's launches, a ticket counter, the symbol workspace of ONE layer's two planes and the region its V streams wait in.
+// Kept by the context between jobs and handed to the next one behind `free_ev`.
+struct lmc_layer_bufs {
+  unsigned long long* agg = nullptr; size_t agg_bytes = 0;
+  u32* sym4 = nullptr; size_t sym4_bytes = 0;
+  u8* vregion = nullptr; size_t v_bytes = 0;
+  u32* ticket = nullptr;
+  hipEvent_t free_ev = nullptr;  // recorded behind the last launch of the job that had them last
+  bool used = false;             // ... if any
+  bool busy = false;             // a live job holds them
+};
+
+struct lmc_layer_job {
+  lmc_ctx* ctx;
+  lmc_layer_bufs* b;
+  lmc_kv_layout src;
+  BinsArg bins;
+  int tok_begin, tok_end, chunk_tokens, nchunks;
+  u8* blobs; uint64_t blob_stride;
+  u32* sizes; u32* status;
+  int chain_gran;            // granules of a plane: G / 8 (a granule per workgroup) or G (per wave)
+  long long vstride;         // bytes of a chunk's slot in the V region
+  int next_layer = 0;
+  u32 tickets_drawn = 0;
+  hipStream_t last_stream = nullptr;  // of the last launch that went out
+  bool queued = false;
+};
+
 struct lmc_ctx {
   int device;
   std::mutex mu;
+  std::vector<lmc_layer_bufs*> layer_pool;  // buffers of the layer-wise encode jobs, live or not
   // Encode workspaces.  An encode job owns a workspace from its first kernel to its last; the job that takes it next
   // waits (on its own stream) for the event behind that last kernel.  TWO of them, so that a worker thread's
   // non-blocking put and the engine thread's put (the reference's model: local_backend.py:41-45, 72-80) run side by side
@@ -98,6 +130,7 @@ int lmc_debug_decode_timeline(void* host_out, size_t bytes) {
 const char* lmc_strerror(int code) {
   switch (code) {
     case LMC_OK: return "ok";
+    case LMC_NOT_LAYERWISE: return "not an error: the job is not eligible for the layer-wise encode";
     case LMC_ERR_INVALID: return "invalid argument or unsupported geometry";
     case LMC_ERR_HIP: return "HIP runtime error (see lmc_last_hip_error)";
     case LMC_ERR_NOMEM: return "out of memory";
@@ -148,6 +181,15 @@ int lmc_ctx_destroy(lmc_ctx* c) {
   if (c->pack_table) (void)hipFree(c->pack_table);
   if (c->store_free) (void)hipEventDestroy(c->store_free);
   if (c->load_free) (void)hipEventDestroy(c->load_free);
+  for (lmc_layer_bufs* b : c->layer_pool) {  // (a job still live at this point is the caller's leak: its handle dangles)
+    if (b->used) (void)hipEventSynchronize(b->free_ev);
+    if (b->agg) (void)hipFree(b->agg);
+    if (b->sym4) (void)hipFree(b->sym4);
+    if (b->vregion) (void)hipFree(b->vregion);
+    if (b->ticket) (void)hipFree(b->ticket);
+    if (b->free_ev) (void)hipEventDestroy(b->free_ev);
+    delete b;
+  }
   for (int i = 0; i < 64; i++) if (c->evpool[i]) (void)hipEventDestroy(c->evpool[i]);
   for (int i = 0; i < 8; i++) if (c->pev[i]) (void)hipEventDestroy(c->pev[i]);
   if (c->status_h) (void)hipHostFree(c->status_h);
@@ -327,17 +369,18 @@ static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
   const int C = a.C;
   if (a.pc_limit < 1) return LMC_OK;
   const unsigned nz = (unsigned)((a.pc_limit + a.P - 1) / a.P);  // chunks that hold the plane-chunks to do
+  const unsigned ny = (unsigned)(a.nplanes ? a.nplanes : a.P);   // planes of the launch (QuantArgs::plane0)
 #define LQ(G, N)                                                                                   \
   do {                                                                                             \
     const int per_wg = 4 * (64 / (G)), TO = (a.TQ + 1) / 2; /* row octs per plane-chunk */         \
-    dim3 grid((unsigned)((TO + per_wg - 1) / per_wg), (unsigned)a.P, nz);                        \
+    dim3 grid((unsigned)((TO + per_wg - 1) / per_wg), ny, nz);                                    \
     hipLaunchKernelGGL((k_quantize<G, N, DT, QUAD, 1, NHDB>), grid, dim3(256), 0, s, a);           \
   } while (0)
   // wide planes, workspace output: SPLIT waves share a row oct, 1024 channels each (k_quantize.h)
 #define LQS(SPLIT)                                                                                 \
   do {                                                                                             \
     const int TO = (a.TQ + 1) / 2, per_wg = 4 / (SPLIT);                                           \
-    dim3 grid((unsigned)((TO + per_wg - 1) / per_wg), (unsigned)a.P, nz);                        \
+    dim3 grid((unsigned)((TO + per_wg - 1) / per_wg), ny, nz);                                    \
     hipLaunchKernelGGL((k_quantize<64, 2, DT, QUAD, QUAD ? SPLIT : 1>), grid, dim3(256), 0, s, a); \
   } while (0)
   if (C <= 128) LQ(16, 1);
@@ -671,6 +714,176 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   HIP_TRY(hipEventRecord(w->ws_free, s));
   w->ws_used = true;
   w->last_stream = s;
+  return LMC_OK;
+}
+
+// ---- the layer-wise encode (include/lmc_hip.h; k_layers.h) ------------------------------------------------------------
+static bool layer_job_ok(const lmc_ctx* c, const lmc_layer_job* j) { return c && j && j->ctx == c && j->b && j->b->busy; }
+
+// caller holds ctx->mu: the job is gone; its buffers go back behind what it queued
+static void layer_job_release(lmc_layer_job* j) {
+  lmc_layer_bufs* b = j->b;
+  if (j->queued && hipEventRecord(b->free_ev, j->last_stream) == hipSuccess) b->used = true;
+  b->busy = false;
+  delete j;
+}
+
+int lmc_encode_layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                            lmc_layer_job** job_out) {
+  int nchunks;
+  if (!job_out) return LMC_ERR_INVALID;
+  *job_out = nullptr;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true) || !blobs || !sizes || ((uintptr_t)blobs & 15) ||
+      (blob_stride & 15))
+    return LMC_ERR_INVALID;
+  const int L = src->num_layers, H = src->num_heads, D = src->head_size;
+  const int P = 2 * L, C = H * D, G = (C + 63) / 64;
+  if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
+  BinsArg bins;
+  if (!bins_ok(bins_h, P, &bins)) return LMC_ERR_INVALID;
+  // eligible: the counts-only coder takes every chunk (2 .. 256 tokens, a ragged last one included) and k_quantize's
+  // one-wave-per-oct instances every plane (at most 1024 channels)
+  const int tail = (tok_end - tok_begin) % chunk_tokens;
+  if (chunk_tokens < (int)LMC_COUNTS_T_MIN || chunk_tokens > (int)LMC_COUNTS_T || (tail && tail < (int)LMC_COUNTS_T_MIN) || C > 1024)
+    return LMC_NOT_LAYERWISE;
+  HIP_TRY(hipSetDevice(c->device));
+  const int gran = G % 8 == 0 ? G / 8 : G;
+  const size_t TQ = ((size_t)chunk_tokens + 3) / 4;
+  const size_t need_agg = (size_t)nchunks * 2 * L * gran * 8;
+  const size_t need_sym = (size_t)nchunks * 2 * TQ * C * 4;
+  const size_t vstride = ((size_t)L * G * lmc_group_cap_bytes((uint32_t)chunk_tokens) + 255) & ~(size_t)255;
+  const size_t need_v = (size_t)nchunks * vstride;
+
+  std::lock_guard<std::mutex> lk(c->mu);
+  lmc_layer_bufs* b = nullptr;
+  for (lmc_layer_bufs* k : c->layer_pool)  // idle buffers that are large enough, else any idle ones (grown below)
+    if (!k->busy && k->agg_bytes >= need_agg && k->sym4_bytes >= need_sym && k->v_bytes >= need_v) { b = k; break; }
+  for (lmc_layer_bufs* k : c->layer_pool)
+    if (!b && !k->busy) b = k;
+  if (!b) {
+    b = new (std::nothrow) lmc_layer_bufs();
+    if (!b) return LMC_ERR_NOMEM;
+    hipError_t e = hipEventCreateWithFlags(&b->free_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void**)&b->ticket, 64);
+    if (e != hipSuccess) {
+      g_last_hip = (int)e;
+      if (b->free_ev) (void)hipEventDestroy(b->free_ev);
+      delete b;
+      return LMC_ERR_HIP;
+    }
+    c->layer_pool.push_back(b);
+  }
+  if (b->agg_bytes < need_agg || b->sym4_bytes < need_sym || b->v_bytes < need_v) {
+    // growing frees memory that the previous job's kernels may still use: wait for them (this call only)
+    if (b->used) HIP_TRY(hipEventSynchronize(b->free_ev));
+    int rc;
+    if ((rc = ws_grow((void**)&b->agg, &b->agg_bytes, need_agg))) return rc;
+    if ((rc = ws_grow((void**)&b->sym4, &b->sym4_bytes, need_sym))) return rc;
+    if ((rc = ws_grow((void**)&b->vregion, &b->v_bytes, need_v))) return rc;
+  }
+  lmc_layer_job* j = new (std::nothrow) lmc_layer_job();
+  if (!j) return LMC_ERR_NOMEM;
+  j->ctx = c; j->b = b; j->src = *src; j->bins = bins;
+  j->tok_begin = tok_begin; j->tok_end = tok_end; j->chunk_tokens = chunk_tokens; j->nchunks = nchunks;
+  j->blobs = (u8*)blobs; j->blob_stride = blob_stride; j->sizes = sizes;
+  j->status = job_status ? job_status : c->status_h;
+  j->chain_gran = gran; j->vstride = (long long)vstride;
+  b->busy = true;
+  *job_out = j;
+  return LMC_OK;
+}
+
+// the coder's view of the job (EncodeArgs of every launch but for its planes)
+static EncodeArgs layer_encode_args(const lmc_layer_job* j) {
+  const lmc_kv_layout* src = &j->src;
+  EncodeArgs ea;
+  memset(&ea, 0, sizeof ea);
+  ea.sym4 = j->b->sym4;
+  ea.tok_begin = j->tok_begin; ea.tok_end = j->tok_end; ea.chunk_tokens = j->chunk_tokens; ea.nchunks = j->nchunks;
+  ea.L = src->num_layers; ea.H = src->num_heads; ea.D = src->head_size;
+  ea.P = 2 * ea.L; ea.C = ea.H * ea.D; ea.G = (ea.C + 63) / 64; ea.TQ = (j->chunk_tokens + 3) / 4;
+  ea.sym_stride = (long long)ea.TQ * ea.C;
+  ea.blobs = j->blobs; ea.blob_stride = (long long)j->blob_stride;
+  ea.status = j->status;
+  ea.bins = j->bins;
+  ea.agg = j->b->agg; ea.sizes = j->sizes;
+  ea.dtype = lmc_math_dtype(src->dtype);
+  ea.ticket = j->b->ticket;
+  ea.chain_gran = j->chain_gran;
+  ea.vregion = j->b->vregion; ea.vstride = j->vstride;
+  return ea;
+}
+
+int lmc_encode_layer(lmc_ctx* c, lmc_layer_job* j, int32_t layer, lmc_stream_t stream) {
+  if (!c) return LMC_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!layer_job_ok(c, j) || layer != j->next_layer || layer >= j->src.num_layers) return LMC_ERR_INVALID;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  lmc_layer_bufs* b = j->b;
+  EncodeArgs ea = layer_encode_args(j);
+  const int L = ea.L;
+  if (layer == 0) {
+    // the job's first launch: behind the buffers' previous job; granules and tickets start from zero ONCE -- the later
+    // layers' look-backs read the prefixes this and every earlier layer leave
+    if (b->used) HIP_TRY(hipStreamWaitEvent(s, b->free_ev, 0));
+    HIP_TRY(hipMemsetAsync(b->agg, 0, (size_t)j->nchunks * 2 * L * j->chain_gran * 8, s));
+    HIP_TRY(hipMemsetAsync(b->ticket, 0, 64, s));
+    j->tickets_drawn = 0;
+    j->queued = true; j->last_stream = s;
+  }
+  ea.plane0 = layer; ea.plane_step = L; ea.nplanes = 2;
+  lmc_blob_header hl;
+  lmc_blob_layout((uint32_t)L, (uint32_t)j->chunk_tokens, (uint32_t)ea.H, (uint32_t)ea.D, &hl);
+  QuantArgs qa;
+  memset(&qa, 0, sizeof qa);
+  qa.src = to_addr(&j->src); qa.bins = j->bins;
+  qa.tok_begin = j->tok_begin; qa.tok_end = j->tok_end; qa.chunk_tokens = j->chunk_tokens; qa.nchunks = j->nchunks;
+  qa.P = ea.P; qa.C = ea.C; qa.TQ = ea.TQ; qa.pc_limit = j->nchunks * ea.P; qa.sym_stride = ea.sym_stride;
+  qa.sym4 = b->sym4;
+  qa.scale_base = j->blobs + hl.off_scales; qa.scale_stride = (long long)j->blob_stride;
+  qa.sizes = layer == 0 ? j->sizes : nullptr;  // 0 = "this chunk's encode did not finish" until k_layers_finish
+  qa.plane0 = layer; qa.plane_step = L; qa.nplanes = 2;
+  int rc = launch_quant<true>(qa, s, j->src.paged_kind == LMC_PAGED_SPLIT);
+  j->queued = true; j->last_stream = s;
+  if (rc) return rc;
+  const long long ngroups = (long long)j->nchunks * 2 * ea.G;
+  const unsigned nwg = (unsigned)((ngroups + 7) / 8);
+  ea.ticket_base = j->tickets_drawn;
+  hipLaunchKernelGGL((k_cdf_encode<true, true, 8, true>), dim3(nwg), dim3(64 * 8), 0, s, ea);
+  HIP_TRY(hipGetLastError());
+  j->tickets_drawn += nwg;
+  j->next_layer = layer + 1;
+  return LMC_OK;
+}
+
+int lmc_encode_layers_finish(lmc_ctx* c, lmc_layer_job* j, lmc_stream_t stream) {
+  if (!c) return LMC_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!layer_job_ok(c, j) || j->next_layer != j->src.num_layers) return LMC_ERR_INVALID;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  LayersFinishArgs fa;
+  memset(&fa, 0, sizeof fa);
+  fa.e = layer_encode_args(j);
+  fa.kv_dtype = lmc_dtype_fp8(j->src.dtype) ? (u32)j->src.dtype : 0u;
+  // the move of a chunk's V streams in pieces of 16 KiB per pass of a workgroup
+  const unsigned nx = (unsigned)std::min<long long>(64, std::max<long long>(1, j->vstride / (16 * 256 * 4)));
+  hipLaunchKernelGGL(k_layers_finish, dim3(nx, (unsigned)j->nchunks), dim3(256), 0, s, fa);
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) { g_last_hip = (int)le; return LMC_ERR_HIP; }
+  j->queued = true; j->last_stream = s;
+  layer_job_release(j);
+  return LMC_OK;
+}
+
+int lmc_encode_layers_abort(lmc_ctx* c, lmc_layer_job* j) {
+  if (!c) return LMC_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!layer_job_ok(c, j)) return LMC_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  layer_job_release(j);
   return LMC_OK;
 }
 

@@ -158,6 +158,10 @@ SYMBOLS = {
     "lmc_calculate_cdf": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lmc_encode_chunks": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_encode_chunks_split": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "lmc_encode_layers_begin": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, ctypes.POINTER(_vp)]),
+    "lmc_encode_layer": (ctypes.c_int, [_vp, _vp, _i32, _vp]),
+    "lmc_encode_layers_finish": (ctypes.c_int, [_vp, _vp, _vp]),
+    "lmc_encode_layers_abort": (ctypes.c_int, [_vp, _vp]),
     "lmc_decode_chunks": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _vp, _vp]),
     "lmc_decode_chunks_layers": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lmc_decode_chunks_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -195,6 +199,8 @@ SYMBOLS = {
 }
 
 ENCODE_PATHS = {"auto": 0, "two_kernels": 1, "fused": 2}  # LMC_ENCODE_PATH_*
+ERR_INVALID = -1      # LMC_ERR_INVALID
+NOT_LAYERWISE = 1     # LMC_NOT_LAYERWISE: lmc_encode_layers_begin found the job not eligible (no error, no job)
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -803,6 +809,19 @@ class Context:
                    chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
         return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
+    def encode_layers_begin(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
+                            blobs_ptr: int, blob_stride: int, sizes_ptr: int, status_ptr: Optional[int] = None
+                            ) -> Optional["LayerEncodeHandle"]:
+        """lmc_encode_layers_begin: the layer-wise form of encode_chunks_split -> the job's handle, or None when the job
+        is not eligible (LMC_NOT_LAYERWISE: the caller encodes in one piece).  `src` is kept alive by the handle."""
+        h = ctypes.c_void_p()
+        rc = lib().lmc_encode_layers_begin(self.handle, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
+                                           self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr, ctypes.byref(h))
+        if rc == NOT_LAYERWISE:
+            return None
+        check(rc, "lmc_encode_layers_begin")
+        return LayerEncodeHandle(self, h, src)
+
     def decode_chunks(self, blobs_ptr: int, blob_stride: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                       chunk_tokens: int, stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
         self._call("lmc_decode_chunks", dst.device, stream, blobs_ptr, blob_stride, nchunks, ctypes.byref(dst.struct),
@@ -946,6 +965,43 @@ class Context:
         if deltas is not None and not (deltas.is_cuda and deltas.dtype == torch.int32 and deltas.is_contiguous()
                                        and (ntok is None or deltas.numel() == ntok)):
             raise ValueError(f"deltas must be a contiguous device int32 tensor of ntok = {ntok} entries")
+
+
+class LayerEncodeHandle:
+    """A live lmc_layer_job: encode_layer(l) for l = 0 .. L-1 in order, then finish() -- or abort() at any point.  The raw
+    return codes are available (`*_rc`) for callers that test the refusals; the plain methods raise NativeError."""
+
+    def __init__(self, ctx: "Context", handle, src: KVLayout):
+        self.ctx, self.handle, self.src = ctx, handle, src
+
+    def encode_layer_rc(self, layer: int, stream: Optional[int] = None) -> int:
+        st = current_stream_ptr(self.src.device) if stream is None else stream
+        return lib().lmc_encode_layer(self.ctx.handle, self.handle, layer, st)
+
+    def encode_layer(self, layer: int, stream: Optional[int] = None) -> None:
+        check(self.encode_layer_rc(layer, stream), "lmc_encode_layer")
+
+    def finish_rc(self, stream: Optional[int] = None) -> int:
+        st = current_stream_ptr(self.src.device) if stream is None else stream
+        rc = lib().lmc_encode_layers_finish(self.ctx.handle, self.handle, st)
+        if rc == 0:
+            self.handle = None  # the job is gone
+        return rc
+
+    def finish(self, stream: Optional[int] = None) -> None:
+        check(self.finish_rc(stream), "lmc_encode_layers_finish")
+
+    def abort(self) -> None:
+        if self.handle is not None:
+            h, self.handle = self.handle, None
+            check(lib().lmc_encode_layers_abort(self.ctx.handle, h), "lmc_encode_layers_abort")
+
+    def __del__(self):
+        try:
+            if self.handle is not None and self.ctx.handle and not sys.is_finalizing():
+                self.abort()
+        except Exception:
+            pass
 
 
 def describe_status(st: int) -> str:

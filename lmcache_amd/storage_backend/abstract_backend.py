@@ -51,6 +51,12 @@ class LMCBackendInterface(abc.ABC):
         for key in keys:
             yield self.get(key) if self.contains(key) else None
 
+    def begin_put_kv_layers(self, keys, src, fmt: str, tok_begin: int, tok_end: int, chunk_tokens: int):
+        """The layer-wise form of put_kv_range (LMCLocalBackend's two CacheGen modes have one): an object with
+        encode_layer(l), layer_event(l) and finish(blocking), or None -- this backend has no layer-wise path and the
+        engine stores in one piece once every layer is there.  The default: None."""
+        return None
+
     @abc.abstractmethod
     def close(self):
         pass

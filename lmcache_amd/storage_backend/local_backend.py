@@ -151,6 +151,36 @@ def _fmt_of_chunk(t: torch.Tensor, fmt_hint: Optional[str]) -> str:
     return fmt_hint or "vllm"
 
 
+class LayerwisePut:
+    """One begin_put_kv_layers() in flight."""
+
+    def __init__(self, backend: "LMCLocalBackend", keys, job, shapes, dtype):
+        self.backend, self.keys, self.job, self.shapes, self.dtype = backend, keys, job, shapes, dtype
+
+    def encode_layer(self, layer: int) -> None:
+        self.job.encode_layer(layer)
+
+    def layer_event(self, layer: int):
+        """Behind it layer `layer`'s KV has been read (torch.cuda.Event)."""
+        return self.job.layer_events[layer]
+
+    def finish(self, blocking: bool = True) -> int:
+        """The last launch behind the last layer, then the tier's copies and the publishing: here, or -- blocking=False --
+        on the backend's worker thread (drain() waits for it).  -> chunks stored."""
+        b, job = self.backend, self.job
+        with torch.cuda.device(job.arena.device):
+            job.finish()
+        if blocking:
+            b._finish_layers(self.keys, job, self.shapes, self.dtype)
+        else:
+            b.put_queue.put(lambda: b._finish_layers(self.keys, job, self.shapes, self.dtype))
+        return len(self.keys)
+
+    def abort(self) -> None:
+        self.job.abort()
+        self.backend._codec().release_layer_stream(self.job)
+
+
 class LMCLocalBackend(LMCBackendInterface):
     supports_kv_layout = True
 
@@ -858,6 +888,56 @@ class LMCLocalBackend(LMCBackendInterface):
 
         self.put_queue.put(finish)
         return n
+
+    def begin_put_kv_layers(self, keys: Sequence[CacheEngineKey], src: native.KVLayout, fmt: str, tok_begin: int,
+                            tok_end: int, chunk_tokens: int) -> Optional["LayerwisePut"]:
+        """put_kv_range whose encode is issued layer by layer, while the forward pass that writes `src` is still running:
+        -> a LayerwisePut (encode_layer(l) for l = 0 .. L-1, layer_event(l), finish(blocking)), or None -- the caller
+        then stores in one piece with put_kv_range once every layer is there.  None is returned by the raw tiers (their
+        gather IS the store) and for a job the layer-wise encoder does not take (CacheGenDeviceCodec.encode_layers: a
+        layout it cannot read in place, chunks outside 2 .. 256 tokens, planes of more than 1024 channels).
+        Replaces the store of the reference behind the forward pass (cache_engine.py:268-282) and the connector's gather
+        of every layer in front of it (docs/source/developer_tutorial/LLM_Engine.rst:91-122).
+        After finish() the backend holds what put_kv_range leaves for the same arguments -- the same keys, the same blob
+        bytes; on the pinned tier the same pack (built from the finished blobs by the repack leg demotion uses,
+        lmc_pack_blobs + DMA, so a later layer-wise retrieve is still cut by layers); budgets, LRU groups and publishing
+        are put_kv_range's.  Nothing is published before finish()."""
+        n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
+        assert n == len(keys), "one key per chunk"
+        if n == 0 or self.mode not in ("cachegen", "hbm-cachegen"):
+            return None
+        L, H, D = src.L, src.H, src.D
+        with torch.cuda.device(src.device):
+            job = self._codec().encode_layers(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L))
+        if job is None:
+            return None
+        shapes = [_chunk_shape(fmt, L, min(chunk_tokens, tok_end - (tok_begin + i * chunk_tokens)), H, D) for i in range(n)]
+        return LayerwisePut(self, list(keys), job, shapes, _coded_dtype(fmt, native.torch_dtype(src.dtype)))
+
+    def _finish_layers(self, keys: Sequence[CacheEngineKey], job, shapes, dtype) -> None:
+        """A finished layer-wise encode job -> the tier, as put_kv_range files its own."""
+        codec = self._codec()
+        try:
+            if not (self.pack_stores and job.nchunks >= 2):
+                self._finish_encoded(keys, job, shapes, dtype)
+                return
+            # the pinned tier's pack, from the finished blobs
+            L, H, D, cs = job.geometry
+            tok = 2 if (self.fmt or "vllm") == "vllm" else 3
+            ntokens = sum(shp[tok] for shp in shapes)
+            sizes = codec.sizes_of(job)
+            blobs = [job.arena[i * job.stride:i * job.stride + sizes[i]] for i in range(job.nchunks)]
+
+            def finish():
+                with torch.cuda.device(self._cuda_device):
+                    pack = codec.demote_blobs(blobs, (L, H, D), cs, ntokens, self.host_arena, ready=[job.done])
+                return [_PackChunk(pack, i, shp, dtype) for i, shp in enumerate(shapes)], r16(pack.blob.nbytes), None
+
+            need = 0 if self._tiers.budget["pinned"] is None else r16(codec.demoted_bytes(sizes, (L, H, D), cs, ntokens))
+            self._store("pinned", need, finish, keys, geometry=(L, H, D), chunk_tokens=cs, ntokens=ntokens)
+            job.offload_issued = True
+        finally:
+            codec.release_layer_stream(job)
 
     def get_kv_range(self, keys: Sequence[CacheEngineKey], dst: native.KVLayout, fmt: str, dst_tok0: int,
                      chunk_tokens: int, layers_per_launch: Optional[int] = None, jobs_out: Optional[list] = None,

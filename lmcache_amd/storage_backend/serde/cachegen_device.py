@@ -340,6 +340,57 @@ class EncodeJob(Job):
         return super().retire()
 
 
+class LayerwiseEncodeJob(EncodeJob):
+    """An encode issued layer by layer (CacheGenDeviceCodec.encode_layers; lmc_encode_layers_*, csrc/k_layers.h):
+    encode_layer(l) for l = 0 .. L-1 in order, then finish().  After finish() it IS an EncodeJob -- arena at blob_bound
+    stride, pinned size words, its own status word, `done` behind its last kernel -- whose blobs are byte for byte those
+    of CacheGenDeviceCodec.encode() for the same source, range, chunk length and bins: sizes_of, offload and
+    keep_on_device take it unchanged.  The coder never runs on the caller's stream: every launch goes to the job's side
+    stream, behind an event recorded on the caller's current stream in encode_layer.
+    layer_events[l] (after encode_layer(l)): behind it layer l's KV has been read -- the cache may be overwritten."""
+
+    def __init__(self, handle: native.LayerEncodeHandle, stream, nlayers: int, **kw):
+        super().__init__(**kw)
+        self.handle, self.stream, self.nlayers = handle, stream, nlayers
+        self.layer_events: List[torch.cuda.Event] = []
+        self.finished = False
+
+    def encode_layer(self, layer: int) -> None:
+        """Layer `layer`'s KV, as the caller's current stream has written it, is quantised and coded on the side stream."""
+        dev = self.arena.device
+        with torch.cuda.device(dev):
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(dev))
+            self.stream.wait_event(ready)
+            self.handle.encode_layer(layer, self.stream.cuda_stream)  # (raises, with nothing queued, out of order)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+            self.layer_events.append(ev)
+
+    def finish(self) -> "LayerwiseEncodeJob":
+        """k_layers_finish behind the last layer; `done` is recorded behind it.  No host wait."""
+        with torch.cuda.device(self.arena.device):
+            self.handle.finish(self.stream.cuda_stream)
+            self.done.record(self.stream)
+        self.finished = True
+        return self
+
+    def abort(self) -> None:
+        """Give the job up: the C side's buffers go back behind what was queued; the job's words once that has run."""
+        if not self.finished:
+            self.handle.abort()
+            self.done.record(self.stream)
+            self.finished = True
+
+    def __del__(self):
+        try:
+            if not getattr(self, "finished", True):
+                self.abort()
+        except Exception:
+            pass
+        super().__del__()
+
+
 @dataclass
 class HostPack:
     """The blobs of one store call in pinned host DRAM, laid out plane-major (include/lmc_format.h, "pack" v3)."""
@@ -583,6 +634,7 @@ class CacheGenDeviceCodec:
         # plane ranges a pack's encode is launched in (store_pack): LMCACHE_AMD_PACK_PARTS=1 is the round-5 behaviour
         # (the whole encode, then the pack, then its copies), for A/B
         self.pack_parts = max(1, min(16, int(os.environ.get("LMCACHE_AMD_PACK_PARTS", "8"))))
+        self._layer_streams: List[torch.cuda.Stream] = []    # side streams of finished layer-wise encode jobs, for the next ones
         self._warned_wide_split = False                      # direct store of an NHDB cache with planes the split quantiser does not read
         self._same_blobs: dict = {}                          # id(caller's list) -> (the list, its blobs' address tuple, largest blob)
         self._table_cache: dict = {}                         # blob-address tuple -> (device table, upload stream)
@@ -656,6 +708,47 @@ class CacheGenDeviceCodec:
             if arena is self._enc_arena:
                 self._shared_job = job
             return job
+
+    def encode_layers(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int,
+                      bins: Sequence[int]) -> Optional[LayerwiseEncodeJob]:
+        """encode() issued layer by layer -> a LayerwiseEncodeJob (encode_layer(l), finish()), or None when the job is
+        not eligible and the caller encodes in one piece: a source the encoders do not read in place (_readable would
+        stage it -- there is nothing to stage before the layers exist), a chunk, the ragged last one included, outside
+        2 .. 256 tokens, planes of more than 1024 channels (lmc_encode_layers_begin).  Nothing is queued here.
+        The job has an arena of its own and a side stream: it spans a forward pass and must not hold the shared encode
+        arena, nor the model's stream."""
+        split = src.struct.paged_kind == native.PAGED_SPLIT
+        if not (src.vector_readable() or (split and src.H * src.D <= 1024)):
+            return None
+        L, H, D = src.L, src.H, src.D
+        n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
+        stride = native.r16(native.blob_bound(L, chunk_tokens, H, D))
+        with self._lock, torch.cuda.device(self.device):
+            side = self._layer_streams.pop() if self._layer_streams else torch.cuda.Stream(device=self.device)
+            arena = torch.empty(n * stride, dtype=torch.uint8, device=self.device)
+            arena.record_stream(side)
+            loans = []
+            with self._launch(side, loans) as (st, st_ptr):
+                sizes = _borrow(loans, self._size_pool, 4 * n, 4 * max(n, 256))
+                handle = self.ctx.encode_layers_begin(src, tok_begin, tok_end, chunk_tokens, bins, arena.data_ptr(), stride,
+                                                      sizes.ptr, status_ptr=st_ptr)
+            if handle is None:  # not eligible: nothing was queued, the words go back as they came
+                self._status.read_release(st)
+                for buf, words in loans:
+                    words.give(buf)
+                self._layer_streams.append(side)
+                return None
+            done = torch.cuda.Event()
+            return LayerwiseEncodeJob(handle, side, L, nchunks=n, stride=stride, arena=arena, sizes=sizes,
+                                      geometry=(L, H, D, chunk_tokens), parts=[(0, n, done)], status_idx=st,
+                                      pool=self._status, loans=loans)
+
+    def release_layer_stream(self, job: LayerwiseEncodeJob) -> None:
+        """A finished job's side stream goes back for the next job (whose work queues behind what is left on it)."""
+        with self._lock:
+            if job.stream is not None and len(self._layer_streams) < 8:
+                self._layer_streams.append(job.stream)
+            job.stream = None
 
     @contextlib.contextmanager
     def _launch(self, stream, loans=()):
