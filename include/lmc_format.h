@@ -95,6 +95,24 @@
  *       channel's empirical entropy to within the 31 bits of final state (T < 256: plus the
  *       rounding of the scaled counts, < 0.5 % on 236-token chunks).
  * See DESIGN.md "Entropy coder" for the recurrences and their bounds.
+ *
+ *   LMC_MODEL_FIXED (2)  any T >= 1.  No entropy coder: every symbol at a fixed 4 or 5 bits -- the tier whose blobs
+ *       stay in HBM, where nothing crosses PCIe and the coder's token loop is pure cost.  Header, bins, scales, scsum and
+ *       gdir are where lmc_blob_layout puts them for every model; only model, stream_bytes, total_bytes, the directory's
+ *       values and the streams differ.  With O = ceil(T / 8), stream (p, g) -- channels 64 g .. 64 g + 63, lane = channel:
+ *         lo   u32[O][64]   lane l, oct o: byte k (0..3) = (s[8o + k] & 15) | (s[8o + 4 + k] & 15) << 4
+ *         hi   u8 [O][64]   planes with bins > 17 only ("wide"): bit j = bit 4 of s[8o + j]
+ *         tail 16 bytes     u32 check, then 12 zero bytes
+ *       s[t] = the symbol of token t of the lane's channel; tokens >= T and lanes whose channel is >= C contribute 0.
+ *       A plane with bins <= 17 ("narrow") has symbols <= 2 (bins / 2 - 1) <= 15, any other <= 30.  The lo dword is the
+ *       nibble-plane dword the quantiser writes for the coder anyway.  check = sum of (2 i + 1) * w_i mod 2^32 over the
+ *       dwords w_i of lo, then hi, in address order: the multiplier is odd, so a change of any single dword shows; it
+ *       stands where the final rANS states stand for the coded models (the scales keep scsum).  A stream's size is a
+ *       function of (bins, T) -- lmc_fixed_stream_bytes -- its allocation is its size and gdir = {beg, beg + size} with
+ *       beg the running sum: nothing depends on the data.  lmc_fixed_blob_bytes <= lmc_blob_bound for every geometry
+ *       (tests/test_fixed_model_host.py), so the arenas sized for the coded models hold these blobs too.
+ *       The rANS encoders never choose this model and the rANS decoders refuse it (lmc_model_for / lmc_model_valid are
+ *       about the coded models); lmc_encode_chunks_fixed writes it and lmc_decode_chunks_fixed_schedule reads it.
  */
 #ifndef LMC_FORMAT_H
 #define LMC_FORMAT_H
@@ -125,6 +143,9 @@ extern "C" {
 
 #define LMC_MODEL_CDF16 0u
 #define LMC_MODEL_COUNTS 1u
+#define LMC_MODEL_FIXED 2u          /* fixed-width symbols, no entropy coder (the HBM-resident tier) */
+#define LMC_FIXED_NARROW_BINS 17u  /* planes with at most this many bins store 4 bits per symbol, the others 5 */
+#define LMC_FIXED_TAIL_BYTES 16u   /* u32 check word + 12 zero bytes behind every fixed-width stream */
 #define LMC_COUNTS_T 256u          /* longest chunk the counts model codes (its probabilities are out of 2^8) ... */
 #define LMC_COUNTS_T_MIN 2u        /* ... and the shortest (T = 1 has no 32-bit reciprocal; it stays on CDF16) */
 #define LMC_COUNTS_BITS 9u         /* its probabilities are 2 * count out of 2^9 */
@@ -300,6 +321,24 @@ static inline void lmc_blob_layout(uint32_t L, uint32_t T, uint32_t H, uint32_t 
   h->off_scsum = h->off_scales + lmc_r16(2u * P * T);
   h->off_gdir = h->off_scsum + lmc_r16(4u * P);
   h->off_streams = h->off_gdir + lmc_r16(8u * P * G);
+}
+
+/* ---- LMC_MODEL_FIXED: sizes (functions of the geometry and the bins alone) ------------------------------------ */
+/* A chunk length the fixed-width model takes (any; the header's ntokens still ends at 65535). */
+static inline int lmc_fixed_valid(uint32_t T) { return T >= 1u && T <= 65535u; }
+/* Bytes of one group stream of a plane with `bins` bins in a chunk of T tokens: lo (256 per oct), hi (64 per oct, wide
+ * planes), tail. */
+static inline uint32_t lmc_fixed_stream_bytes(uint32_t bins, uint32_t T) {
+  const uint32_t O = (T + 7u) / 8u;
+  return (bins <= LMC_FIXED_NARROW_BINS ? 256u : 320u) * O + LMC_FIXED_TAIL_BYTES;
+}
+/* Exact size of a fixed-width blob; bins: the per-plane bins [2 L]. */
+static inline uint64_t lmc_fixed_blob_bytes(uint32_t L, uint32_t T, uint32_t H, uint32_t D, const uint8_t* bins) {
+  lmc_blob_header h;
+  lmc_blob_layout(L, T, H, D, &h);
+  uint64_t n = h.off_streams;
+  for (uint32_t p = 0; p < h.nplanes; p++) n += (uint64_t)h.ngroups * lmc_fixed_stream_bytes(bins[p], T);
+  return n;
 }
 
 /* Capacity (bytes) reserved for one group stream: the largest head, and for words and states -- proof that

@@ -187,7 +187,8 @@ int lmc_ctx_set_encode_path(lmc_ctx* ctx, int path);
  * caller's stream.  lmc_ctx_profile_read (after the caller has synchronised
  * that stream) returns the durations in ms of the last profiled call, in
  * launch order (encode: k_encode_fused, or k_quantize, k_cdf_encode [which also compacts the streams
- * into the blob]; decode: k_decode) and the number of entries written (<= cap). */
+ * into the blob]; decode: k_decode; lmc_encode_chunks_fixed: k_fixed_encode; lmc_decode_chunks_fixed_schedule:
+ * k_fixed_decode of the last range) and the number of entries written (<= cap). */
 int lmc_ctx_profile(lmc_ctx* ctx, int enable);
 int lmc_ctx_profile_read(lmc_ctx* ctx, float* ms_out, int cap);
 
@@ -243,6 +244,18 @@ int lmc_encode_chunks(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin,
  * nothing is launched.  Any other source: exactly lmc_encode_chunks.
  */
 int lmc_encode_chunks_split(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
+                            int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
+                            uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
+
+/*
+ * lmc_encode_chunks with the blobs written in the FIXED-WIDTH model (lmc_format.h: LMC_MODEL_FIXED; additive in ABI 6;
+ * csrc/k_fixed.h): the same quantisation, scales and checksums, every symbol at 4 or 5 bits and no entropy coder -- for
+ * blobs that stay in HBM, where the coder's bytes buy nothing.  One launch, one pass over the source.  Arguments and
+ * refusals are lmc_encode_chunks' (an LMC_PAGED_SPLIT source is LMC_ERR_INVALID: gather it first), and so is
+ * blob_stride >= lmc_blob_bound: a fixed-width blob never outgrows the coded models' slot.  fp8 KV is LMC_ERR_INVALID.
+ * sizes[i] receives lmc_fixed_blob_bytes of chunk i, a function of the geometry and the bins alone.
+ */
+int lmc_encode_chunks_fixed(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
                             int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
                             uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
 
@@ -362,6 +375,22 @@ int lmc_decode_chunks_schedule_post(lmc_ctx* ctx, const void* const* blob_ptrs, 
                                     const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
                                     const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
                                     lmc_stream_t stream, const lmc_range_post* post);
+
+/*
+ * lmc_decode_chunks_schedule_post for LMC_MODEL_FIXED blobs (k_fixed_decode; one body with it, only the launch differs).
+ * post NULL is the plain schedule; one range that ends at num_layers is the one-piece decode.  Every byte a section's
+ * address depends on is checked before the section is read, and nothing is read past max_blob_bytes: magic, version,
+ * geometry against `dst`, model == LMC_MODEL_FIXED, the totals and the directory entry of every stream decoded against
+ * the layout the bins give (LMC_STATUS_BAD_HEADER -- a coded blob handed to this call is one, as a fixed-width blob is to
+ * the coded models' decoders).  A stream whose check word does not match is LMC_STATUS_BAD_STREAM, scales that do not
+ * match scsum LMC_STATUS_BAD_SCALES; the destination is undefined then, as for the coded models.
+ * `dst` is 16-bit rows (LMC_PAGED_ROWS, with or without a slot mapping): an LMC_PAGED_SPLIT or fp8 destination is
+ * LMC_ERR_INVALID with nothing queued -- an "NHDB" cache is filled through a staged chunk and post->scatter_dst.
+ */
+int lmc_decode_chunks_fixed_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                     const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                     const int32_t* layer_ends_h, const lmc_event_t* events_h, const lmc_range_post* post,
+                                     uint32_t* job_status, lmc_stream_t stream);
 
 /* Entropy-decode only (debug / parity): blob -> sym_out int8 [P][T][C].
  * Stands where torchac_cuda.decode_fast_prefsum stands (cachegen_decoder.py:65-66). */
@@ -582,8 +611,13 @@ int lmc_event_elapsed_ms(lmc_event_t start, lmc_event_t stop, float* ms);
 /* Host-side blob header check/parse (no GPU).  Stands where
  * CacheGenEncoderOutput.from_bytes is used to inspect a blob
  * (tests/test_serde.py:60-62).  A kv_dtype other than 0, LMC_DTYPE_FP8_E4M3 or LMC_DTYPE_FP8_E5M2, or an fp8 kv_dtype on a
- * blob whose dtype is not bf16, is refused like any other damaged header. */
+ * blob whose dtype is not bf16, is refused like any other damaged header.  Only the 128 header bytes are read (callers
+ * hand over the header of a blob that lies in device memory, with its length), so of an LMC_MODEL_FIXED blob this call
+ * checks what the header alone can say (the totals against each other and against the smallest and largest layout);
+ * lmc_fixed_blob_info takes the WHOLE blob (nbytes readable bytes), accepts LMC_MODEL_FIXED only, and also holds the
+ * bins, total_bytes and every directory entry against the layout the bins give (lmc_fixed_stream_bytes). */
 int lmc_blob_info(const void* blob_h, size_t nbytes, lmc_blob_header* out);
+int lmc_fixed_blob_info(const void* blob_h, size_t nbytes, lmc_blob_header* out);
 
 #ifdef __cplusplus
 }

@@ -335,6 +335,7 @@ class LMCacheEngine:
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
+        direct = self._direct_retrieve(direct, layout)
         if rope is not None:
             if direct and layout == "NHDB":
                 raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
@@ -367,6 +368,17 @@ class LMCacheEngine:
                 if staged:
                     ctx.copy_kv(rows, 0, got, dst, 0)
         return ret_mask
+
+    def _direct_retrieve(self, direct: bool, layout: str) -> bool:
+        """`direct` as the backend can honour it: the fixed-width HBM tier (local_serde="cachegen-fixed") decodes into rows
+        only, so a direct retrieve into an "NHDB" cache takes the staged path there (logged once)."""
+        if direct and layout == "NHDB" and getattr(self.engine_, "model", None) == "fixed":
+            if not getattr(self, "_fixed_direct_logged", False):
+                self._fixed_direct_logged = True
+                logger.info("retrieve_into_paged(direct=True): the fixed-width tier decodes into rows; an \"NHDB\" cache is "
+                            "filled through the staged chunk (logged once)")
+            return False
+        return direct
 
     @staticmethod
     def _check_rope(rope: RopeShift, kv_caches, layout: str, ntokens: int) -> None:
@@ -463,6 +475,7 @@ class LMCacheEngine:
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
+        direct = self._direct_retrieve(direct, layout)
         if rope is not None:
             if direct and layout == "NHDB":
                 raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "

@@ -1,0 +1,311 @@
+// k_fixed.h -- LMC_MODEL_FIXED (include/lmc_format.h): the CacheGen quantisation with every symbol stored at a fixed 4 or
+// 5 bits and no entropy coder.  For the tier whose blobs stay in HBM: nothing crosses PCIe there, so the bytes the coder
+// saves buy nothing and its token loop is the whole cost.  Quantiser, scales, dequantisation and casts are the coded
+// models': a chunk decodes to the same bits whichever model stored it.
+//
+// k_fixed_encode -- one pass, source -> blob; the symbols never see a workspace.  A WORKGROUP OWNS A PLANE of a chunk: its
+// waves walk the plane's row octs with k_quantize.h's quantize_task (same loads, row max, quant_z2 / quant_fast /
+// quant_special, special-row rule), which hands each lane the eight nibble dwords of its 8 channels x 8 tokens in
+// registers (FixedSink) instead of storing them to the workspace: two 16-byte stores into `lo`, and for a wide plane one
+// 8-byte store into `hi`.  Why this mapping and not one atomic per (task, group): the check word of a stream and the
+// plane's scsum are sums over the whole plane; with the plane in one workgroup they are summed on chip (LDS adds, integer:
+// order-free, so deterministic) and stored once -- no pre-zeroed words, no memset dispatch in front, no global atomics
+// (2 M single-lane atomics per 16 k context otherwise; cdna_hip_programming.md guideline 12: sum on chip what shares a
+// destination).  The price is a grid of chunks x planes workgroups, which a job of a few chunks does not fill, and
+// workgroups that live as long as a plane takes (FIXED_ENC_WAVES below).
+// The workgroup of plane 0 also writes header, bins and pads; every workgroup its plane's directory entries and scsum.
+//
+// k_fixed_decode -- a wave takes a stream and walks it in tiles of four octs (32 tokens): 16-byte loads of `lo` (lane =
+// 4 channels of one oct) and a dword of `hi`, staged in 1.3 KiB of LDS and read back transposed -- lane = (8 channels,
+// one token) -- so that every lane dequantises one 16-byte row vector per oct: t = ((q - C) / C) * max1 from k_decode.h's
+// LUT construction, one RNE cast (fp16: two roundings, as there), one 16-byte store (element stores where the
+// destination's rows are not vector-addressable).  The next tile's loads are in flight while this one is stored.  The
+// check word is summed over exactly the dwords the wave loaded and compared at the end (BAD_STREAM), the plane's first
+// wave checks scsum (BAD_SCALES); everything a section's address depends on is validated before the section is read
+// (BAD_HEADER).  Block-ordered paged destinations take the same per-token path: a token's row is one slot_mapping load
+// per lane and oct (k_decode.h's eight-row blocks were built around its scalar stores and are not needed here).
+#pragma once
+#include "k_encode.h"
+#include "k_quantize.h"
+#include "k_decode.h"
+
+__device__ __forceinline__ u32 fixed_stream_bytes_dev(u32 bins, u32 O) {  // lmc_fixed_stream_bytes
+  return (bins <= LMC_FIXED_NARROW_BINS ? 256u : 320u) * O + LMC_FIXED_TAIL_BYTES;
+}
+
+struct FixedEncArgs {
+  KvAddr src;
+  EncodeArgs e;  // tok_begin .. nchunks, P, C, G, blobs, blob_stride, bins, sizes, L, H, D, dtype
+};
+
+// What quantize_task hands over (k_quantize.h, SINK).  o0 / o1: byte r of dword e = symbol of (token 8 oct + r / + 4 + r,
+// channel c0 + e).
+typedef __attribute__((address_space(3))) u32 LdsU32;
+struct FixedSink {
+  u8* plane_streams;  // stream (p, 0)
+  LdsU32* chk;        // LDS [NG]: the streams' check sums
+  u32 ssize, O, NG, oct_i, scs;
+  bool wide;
+  __device__ __forceinline__ void scale(u32 t, u32 bits) { scs += (t + 1u) * (bits + 1u); }  // lmc_scale_checksum_term
+  __device__ __forceinline__ void oct_store(int c0, const u32 (&o0)[8], const u32 (&o1)[8]) {
+    if ((u32)c0 >= 64u * NG) return;  // (runs past C inside the last group store their zeros)
+    const u32 g = (u32)c0 >> 6, l0 = (u32)c0 & 63u;
+    u8* const sb = plane_streams + (size_t)g * ssize;
+    const u32 i0 = oct_i * 64u + l0;
+    u32 w[8], sum = 0;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      w[e] = (o0[e] & 0x0f0f0f0fu) | ((o1[e] & 0x0f0f0f0fu) << 4);
+      sum += (2u * (i0 + (u32)e) + 1u) * w[e];
+    }
+    LMC_GLOBAL u32x4_t* const lo = (LMC_GLOBAL u32x4_t*)(sb + 4u * (size_t)i0);
+    lo[0] = u32x4_t{w[0], w[1], w[2], w[3]};
+    lo[1] = u32x4_t{w[4], w[5], w[6], w[7]};
+    if (wide) {
+      // bit 4 of the four bytes of a dword -> four adjacent bits (the products' bit positions are all distinct: no carries)
+      u32 h[2] = {0u, 0u};
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        const u32 b = ((((o0[e] >> 4) & 0x01010101u) * 0x01020408u) >> 24) | (((((o1[e] >> 4) & 0x01010101u) * 0x01020408u) >> 24) << 4);
+        h[e >> 2] |= b << (8 * (e & 3));
+      }
+      const u32 j0 = 64u * O + oct_i * 16u + (l0 >> 2);
+      sum += (2u * j0 + 1u) * h[0] + (2u * j0 + 3u) * h[1];
+      *(LMC_GLOBAL u32x2_t*)(sb + 256u * (size_t)O + oct_i * 64u + l0) = u32x2_t{h[0], h[1]};
+    }
+    __hip_atomic_fetch_add(chk + g, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // ds_add_u32
+  }
+  __device__ __forceinline__ void oct(int c0, const u32 (&o0)[8], const u32 (&o1)[8]) { oct_store(c0, o0, o1); }
+};
+
+// grid = (P, nchunks), FIXED_ENC_WAVES waves.  G lanes per row oct, NITER channel runs per lane, SPLIT waves per oct of
+// a plane of more than 1024 channels: k_quantize's workspace instances.
+#ifndef FIXED_ENC_WAVES
+#define FIXED_ENC_WAVES 8  // 8 waves walk a 256-token plane in 4 passes: measured against 4 waves (8 passes, workgroups that
+                           // live twice as long) on a 16 k Llama-3-8B context, same box, alternating: 0.557 against 0.614 ms
+#endif
+template <int G, int NITER, int DT, int SPLIT>
+__global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncArgs a) {
+  constexpr int NW = FIXED_ENC_WAVES;
+  static_assert(SPLIT == 1 || (G == LMC_WAVE && NITER == 2 && (SPLIT == 2 || SPLIT == 4)), "split tasks: whole waves");
+  constexpr int RPW = LMC_WAVE / G;
+  constexpr int PER_PASS = SPLIT > 1 ? NW / SPLIT : NW * RPW;  // row octs a workgroup takes at a time
+  __shared__ u32 xmax[SPLIT > 1 ? (NW / SPLIT) * 8 * SPLIT : 1];
+  __shared__ u32 chk[LMC_MAX_CHANNELS / 64];
+  __shared__ u32 scs_all;
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int sub = lane / G, sl = lane % G;
+  const int p = (int)blockIdx.x, chunk = (int)blockIdx.y;
+  const EncodeArgs& e = a.e;
+  const int tok0 = e.tok_begin + chunk * e.chunk_tokens;
+  const int Tc = min(e.chunk_tokens, e.tok_end - tok0);
+  const u32 O = ((u32)Tc + 7u) >> 3, NG = (u32)e.G;
+  const int bins = (int)e.bins.b[p];
+  const float maxf = (float)(bins / 2 - 1);
+  u32 beg = 0, total = 0;  // this plane's first stream, the streams section (wave-uniform: scalar code)
+  for (int q = 0; q < e.P; q++) {
+    const u32 sz = NG * fixed_stream_bytes_dev((u32)e.bins.b[q], O);
+    if (q < p) beg += sz;
+    total += sz;
+  }
+  const u32 ssize = fixed_stream_bytes_dev((u32)bins, O);
+  const BlobOff bo = lmc_blob_off((u32)e.P, (u32)Tc, NG);
+  u8* const blob = e.blobs + (long long)chunk * e.blob_stride;
+  if (tid < LMC_MAX_CHANNELS / 64) chk[tid] = 0u;
+  if (tid == 0) scs_all = 0u;
+  __syncthreads();
+
+  FixedSink sink;
+  sink.plane_streams = blob + bo.streams + beg;
+  sink.chk = (LdsU32*)chk;
+  sink.ssize = ssize; sink.O = O; sink.NG = NG; sink.oct_i = 0u; sink.scs = 0u;
+  sink.wide = !lmc_sym_nibbles(bins);
+  const int slice = SPLIT > 1 ? wave % SPLIT : 0;
+  u32* const xm = xmax + (SPLIT > 1 ? (wave / SPLIT) * 8 * SPLIT : 0);
+  const u32 npass = (O + PER_PASS - 1u) / PER_PASS;  // the same for every wave: the split tasks meet at barriers
+  for (u32 pass = 0; pass < npass; pass++) {
+    int oct = SPLIT > 1 ? (int)pass * PER_PASS + wave / SPLIT : ((int)pass * NW + wave) * RPW + sub;
+    const bool ovalid = (u32)oct < O;
+    if (!ovalid) oct = 0;
+    sink.oct_i = (u32)oct;
+    u16* const scale_out = reinterpret_cast<u16*>(blob + bo.scales) + ((long long)p * Tc + oct * 8);
+    if (lmc_sym_nibbles(bins))
+      quantize_task<G, NITER, DT, true, true, 8, 2, SPLIT, false, false, FixedSink>(a.src, p, tok0, Tc, oct * 8, ovalid, true, e.C, maxf,
+                                                                                   nullptr, nullptr, scale_out, sl, slice, xm, 0u, 0, &sink);
+    else
+      quantize_task<G, NITER, DT, true, false, 8, 2, SPLIT, false, false, FixedSink>(a.src, p, tok0, Tc, oct * 8, ovalid, true, e.C, maxf,
+                                                                                    nullptr, nullptr, scale_out, sl, slice, xm, 0u, 0, &sink);
+    if constexpr (SPLIT > 1) __syncthreads();  // the next pass writes the exchange slots this one has read
+  }
+  if (sink.scs) __hip_atomic_fetch_add((LdsU32*)&scs_all, sink.scs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __syncthreads();
+  if ((u32)tid < NG) {  // tails and directory entries of the plane's streams
+    u8* const sb = sink.plane_streams + (size_t)tid * ssize;
+    *(LMC_GLOBAL u32x4_t*)(sb + ssize - LMC_FIXED_TAIL_BYTES) = u32x4_t{chk[tid], 0u, 0u, 0u};
+    const u32 b0 = beg + (u32)tid * ssize;
+    *(LMC_GLOBAL u32x2_t*)(blob + bo.gdir + 8u * ((u32)p * NG + (u32)tid)) = u32x2_t{b0, b0 + ssize};
+  }
+  if (tid == 0) reinterpret_cast<u32*>(blob + bo.scsum)[p] = scs_all;
+  if (p == 0 && wave == NW - 1) {  // (the last wave: not the one that stores the tails)
+    write_blob_static(blob, bo, e, (u32)Tc, total, lane);
+    if (lane == 22) reinterpret_cast<u32*>(blob)[22] = LMC_MODEL_FIXED;  // (the lane that wrote the coded models' word)
+    if (lane == 0 && e.sizes) e.sizes[chunk] = bo.streams + total;
+  }
+}
+
+struct FixedDecArgs {
+  DecodeArgs d;
+  int vec;  // the destination's rows take 16-byte stores of 8 channels (what the encoders ask of a source)
+};
+
+#define FIXED_DEC_WAVES 4
+#define FIXED_DEC_WAVE_DWORDS (256 + 64 + 32 + 32)  // lo tile | hi tile | scales of the tile's tokens | LUT
+
+template <int DT_OUT, int KIND>
+__global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecArgs fa) {
+  static_assert(!lmc_dtype_fp8(DT_OUT) && KIND != DEC_PAGED_SPLIT, "16-bit rows");
+  __shared__ __attribute__((aligned(16))) u32 lds_all[FIXED_DEC_WAVES * FIXED_DEC_WAVE_DWORDS];
+  const DecodeArgs& a = fa.d;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const u32 gid = blockIdx.x * (u32)FIXED_DEC_WAVES + (u32)wave;
+  const int n = 2 * a.layer_count * a.G;  // streams of a chunk in this launch
+  if (gid >= (u32)a.nchunks * (u32)n) return;
+  u32* const lo_t = lds_all + wave * FIXED_DEC_WAVE_DWORDS;
+  u32* const hi_t = lo_t + 256;
+  float* const sc_t = reinterpret_cast<float*>(hi_t + 64);
+  float* const lut = sc_t + 32;
+  const int chunk = (int)(gid / (u32)n);
+  const int r = (int)(gid - (u32)chunk * (u32)n);
+  const int pidx = r / a.G, g = r - pidx * a.G;
+  const int p = pidx < a.layer_count ? a.layer_begin + pidx : (a.P >> 1) + a.layer_begin + pidx - a.layer_count;
+  const u8* const blob = a.blob_ptrs ? (const u8*)uniform_ptr(a.blob_ptrs[chunk]) : a.blobs + (long long)chunk * a.blob_stride;
+  auto fail = [&](u32 bit) { if (lane == 0) atomicOr(a.status, bit); };
+
+  // ---- header (the host has seen to it that 128 bytes may be read) -----------------------------------------------------
+  const u32 hv = ((const LMC_GLOBAL u32*)blob)[lane & 31];
+  auto hdw = [&](int i) { return (u32)__builtin_amdgcn_readlane((int)hv, i); };
+  const u32 T = hdw(4), src_dtype = hdw(2);
+  const BlobOff bo = lmc_blob_off((u32)a.P, T, (u32)a.G);
+  if (hdw(0) != LMC_BLOB_MAGIC || (hdw(1) & 0xffffu) != LMC_BLOB_VERSION || hdw(7) != (u32)a.C || T == 0u || T > 65535u ||
+      T > (u32)a.chunk_tokens || hdw(8) != (u32)a.P || hdw(22) != LMC_MODEL_FIXED || hdw(15) != bo.streams ||
+      (src_dtype != (u32)LMC_DTYPE_BF16 && src_dtype != (u32)LMC_DTYPE_FP16) ||
+      (unsigned long long)hdw(15) + (unsigned long long)hdw(16) != (unsigned long long)hdw(17) ||
+      (unsigned long long)hdw(17) > (unsigned long long)a.blob_stride) {
+    return fail(LMC_ST_BAD_HEADER);
+  }
+  // ---- the layout the bins say (they lie in front of off_streams <= total_bytes <= the blob's room) -------------------
+  const u32 O = (T + 7u) >> 3;
+  u32 mine = 0, before = 0;
+  bool bad = false;
+  for (int q = lane; q < a.P; q += 64) {
+    const u32 b = (u32)((const LMC_GLOBAL u8*)blob)[LMC_HEADER_BYTES + q];
+    bad = bad || b < 4u || b > (u32)LMC_MAX_BINS;
+    const u32 sz = (u32)a.G * fixed_stream_bytes_dev(b, O);
+    mine += sz;
+    if (q < p) before += sz;
+  }
+  const u32 total = wave_sum_u32(mine);
+  const u32 pbeg = wave_sum_u32(before);
+  const u32 bins_p = (u32)__builtin_amdgcn_readfirstlane((int)(u32)((const LMC_GLOBAL u8*)blob)[LMC_HEADER_BYTES + p]);
+  const u32 ssize = fixed_stream_bytes_dev(bins_p, O);
+  const u32 beg = pbeg + (u32)g * ssize;
+  const u32x2_t gd = *(const LMC_GLOBAL u32x2_t*)(blob + bo.gdir + 8u * (u32)(p * a.G + g));
+  if (__ballot(bad) != 0ull || total != hdw(16) || (u32)__builtin_amdgcn_readfirstlane((int)gd.x) != beg ||
+      (u32)__builtin_amdgcn_readfirstlane((int)gd.y) != beg + ssize) {
+    return fail(LMC_ST_BAD_HEADER);
+  }
+  const u8* const sbytes = blob + bo.streams + beg;  // beg + ssize <= total: inside the blob
+  const bool wide = bins_p > LMC_FIXED_NARROW_BINS;  // (wave-uniform)
+
+  const u16* const scl = reinterpret_cast<const u16*>(blob + bo.scales) + (long long)p * T;
+  if (g == 0) {  // the plane's first wave checks the scales (k_decode.h: the others do not wait for the verdict)
+    const u32 want = (u32)__builtin_amdgcn_readfirstlane((int)((const LMC_GLOBAL u32*)(blob + bo.scsum))[p]);
+    if (scale_checksum(scl, T, lane) != want) return fail(LMC_ST_BAD_SCALES);
+  }
+  if (lane < 32) {  // (q - C) / C, k_decode.h's table
+    const float Cf = (float)((int)bins_p / 2 - 1);
+    const float v = (float)lane - Cf;
+    lut[lane] = v / Cf;
+  }
+
+  // ---- destination ---------------------------------------------------------------------------------------------------
+  typedef typename KvElem<DT_OUT>::T E;
+  const int cj = lane & 7, tj = lane >> 3;
+  const int c0 = g * 64 + 8 * cj;
+  const bool cok = c0 < a.C;
+  E* const pbase = const_cast<E*>(lmc_plane_base<E>(a.dst, p));
+  const int h0 = c0 / a.dst.D, d0 = c0 - h0 * a.dst.D;
+  const long long coff = (long long)h0 * a.dst.stride_head + d0;  // vec: the 8 channels are contiguous from here
+  const int tdst0 = a.dst_tok0 + chunk * a.chunk_tokens;
+  const u32 sh = 8u * ((u32)tj & 3u) + 4u * ((u32)tj >> 2);
+
+  const LMC_GLOBAL u32x4_t* const lo_g = (const LMC_GLOBAL u32x4_t*)sbytes;
+  const LMC_GLOBAL u32* const hi_g = (const LMC_GLOBAL u32*)(sbytes + 256u * (size_t)O);
+  const u32 ntile = (O + 3u) >> 2;
+  u32 acc = 0;
+  struct Tile { u32x4_t lo; u32 hi; u32 sc; };
+  auto load_tile = [&](u32 tile) -> Tile {
+    Tile t;
+    const bool in = tile * 4u + ((u32)lane >> 4) < O;
+    t.lo = in ? __builtin_nontemporal_load(lo_g + (tile * 64u + (u32)lane)) : u32x4_t{0u, 0u, 0u, 0u};
+    t.hi = (wide && in) ? __builtin_nontemporal_load(hi_g + (tile * 64u + (u32)lane)) : 0u;
+    const u32 tt = tile * 32u + (u32)lane;
+    t.sc = (lane < 32 && tt < T) ? (u32)scl[tt] : 0u;
+    return t;
+  };
+  Tile cur = load_tile(0);
+  for (u32 tile = 0; tile < ntile; tile++) {
+    {  // the check word over exactly what was loaded; then the tile goes to LDS as it lies in the stream
+      const u32 i0 = tile * 256u + 4u * (u32)lane;
+      acc += (2u * i0 + 1u) * cur.lo.x + (2u * i0 + 3u) * cur.lo.y + (2u * i0 + 5u) * cur.lo.z + (2u * i0 + 7u) * cur.lo.w;
+      acc += (2u * (64u * O + tile * 64u + (u32)lane) + 1u) * cur.hi;
+      *reinterpret_cast<u32x4_t*>(lo_t + 4 * lane) = cur.lo;
+      hi_t[lane] = cur.hi;
+      if (lane < 32) sc_t[lane] = h2f_rt(cur.sc, (int)src_dtype);
+    }
+    wave_lds_fence();
+    if (tile + 1u < ntile) cur = load_tile(tile + 1u);  // in flight while this tile is stored
+    const u32 noct = min(4u, O - tile * 4u);
+    for (u32 oo = 0; oo < noct; oo++) {
+      const u32 t = (tile * 4u + oo) * 8u + (u32)tj;
+      const int tdst = tdst0 + (int)t;
+      const bool ok = cok && t < T && tdst >= 0;
+      const u32x4_t wa = *reinterpret_cast<const u32x4_t*>(lo_t + oo * 64u + 8u * (u32)cj);
+      const u32x4_t wb = *reinterpret_cast<const u32x4_t*>(lo_t + oo * 64u + 8u * (u32)cj + 4u);
+      const u32x2_t hb = *reinterpret_cast<const u32x2_t*>(hi_t + oo * 16u + 2u * (u32)cj);
+      const float scale = sc_t[oo * 8u + (u32)tj];
+      const u32 w[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+      u32 bits[8];
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        u32 q = (w[e] >> sh) & 15u;
+        if (wide) q |= ((((e < 4 ? hb.x : hb.y) >> (8 * (e & 3))) >> (u32)tj) & 1u) << 4;
+        float val = lut[q] * scale;
+        if constexpr (DT_OUT == LMC_DTYPE_BF16) bits[e] = (u32)__builtin_bit_cast(unsigned short, (__bf16)val);
+        else {
+          asm volatile("" : "+v"(val));  // the product is rounded to fp32 first, to fp16 second (k_decode.h)
+          bits[e] = f2fp16(val);
+        }
+      }
+      if (ok) {
+        const long long toff = KIND == DEC_ROWS ? (long long)tdst * a.dst.stride_token : dec_tok_off(a.dst, tdst);
+        if (fa.vec) {
+          const u32x4_t v = {bits[0] | (bits[1] << 16), bits[2] | (bits[3] << 16), bits[4] | (bits[5] << 16), bits[6] | (bits[7] << 16)};
+          __builtin_nontemporal_store(v, (LMC_GLOBAL u32x4_t*)(pbase + toff + coff));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; e++) {
+            const int c = c0 + e, h = c / a.dst.D, d = c - h * a.dst.D;
+            *((LMC_GLOBAL u16*)(pbase + toff + (long long)h * a.dst.stride_head + d)) = (u16)bits[e];
+          }
+        }
+      }
+    }
+    wave_lds_fence();  // the tile has been read: the next one may take its place
+  }
+  const u32 got = wave_sum_u32(acc);
+  const u32 tw = lane < 4 ? ((const LMC_GLOBAL u32*)(sbytes + ssize - LMC_FIXED_TAIL_BYTES))[lane] : 0u;
+  if (__ballot(lane < 4 && tw != (lane == 0 ? got : 0u)) != 0ull) fail(LMC_ST_BAD_STREAM);
+}

@@ -196,12 +196,18 @@ __device__ __forceinline__ bool split_load_oct(const KvAddr& src, int p, int tok
 // quantises row octs of ONE plane).
 // NHDB: the source is an LMC_PAGED_SPLIT cache (split_load_oct above): the loads, and for a V oct on its fast path the
 // max and the conversion in their channel-major form; from o[][][] on the task is the same.
+// SINK (k_fixed.h, the fixed-width model): the task's symbols do not go to the workspace but to `sink`, in registers --
+// sink.oct(c0, lo quad dwords, hi quad dwords) per channel run of a valid task, runs past C included (their dwords are 0),
+// and sink.scale(token, bits) with every scale the task stores.  NoSink: the task as it always was.
+struct NoSink {};
 template <int G, int NITER, int DT, bool QUAD, bool NIB, int ROWS = 4, int NQ = NIB ? 2 : 1, int SPLIT = 1, bool HIST = false,
-          bool NHDB = false>
+          bool NHDB = false, class SINK = NoSink>
 __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0, int Tc, int t_first, bool qvalid,
                                               bool q1valid, int C, float maxf, u32* sym_out, int8_t* sym8_plane,
                                               u16* scale_out, int sl, int slice = 0, u32* xmax = nullptr,
-                                              u32 hist_lane4 = 0, int hist_it = 0) {
+                                              u32 hist_lane4 = 0, int hist_it = 0, SINK* sink = nullptr) {
+  constexpr bool HAS_SINK = !__is_same(SINK, NoSink);
+  static_assert(!HAS_SINK || (QUAD && NQ == 2 && ROWS == 8 && !HIST), "a sink takes whole octs");
   static_assert(!HIST || (QUAD && NITER == 1 && NQ == 2 && SPLIT == 1), "the histogram rides on the fused kernel's narrow tasks");
   static_assert(SPLIT == 1 || (QUAD && ROWS == 4 * NQ), "a split task exchanges all its rows' maxima at once");
   static_assert(ROWS == 2 || ROWS == 4 || (ROWS == 8 && NQ == 2), "rows in flight: a power of two within the task");
@@ -324,7 +330,10 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
     if (sl == 0 && slice == 0) {
 #pragma unroll
       for (int r = 0; r < ROWS; r++)
-        if (tv[r]) scale_out[r0 + r] = (u16)mrow[r];
+        if (tv[r]) {
+          scale_out[r0 + r] = (u16)mrow[r];
+          if constexpr (HAS_SINK) sink->scale((u32)(t_first + r0 + r), mrow[r]);
+        }
     }
 
     float factor[ROWS];
@@ -406,7 +415,12 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
       }
     }
   }
-  if (QUAD && qvalid) {
+  if constexpr (HAS_SINK) {
+    if (qvalid) {
+#pragma unroll
+      for (int it = 0; it < NITER; it++) sink->oct(c0[it], o[0][it], o[1][it]);
+    }
+  } else if (QUAD && qvalid) {
 #pragma unroll
     for (int it = 0; it < NITER; it++) {
       if (!cval[it]) continue;

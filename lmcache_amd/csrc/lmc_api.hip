@@ -19,6 +19,7 @@
 #include "k_copy_split.h"
 #include "k_decode.h"
 #include "k_encode_counts.h"
+#include "k_fixed.h"
 #include "k_fused.h"
 #include "k_layers.h"
 #include "k_offload.h"
@@ -461,6 +462,22 @@ static int reserve_locked(lmc_ctx::Workspace* c, int L, int H, int D, int chunk_
   return LMC_OK;
 }
 
+// ---- LMC_MODEL_FIXED (k_fixed.h): one launch, a workgroup per (plane, chunk); no workspace, so no context state beyond
+// the profiling marks ------------------------------------------------------------------------------------------------
+template <int DT>
+static int launch_fixed_encode(const FixedEncArgs& fa, hipStream_t s) {
+  const int C = fa.e.C;
+  const dim3 grid((unsigned)fa.e.P, (unsigned)fa.e.nchunks), block(64 * FIXED_ENC_WAVES);
+  if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1>), grid, block, 0, s, fa);
+  else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1>), grid, block, 0, s, fa);
+  else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1>), grid, block, 0, s, fa);
+  else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1>), grid, block, 0, s, fa);
+  else if (C <= 2048) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 2>), grid, block, 0, s, fa);
+  else hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 4>), grid, block, 0, s, fa);  // C <= LMC_MAX_CHANNELS: layout_ok
+  HIP_TRY(hipGetLastError());
+  return LMC_OK;
+}
+
 extern "C" {
 
 int lmc_ctx_reserve(lmc_ctx* c, int L, int H, int D, int chunk_tokens, int max_chunks) {
@@ -717,6 +734,39 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   return LMC_OK;
 }
 
+int lmc_encode_chunks_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                            lmc_stream_t stream) {
+  int nchunks;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, false) || lmc_dtype_fp8(src->dtype) || !blobs || !sizes ||
+      ((uintptr_t)blobs & 15) || (blob_stride & 15))
+    return LMC_ERR_INVALID;
+  const int L = src->num_layers, H = src->num_heads, D = src->head_size;
+  if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
+  FixedEncArgs fa;
+  memset(&fa, 0, sizeof fa);
+  if (!bins_ok(bins_h, 2 * L, &fa.e.bins)) return LMC_ERR_INVALID;
+  // the header's size words are 32 bits (the coded models' bound is checked by whoever sized the arena: blob_stride)
+  if (lmc_fixed_blob_bytes((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, fa.e.bins.b) > 0xffffffffull) return LMC_ERR_INVALID;
+  fa.src = to_addr(src);
+  fa.e.tok_begin = tok_begin; fa.e.tok_end = tok_end; fa.e.chunk_tokens = chunk_tokens; fa.e.nchunks = nchunks;
+  fa.e.P = 2 * L; fa.e.C = H * D; fa.e.G = (fa.e.C + 63) / 64;
+  fa.e.blobs = (u8*)blobs; fa.e.blob_stride = (long long)blob_stride;
+  fa.e.sizes = sizes;
+  fa.e.status = job_status ? job_status : c->status_h;  // (nothing the kernel can report: kept for the shape of the job)
+  fa.e.L = L; fa.e.H = H; fa.e.D = D; fa.e.dtype = src->dtype;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);  // (the profiling marks are the context's)
+  c->pn = 0;
+  int rc;
+  if ((rc = prof_mark(c, s))) return rc;
+  if (src->dtype == LMC_DTYPE_BF16) rc = launch_fixed_encode<LMC_DTYPE_BF16>(fa, s);
+  else rc = launch_fixed_encode<LMC_DTYPE_FP16>(fa, s);
+  if (rc) return rc;
+  return prof_mark(c, s);
+}
+
 // ---- the layer-wise encode (include/lmc_hip.h; k_layers.h) ------------------------------------------------------------
 static bool layer_job_ok(const lmc_ctx* c, const lmc_layer_job* j) { return c && j && j->ctx == c && j->b && j->b->busy; }
 
@@ -931,13 +981,30 @@ static void launch_decode(int dtype, int kind, dim3 grid, hipStream_t s, const D
 // One range of layers of a decode: k_decode over the streams of layers [l0, l0 + nl) of the job's chunks, then `ev`
 // (if any) recorded behind it.  The lock is not needed for the launch itself: the load paths call this with c->mu held.
 static int range_post(lmc_ctx* c, const lmc_kv_layout* dst, const lmc_range_post* post, int l0, int nl, hipStream_t s);
+// k_fixed_decode (LMC_MODEL_FIXED blobs) for a 16-bit destination of rows: a wave per stream, FIXED_DEC_WAVES per workgroup
+static void launch_fixed_decode(const lmc_kv_layout* dst, long long nstreams, hipStream_t s, const DecodeArgs& a) {
+  FixedDecArgs fa;
+  fa.d = a;
+  fa.vec = layout_ok(dst) ? 1 : 0;  // rows that take 16-byte vectors of 8 channels: what the encoders ask of a source
+  const dim3 grid((unsigned)((nstreams + FIXED_DEC_WAVES - 1) / FIXED_DEC_WAVES)), block(64 * FIXED_DEC_WAVES);
+  const bool paged = dst->slot_mapping != nullptr;
+  if (dst->dtype == LMC_DTYPE_BF16) {
+    if (paged) hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_BF16, DEC_PAGED_ROWS>), grid, block, 0, s, fa);
+    else hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_BF16, DEC_ROWS>), grid, block, 0, s, fa);
+  } else {
+    if (paged) hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_FP16, DEC_PAGED_ROWS>), grid, block, 0, s, fa);
+    else hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_FP16, DEC_ROWS>), grid, block, 0, s, fa);
+  }
+}
+
 static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev,
-                               lmc_ctx* c = nullptr, const lmc_range_post* post = nullptr) {
+                               lmc_ctx* c = nullptr, const lmc_range_post* post = nullptr, bool fixed = false) {
   a.layer_begin = l0; a.layer_count = nl;
   const long long n = (long long)a.nchunks * 2 * nl * a.G;
   const dim3 grid((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES));
   const int kind = dst->paged_kind == LMC_PAGED_SPLIT ? DEC_PAGED_SPLIT : dst->slot_mapping ? DEC_PAGED_ROWS : DEC_ROWS;
-  launch_decode(dst->dtype, kind, grid, s, a);
+  if (fixed) launch_fixed_decode(dst, n, s, a);
+  else launch_decode(dst->dtype, kind, grid, s, a);
   HIP_TRY(hipGetLastError());
   if (post) {  // (none of its launches needs the lock)
     const int rc = range_post(c, dst, post, l0, nl, s);
@@ -950,13 +1017,13 @@ static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, 
 // The same for the decode entry points, which do not hold the lock: taken here, and the launch bracketed by the
 // profiling marks (the range's event follows the second mark).
 static int decode_range(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev,
-                        const lmc_range_post* post = nullptr) {
+                        const lmc_range_post* post = nullptr, bool fixed = false) {
   int rc;
   {
     std::lock_guard<std::mutex> lk(c->mu);
     c->pn = 0;
     if ((rc = prof_mark(c, s))) return rc;
-    if ((rc = decode_range_locked(a, dst, l0, nl, s, nullptr))) return rc;
+    if ((rc = decode_range_locked(a, dst, l0, nl, s, nullptr, nullptr, nullptr, fixed))) return rc;
     if ((rc = prof_mark(c, s))) return rc;
   }
   if (post && (rc = range_post(c, dst, post, l0, nl, s))) return rc;
@@ -989,23 +1056,43 @@ int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t 
 
 static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* post);
 
-int lmc_decode_chunks_schedule_post(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
-                                    const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
-                                    const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
-                                    lmc_stream_t stream, const lmc_range_post* post) {
+// One body for the two schedules: the coded models' k_decode, or -- `fixed` -- k_fixed_decode for LMC_MODEL_FIXED blobs,
+// which fills 16-bit rows only (an LMC_PAGED_SPLIT cache is filled through a staged chunk and post->scatter_dst).
+static int decode_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                           const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                           const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
+                           lmc_stream_t stream, const lmc_range_post* post, bool fixed) {
   DecodeArgs a;
-  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, true);
+  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, !fixed);
   if (rc) return rc;
+  if (fixed && (lmc_dtype_fp8(dst->dtype) || max_blob_bytes < LMC_HEADER_BYTES)) return LMC_ERR_INVALID;
   if (!decode_blobs(a, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, blob_ptrs) || nranges < 1 || !layer_ends_h)
     return LMC_ERR_INVALID;
+  if (fixed) a.blob_stride = (long long)max_blob_bytes;  // the read bound itself: k_fixed_decode reads nothing speculatively
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)  // the whole schedule is checked before anything is launched
     if (layer_ends_h[i] <= prev || layer_ends_h[i] > dst->num_layers) return LMC_ERR_INVALID;
   if (layer_ends_h[nranges - 1] != dst->num_layers || !post_ok(dst, post)) return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)
-    if ((rc = decode_range(c, a, dst, prev, layer_ends_h[i] - prev, (hipStream_t)stream, events_h ? events_h[i] : nullptr, post)))
+    if ((rc = decode_range(c, a, dst, prev, layer_ends_h[i] - prev, (hipStream_t)stream, events_h ? events_h[i] : nullptr, post, fixed)))
       return rc;
   return LMC_OK;
+}
+
+int lmc_decode_chunks_schedule_post(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                    const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                    const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
+                                    lmc_stream_t stream, const lmc_range_post* post) {
+  return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
+                         job_status, stream, post, false);
+}
+
+int lmc_decode_chunks_fixed_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                     const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                     const int32_t* layer_ends_h, const lmc_event_t* events_h, const lmc_range_post* post,
+                                     uint32_t* job_status, lmc_stream_t stream) {
+  return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
+                         job_status, stream, post, true);
 }
 
 int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
@@ -1767,7 +1854,9 @@ int lmc_blob_info(const void* blob_h, size_t nbytes, lmc_blob_header* out) {
   memcpy(&h, blob_h, sizeof h);
   if (h.magic != LMC_BLOB_MAGIC || h.version != LMC_BLOB_VERSION || h.header_bytes != LMC_HEADER_BYTES) return LMC_ERR_INVALID;
   if (h.num_layers == 0 || h.ntokens == 0 || h.num_heads == 0 || h.head_size == 0) return LMC_ERR_INVALID;
-  if (h.num_layers > LMC_MAX_PLANES / 2 || h.ntokens > 65535u || !lmc_model_valid(h.model, h.ntokens)) return LMC_ERR_INVALID;
+  const bool fixed = h.model == LMC_MODEL_FIXED;  // (lmc_model_valid is about the coded models)
+  if (h.num_layers > LMC_MAX_PLANES / 2 || h.ntokens > 65535u || !(fixed ? lmc_fixed_valid(h.ntokens) : lmc_model_valid(h.model, h.ntokens)))
+    return LMC_ERR_INVALID;
   if ((uint64_t)h.num_heads * h.head_size > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
   lmc_blob_header ref;
   memset(&ref, 0, sizeof ref);
@@ -1779,6 +1868,38 @@ int lmc_blob_info(const void* blob_h, size_t nbytes, lmc_blob_header* out) {
   if (h.total_bytes != h.off_streams + h.stream_bytes || h.total_bytes > nbytes) return LMC_ERR_INVALID;
   if (h.kv_dtype != 0u && !((h.kv_dtype == LMC_DTYPE_FP8_E4M3 || h.kv_dtype == LMC_DTYPE_FP8_E5M2) && h.dtype == LMC_DTYPE_BF16))
     return LMC_ERR_INVALID;
+  if (fixed) {
+    // (this call may be handed the header alone, with the blob's length: what the header can say is checked here, the
+    // bins and the directory by lmc_fixed_blob_info)
+    const uint64_t n = (uint64_t)h.nplanes * h.ngroups;
+    if (h.kv_dtype != 0u || (uint64_t)h.stream_bytes < n * lmc_fixed_stream_bytes(4u, h.ntokens) ||
+        (uint64_t)h.stream_bytes > n * lmc_fixed_stream_bytes(LMC_MAX_BINS, h.ntokens))
+      return LMC_ERR_INVALID;
+  }
+  *out = h;
+  return LMC_OK;
+}
+
+int lmc_fixed_blob_info(const void* blob_h, size_t nbytes, lmc_blob_header* out) {
+  lmc_blob_header h;
+  const int rc = lmc_blob_info(blob_h, nbytes, &h);
+  if (rc) return rc;
+  if (h.model != LMC_MODEL_FIXED || !out) return LMC_ERR_INVALID;
+  // totals and directory are functions of (bins, T): held against the computed layout (total_bytes <= nbytes: lmc_blob_info)
+  const uint8_t* const b = (const uint8_t*)blob_h;
+  for (uint32_t p = 0; p < h.nplanes; p++)
+    if (b[h.off_bins + p] < 4u || b[h.off_bins + p] > LMC_MAX_BINS) return LMC_ERR_INVALID;
+  if ((uint64_t)h.total_bytes != lmc_fixed_blob_bytes(h.num_layers, h.ntokens, h.num_heads, h.head_size, b + h.off_bins))
+    return LMC_ERR_INVALID;
+  uint32_t beg = 0;
+  for (uint32_t p = 0; p < h.nplanes; p++) {
+    const uint32_t sz = lmc_fixed_stream_bytes(b[h.off_bins + p], h.ntokens);
+    for (uint32_t g = 0; g < h.ngroups; g++, beg += sz) {
+      uint32_t gd[2];
+      memcpy(gd, b + h.off_gdir + 8u * (p * h.ngroups + g), sizeof gd);
+      if (gd[0] != beg || gd[1] != beg + sz) return LMC_ERR_INVALID;
+    }
+  }
   *out = h;
   return LMC_OK;
 }

@@ -158,6 +158,7 @@ SYMBOLS = {
     "lmc_calculate_cdf": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lmc_encode_chunks": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_encode_chunks_split": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "lmc_encode_chunks_fixed": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_encode_layers_begin": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, ctypes.POINTER(_vp)]),
     "lmc_encode_layer": (ctypes.c_int, [_vp, _vp, _i32, _vp]),
     "lmc_encode_layers_finish": (ctypes.c_int, [_vp, _vp, _vp]),
@@ -167,6 +168,8 @@ SYMBOLS = {
     "lmc_decode_chunks_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "lmc_decode_chunks_schedule_post": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                                        ctypes.POINTER(RangePostStruct)]),
+    "lmc_decode_chunks_fixed_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
+                                                        ctypes.POINTER(RangePostStruct), _vp, _vp]),
     "lmc_decode_symbols": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "lmc_store_chunks": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "lmc_load_chunks": (ctypes.c_int, [_vp, _vp, _vp, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -196,6 +199,7 @@ SYMBOLS = {
     "lmc_event_query": (ctypes.c_int, [_vp]),
     "lmc_event_elapsed_ms": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_float)]),
     "lmc_blob_info": (ctypes.c_int, [_vp, _sz, ctypes.POINTER(BlobHeader)]),
+    "lmc_fixed_blob_info": (ctypes.c_int, [_vp, _sz, ctypes.POINTER(BlobHeader)]),
 }
 
 ENCODE_PATHS = {"auto": 0, "two_kernels": 1, "fused": 2}  # LMC_ENCODE_PATH_*
@@ -331,6 +335,22 @@ def blob_bound(L: int, T: int, H: int, D: int) -> int:
     C, P = H * D, 2 * L
     G = (C + LANES - 1) // LANES
     return blob_static_bytes(L, T, H, D) + P * G * group_cap_bytes(T)
+
+
+MODEL_CDF16, MODEL_COUNTS, MODEL_FIXED = 0, 1, 2  # LMC_MODEL_*: the header's `model` word
+FIXED_NARROW_BINS = 17                            # LMC_FIXED_NARROW_BINS
+
+
+def fixed_stream_bytes(bins: int, T: int) -> int:
+    """lmc_fixed_stream_bytes: one group stream of the fixed-width model (lo, hi of a wide plane, tail)."""
+    return (256 if bins <= FIXED_NARROW_BINS else 320) * ((T + 7) // 8) + 16
+
+
+def fixed_blob_bytes(L: int, T: int, H: int, D: int, bins: Sequence[int]) -> int:
+    """lmc_fixed_blob_bytes: the exact size of an LMC_MODEL_FIXED blob; bins: the per-plane bins [2 L]."""
+    assert len(bins) == 2 * L
+    G = (H * D + LANES - 1) // LANES
+    return blob_static_bytes(L, T, H, D) + G * sum(fixed_stream_bytes(int(b), T) for b in bins)
 
 
 def current_stream_ptr(device=None) -> int:
@@ -809,6 +829,14 @@ class Context:
                    chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
         return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
+    def encode_chunks_fixed(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
+                            blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
+                            status_ptr: Optional[int] = None) -> int:
+        """encode_chunks with the blobs in the fixed-width model (lmc_encode_chunks_fixed): sizes are fixed_blob_bytes."""
+        self._call("lmc_encode_chunks_fixed", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end,
+                   chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
+        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+
     def encode_layers_begin(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
                             blobs_ptr: int, blob_stride: int, sizes_ptr: int, status_ptr: Optional[int] = None
                             ) -> Optional["LayerEncodeHandle"]:
@@ -865,6 +893,19 @@ class Context:
                                                     dst_tok0, chunk_tokens, n, ends, evs, status_ptr, st,
                                                     None if post is None else ctypes.byref(post)),
               "lmc_decode_chunks_schedule_post")
+
+    def decode_chunks_fixed_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
+                                     chunk_tokens: int, layer_ends, events, post: Optional[RangePostStruct] = None,
+                                     stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
+        """lmc_decode_chunks_fixed_schedule: decode_chunks_schedule_post for LMC_MODEL_FIXED blobs (post None: no post-op)."""
+        n = len(layer_ends)
+        ends = layer_ends if isinstance(layer_ends, ctypes.Array) else (ctypes.c_int32 * n)(*layer_ends)
+        evs = events if events is None or isinstance(events, ctypes.Array) else (ctypes.c_void_p * n)(*[e.handle for e in events])
+        st = current_stream_ptr(dst.device) if stream is None else stream
+        check(lib().lmc_decode_chunks_fixed_schedule(self.handle, blob_ptrs, max_blob_bytes, nchunks, ctypes.byref(dst.struct),
+                                                     dst_tok0, chunk_tokens, n, ends, evs,
+                                                     None if post is None else ctypes.byref(post), status_ptr, st),
+              "lmc_decode_chunks_fixed_schedule")
 
     def store_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, host_arena_ptr: int,
                      host_cap: int, offsets_ptr: int, sizes_ptr: int, stream: Optional[int] = None,
@@ -1073,6 +1114,10 @@ def blob_info(blob: bytes, total_len: Optional[int] = None) -> BlobHeader:
     buf = (ctypes.c_uint8 * HEADER_BYTES).from_buffer_copy(bytes(blob[:HEADER_BYTES]))
     rc = lib().lmc_blob_info(buf, len(blob) if total_len is None else total_len, ctypes.byref(h))
     check(rc, "lmc_blob_info")
+    if h.model == MODEL_FIXED and total_len is None:
+        # the whole blob is here: its bins, totals and stream directory against the computed layout (lmc_fixed_blob_info)
+        full = (ctypes.c_uint8 * len(blob)).from_buffer_copy(bytes(blob))
+        check(lib().lmc_fixed_blob_info(full, len(blob), ctypes.byref(h)), "lmc_fixed_blob_info")
     return h
 
 

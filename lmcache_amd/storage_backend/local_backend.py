@@ -19,6 +19,11 @@ Three storage modes, chosen by the config:
                                            288 GB than raw chunks, and the one tier whose retrieve (a decode,
                                            no PCIe) can hide behind the model layer by layer
                                            (get_kv_range(..., layers_per_launch=...))
+  local_device="cuda", local_serde="cachegen-fixed"
+                                           the same tier (mode "hbm-cachegen", model "fixed") with FIXED-WIDTH blobs
+                                           (LMC_MODEL_FIXED: 3.8x instead of 4.6x, no entropy coder on either leg).
+                                           Rows only: an "NHDB" cache is staged; no layer-wise store; an HBM budget
+                                           drops its LRU groups, never demotes them.  ValueError with any other device.
 
 Bounded tiers.  LMCACHE_AMD_HBM_BYTES / LMCACHE_AMD_PINNED_BYTES (integers, optional K / M / G suffix; read at
 construction, unset = unbounded) or set_capacity() give the HBM and the pinned tier a byte budget.  The unit of
@@ -62,7 +67,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 import torch
 
 from lmcache_amd import native
-from lmcache_amd.config import LMCacheEngineConfig, LMCacheEngineMetadata
+from lmcache_amd.config import LMCacheEngineConfig, LMCacheEngineMetadata, check_local_serde
 from lmcache_amd.logging import init_logger
 from lmcache_amd.storage_backend.abstract_backend import LMCBackendInterface
 from lmcache_amd.storage_backend.serde.cachegen_basics import CacheGenConfig
@@ -193,14 +198,20 @@ class LMCLocalBackend(LMCBackendInterface):
         self.fmt = metadata.fmt if metadata is not None else None
         self.device = config.local_device
         self.dst_device = "cuda"
+        # the coder model of an encoded tier: "rans" (the entropy-coded blobs) or "fixed" (local_serde="cachegen-fixed":
+        # LMC_MODEL_FIXED, fixed-width symbols -- HBM-resident only); None on the raw tiers
+        self.model: Optional[str] = None
+        if config.local_serde not in (None, "cachegen", "cachegen-fixed"):
+            raise ValueError(f"Invalid local_serde: {config.local_serde}")
         if self.device == "cuda":
-            self.mode = "hbm-cachegen" if config.local_serde == "cachegen" else "hbm"
+            self.mode = "hbm-cachegen" if config.local_serde in ("cachegen", "cachegen-fixed") else "hbm"
         elif self.device == "cpu":
+            check_local_serde(self.device, config.local_serde)  # "cachegen-fixed": ValueError, the pinned tier is PCIe-bound
             self.mode = "cachegen" if config.local_serde == "cachegen" else "raw"
         else:
             raise ValueError(f"LMCLocalBackend: unsupported local_device {self.device!r}")
-        if config.local_serde not in (None, "cachegen"):
-            raise ValueError(f"Invalid local_serde: {config.local_serde}")
+        if self.mode in ("cachegen", "hbm-cachegen"):
+            self.model = "fixed" if config.local_serde == "cachegen-fixed" else "rans"
         self.cachegen_config = None
         if self.mode in ("cachegen", "hbm-cachegen"):
             if metadata is None:
@@ -229,8 +240,9 @@ class LMCLocalBackend(LMCBackendInterface):
         self._next_gid = 0
         self._promoting: set = set()
         self._oversize_logged = False
-        self._tiers = Tiers(self._lru, self._demote_group if self.mode == "hbm-cachegen" else None, self._drop_group,
-                            self._demoted_size)
+        # (fixed-width blobs are not repacked: with both budgets set their LRU groups are dropped, not demoted)
+        self._tiers = Tiers(self._lru, self._demote_group if self.mode == "hbm-cachegen" and self.model != "fixed" else None,
+                            self._drop_group, self._demoted_size)
         self.put_queue: "queue.Queue" = queue.Queue()
         self.put_thread = threading.Thread(target=self.put_worker, daemon=True)
         self.put_thread.start()
@@ -288,7 +300,7 @@ class LMCLocalBackend(LMCBackendInterface):
             self._tiers.budget["hbm"], self._tiers.budget["pinned"] = hbm_bytes, pinned_bytes
             if _keep_unset and hbm_bytes is None and pinned_bytes is None:
                 return
-            if self.mode == "hbm-cachegen" and pinned_bytes is not None and self.host_arena is None:
+            if self.mode == "hbm-cachegen" and self.model != "fixed" and pinned_bytes is not None and self.host_arena is None:
                 self.host_arena = PinnedArena()
             if self.host_arena is not None:
                 self.host_arena.set_budget(pinned_bytes)
@@ -580,6 +592,10 @@ class LMCLocalBackend(LMCBackendInterface):
     def _codec(self):
         return get_codec(self._cuda_device)
 
+    def _coder(self) -> dict:
+        """The codec's `model` argument for this tier's encode / decode_device calls."""
+        return {"model": "fixed"} if self.model == "fixed" else {}
+
     def _finish_encoded(self, keys: Sequence[CacheEngineKey], job, shapes, dtype) -> None:
         codec = self._codec()
         L, H, D, cs = job.geometry
@@ -670,7 +686,7 @@ class LMCLocalBackend(LMCBackendInterface):
         if self.mode in ("cachegen", "hbm-cachegen"):
             out_dt = _coded_dtype(fmt, kv_chunk.dtype)
             with torch.cuda.device(kv_chunk.device):
-                job = self._codec().encode(lay, 0, lay.ntokens, lay.ntokens, self.cachegen_config.plane_bins(lay.L))
+                job = self._codec().encode(lay, 0, lay.ntokens, lay.ntokens, self.cachegen_config.plane_bins(lay.L), **self._coder())
             self._finish_encoded([key], job, [shape], out_dt)
             return
         # raw: contiguous chunk -> pinned host
@@ -740,7 +756,7 @@ class LMCLocalBackend(LMCBackendInterface):
             T = entry.shape[2] if fmt == "vllm" else entry.shape[3]
             codec = self._codec()
             try:
-                codec.finish_decode(codec.decode_device([entry.blob], native.KVLayout.from_chunk(out, fmt), 0, T))
+                codec.finish_decode(codec.decode_device([entry.blob], native.KVLayout.from_chunk(out, fmt), 0, T, **self._coder()))
             except native.NativeError:
                 logger.exception("stored chunk does not decode: treated as a miss")
                 return None
@@ -804,7 +820,8 @@ class LMCLocalBackend(LMCBackendInterface):
                     self.put_queue.put(lambda: self._finish_pack(list(keys), pjob, shapes, out_dt))
                 return n
             with torch.cuda.device(dev):
-                job = self._codec().encode(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L), direct=direct)
+                job = self._codec().encode(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L), direct=direct,
+                                           **self._coder())
             if blocking:
                 self._finish_encoded(keys, job, shapes, out_dt)
             else:
@@ -904,7 +921,7 @@ class LMCLocalBackend(LMCBackendInterface):
         are put_kv_range's.  Nothing is published before finish()."""
         n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
         assert n == len(keys), "one key per chunk"
-        if n == 0 or self.mode not in ("cachegen", "hbm-cachegen"):
+        if n == 0 or self.mode not in ("cachegen", "hbm-cachegen") or self.model == "fixed":  # (no layer-wise store of the fixed-width model yet)
             return None
         L, H, D = src.L, src.H, src.D
         with torch.cuda.device(src.device):
@@ -974,7 +991,7 @@ class LMCLocalBackend(LMCBackendInterface):
                 # (`entries` is the SAME list object for a repeated lookup of one prefix -- _prefix_entries -- and the codec
                 # keeps the uploaded address table of the last few lists it has seen)
                 job = codec.decode_device([e.blob for e in entries], dst, dst_tok0, chunk_tokens, layers_per_launch,
-                                          same_blobs_as=entries, post=post)
+                                          same_blobs_as=entries, post=post, **self._coder())
             self._touch(keys[:len(entries)], [job.done])
             if jobs_out is not None:
                 jobs_out.append((codec, job))
@@ -1017,7 +1034,7 @@ class LMCLocalBackend(LMCBackendInterface):
                 with torch.cuda.device(dev):
                     if kind == "dev":
                         job = codec.decode_device([e.blob for e in entries[i:j]], dst, tok0, chunk_tokens, layers_per_launch,
-                                                  post=post)
+                                                  post=post, **self._coder())
                     elif kind == "pack":
                         job = codec.load_pack(entries[i].pack, entries[i].index, j - i, dst, tok0, layers_per_launch, post=post)
                     else:

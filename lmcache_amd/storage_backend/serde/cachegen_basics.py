@@ -104,6 +104,12 @@ class CacheGenGPUEncoderOutput:
         self.ntokens = int(h.ntokens)
         self.dtype = native.stored_dtype(h)  # fp8 KV: its fp8 dtype (the scales are held in it, as the reference holds max1)
         self._scale_dtype = native.torch_dtype(int(h.dtype))
+        self.model = int(h.model)  # LMC_MODEL_*: the fixed-width model (2) has neither symbol counts nor a bytestream
+
+    def _coded_only(self, what: str) -> None:
+        if self.model == native.MODEL_FIXED:
+            raise ValueError(f"{what}: this blob is of the fixed-width model (LMC_MODEL_FIXED, header model word 2): it "
+                             "stores no symbol counts and no entropy-coded bytestream")
 
     def _section(self, off, count, dt):
         return np.frombuffer(self._blob, dtype=dt, count=count, offset=off)
@@ -139,7 +145,8 @@ class CacheGenGPUEncoderOutput:
     def cdf(self) -> torch.Tensor:
         """int16 [2L, C, 33] -- the reference's `cdf` tensor, rebuilt from the blob: every stream opens with the
         symbol counts of its 64 channels, and cdf[i] = RNE(N_i * 65504 / T) + i with N_i the number of symbols
-        < i (cachegen_encoder.py:95-126; include/lmc_format.h)."""
+        < i (cachegen_encoder.py:95-126; include/lmc_format.h).  ValueError for a blob of the fixed-width model."""
+        self._coded_only("cdf")
         h = self.header
         P, C, G, LP, T = int(h.nplanes), int(h.nchannels), int(h.ngroups), int(h.lp), int(h.ntokens)
         full = np.empty((P, C, LP), np.uint16)
@@ -176,6 +183,7 @@ class CacheGenGPUEncoderOutput:
 
     @property
     def data_chunks(self) -> List[CacheGenGPUBytestream]:
+        self._coded_only("data_chunks")
         h = self.header
         d = self._stream_dir()
         lens = (d[:, 1] - d[:, 0]).astype(np.int32).reshape(h.nplanes, h.ngroups)
