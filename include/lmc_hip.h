@@ -100,15 +100,20 @@ int lmc_abi_version(void);
  *     head / granule / element is its 32-bit offset, a token its block, 64-bit, plus its slot's step).  Its 32-bit
  *     offsets end at   stride_head >= 0  and  ((H-1)*stride_head + D*block_size)*E + 7*16 <= 0xfffffff0;
  *     beyond that LMC_ERR_INVALID before anything is queued (blocks and planes may lie any distance apart).
+ *     For LMC_MODEL_FIXED blobs, lmc_decode_chunks_fixed_split_schedule (16-bit elements; k_fixed.h: a K token's granule
+ *     by one 16-byte store, a V oct that is eight consecutive slots of a block from slot % 8 == 0 on by one 16-byte store
+ *     per channel, anything else element by element), under the same rule for the 32-bit offsets.
  *   - NOT lmc_decode_chunks: it is the replacement of the reference's from_bytes, whose caller wants a tensor of rows.
  *   - as an ENCODE SOURCE, lmc_encode_chunks_split and the stores (lmc_store_chunks, lmc_store_pack,
  *     lmc_store_pack_parts): k_quantize.h reads the split blocks in place (a V oct whose tokens are eight consecutive
  *     slots of a block, from slot % 8 == 0 on, as 16-byte runs of one channel; a K token's granules where they lie;
  *     anything else element by element), then k_cdf_encode -- never the fused kernel, so a pack store is one part.
  *     Planes of at most 1024 channels (H * D), stride_head >= 0 and ((H-1)*stride_head + D*block_size)*E <= 0xfffffff0;
- *     beyond that LMC_ERR_INVALID before anything is queued.
+ *     beyond that LMC_ERR_INVALID before anything is queued.  lmc_encode_chunks_fixed_split reads it the same way
+ *     (k_fixed.h, one kernel) under the same limits, for 16-bit elements.
  *   - NOT lmc_encode_chunks and lmc_quantize: they stand for the reference's to_bytes / torch_quant_vectorized, whose
- *     caller holds a tensor of rows.
+ *     caller holds a tensor of rows.  NOT lmc_encode_chunks_fixed and lmc_decode_chunks_fixed_schedule either: their
+ *     _split twins are the ones that take it.
  * Every other entry point -- lmc_rope_shift among them -- reads and writes rows and returns LMC_ERR_INVALID for it: bring
  * the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot read.  Any other paged_kind is
  * LMC_ERR_INVALID; a caller that zeroes the struct gets LMC_PAGED_ROWS.
@@ -251,13 +256,25 @@ int lmc_encode_chunks_split(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_
  * lmc_encode_chunks with the blobs written in the FIXED-WIDTH model (lmc_format.h: LMC_MODEL_FIXED; additive in ABI 6;
  * csrc/k_fixed.h): the same quantisation, scales and checksums, every symbol at 4 or 5 bits and no entropy coder -- for
  * blobs that stay in HBM, where the coder's bytes buy nothing.  One launch, one pass over the source.  Arguments and
- * refusals are lmc_encode_chunks' (an LMC_PAGED_SPLIT source is LMC_ERR_INVALID: gather it first), and so is
- * blob_stride >= lmc_blob_bound: a fixed-width blob never outgrows the coded models' slot.  fp8 KV is LMC_ERR_INVALID.
- * sizes[i] receives lmc_fixed_blob_bytes of chunk i, a function of the geometry and the bins alone.
+ * refusals are lmc_encode_chunks' (an LMC_PAGED_SPLIT source is LMC_ERR_INVALID here: lmc_encode_chunks_fixed_split
+ * takes it), and so is blob_stride >= lmc_blob_bound: a fixed-width blob never outgrows the coded models' slot.  fp8 KV
+ * is LMC_ERR_INVALID.  sizes[i] receives lmc_fixed_blob_bytes of chunk i, a function of the geometry and the bins alone.
  */
 int lmc_encode_chunks_fixed(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
                             int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
                             uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
+
+/*
+ * lmc_encode_chunks_fixed for any source it takes AND a 16-bit LMC_PAGED_SPLIT one (additive in ABI 6; what
+ * lmc_encode_chunks_split is to lmc_encode_chunks): the cache is read in place by k_fixed_encode's split instances, no
+ * staged chunk and no lmc_copy_kv in front, and the blobs are byte for byte those lmc_encode_chunks_fixed writes from the
+ * gathered chunk.  Only slots of the job's own tokens are read.  A split source with more than 1024 channels per plane,
+ * stride_head < 0 or ((H-1)*stride_head + D*block_size)*E > 0xfffffff0, or fp8 elements, is LMC_ERR_INVALID and nothing
+ * is launched.  Any other source: exactly lmc_encode_chunks_fixed.
+ */
+int lmc_encode_chunks_fixed_split(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
+                                  int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
+                                  uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
 
 /*
  * The same encode issued LAYER BY LAYER (additive in ABI 6; csrc/k_layers.h).  Replaces the store of the reference, which
@@ -385,12 +402,28 @@ int lmc_decode_chunks_schedule_post(lmc_ctx* ctx, const void* const* blob_ptrs, 
  * the coded models' decoders).  A stream whose check word does not match is LMC_STATUS_BAD_STREAM, scales that do not
  * match scsum LMC_STATUS_BAD_SCALES; the destination is undefined then, as for the coded models.
  * `dst` is 16-bit rows (LMC_PAGED_ROWS, with or without a slot mapping): an LMC_PAGED_SPLIT or fp8 destination is
- * LMC_ERR_INVALID with nothing queued -- an "NHDB" cache is filled through a staged chunk and post->scatter_dst.
+ * LMC_ERR_INVALID with nothing queued -- here an "NHDB" cache is filled through a staged chunk and post->scatter_dst;
+ * lmc_decode_chunks_fixed_split_schedule decodes straight into it.
  */
 int lmc_decode_chunks_fixed_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
                                      const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
                                      const int32_t* layer_ends_h, const lmc_event_t* events_h, const lmc_range_post* post,
                                      uint32_t* job_status, lmc_stream_t stream);
+
+/*
+ * lmc_decode_chunks_fixed_schedule for any destination it takes (one body: exactly that call) AND a 16-bit
+ * LMC_PAGED_SPLIT one (additive in ABI 6): k_fixed_decode's split instances store into the cache of vLLM's ROCm
+ * paged-attention kernels, per range and with the ranges' events as there, no staged chunk and no scatter behind.  The
+ * validation is the same and comes before every read; only slots of the call's own tokens are written (a token in front
+ * of dst_tok0 + ... = 0 or past the blob's count is neither written nor looked up in slot_mapping).  The decoded bits
+ * are those the row decode leaves in a chunk.  The split destination's 32-bit offsets follow the rule stated at
+ * lmc_kv_layout for the coded decoders (LMC_ERR_INVALID beyond it, as for fp8), and `post` follows
+ * lmc_decode_chunks_schedule_post: a rotation of a split `dst` is LMC_ERR_INVALID.
+ */
+int lmc_decode_chunks_fixed_split_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes,
+                                           int32_t nchunks, const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens,
+                                           int32_t nranges, const int32_t* layer_ends_h, const lmc_event_t* events_h,
+                                           const lmc_range_post* post, uint32_t* job_status, lmc_stream_t stream);
 
 /* Entropy-decode only (debug / parity): blob -> sym_out int8 [P][T][C].
  * Stands where torchac_cuda.decode_fast_prefsum stands (cachegen_decoder.py:65-66). */

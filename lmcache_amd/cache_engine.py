@@ -184,7 +184,10 @@ class LMCacheEngine:
                   overlap of the part copies with the encode: it buys memory first, time only
                   where profiles/paged_split_encode.md says so.  Planes of more than 1024 channels (H * D) are staged all
                   the same.  It means nothing for "NBHD" / "NHBD", which are read in place anyway, and nothing for the raw
-                  tiers and the chunk-tensor backends, whose gather IS the store.  The stored bytes are the same."""
+                  tiers and the chunk-tensor backends, whose gather IS the store.  The stored bytes are the same.
+                  The fixed-width HBM tier (local_serde="cachegen-fixed") reads the split blocks with its one kernel
+                  (lmc_encode_chunks_fixed_split; k_fixed.h) under the same 1024-channel limit: no gather there either,
+                  and on block-ordered slots less time as well (profiles/fixed_model.md)."""
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens.shape) == 1, f"Invalid shape of tokens: {tokens.shape}"
         assert len(kv_caches) > 0, "Empty kv_caches"
@@ -323,7 +326,10 @@ class LMCacheEngine:
                   effect above: a stored chunk that fails to decode is a miss in ret_mask, but the slots of the call's
                   tokens may hold garbage by then, as for the row layouts.  With a row layout the keyword changes
                   nothing.  Not with `rope` (ValueError before anything is queued): lmc_rope_shift has no split
-                  addressing, and the staged chunk is where the keys are rotated.
+                  addressing, and the staged chunk is where the keys are rotated.  The fixed-width HBM tier
+                  (local_serde="cachegen-fixed") decodes into the split blocks the same way
+                  (lmc_decode_chunks_fixed_split_schedule); asked for `direct` WITH `rope` it does not raise but takes
+                  the staged path (logged once).
           rope  a lmcache_amd.rope.RopeShift: the keys of the retrieved tokens are re-rotated to new positions on the way
                 (a segment that was prefilled on its own and is placed at offset p: delta = p; a per-token delta tensor
                 has one entry per token of `tokens`).  One lmc_rope_shift (k_rope.h) on the current stream behind the
@@ -335,7 +341,7 @@ class LMCacheEngine:
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
-        direct = self._direct_retrieve(direct, layout)
+        direct = self._direct_retrieve(direct, layout, rope)
         if rope is not None:
             if direct and layout == "NHDB":
                 raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
@@ -369,14 +375,15 @@ class LMCacheEngine:
                     ctx.copy_kv(rows, 0, got, dst, 0)
         return ret_mask
 
-    def _direct_retrieve(self, direct: bool, layout: str) -> bool:
-        """`direct` as the backend can honour it: the fixed-width HBM tier (local_serde="cachegen-fixed") decodes into rows
-        only, so a direct retrieve into an "NHDB" cache takes the staged path there (logged once)."""
-        if direct and layout == "NHDB" and getattr(self.engine_, "model", None) == "fixed":
+    def _direct_retrieve(self, direct: bool, layout: str, rope: Optional[RopeShift] = None) -> bool:
+        """`direct` as the backend honours it.  The fixed-width HBM tier (local_serde="cachegen-fixed") decodes straight
+        into an "NHDB" cache (lmc_decode_chunks_fixed_split_schedule); asked for that together with a `rope` it does not
+        raise as the coded tiers do but takes the staged path, where the keys are rotated (logged once)."""
+        if direct and layout == "NHDB" and rope is not None and getattr(self.engine_, "model", None) == "fixed":
             if not getattr(self, "_fixed_direct_logged", False):
                 self._fixed_direct_logged = True
-                logger.info("retrieve_into_paged(direct=True): the fixed-width tier decodes into rows; an \"NHDB\" cache is "
-                            "filled through the staged chunk (logged once)")
+                logger.info("retrieve_into_paged(direct=True) with rope on the fixed-width tier: the keys are re-rotated in "
+                            "the staged chunk, so the \"NHDB\" cache is filled through it (logged once)")
             return False
         return direct
 
@@ -475,7 +482,7 @@ class LMCacheEngine:
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
-        direct = self._direct_retrieve(direct, layout)
+        direct = self._direct_retrieve(direct, layout, rope)
         if rope is not None:
             if direct and layout == "NHDB":
                 raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "

@@ -24,6 +24,22 @@
 // wave checks scsum (BAD_SCALES); everything a section's address depends on is validated before the section is read
 // (BAD_HEADER).  Block-ordered paged destinations take the same per-token path: a token's row is one slot_mapping load
 // per lane and oct (k_decode.h's eight-row blocks were built around its scalar stores and are not needed here).
+//
+// LMC_PAGED_SPLIT ("NHDB", the cache of vLLM's ROCm paged-attention kernels: include/lmc_hip.h) on both sides, 16-bit
+// elements.  k_fixed_encode<..., NHDB = true>: quantize_task's split source form (k_quantize.h, split_load_oct) with the
+// same sink -- the loads differ, the blob does not; planes of up to 1024 channels (SPLIT == 1).
+// k_fixed_decode<DT, DEC_PAGED_SPLIT>: a K plane goes through the same transpose, and the lane's 8 channels of a token are
+// one x-granule (x = 8): the same 16-byte store at block * stride_block + h * stride_head + (d / 8) * (block_size * 8) +
+// w * 8.  A V plane skips the transpose: AS LOADED, lane l holds `lo` dwords 4 l .. 4 l + 3 and `hi` dword l of the tile,
+// i.e. every bit of channels 4 (l & 15) .. + 3 for the eight tokens of oct l >> 4, and eight consecutive slots of one
+// channel are 16 contiguous bytes of the plane -- four 16-byte stores per lane where the oct's tokens lie at slots s ..
+// s + 7 of one block, s % 8 == 0, all eight of them to be written, and base and strides keep the vector aligned (the
+// encoder's V-form condition; a ballot sends the tile's four octs one way).  Any other oct -- a ragged tail, the
+// first-chunk trim, a run that enters a block at offset 5 or breaks, single tokens at random slots, a base 2 bytes off --
+// is stored element by element, live tokens only; a slot is read from slot_mapping only for a token that is written.
+// The split stores carry no non-temporal hint: 16-byte pieces whose neighbours arrive later want L2 to merge them
+// (k_decode.h, LMC_DEC_SPLIT_NT: 1.47 against 3.11 ms there).  A V store of 32 contiguous bytes per channel (two octs of
+// a 16-slot block regrouped through LDS) was not built, so not compared.
 #pragma once
 #include "k_encode.h"
 #include "k_quantize.h"
@@ -84,9 +100,10 @@ struct FixedSink {
 #define FIXED_ENC_WAVES 8  // 8 waves walk a 256-token plane in 4 passes: measured against 4 waves (8 passes, workgroups that
                            // live twice as long) on a 16 k Llama-3-8B context, same box, alternating: 0.557 against 0.614 ms
 #endif
-template <int G, int NITER, int DT, int SPLIT>
+template <int G, int NITER, int DT, int SPLIT, bool NHDB = false>
 __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncArgs a) {
   constexpr int NW = FIXED_ENC_WAVES;
+  static_assert(!NHDB || SPLIT == 1, "a split source: planes of up to 1024 channels");
   static_assert(SPLIT == 1 || (G == LMC_WAVE && NITER == 2 && (SPLIT == 2 || SPLIT == 4)), "split tasks: whole waves");
   constexpr int RPW = LMC_WAVE / G;
   constexpr int PER_PASS = SPLIT > 1 ? NW / SPLIT : NW * RPW;  // row octs a workgroup takes at a time
@@ -131,10 +148,10 @@ __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncA
     sink.oct_i = (u32)oct;
     u16* const scale_out = reinterpret_cast<u16*>(blob + bo.scales) + ((long long)p * Tc + oct * 8);
     if (lmc_sym_nibbles(bins))
-      quantize_task<G, NITER, DT, true, true, 8, 2, SPLIT, false, false, FixedSink>(a.src, p, tok0, Tc, oct * 8, ovalid, true, e.C, maxf,
+      quantize_task<G, NITER, DT, true, true, 8, 2, SPLIT, false, NHDB, FixedSink>(a.src, p, tok0, Tc, oct * 8, ovalid, true, e.C, maxf,
                                                                                    nullptr, nullptr, scale_out, sl, slice, xm, 0u, 0, &sink);
     else
-      quantize_task<G, NITER, DT, true, false, 8, 2, SPLIT, false, false, FixedSink>(a.src, p, tok0, Tc, oct * 8, ovalid, true, e.C, maxf,
+      quantize_task<G, NITER, DT, true, false, 8, 2, SPLIT, false, NHDB, FixedSink>(a.src, p, tok0, Tc, oct * 8, ovalid, true, e.C, maxf,
                                                                                     nullptr, nullptr, scale_out, sl, slice, xm, 0u, 0, &sink);
     if constexpr (SPLIT > 1) __syncthreads();  // the next pass writes the exchange slots this one has read
   }
@@ -164,7 +181,8 @@ struct FixedDecArgs {
 
 template <int DT_OUT, int KIND>
 __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecArgs fa) {
-  static_assert(!lmc_dtype_fp8(DT_OUT) && KIND != DEC_PAGED_SPLIT, "16-bit rows");
+  static_assert(!lmc_dtype_fp8(DT_OUT), "16-bit elements");
+  constexpr bool SPLIT = KIND == DEC_PAGED_SPLIT;
   __shared__ __attribute__((aligned(16))) u32 lds_all[FIXED_DEC_WAVES * FIXED_DEC_WAVE_DWORDS];
   const DecodeArgs& a = fa.d;
   const int lane = threadIdx.x & 63;
@@ -238,6 +256,18 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
   E* const pbase = const_cast<E*>(lmc_plane_base<E>(a.dst, p));
   const int h0 = c0 / a.dst.D, d0 = c0 - h0 * a.dst.D;
   const long long coff = (long long)h0 * a.dst.stride_head + d0;  // vec: the 8 channels are contiguous from here
+  // LMC_PAGED_SPLIT (k_quantize.h has the two address forms): the block offset is 64-bit, the lane's part 32-bit (lmc_api.hip,
+  // decode_dst_ok).  A key plane: the lane's 8 channels are one x-granule, x = 8 (head_size is whole granules).  A value
+  // plane: the lane keeps what it loaded, the eight tokens of oct lane >> 4 for the four channels vc0 .. vc0 + 3 (one head:
+  // head_size % 8 == 0), each channel's eight slots 16 contiguous bytes where the oct lies as the encoder's V form asks.
+  const bool is_v = SPLIT && p >= a.dst.L;  // (wave-uniform)
+  const u32 bs = (u32)a.dst.block_size;
+  const bool aligned = SPLIT && ((((uintptr_t)pbase) & 15u) | (uintptr_t)((a.dst.stride_block | a.dst.stride_head) & 7)) == 0;
+  const u32 k_in = (u32)h0 * (u32)a.dst.stride_head + ((u32)d0 >> 3) * (bs * 8u);
+  const int vc0 = g * 64 + 4 * (lane & 15);
+  const bool vcok = vc0 < a.C;
+  const int vh = vc0 / a.dst.D;
+  const u32 v_in = (u32)vh * (u32)a.dst.stride_head + (u32)(vc0 - vh * a.dst.D) * bs;
   const int tdst0 = a.dst_tok0 + chunk * a.chunk_tokens;
   const u32 sh = 8u * ((u32)tj & 3u) + 4u * ((u32)tj >> 2);
 
@@ -261,12 +291,71 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
       const u32 i0 = tile * 256u + 4u * (u32)lane;
       acc += (2u * i0 + 1u) * cur.lo.x + (2u * i0 + 3u) * cur.lo.y + (2u * i0 + 5u) * cur.lo.z + (2u * i0 + 7u) * cur.lo.w;
       acc += (2u * (64u * O + tile * 64u + (u32)lane) + 1u) * cur.hi;
-      *reinterpret_cast<u32x4_t*>(lo_t + 4 * lane) = cur.lo;
-      hi_t[lane] = cur.hi;
+      if (!is_v) {
+        *reinterpret_cast<u32x4_t*>(lo_t + 4 * lane) = cur.lo;
+        hi_t[lane] = cur.hi;
+      }
       if (lane < 32) sc_t[lane] = h2f_rt(cur.sc, (int)src_dtype);
     }
     wave_lds_fence();
+    const Tile mine = cur;
     if (tile + 1u < ntile) cur = load_tile(tile + 1u);  // in flight while this tile is stored
+    if constexpr (SPLIT) {
+      if (is_v) {
+        // the lane's oct: slots of its live tokens only (t < T, not trimmed), and nothing of a token that is not live
+        const u32 oo = (u32)lane >> 4, t0 = (tile * 4u + oo) * 8u;
+        bool live[8], all = vcok, any = false;
+        u32 sl[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+          live[r] = vcok && t0 + (u32)r < T && tdst0 + (int)(t0 + (u32)r) >= 0;
+          sl[r] = live[r] ? (u32)a.dst.slot_mapping[tdst0 + (int)(t0 + (u32)r)] : 0u;
+          all = all && live[r];
+          any = any || live[r];
+        }
+        const u32 b0 = sl[0] / bs, w0 = sl[0] - b0 * bs;
+        bool run = all && aligned && (w0 & 7u) == 0u && (bs & 7u) == 0u;
+#pragma unroll
+        for (int r = 1; r < 8; r++) run = run && sl[r] == sl[0] + (u32)r;
+        const u32 lw[4] = {mine.lo.x, mine.lo.y, mine.lo.z, mine.lo.w};
+        u32 bits[4][8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+          const float scale = sc_t[oo * 8u + (u32)r];
+#pragma unroll
+          for (int e = 0; e < 4; e++) {
+            u32 q = (lw[e] >> (8u * ((u32)r & 3u) + 4u * ((u32)r >> 2))) & 15u;
+            if (wide) q |= ((mine.hi >> (8u * (u32)e + (u32)r)) & 1u) << 4;
+            float val = lut[q] * scale;
+            if constexpr (DT_OUT == LMC_DTYPE_BF16) bits[e][r] = (u32)__builtin_bit_cast(unsigned short, (__bf16)val);
+            else {
+              asm volatile("" : "+v"(val));  // two roundings, as in the rows
+              bits[e][r] = f2fp16(val);
+            }
+          }
+        }
+        if (__ballot(any && !run) == 0ull) {  // every oct of the tile that writes at all is a whole aligned run
+          if (run) {
+            LMC_GLOBAL u16* const blk = (LMC_GLOBAL u16*)(pbase + (long long)b0 * a.dst.stride_block);
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+              *(LMC_GLOBAL u32x4_t*)(blk + (v_in + (u32)e * bs + w0)) = u32x4_t{bits[e][0] | (bits[e][1] << 16), bits[e][2] | (bits[e][3] << 16),
+                                                                               bits[e][4] | (bits[e][5] << 16), bits[e][6] | (bits[e][7] << 16)};
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 8; r++) {
+            if (!live[r]) continue;
+            const u32 br = sl[r] / bs, wr = sl[r] - br * bs;
+            LMC_GLOBAL u16* const blk = (LMC_GLOBAL u16*)(pbase + (long long)br * a.dst.stride_block);
+#pragma unroll
+            for (int e = 0; e < 4; e++) blk[v_in + (u32)e * bs + wr] = (u16)bits[e][r];
+          }
+        }
+        wave_lds_fence();  // the scales have been read
+        continue;
+      }
+    }
     const u32 noct = min(4u, O - tile * 4u);
     for (u32 oo = 0; oo < noct; oo++) {
       const u32 t = (tile * 4u + oo) * 8u + (u32)tj;
@@ -289,7 +378,17 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
           bits[e] = f2fp16(val);
         }
       }
-      if (ok) {
+      if constexpr (SPLIT) {
+        if (ok) {
+          LMC_GLOBAL u16* const gp = (LMC_GLOBAL u16*)(pbase + dec_tok_off_split(a.dst, tdst, 8u)) + k_in;
+          if (aligned) {
+            *(LMC_GLOBAL u32x4_t*)gp = u32x4_t{bits[0] | (bits[1] << 16), bits[2] | (bits[3] << 16), bits[4] | (bits[5] << 16), bits[6] | (bits[7] << 16)};
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++) gp[e] = (u16)bits[e];
+          }
+        }
+      } else if (ok) {
         const long long toff = KIND == DEC_ROWS ? (long long)tdst * a.dst.stride_token : dec_tok_off(a.dst, tdst);
         if (fa.vec) {
           const u32x4_t v = {bits[0] | (bits[1] << 16), bits[2] | (bits[3] << 16), bits[4] | (bits[5] << 16), bits[6] | (bits[7] << 16)};

@@ -464,11 +464,19 @@ static int reserve_locked(lmc_ctx::Workspace* c, int L, int H, int D, int chunk_
 
 // ---- LMC_MODEL_FIXED (k_fixed.h): one launch, a workgroup per (plane, chunk); no workspace, so no context state beyond
 // the profiling marks ------------------------------------------------------------------------------------------------
+// NHDB: the source is an LMC_PAGED_SPLIT cache (k_quantize.h, split_load_oct): instances of their own, planes of up to
+// 1024 channels (encode_job_ok)
 template <int DT>
-static int launch_fixed_encode(const FixedEncArgs& fa, hipStream_t s) {
+static int launch_fixed_encode(const FixedEncArgs& fa, hipStream_t s, bool nhdb) {
   const int C = fa.e.C;
   const dim3 grid((unsigned)fa.e.P, (unsigned)fa.e.nchunks), block(64 * FIXED_ENC_WAVES);
-  if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1>), grid, block, 0, s, fa);
+  if (nhdb) {
+    if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1, true>), grid, block, 0, s, fa);
+    else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1, true>), grid, block, 0, s, fa);
+    else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1, true>), grid, block, 0, s, fa);
+    else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1, true>), grid, block, 0, s, fa);
+    else return LMC_ERR_INVALID;
+  } else if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1>), grid, block, 0, s, fa);
   else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1>), grid, block, 0, s, fa);
   else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1>), grid, block, 0, s, fa);
   else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1>), grid, block, 0, s, fa);
@@ -734,11 +742,14 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   return LMC_OK;
 }
 
-int lmc_encode_chunks_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
-                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
-                            lmc_stream_t stream) {
+}  // extern "C"
+
+// One body for the two fixed-width encodes.  `split_ok`: the entry point takes an LMC_PAGED_SPLIT source (encode_job_ok).
+static int encode_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                        const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                        lmc_stream_t stream, bool split_ok) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, false) || lmc_dtype_fp8(src->dtype) || !blobs || !sizes ||
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok) || lmc_dtype_fp8(src->dtype) || !blobs || !sizes ||
       ((uintptr_t)blobs & 15) || (blob_stride & 15))
     return LMC_ERR_INVALID;
   const int L = src->num_layers, H = src->num_heads, D = src->head_size;
@@ -761,10 +772,25 @@ int lmc_encode_chunks_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_be
   c->pn = 0;
   int rc;
   if ((rc = prof_mark(c, s))) return rc;
-  if (src->dtype == LMC_DTYPE_BF16) rc = launch_fixed_encode<LMC_DTYPE_BF16>(fa, s);
-  else rc = launch_fixed_encode<LMC_DTYPE_FP16>(fa, s);
+  const bool nhdb = src->paged_kind == LMC_PAGED_SPLIT;
+  if (src->dtype == LMC_DTYPE_BF16) rc = launch_fixed_encode<LMC_DTYPE_BF16>(fa, s, nhdb);
+  else rc = launch_fixed_encode<LMC_DTYPE_FP16>(fa, s, nhdb);
   if (rc) return rc;
   return prof_mark(c, s);
+}
+
+extern "C" {
+
+int lmc_encode_chunks_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                            lmc_stream_t stream) {
+  return encode_fixed(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream, false);
+}
+
+int lmc_encode_chunks_fixed_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                                  const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                                  lmc_stream_t stream) {
+  return encode_fixed(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream, true);
 }
 
 // ---- the layer-wise encode (include/lmc_hip.h; k_layers.h) ------------------------------------------------------------
@@ -981,14 +1007,19 @@ static void launch_decode(int dtype, int kind, dim3 grid, hipStream_t s, const D
 // One range of layers of a decode: k_decode over the streams of layers [l0, l0 + nl) of the job's chunks, then `ev`
 // (if any) recorded behind it.  The lock is not needed for the launch itself: the load paths call this with c->mu held.
 static int range_post(lmc_ctx* c, const lmc_kv_layout* dst, const lmc_range_post* post, int l0, int nl, hipStream_t s);
-// k_fixed_decode (LMC_MODEL_FIXED blobs) for a 16-bit destination of rows: a wave per stream, FIXED_DEC_WAVES per workgroup
+// k_fixed_decode (LMC_MODEL_FIXED blobs) for a 16-bit destination, rows or an LMC_PAGED_SPLIT cache: a wave per stream,
+// FIXED_DEC_WAVES per workgroup
 static void launch_fixed_decode(const lmc_kv_layout* dst, long long nstreams, hipStream_t s, const DecodeArgs& a) {
   FixedDecArgs fa;
   fa.d = a;
   fa.vec = layout_ok(dst) ? 1 : 0;  // rows that take 16-byte vectors of 8 channels: what the encoders ask of a source
   const dim3 grid((unsigned)((nstreams + FIXED_DEC_WAVES - 1) / FIXED_DEC_WAVES)), block(64 * FIXED_DEC_WAVES);
   const bool paged = dst->slot_mapping != nullptr;
-  if (dst->dtype == LMC_DTYPE_BF16) {
+  if (dst->paged_kind == LMC_PAGED_SPLIT) {
+    fa.vec = 0;  // (the kernel looks at the plane's own alignment: k_fixed.h)
+    if (dst->dtype == LMC_DTYPE_BF16) hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_BF16, DEC_PAGED_SPLIT>), grid, block, 0, s, fa);
+    else hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_FP16, DEC_PAGED_SPLIT>), grid, block, 0, s, fa);
+  } else if (dst->dtype == LMC_DTYPE_BF16) {
     if (paged) hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_BF16, DEC_PAGED_ROWS>), grid, block, 0, s, fa);
     else hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_BF16, DEC_ROWS>), grid, block, 0, s, fa);
   } else {
@@ -1057,13 +1088,15 @@ int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t 
 static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* post);
 
 // One body for the two schedules: the coded models' k_decode, or -- `fixed` -- k_fixed_decode for LMC_MODEL_FIXED blobs,
-// which fills 16-bit rows only (an LMC_PAGED_SPLIT cache is filled through a staged chunk and post->scatter_dst).
+// which fills 16-bit rows and -- `fixed_split`: lmc_decode_chunks_fixed_split_schedule -- a 16-bit LMC_PAGED_SPLIT cache
+// (lmc_decode_chunks_fixed_schedule keeps refusing one: such a cache is filled through a staged chunk and
+// post->scatter_dst there).
 static int decode_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
                            const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
                            const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
-                           lmc_stream_t stream, const lmc_range_post* post, bool fixed) {
+                           lmc_stream_t stream, const lmc_range_post* post, bool fixed, bool fixed_split = false) {
   DecodeArgs a;
-  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, !fixed);
+  int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, !fixed || fixed_split);
   if (rc) return rc;
   if (fixed && (lmc_dtype_fp8(dst->dtype) || max_blob_bytes < LMC_HEADER_BYTES)) return LMC_ERR_INVALID;
   if (!decode_blobs(a, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, blob_ptrs) || nranges < 1 || !layer_ends_h)
@@ -1093,6 +1126,14 @@ int lmc_decode_chunks_fixed_schedule(lmc_ctx* c, const void* const* blob_ptrs, u
                                      uint32_t* job_status, lmc_stream_t stream) {
   return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
                          job_status, stream, post, true);
+}
+
+int lmc_decode_chunks_fixed_split_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                           const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                           const int32_t* layer_ends_h, const lmc_event_t* events_h, const lmc_range_post* post,
+                                           uint32_t* job_status, lmc_stream_t stream) {
+  return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
+                         job_status, stream, post, true, true);
 }
 
 int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,

@@ -159,6 +159,7 @@ SYMBOLS = {
     "lmc_encode_chunks": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_encode_chunks_split": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_encode_chunks_fixed": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "lmc_encode_chunks_fixed_split": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_encode_layers_begin": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, ctypes.POINTER(_vp)]),
     "lmc_encode_layer": (ctypes.c_int, [_vp, _vp, _i32, _vp]),
     "lmc_encode_layers_finish": (ctypes.c_int, [_vp, _vp, _vp]),
@@ -170,6 +171,8 @@ SYMBOLS = {
                                                        ctypes.POINTER(RangePostStruct)]),
     "lmc_decode_chunks_fixed_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
                                                         ctypes.POINTER(RangePostStruct), _vp, _vp]),
+    "lmc_decode_chunks_fixed_split_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
+                                                              ctypes.POINTER(RangePostStruct), _vp, _vp]),
     "lmc_decode_symbols": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "lmc_store_chunks": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "lmc_load_chunks": (ctypes.c_int, [_vp, _vp, _vp, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -837,6 +840,15 @@ class Context:
                    chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
         return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
+    def encode_chunks_fixed_split(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
+                                  blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
+                                  status_ptr: Optional[int] = None) -> int:
+        """encode_chunks_fixed for any source it takes and a 16-bit PAGED_SPLIT ("NHDB") one of up to 1024 channels per
+        plane, read in place (lmc_encode_chunks_fixed_split)."""
+        self._call("lmc_encode_chunks_fixed_split", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end,
+                   chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
+        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+
     def encode_layers_begin(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
                             blobs_ptr: int, blob_stride: int, sizes_ptr: int, status_ptr: Optional[int] = None
                             ) -> Optional["LayerEncodeHandle"]:
@@ -906,6 +918,21 @@ class Context:
                                                      dst_tok0, chunk_tokens, n, ends, evs,
                                                      None if post is None else ctypes.byref(post), status_ptr, st),
               "lmc_decode_chunks_fixed_schedule")
+
+    def decode_chunks_fixed_split_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout,
+                                           dst_tok0: int, chunk_tokens: int, layer_ends, events,
+                                           post: Optional[RangePostStruct] = None, stream: Optional[int] = None,
+                                           status_ptr: Optional[int] = None) -> None:
+        """lmc_decode_chunks_fixed_split_schedule: decode_chunks_fixed_schedule for any destination it takes and a 16-bit
+        PAGED_SPLIT ("NHDB") one, stored into in place."""
+        n = len(layer_ends)
+        ends = layer_ends if isinstance(layer_ends, ctypes.Array) else (ctypes.c_int32 * n)(*layer_ends)
+        evs = events if events is None or isinstance(events, ctypes.Array) else (ctypes.c_void_p * n)(*[e.handle for e in events])
+        st = current_stream_ptr(dst.device) if stream is None else stream
+        check(lib().lmc_decode_chunks_fixed_split_schedule(self.handle, blob_ptrs, max_blob_bytes, nchunks,
+                                                           ctypes.byref(dst.struct), dst_tok0, chunk_tokens, n, ends, evs,
+                                                           None if post is None else ctypes.byref(post), status_ptr, st),
+              "lmc_decode_chunks_fixed_split_schedule")
 
     def store_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, host_arena_ptr: int,
                      host_cap: int, offsets_ptr: int, sizes_ptr: int, stream: Optional[int] = None,

@@ -636,7 +636,6 @@ class CacheGenDeviceCodec:
         self.pack_parts = max(1, min(16, int(os.environ.get("LMCACHE_AMD_PACK_PARTS", "8"))))
         self._layer_streams: List[torch.cuda.Stream] = []    # side streams of finished layer-wise encode jobs, for the next ones
         self._warned_wide_split = False                      # direct store of an NHDB cache with planes the split quantiser does not read
-        self._warned_fixed_split = False                     # direct store of an NHDB cache in the fixed-width model
         self._same_blobs: dict = {}                          # id(caller's list) -> (the list, its blobs' address tuple, largest blob)
         self._table_cache: dict = {}                         # blob-address tuple -> (device table, upload stream)
 
@@ -648,22 +647,17 @@ class CacheGenDeviceCodec:
         vLLM's ROCm paged-attention kernels, which has no rows at all -- is first brought into a contiguous vllm chunk on
         the device (lmc_copy_kv: element-wise for the former, k_copy_split.h's gather for the latter) and encoded from
         there.  direct: an "NHDB" cache with planes of at most 1024 channels goes to the encoder as it is
-        (lmc_encode_chunks_split and the stores read the split blocks: k_quantize.h); wider planes are staged all the same.
-        model "fixed": lmc_encode_chunks_fixed reads rows only, so a split source is staged whatever `direct` says."""
+        (lmc_encode_chunks_split, lmc_encode_chunks_fixed_split and the stores read the split blocks: k_quantize.h); wider
+        planes are staged all the same, whichever `model`."""
         if src.vector_readable():
             return src, tok_begin, tok_end
         if direct and src.struct.paged_kind == native.PAGED_SPLIT:
-            if model == "fixed":
-                if not self._warned_fixed_split:
-                    self._warned_fixed_split = True
-                    logger.warning("direct store from an NHDB cache: the fixed-width encoder reads rows only; staging "
-                                   "through lmc_copy_kv")
-            elif src.H * src.D <= 1024:
+            if src.H * src.D <= 1024:
                 return src, tok_begin, tok_end
-            elif not self._warned_wide_split:
+            if not self._warned_wide_split:
                 self._warned_wide_split = True
                 logger.warning("direct store from an NHDB cache: planes of %d channels are wider than the 1024 the split "
-                               "quantiser reads; staging through lmc_copy_kv", src.H * src.D)
+                               "encoders (coded and fixed-width) read; staging through lmc_copy_kv", src.H * src.D)
         n = tok_end - tok_begin
         with torch.cuda.device(self.device):
             chunk = torch.empty((src.L, 2, n, src.H, src.D), dtype=native.torch_dtype(src.dtype), device=src.device)
@@ -674,15 +668,15 @@ class CacheGenDeviceCodec:
                bins: Sequence[int], direct: bool = False, model: Optional[str] = None) -> EncodeJob:
         """Launch the fused encode of every chunk of [tok_begin, tok_end) on the CURRENT stream
         (so it is ordered after whatever produced the KV).  Asynchronous.  direct: see _readable.
-        model: None -- the entropy-coded blobs; "fixed" -- LMC_MODEL_FIXED (lmc_encode_chunks_fixed: fixed-width symbols,
-        for blobs that stay in HBM; 16-bit KV only)."""
+        model: None -- the entropy-coded blobs; "fixed" -- LMC_MODEL_FIXED (lmc_encode_chunks_fixed, for a split source
+        lmc_encode_chunks_fixed_split: fixed-width symbols, for blobs that stay in HBM; 16-bit KV only)."""
         if model not in (None, "fixed"):
             raise ValueError(f"unknown coder model {model!r} (None or 'fixed')")
         if model == "fixed" and native.elem_bytes(src.dtype) != 2:
             raise ValueError("the fixed-width model stores bf16 / fp16 KV only")
         src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end, direct, model)
         if model == "fixed":
-            encode_chunks = self.ctx.encode_chunks_fixed
+            encode_chunks = self.ctx.encode_chunks_fixed_split if src.struct.paged_kind == native.PAGED_SPLIT else self.ctx.encode_chunks_fixed
         else:
             encode_chunks = self.ctx.encode_chunks_split if src.struct.paged_kind == native.PAGED_SPLIT else self.ctx.encode_chunks
         L, H, D = src.L, src.H, src.D
@@ -883,8 +877,8 @@ class CacheGenDeviceCodec:
         early, large ones later (a launch of few layers does not fill the GPU, and every launch costs an event).
         post: a native.RangePost done to every range between its launch and its event, by the same C call
         (lmc_decode_chunks_schedule_post); its struct is filled here, per call -- the kept tables are not touched.
-        model "fixed": the blobs are LMC_MODEL_FIXED (lmc_decode_chunks_fixed_schedule; `dst` is 16-bit rows); the ranges,
-        their events and `post` are the same."""
+        model "fixed": the blobs are LMC_MODEL_FIXED (lmc_decode_chunks_fixed_schedule; `dst` is 16-bit rows, or a 16-bit
+        "NHDB" cache through lmc_decode_chunks_fixed_split_schedule); the ranges, their events and `post` are the same."""
         n = len(blobs)
         if n == 0:
             return None
@@ -934,9 +928,11 @@ class CacheGenDeviceCodec:
                 ends = [l1 for _, l1 in ranges]
                 evs = [native.NativeEvent() for _ in ranges]
                 if model == "fixed":
-                    self.ctx.decode_chunks_fixed_schedule(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
-                                                          None if post is None else post.struct(*post.window(dst, dst_tok0, n, chunk_tokens)),
-                                                          stream=cur.cuda_stream, status_ptr=st_ptr)
+                    split = dst.struct.paged_kind == native.PAGED_SPLIT
+                    decode_fixed = self.ctx.decode_chunks_fixed_split_schedule if split else self.ctx.decode_chunks_fixed_schedule
+                    decode_fixed(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
+                                 None if post is None else post.struct(*post.window(dst, dst_tok0, n, chunk_tokens)),
+                                 stream=cur.cuda_stream, status_ptr=st_ptr)
                 elif post is None:
                     self.ctx.decode_chunks_schedule(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
                                                     stream=cur.cuda_stream, status_ptr=st_ptr)
