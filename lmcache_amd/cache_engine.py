@@ -188,10 +188,7 @@ class LMCacheEngine:
                   The fixed-width HBM tier (local_serde="cachegen-fixed") reads the split blocks with its one kernel
                   (lmc_encode_chunks_fixed_split; k_fixed.h) under the same 1024-channel limit: no gather there either,
                   and on block-ordered slots less time as well (profiles/fixed_model.md)."""
-        assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
-        assert len(tokens.shape) == 1, f"Invalid shape of tokens: {tokens.shape}"
-        assert len(kv_caches) > 0, "Empty kv_caches"
-        assert len(tokens) == slot_mapping.numel(), "one slot per token"
+        self._check_paged_store(tokens, kv_caches, slot_mapping)
         self._store_from(tokens, lambda: native.KVLayout.paged(kv_caches, slot_mapping, block_size, layout),
                          skip_existing, blocking, direct=direct and layout == "NHDB")
 
@@ -219,18 +216,12 @@ class LMCacheEngine:
         gather needs every layer.  save_layer is then a no-op, layer_event(l) is None (nothing has been read: the cache
         must keep every layer until finish), and finish() runs today's store_paged path for the keys resolved here.
         That is correct, not layer-wise -- the rule retrieve_into_paged_layerwise states for its side; logged once."""
-        assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
-        assert len(tokens.shape) == 1, f"Invalid shape of tokens: {tokens.shape}"
-        assert len(kv_caches) > 0, "Empty kv_caches"
-        assert len(tokens) == slot_mapping.numel(), "one slot per token"
+        self._check_paged_store(tokens, kv_caches, slot_mapping)
         fmt, cs, ntok = self.metadata.fmt, self.chunk_size, len(tokens)
-        chunk_hashes = self._prefix_hashes_of(tokens)
-        first = 0
-        if skip_existing:
-            first = self._first_missing_chunk(chunk_hashes, fmt)
-            if first is None:
-                return LayerwiseStore(self, None, [], None, 0, 0, False)
-        keys = [self._make_key(h, fmt) for h in chunk_hashes[first:]]
+        plan = self._plan_store(tokens, skip_existing)
+        if plan is None:
+            return LayerwiseStore(self, None, [], None, 0, 0, False)
+        first, keys = plan
         direct = direct and layout == "NHDB"
         src = native.KVLayout.paged(kv_caches, slot_mapping, block_size, layout)
         put = None
@@ -244,25 +235,38 @@ class LMCacheEngine:
                         "(logged once)")
         return LayerwiseStore(self, put, keys, src, first * cs, ntok, direct)
 
+    def _check_paged_store(self, tokens: torch.Tensor, kv_caches, slot_mapping: torch.Tensor) -> None:
+        assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
+        assert len(tokens.shape) == 1, f"Invalid shape of tokens: {tokens.shape}"
+        assert len(kv_caches) > 0, "Empty kv_caches"
+        assert len(tokens) == slot_mapping.numel(), "one slot per token"
+
+    def _plan_store(self, tokens: torch.Tensor, skip_existing: bool) -> Optional[Tuple[int, List[CacheEngineKey]]]:
+        """Hashes, the skip-existing scan and the keys of a store -> (first chunk to store, its keys on), None: all present."""
+        fmt = self.metadata.fmt
+        chunk_hashes = self._prefix_hashes_of(tokens)
+        first = self._first_missing_chunk(chunk_hashes, fmt) if skip_existing else 0
+        if first is None:
+            return None
+        return first, [self._make_key(h, fmt) for h in chunk_hashes[first:]]
+
+    def _put_range(self, keys, src: native.KVLayout, t0: int, t1: int, blocking: bool, direct: bool) -> int:
+        """Tokens [t0, t1) of `src` under `keys`: read in place by a backend that takes a layout, else gathered -> chunks stored."""
+        fmt, kw = self.metadata.fmt, {"direct": True} if direct else {}
+        if getattr(self.engine_, "supports_kv_layout", False):
+            return self.engine_.put_kv_range(keys, src, fmt, t0, t1, self.chunk_size, blocking=blocking, **kw)
+        return self.engine_.batched_put(self._gather_chunks(keys, src, fmt, t0, t1), blocking=blocking)
+
     def _store_from(self, tokens: torch.Tensor, make_src, skip_existing: bool, blocking: bool, direct: bool = False) -> None:
         t_start = time.perf_counter()
-        fmt = self.metadata.fmt
-        ntok = len(tokens)
-        cs = self.chunk_size
-        chunk_hashes = self._prefix_hashes_of(tokens)
-        first = 0
-        if skip_existing:
-            first = self._first_missing_chunk(chunk_hashes, fmt)
-            if first is None:
-                logger.info("Stored/updated 0 chunks (all present)")
-                return
-        keys = [self._make_key(h, fmt) for h in chunk_hashes[first:]]
+        plan = self._plan_store(tokens, skip_existing)
+        if plan is None:
+            logger.info("Stored/updated 0 chunks (all present)")
+            return
+        first, keys = plan
         src = make_src()
         t_plan = time.perf_counter()
-        if getattr(self.engine_, "supports_kv_layout", False):
-            n = self.engine_.put_kv_range(keys, src, fmt, first * cs, ntok, cs, blocking=blocking, **({"direct": True} if direct else {}))
-        else:
-            n = self.engine_.batched_put(self._gather_chunks(keys, src, fmt, first * cs, ntok), blocking=blocking)
+        n = self._put_range(keys, src, first * self.chunk_size, len(tokens), blocking, direct)
         logger.info("Stored/updated %d chunks, total time %.4fs, planning %.4fs", n,
                     time.perf_counter() - t_start, t_plan - t_start)
 
@@ -285,21 +289,12 @@ class LMCacheEngine:
     def retrieve(self, tokens: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Tuple[KVCache, torch.Tensor]:
         """Prefix hits only; `mask` (suffix mask) marks the tokens whose KV is wanted.
         Returns (per-layer (K, V) tuple or (), ret_mask)."""
-        fmt = self.metadata.fmt
-        tdim = _token_dim(fmt)
-        box = {}
-
-        def make_dst(nret, L, H, D, dtype, dev):
-            shape = (L, 2, nret, H, D) if fmt == "vllm" else (L, 2, H, nret, D)
-            box["blob"] = torch.empty(shape, dtype=dtype, device=dev)
-            return native.KVLayout.from_chunk(box["blob"], fmt)
-
-        got, ret_mask = self._retrieve_into(tokens, mask, make_dst)
+        target = _DenseTarget(self.metadata.fmt)
+        got, ret_mask = self._retrieve_into(tokens, mask, target.make_dst)
         if got == 0:
             return (), ret_mask
-        blob = box["blob"].narrow(2 if fmt == "vllm" else 3, 0, got)
-        ret = self._blob_to_tuple_kv(blob)
-        assert ret[0][0].shape[tdim] == got
+        ret = self._blob_to_tuple_kv(target.head(got))
+        assert ret[0][0].shape[_token_dim(self.metadata.fmt)] == got
         return ret, ret_mask
 
     @_lmcache_nvtx_annotate
@@ -337,43 +332,13 @@ class LMCacheEngine:
                 scatter for "NHDB".  Nothing is launched on a miss.  The cache must be bf16 / fp16 and rope.rot_dim at
                 most its head size (ValueError before anything is queued).  A per-token delta outside the table leaves
                 that token's keys as stored and raises LMC_STATUS_BAD_POSITION in the context's status word (a delta
-                tensor that lives on the CPU is checked here instead: ValueError)."""
-        assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
-        assert len(tokens) == slot_mapping.numel(), "one slot per token"
-        num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
-        direct = self._direct_retrieve(direct, layout, rope)
-        if rope is not None:
-            if direct and layout == "NHDB":
-                raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
-                                 "not address an \"NHDB\" cache); use the staged retrieve")
-            self._check_rope(rope, kv_caches, layout, len(tokens))
-        staged, made = {}, {}
-
-        def make_dst(nret, L, H, D, dtype, dev):
-            dst = native.KVLayout.paged(kv_caches, slot_mapping[num_skip_tok:num_skip_tok + nret], block_size, layout)
-            assert dst.L == L and native.torch_dtype(dst.dtype) == dtype, "cache geometry / dtype differs from the stored chunks"
-            if layout != "NHDB" or direct:
-                assert layout != "NHDB" or (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
-                made["dst"] = dst
-                return dst
-            assert (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
-            staged["dst"] = dst
-            staged["chunk"] = torch.empty((L, 2, nret, H, D), dtype=dtype, device=dst.device)
-            return native.KVLayout.from_chunk(staged["chunk"], "vllm")
-
-        got, ret_mask = self._retrieve_into(tokens, mask, make_dst)
-        if got > 0 and (staged or rope is not None):
-            dst = staged["dst"] if staged else made["dst"]
-            rows = native.KVLayout.from_chunk(staged["chunk"], "vllm") if staged else dst  # where the tokens lie as rows
-            with torch.cuda.device(dst.device):
-                ctx = native.get_context(dst.device.index)
-                if rope is not None:
-                    ctx.rope_shift(rows, 0, got, rope.cos_sin.to(dst.device), rope.rot_dim, rope.is_neox,
-                                   delta=0 if isinstance(rope.delta, torch.Tensor) else rope.delta,
-                                   deltas=rope.deltas_for(num_skip_tok, got, len(tokens), dst.device))
-                if staged:
-                    ctx.copy_kv(rows, 0, got, dst, 0)
-        return ret_mask
+                tensor that lives on the CPU is checked here instead: ValueError).  A cos_sin that is not a contiguous
+                device fp32 table once moved to the cache's device is refused when the destination is made (ValueError
+                of native.RangePost), before the decode is queued."""
+        target = _PagedTarget(self, tokens, kv_caches, slot_mapping, block_size, layout, mask, rope, direct)
+        # (without jobs_out no decode job takes the post-ops: _retrieve_into queues them itself, native.RangePost.apply
+        # over tokens [0, got) behind the last write, and only when the retrieve did not miss)
+        return self._retrieve_into(tokens, mask, target.make_dst, post=target.post)[1]
 
     def _direct_retrieve(self, direct: bool, layout: str, rope: Optional[RopeShift] = None) -> bool:
         """`direct` as the backend honours it.  The fixed-width HBM tier (local_serde="cachegen-fixed") decodes straight
@@ -421,31 +386,12 @@ class LMCacheEngine:
         cannot cut their retrieve by layer return one event that covers everything.  Call finish() before
         trusting the KV for good: it waits for the decode and raises if a stored blob was corrupt.
         layers_per_launch: a range size, or a schedule of range sizes whose last entry repeats, e.g. (2, 6, 24)."""
-        fmt = self.metadata.fmt
-        box, jobs = {}, []
-
-        def make_dst(nret, L, H, D, dtype, dev):
-            shape = (L, 2, nret, H, D) if fmt == "vllm" else (L, 2, H, nret, D)
-            box["blob"] = torch.empty(shape, dtype=dtype, device=dev)
-            box["L"] = L
-            return native.KVLayout.from_chunk(box["blob"], fmt)
-
-        got, ret_mask = self._retrieve_into(tokens, mask, make_dst, layers_per_launch=layers_per_launch, jobs_out=jobs)
+        target, jobs = _DenseTarget(self.metadata.fmt), []
+        got, ret_mask = self._retrieve_into(tokens, mask, target.make_dst, layers_per_launch=layers_per_launch, jobs_out=jobs)
         if got == 0:
             return LayerwiseRetrieval((), ret_mask, [], [])
-        blob = box["blob"].narrow(2 if fmt == "vllm" else 3, 0, got)
-        # one list of (first layer after the range, event) per decode job: a retrieve that spans several stores is
-        # several runs (local_backend.get_kv_range), i.e. several jobs, and layer l is complete when EVERY job's range
-        # that holds l is (round 4 kept only the last job's events and was right only because all jobs share a stream)
-        event_sets = [list(job.layer_events) for _, job in jobs if job is not None and job.layer_events]
-        if not event_sets or len(event_sets) < len(jobs):
-            # some run of the retrieve (or all of it) carries no per-layer events -- a backend that finished or queued its
-            # part in one piece: ONE event recorded now on the current stream, behind everything _retrieve_into queued,
-            # covers those runs for every layer (ADVICE r05: wait_layer used to skip them, which was right only while
-            # every run shared this stream AND stood in front of the other runs' events)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(blob.device))
-            event_sets.append([(box["L"], ev)])
+        blob = target.head(got)
+        event_sets = self._event_sets(jobs, target.L, blob.device)
         # (the per-layer (K, V) views are made when `kv` is first read: 33 tensor calls that need not stand between the
         # launches above and the caller's first wait_layer)
         return LayerwiseRetrieval(lambda: self._blob_to_tuple_kv(blob), ret_mask, event_sets[-1], jobs, event_sets)
@@ -479,47 +425,30 @@ class LMCacheEngine:
         everything, then the post-ops for all layers behind it, and ONE event covers every layer: correct, not layer-wise.
         Call finish() before trusting the cache for good: it waits for the decode and raises NativeError if a stored
         blob was corrupt -- the slots of the call's tokens may hold garbage then, as for retrieve_into_paged(direct=True)."""
-        assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
-        assert len(tokens) == slot_mapping.numel(), "one slot per token"
-        num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
-        direct = self._direct_retrieve(direct, layout, rope)
-        if rope is not None:
-            if direct and layout == "NHDB":
-                raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
-                                 "not address an \"NHDB\" cache); use the staged retrieve")
-            self._check_rope(rope, kv_caches, layout, len(tokens))
-        box, jobs = {}, []
-
-        def make_dst(nret, L, H, D, dtype, dev):
-            dst = native.KVLayout.paged(kv_caches, slot_mapping[num_skip_tok:num_skip_tok + nret], block_size, layout)
-            assert dst.L == L and native.torch_dtype(dst.dtype) == dtype, "cache geometry / dtype differs from the stored chunks"
-            staged = layout == "NHDB" and not direct
-            assert layout != "NHDB" or (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
-            rows = dst
-            if staged:
-                box["chunk"] = torch.empty((L, 2, nret, H, D), dtype=dtype, device=dst.device)
-                rows = native.KVLayout.from_chunk(box["chunk"], "vllm")
-            box["L"], box["dev"] = L, dst.device
-            if staged or rope is not None:
-                box["post"] = native.RangePost(
-                    cos_sin=None if rope is None else rope.cos_sin.to(dst.device),
-                    rot_dim=0 if rope is None else rope.rot_dim, is_neox=rope is None or rope.is_neox,
-                    delta=0 if rope is None or isinstance(rope.delta, torch.Tensor) else rope.delta,
-                    deltas=None if rope is None else rope.deltas_for(num_skip_tok, nret, len(tokens), dst.device),
-                    scatter_dst=dst if staged else None)
-            return rows
-
-        got, ret_mask = self._retrieve_into(tokens, mask, make_dst, layers_per_launch=layers_per_launch, jobs_out=jobs,
-                                            post=lambda: box.get("post"))
+        target, jobs = _PagedTarget(self, tokens, kv_caches, slot_mapping, block_size, layout, mask, rope, direct), []
+        got, ret_mask = self._retrieve_into(tokens, mask, target.make_dst, layers_per_launch=layers_per_launch, jobs_out=jobs,
+                                            post=target.post)
         if got == 0:
             return LayerwiseRetrieval((), ret_mask, [], [])
-        # (the events of every decode job, or one event behind everything: as retrieve_layerwise)
+        event_sets = self._event_sets(jobs, target.L, target.device)
+        return LayerwiseRetrieval((), ret_mask, event_sets[-1], jobs, event_sets, hold=target.hold)
+
+    @staticmethod
+    def _event_sets(jobs: list, L: int, device) -> list:
+        """The events of a layer-wise retrieve: one list of (first layer after the range, event) per decode job.  A retrieve
+        that spans several stores is several runs (local_backend.get_kv_range), i.e. several jobs, and layer l is complete
+        when EVERY job's range that holds l is (round 4 kept only the last job's events and was right only because all
+        jobs share a stream)."""
         event_sets = [list(job.layer_events) for _, job in jobs if job is not None and job.layer_events]
         if not event_sets or len(event_sets) < len(jobs):
+            # some run of the retrieve (or all of it) carries no per-layer events -- a backend that finished or queued its
+            # part in one piece: ONE event recorded now on the current stream, behind everything _retrieve_into queued,
+            # covers those runs for every layer (ADVICE r05: wait_layer used to skip them, which was right only while
+            # every run shared this stream AND stood in front of the other runs' events)
             ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(box["dev"]))
-            event_sets.append([(box["L"], ev)])
-        return LayerwiseRetrieval((), ret_mask, event_sets[-1], jobs, event_sets, hold=(box.get("chunk"), box.get("post")))
+            ev.record(torch.cuda.current_stream(device))
+            event_sets.append([(L, ev)])
+        return event_sets
 
     def _retrieve_into(self, tokens: torch.Tensor, mask: Optional[torch.Tensor], make_dst,
                        layers_per_launch: Optional[int] = None, jobs_out: Optional[list] = None,
@@ -636,6 +565,67 @@ class LMCacheEngine:
         self.engine_.close()
 
 
+class _DenseTarget:
+    """Where retrieve and retrieve_layerwise write: a blob of the engine's format, made once the geometry is known."""
+
+    def __init__(self, fmt: str):
+        self.fmt, self.blob, self.L = fmt, None, None
+
+    def make_dst(self, nret, L, H, D, dtype, dev) -> native.KVLayout:
+        shape = (L, 2, nret, H, D) if self.fmt == "vllm" else (L, 2, H, nret, D)
+        self.blob, self.L = torch.empty(shape, dtype=dtype, device=dev), L
+        return native.KVLayout.from_chunk(self.blob, self.fmt)
+
+    def head(self, got: int) -> torch.Tensor:
+        return self.blob.narrow(2 if self.fmt == "vllm" else 3, 0, got)
+
+
+class _PagedTarget:
+    """Where retrieve_into_paged and retrieve_into_paged_layerwise write.  Constructing it is what both refuse before
+    anything is queued; make_dst is _retrieve_into's destination -- the paged cache itself, or for a staged "NHDB" retrieve
+    a [L,2,nret,H,D] chunk of rows -- and post() the native.RangePost that finishes it (the rotation of `rope`, the scatter
+    of the staged chunk), None when there is nothing to do."""
+
+    def __init__(self, engine: "LMCacheEngine", tokens, kv_caches, slot_mapping, block_size: int, layout: str, mask, rope, direct):
+        assert engine.metadata.fmt == "vllm", "paged KV is a vLLM layout"
+        assert len(tokens) == slot_mapping.numel(), "one slot per token"
+        self.num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
+        direct = engine._direct_retrieve(direct, layout, rope)
+        if rope is not None:
+            if direct and layout == "NHDB":
+                raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
+                                 "not address an \"NHDB\" cache); use the staged retrieve")
+            engine._check_rope(rope, kv_caches, layout, len(tokens))
+        self._cache = (kv_caches, slot_mapping, block_size, layout)
+        self.ntokens, self.rope, self.staged = len(tokens), rope, layout == "NHDB" and not direct
+        self.L = self.device = self._post = None
+        self.hold = (None, None)  # what a caller that returns before the kernels have run keeps alive
+
+    def make_dst(self, nret, L, H, D, dtype, dev) -> native.KVLayout:
+        kv_caches, slot_mapping, block_size, layout = self._cache
+        skip, rope = self.num_skip_tok, self.rope
+        dst = native.KVLayout.paged(kv_caches, slot_mapping[skip:skip + nret], block_size, layout)
+        assert dst.L == L and native.torch_dtype(dst.dtype) == dtype, "cache geometry / dtype differs from the stored chunks"
+        assert layout != "NHDB" or (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
+        self.L, self.device = L, dst.device
+        rows, chunk = dst, None  # where the tokens lie as rows
+        if self.staged:
+            chunk = torch.empty((L, 2, nret, H, D), dtype=dtype, device=dst.device)
+            rows = native.KVLayout.from_chunk(chunk, "vllm")
+        if self.staged or rope is not None:
+            self._post = native.RangePost(
+                cos_sin=None if rope is None else rope.cos_sin.to(dst.device),
+                rot_dim=0 if rope is None else rope.rot_dim, is_neox=rope is None or rope.is_neox,
+                delta=0 if rope is None or isinstance(rope.delta, torch.Tensor) else rope.delta,
+                deltas=None if rope is None else rope.deltas_for(skip, nret, self.ntokens, dst.device),
+                scatter_dst=dst if self.staged else None)
+        self.hold = (chunk, self._post)
+        return rows
+
+    def post(self) -> Optional[native.RangePost]:
+        return self._post
+
+
 class LayerwiseStore:
     """What store_paged_layerwise returns.  `layerwise`: the encode runs per layer (else: in one piece at finish, or --
     nothing to store -- never); `nchunks`: chunks that will be stored."""
@@ -673,11 +663,8 @@ class LayerwiseStore:
         eng, (t0, t1) = self._engine, self._range
         if self._put is not None:
             n = self._put.finish(blocking=blocking)
-        elif getattr(eng.engine_, "supports_kv_layout", False):
-            n = eng.engine_.put_kv_range(self._keys, self._src, eng.metadata.fmt, t0, t1, eng.chunk_size, blocking=blocking,
-                                         **({"direct": True} if self._direct else {}))
         else:
-            n = eng.engine_.batched_put(eng._gather_chunks(self._keys, self._src, eng.metadata.fmt, t0, t1), blocking=blocking)
+            n = eng._put_range(self._keys, self._src, t0, t1, blocking, self._direct)
         self._src = None
         return n
 

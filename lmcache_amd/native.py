@@ -205,6 +205,11 @@ SYMBOLS = {
     "lmc_fixed_blob_info": (ctypes.c_int, [_vp, _sz, ctypes.POINTER(BlobHeader)]),
 }
 
+# where the lmc_range_post pointer stands among the last three arguments of the symbols that take one ("status, stream,
+# post" or "post, status, stream"): read off the argument types above
+_RP = ctypes.POINTER(RangePostStruct)
+_POST_SLOT = {name: args.index(_RP) - (len(args) - 3) for name, (_, args) in SYMBOLS.items() if _RP in args}
+
 ENCODE_PATHS = {"auto": 0, "two_kernels": 1, "fused": 2}  # LMC_ENCODE_PATH_*
 ERR_INVALID = -1      # LMC_ERR_INVALID
 NOT_LAYERWISE = 1     # LMC_NOT_LAYERWISE: lmc_encode_layers_begin found the job not eligible (no error, no job)
@@ -672,8 +677,8 @@ class RangePost:
 
     def apply(self, ctx: "Context", dst: "KVLayout", tok_begin: int, ntok: int) -> None:
         """The same work from Python, for ALL layers of destination tokens [tok_begin, +ntok), on the current stream:
-        lmc_rope_shift on the rows, then lmc_copy_kv into scatter_dst -- what retrieve_into_paged queues.  For the
-        tiers whose decode is not cut by the C side."""
+        lmc_rope_shift on the rows, then lmc_copy_kv into scatter_dst.  For retrieve_into_paged, and for the tiers whose
+        decode is not cut by the C side."""
         if self.cos_sin is not None:
             ctx.rope_shift(dst, tok_begin, ntok, self.cos_sin, self.rot_dim, self.is_neox, delta=self.delta,
                            deltas=None if self.deltas is None else self.deltas[tok_begin:tok_begin + ntok])
@@ -815,39 +820,42 @@ class Context:
         self._call("lmc_calculate_cdf", sym.device, stream, sym.data_ptr(), P, T, C, max_bins, out.data_ptr())
         return out
 
+    def _encode_job(self, symbol: str, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, blobs_ptr: int,
+                    blob_stride: int, sizes_ptr: int, stream: Optional[int], status_ptr: Optional[int]) -> int:
+        """The marshalling of the lmc_encode_chunks* exports and lmc_store_pack (one argument list) -> the job's chunks."""
+        self._call(symbol, src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens, self._bins(bins),
+                   blobs_ptr, blob_stride, sizes_ptr, status_ptr)
+        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+
     def encode_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
                       blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
                       status_ptr: Optional[int] = None) -> int:
         """status_ptr: device-accessible uint32 (pinned host) that receives THIS job's LMC_STATUS_* bits
         (None: the context's sticky word)."""
-        self._call("lmc_encode_chunks", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
-                   self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
-        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+        return self._encode_job("lmc_encode_chunks", src, tok_begin, tok_end, chunk_tokens, bins, blobs_ptr, blob_stride,
+                                sizes_ptr, stream, status_ptr)
 
     def encode_chunks_split(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
                             blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
                             status_ptr: Optional[int] = None) -> int:
         """encode_chunks for any source it takes and a PAGED_SPLIT ("NHDB") one, read in place (lmc_encode_chunks_split)."""
-        self._call("lmc_encode_chunks_split", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end,
-                   chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
-        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+        return self._encode_job("lmc_encode_chunks_split", src, tok_begin, tok_end, chunk_tokens, bins, blobs_ptr, blob_stride,
+                                sizes_ptr, stream, status_ptr)
 
     def encode_chunks_fixed(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
                             blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
                             status_ptr: Optional[int] = None) -> int:
         """encode_chunks with the blobs in the fixed-width model (lmc_encode_chunks_fixed): sizes are fixed_blob_bytes."""
-        self._call("lmc_encode_chunks_fixed", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end,
-                   chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
-        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+        return self._encode_job("lmc_encode_chunks_fixed", src, tok_begin, tok_end, chunk_tokens, bins, blobs_ptr, blob_stride,
+                                sizes_ptr, stream, status_ptr)
 
     def encode_chunks_fixed_split(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
                                   blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
                                   status_ptr: Optional[int] = None) -> int:
         """encode_chunks_fixed for any source it takes and a 16-bit PAGED_SPLIT ("NHDB") one of up to 1024 channels per
         plane, read in place (lmc_encode_chunks_fixed_split)."""
-        self._call("lmc_encode_chunks_fixed_split", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end,
-                   chunk_tokens, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
-        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+        return self._encode_job("lmc_encode_chunks_fixed_split", src, tok_begin, tok_end, chunk_tokens, bins, blobs_ptr,
+                                blob_stride, sizes_ptr, stream, status_ptr)
 
     def encode_layers_begin(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
                             blobs_ptr: int, blob_stride: int, sizes_ptr: int, status_ptr: Optional[int] = None
@@ -874,50 +882,47 @@ class Context:
         self._call("lmc_decode_chunks_layers", dst.device, stream, blob_ptrs, max_blob_bytes, nchunks,
                    ctypes.byref(dst.struct), dst_tok0, chunk_tokens, layer_begin, layer_count, status_ptr)
 
+    def _call_post(self, symbol: str, device, stream: Optional[int], status_ptr: Optional[int], post, *args) -> None:
+        """_call for the symbols that end in status, stream and -- some -- a post pointer, in the order `symbol` declares them."""
+        tail = [status_ptr, current_stream_ptr(device) if stream is None else stream]
+        if symbol in _POST_SLOT:
+            tail.insert(_POST_SLOT[symbol], None if post is None else ctypes.byref(post))
+        else:
+            assert post is None, f"{symbol} takes no lmc_range_post"
+        check(getattr(lib(), symbol)(self.handle, *args, *tail), symbol)
+
+    def _schedule(self, symbol: str, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
+                  chunk_tokens: int, layer_ends, events, post, stream: Optional[int], status_ptr: Optional[int]) -> None:
+        """The marshalling of the four lmc_decode_chunks*_schedule* exports; layer_ends / events as decode_chunks_schedule."""
+        n = len(layer_ends)
+        ends = layer_ends if isinstance(layer_ends, ctypes.Array) else (ctypes.c_int32 * n)(*layer_ends)
+        evs = events if events is None or isinstance(events, ctypes.Array) else (ctypes.c_void_p * n)(*[e.handle for e in events])
+        self._call_post(symbol, dst.device, stream, status_ptr, post, blob_ptrs, max_blob_bytes, nchunks,
+                        ctypes.byref(dst.struct), dst_tok0, chunk_tokens, n, ends, evs)
+
     def decode_chunks_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                                chunk_tokens: int, layer_ends, events, stream: Optional[int] = None,
                                status_ptr: Optional[int] = None) -> None:
         """lmc_decode_chunks_schedule: one launch per range of layers [layer_ends[i - 1], layer_ends[i]) and one event
         record behind each (events: NativeEvent objects), in ONE call.  layer_ends / events may be prebuilt ctypes arrays
         (a cached retrieval plan passes the same ones every time)."""
-        if isinstance(layer_ends, ctypes.Array):
-            ends, n = layer_ends, len(layer_ends)
-        else:
-            n = len(layer_ends)
-            ends = (ctypes.c_int32 * n)(*layer_ends)
-        if events is None or isinstance(events, ctypes.Array):
-            evs = events
-        else:
-            evs = (ctypes.c_void_p * n)(*[e.handle for e in events])
-        self._call("lmc_decode_chunks_schedule", dst.device, stream, blob_ptrs, max_blob_bytes, nchunks,
-                   ctypes.byref(dst.struct), dst_tok0, chunk_tokens, n, ends, evs, status_ptr)
+        self._schedule("lmc_decode_chunks_schedule", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens,
+                       layer_ends, events, None, stream, status_ptr)
 
     def decode_chunks_schedule_post(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                                     chunk_tokens: int, layer_ends, events, post: Optional[RangePostStruct],
                                     stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
         """lmc_decode_chunks_schedule_post: decode_chunks_schedule with `post` (RangePost.struct) done to every range
         between its launch and its event, still ONE call.  post None is decode_chunks_schedule."""
-        n = len(layer_ends)
-        ends = layer_ends if isinstance(layer_ends, ctypes.Array) else (ctypes.c_int32 * n)(*layer_ends)
-        evs = events if events is None or isinstance(events, ctypes.Array) else (ctypes.c_void_p * n)(*[e.handle for e in events])
-        st = current_stream_ptr(dst.device) if stream is None else stream
-        check(lib().lmc_decode_chunks_schedule_post(self.handle, blob_ptrs, max_blob_bytes, nchunks, ctypes.byref(dst.struct),
-                                                    dst_tok0, chunk_tokens, n, ends, evs, status_ptr, st,
-                                                    None if post is None else ctypes.byref(post)),
-              "lmc_decode_chunks_schedule_post")
+        self._schedule("lmc_decode_chunks_schedule_post", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens,
+                       layer_ends, events, post, stream, status_ptr)
 
     def decode_chunks_fixed_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                                      chunk_tokens: int, layer_ends, events, post: Optional[RangePostStruct] = None,
                                      stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
         """lmc_decode_chunks_fixed_schedule: decode_chunks_schedule_post for LMC_MODEL_FIXED blobs (post None: no post-op)."""
-        n = len(layer_ends)
-        ends = layer_ends if isinstance(layer_ends, ctypes.Array) else (ctypes.c_int32 * n)(*layer_ends)
-        evs = events if events is None or isinstance(events, ctypes.Array) else (ctypes.c_void_p * n)(*[e.handle for e in events])
-        st = current_stream_ptr(dst.device) if stream is None else stream
-        check(lib().lmc_decode_chunks_fixed_schedule(self.handle, blob_ptrs, max_blob_bytes, nchunks, ctypes.byref(dst.struct),
-                                                     dst_tok0, chunk_tokens, n, ends, evs,
-                                                     None if post is None else ctypes.byref(post), status_ptr, st),
-              "lmc_decode_chunks_fixed_schedule")
+        self._schedule("lmc_decode_chunks_fixed_schedule", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens,
+                       layer_ends, events, post, stream, status_ptr)
 
     def decode_chunks_fixed_split_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout,
                                            dst_tok0: int, chunk_tokens: int, layer_ends, events,
@@ -925,14 +930,8 @@ class Context:
                                            status_ptr: Optional[int] = None) -> None:
         """lmc_decode_chunks_fixed_split_schedule: decode_chunks_fixed_schedule for any destination it takes and a 16-bit
         PAGED_SPLIT ("NHDB") one, stored into in place."""
-        n = len(layer_ends)
-        ends = layer_ends if isinstance(layer_ends, ctypes.Array) else (ctypes.c_int32 * n)(*layer_ends)
-        evs = events if events is None or isinstance(events, ctypes.Array) else (ctypes.c_void_p * n)(*[e.handle for e in events])
-        st = current_stream_ptr(dst.device) if stream is None else stream
-        check(lib().lmc_decode_chunks_fixed_split_schedule(self.handle, blob_ptrs, max_blob_bytes, nchunks,
-                                                           ctypes.byref(dst.struct), dst_tok0, chunk_tokens, n, ends, evs,
-                                                           None if post is None else ctypes.byref(post), status_ptr, st),
-              "lmc_decode_chunks_fixed_split_schedule")
+        self._schedule("lmc_decode_chunks_fixed_split_schedule", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0,
+                       chunk_tokens, layer_ends, events, post, stream, status_ptr)
 
     def store_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, host_arena_ptr: int,
                      host_cap: int, offsets_ptr: int, sizes_ptr: int, stream: Optional[int] = None,
@@ -953,9 +952,8 @@ class Context:
     def store_pack(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, pack_ptr: int, pack_cap: int,
                    sizes_ptr: int, stream: Optional[int] = None, status_ptr: Optional[int] = None) -> int:
         """lmc_store_pack: encode + the job's blobs transposed plane-major into one region, no host wait."""
-        self._call("lmc_store_pack", src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
-                   self._bins(bins), pack_ptr, pack_cap, sizes_ptr, status_ptr)
-        return self._nchunks(tok_begin, tok_end, chunk_tokens)
+        return self._encode_job("lmc_store_pack", src, tok_begin, tok_end, chunk_tokens, bins, pack_ptr, pack_cap, sizes_ptr,
+                                stream, status_ptr)
 
     def store_pack_parts(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, pack_ptr: int,
                          pack_cap: int, sizes_ptr: int, nparts: int, part_info_ptr: int, part_events,
@@ -973,17 +971,15 @@ class Context:
                   status_ptr: Optional[int] = None) -> None:
         """lmc_load_pack: chunks [chunk_begin, chunk_begin + nchunks) (nchunks 0 = all that follow) of a pack in pinned
         host memory -> decoded KV, one transfer and one decode per range of layers."""
-        self._call("lmc_load_pack", dst.device, stream, pack_ptr, pack_bytes, chunk_begin, nchunks, ctypes.byref(dst.struct),
-                   dst_tok0, layers_per_range, range_events_ptr, status_ptr)
+        self._call_post("lmc_load_pack", dst.device, stream, status_ptr, None, pack_ptr, pack_bytes, chunk_begin, nchunks,
+                        ctypes.byref(dst.struct), dst_tok0, layers_per_range, range_events_ptr)
 
     def load_pack_post(self, pack_ptr: int, pack_bytes: int, chunk_begin: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                        layers_per_range: int, range_events_ptr: Optional[int], post: Optional[RangePostStruct],
                        stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
         """lmc_load_pack_post: load_pack with `post` (RangePost.struct) done to every range between its decode and its event."""
-        st = current_stream_ptr(dst.device) if stream is None else stream
-        check(lib().lmc_load_pack_post(self.handle, pack_ptr, pack_bytes, chunk_begin, nchunks, ctypes.byref(dst.struct), dst_tok0,
-                                       layers_per_range, range_events_ptr, status_ptr, st,
-                                       None if post is None else ctypes.byref(post)), "lmc_load_pack_post")
+        self._call_post("lmc_load_pack_post", dst.device, stream, status_ptr, post, pack_ptr, pack_bytes, chunk_begin, nchunks,
+                        ctypes.byref(dst.struct), dst_tok0, layers_per_range, range_events_ptr)
 
     def pack_blobs(self, blob_ptrs: int, blob_bytes_ptr: int, nchunks: int, L: int, H: int, D: int, chunk_tokens: int,
                    ntokens: int, pack_ptr: int, pack_cap: int, device, stream: Optional[int] = None,

@@ -144,6 +144,11 @@ def _chunk_shape(fmt: str, L: int, T: int, H: int, D: int) -> Tuple[int, ...]:
     raise ValueError(f"Invalid format: {fmt}")
 
 
+def _token_axis(fmt: str) -> int:
+    """The token dimension of a chunk shape (_chunk_shape)."""
+    return 2 if fmt == "vllm" else 3
+
+
 def _coded_dtype(fmt: str, kv_dtype: torch.dtype) -> torch.dtype:
     """The dtype a cachegen-tier chunk is retrieved as: the reference's rule for 16-bit KV (output_spec: bf16 for vllm,
     fp16 for huggingface), the stored dtype for fp8 KV."""
@@ -596,11 +601,14 @@ class LMCLocalBackend(LMCBackendInterface):
         """The codec's `model` argument for this tier's encode / decode_device calls."""
         return {"model": "fixed"} if self.model == "fixed" else {}
 
+    def _group_of(self, geometry: tuple, chunk_tokens: int, shapes) -> dict:
+        """What _store keeps about a CacheGen group beside its entries (the repack legs of demotion and promotion need it)."""
+        tok = _token_axis(self.fmt or "vllm")
+        return dict(geometry=tuple(geometry), chunk_tokens=chunk_tokens, ntokens=sum(shp[tok] for shp in shapes))
+
     def _finish_encoded(self, keys: Sequence[CacheEngineKey], job, shapes, dtype) -> None:
         codec = self._codec()
-        L, H, D, cs = job.geometry
-        tok = 2 if (self.fmt or "vllm") == "vllm" else 3
-        group = dict(geometry=(L, H, D), chunk_tokens=cs, ntokens=sum(shp[tok] for shp in shapes))
+        group = self._group_of(job.geometry[:3], job.geometry[3], shapes)
         if self.mode == "hbm-cachegen":
             def keep():
                 if self.dev_arena is None:
@@ -641,9 +649,6 @@ class LMCLocalBackend(LMCBackendInterface):
         return [_HostChunk(hb, None, shp, dtype, True) for hb, shp in zip(blobs, shapes)], sum(r16(hb.nbytes) for hb in blobs), None
 
     def _finish_pack(self, keys: Sequence[CacheEngineKey], job, shapes, dtype) -> None:
-        L, H, D = job.geometry
-        tok = 2 if (self.fmt or "vllm") == "vllm" else 3
-
         def finish():
             pack = self._codec().finish_pack(job, self.host_arena)
             return [_PackChunk(pack, i, shp, dtype) for i, shp in enumerate(shapes)], r16(pack.blob.nbytes), None
@@ -657,8 +662,7 @@ class LMCLocalBackend(LMCBackendInterface):
             need = r16(job.cap)
             if self._lru.live("pinned") + need > b:
                 need = r16(max(self._codec().pack_bytes(job), 16))
-        if not self._store("pinned", need, finish, keys, geometry=(L, H, D), chunk_tokens=job.chunk_tokens,
-                           ntokens=sum(shp[tok] for shp in shapes)):
+        if not self._store("pinned", need, finish, keys, **self._group_of(job.geometry, job.chunk_tokens, shapes)):
             if not job.d2h_issued:  # never taken by finish_pack: its kernels finish, its words and the staging go back
                 job.done.synchronize()
                 with self._codec()._lock:
@@ -802,7 +806,7 @@ class LMCLocalBackend(LMCBackendInterface):
         assert n == len(keys), "one key per chunk"
         if n == 0:
             return 0
-        L, H, D = src.L, src.H, src.D
+        L, H, D, tok = src.L, src.H, src.D, _token_axis(fmt)
         dt = native.torch_dtype(src.dtype)
         shapes = [_chunk_shape(fmt, L, min(chunk_tokens, tok_end - (tok_begin + i * chunk_tokens)), H, D)
                   for i in range(n)]
@@ -828,15 +832,14 @@ class LMCLocalBackend(LMCBackendInterface):
                 self.put_queue.put(lambda: self._finish_encoded(list(keys), job, shapes, out_dt))
             return n
         if self.mode == "hbm":
-            b = self._tiers.budget["hbm"]
-            if b is not None and sum(L * 2 * shp[2 if fmt == "vllm" else 3] * H * D for shp in shapes) * dt.itemsize > b:
-                # (not even gathered: it fits nowhere)
-                self._not_cached(sum(L * 2 * shp[2 if fmt == "vllm" else 3] * H * D for shp in shapes) * dt.itemsize)
+            b, raw = self._tiers.budget["hbm"], sum(L * 2 * shp[tok] * H * D for shp in shapes) * dt.itemsize
+            if b is not None and raw > b:
+                self._not_cached(raw)  # (not even gathered: it fits nowhere)
                 return n
             chunks = []
             for shp, i in zip(shapes, range(n)):
                 chunk = torch.empty(shp, dtype=dt, device=dev)
-                T = shp[2] if fmt == "vllm" else shp[3]
+                T = shp[tok]
                 ctx.copy_kv(src, tok_begin + i * chunk_tokens, T, native.KVLayout.from_chunk(chunk, fmt), 0)
                 chunks.append(chunk)
             self._keep_tensors(list(keys), chunks)
@@ -855,7 +858,7 @@ class LMCLocalBackend(LMCBackendInterface):
             for s in shp:
                 numel *= s
             v = stage[i * chunk_bytes:i * chunk_bytes + numel * eb].view(dt).view(shp)
-            T = shp[2] if fmt == "vllm" else shp[3]
+            T = shp[tok]
             ctx.copy_kv(src, tok_begin + i * chunk_tokens, T, native.KVLayout.from_chunk(v, fmt), 0)
             views.append(v)
         gathered = torch.cuda.Event()
@@ -940,8 +943,8 @@ class LMCLocalBackend(LMCBackendInterface):
                 return
             # the pinned tier's pack, from the finished blobs
             L, H, D, cs = job.geometry
-            tok = 2 if (self.fmt or "vllm") == "vllm" else 3
-            ntokens = sum(shp[tok] for shp in shapes)
+            group = self._group_of((L, H, D), cs, shapes)
+            ntokens = group["ntokens"]
             sizes = codec.sizes_of(job)
             blobs = [job.arena[i * job.stride:i * job.stride + sizes[i]] for i in range(job.nchunks)]
 
@@ -951,7 +954,7 @@ class LMCLocalBackend(LMCBackendInterface):
                 return [_PackChunk(pack, i, shp, dtype) for i, shp in enumerate(shapes)], r16(pack.blob.nbytes), None
 
             need = 0 if self._tiers.budget["pinned"] is None else r16(codec.demoted_bytes(sizes, (L, H, D), cs, ntokens))
-            self._store("pinned", need, finish, keys, geometry=(L, H, D), chunk_tokens=cs, ntokens=ntokens)
+            self._store("pinned", need, finish, keys, **group)
             job.offload_issued = True
         finally:
             codec.release_layer_stream(job)

@@ -640,7 +640,7 @@ class CacheGenDeviceCodec:
         self._table_cache: dict = {}                         # blob-address tuple -> (device table, upload stream)
 
     # ---- encode ------------------------------------------------------------------
-    def _readable(self, src: native.KVLayout, tok_begin: int, tok_end: int, direct: bool = False, model: Optional[str] = None):
+    def _readable(self, src: native.KVLayout, tok_begin: int, tok_end: int, direct: bool = False):
         """The encoders read 16-byte vectors (native.KVLayout.vector_readable).  The reference's serde takes any shape
         (torch_quant_vectorized, cachegen_encoder.py:40-61), so a range of a layout that is not -- a head_size that is no
         multiple of 8 under a huggingface / NHBD layout, rows off a 16-byte boundary, or by default the "NHDB" cache of
@@ -648,7 +648,7 @@ class CacheGenDeviceCodec:
         the device (lmc_copy_kv: element-wise for the former, k_copy_split.h's gather for the latter) and encoded from
         there.  direct: an "NHDB" cache with planes of at most 1024 channels goes to the encoder as it is
         (lmc_encode_chunks_split, lmc_encode_chunks_fixed_split and the stores read the split blocks: k_quantize.h); wider
-        planes are staged all the same, whichever `model`."""
+        planes are staged all the same, whichever coder model."""
         if src.vector_readable():
             return src, tok_begin, tok_end
         if direct and src.struct.paged_kind == native.PAGED_SPLIT:
@@ -664,24 +664,36 @@ class CacheGenDeviceCodec:
             self.ctx.copy_kv(src, tok_begin, n, native.KVLayout.from_chunk(chunk, "vllm"), 0)
         return native.KVLayout.from_chunk(chunk, "vllm"), 0, n
 
+    # (coder model, split layout) -> the context's method; the coded schedules take a split destination themselves
+    _ENCODERS = {(None, False): "encode_chunks", (None, True): "encode_chunks_split",
+                 ("fixed", False): "encode_chunks_fixed", ("fixed", True): "encode_chunks_fixed_split"}
+    _SCHEDULES = {("fixed", False): "decode_chunks_fixed_schedule", ("fixed", True): "decode_chunks_fixed_split_schedule"}
+
+    def _entry(self, names: dict, model: Optional[str], layout: native.KVLayout, default: Optional[str] = None):
+        """self.ctx's method, looked up at call time, for an encode from / a decode into `layout` in coder `model`: the one
+        place that knows the models -- None, the entropy-coded blobs, and "fixed", LMC_MODEL_FIXED, 16-bit KV only."""
+        if model not in (None, "fixed"):
+            raise ValueError(f"unknown coder model {model!r} (None or 'fixed')")
+        if model == "fixed" and native.elem_bytes(layout.dtype) != 2:
+            raise ValueError("the fixed-width model stores bf16 / fp16 KV only")
+        return getattr(self.ctx, names.get((model, layout.struct.paged_kind == native.PAGED_SPLIT), default))
+
+    @staticmethod
+    def _job_size(src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int) -> tuple:
+        """(chunks, arena stride of a blob) of an encode job."""
+        return -(-(tok_end - tok_begin) // chunk_tokens), native.r16(native.blob_bound(src.L, chunk_tokens, src.H, src.D))
+
     def encode(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int,
                bins: Sequence[int], direct: bool = False, model: Optional[str] = None) -> EncodeJob:
         """Launch the fused encode of every chunk of [tok_begin, tok_end) on the CURRENT stream
         (so it is ordered after whatever produced the KV).  Asynchronous.  direct: see _readable.
         model: None -- the entropy-coded blobs; "fixed" -- LMC_MODEL_FIXED (lmc_encode_chunks_fixed, for a split source
         lmc_encode_chunks_fixed_split: fixed-width symbols, for blobs that stay in HBM; 16-bit KV only)."""
-        if model not in (None, "fixed"):
-            raise ValueError(f"unknown coder model {model!r} (None or 'fixed')")
-        if model == "fixed" and native.elem_bytes(src.dtype) != 2:
-            raise ValueError("the fixed-width model stores bf16 / fp16 KV only")
-        src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end, direct, model)
-        if model == "fixed":
-            encode_chunks = self.ctx.encode_chunks_fixed_split if src.struct.paged_kind == native.PAGED_SPLIT else self.ctx.encode_chunks_fixed
-        else:
-            encode_chunks = self.ctx.encode_chunks_split if src.struct.paged_kind == native.PAGED_SPLIT else self.ctx.encode_chunks
+        self._entry(self._ENCODERS, model, src)  # (what is refused is refused before anything is staged)
+        src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end, direct)
+        encode_chunks = self._entry(self._ENCODERS, model, src)
         L, H, D = src.L, src.H, src.D
-        n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
-        stride = native.r16(native.blob_bound(L, chunk_tokens, H, D))
+        n, stride = self._job_size(src, tok_begin, tok_end, chunk_tokens)
         with self._lock:
             with torch.cuda.device(self.device):
                 # The shared arena may be rewritten only after the copies of the last job that used it have been
@@ -731,8 +743,7 @@ class CacheGenDeviceCodec:
         if not (src.vector_readable() or (split and src.H * src.D <= 1024)):
             return None
         L, H, D = src.L, src.H, src.D
-        n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
-        stride = native.r16(native.blob_bound(L, chunk_tokens, H, D))
+        n, stride = self._job_size(src, tok_begin, tok_end, chunk_tokens)
         with self._lock, torch.cuda.device(self.device):
             side = self._layer_streams.pop() if self._layer_streams else torch.cuda.Stream(device=self.device)
             arena = torch.empty(n * stride, dtype=torch.uint8, device=self.device)
@@ -882,8 +893,8 @@ class CacheGenDeviceCodec:
         n = len(blobs)
         if n == 0:
             return None
-        L = dst.L
-        ranges = layer_ranges(L, layers_per_launch)
+        # (the coded schedule without a post-op is an export of its own: lmc_decode_chunks_schedule)
+        schedule = self._entry(self._SCHEDULES, model, dst, "decode_chunks_schedule" if post is None else "decode_chunks_schedule_post")
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             # The blob addresses of THIS call: any number of chunks (a 128 k-token retrieve is 512 of them), uploaded
@@ -923,25 +934,20 @@ class CacheGenDeviceCodec:
                     cur.wait_stream(up)
                     self._table_cache[ptrs] = (table, cur)
             with self._launch(cur) as (st, st_ptr):
-                # ONE C-ABI call issues every range's launch and records its event (lmc_decode_chunks_schedule): the
-                # ranges used to be one ctypes call + one torch event each
-                ends = [l1 for _, l1 in ranges]
-                evs = [native.NativeEvent() for _ in ranges]
-                if model == "fixed":
-                    split = dst.struct.paged_kind == native.PAGED_SPLIT
-                    decode_fixed = self.ctx.decode_chunks_fixed_split_schedule if split else self.ctx.decode_chunks_fixed_schedule
-                    decode_fixed(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
-                                 None if post is None else post.struct(*post.window(dst, dst_tok0, n, chunk_tokens)),
-                                 stream=cur.cuda_stream, status_ptr=st_ptr)
-                elif post is None:
-                    self.ctx.decode_chunks_schedule(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
-                                                    stream=cur.cuda_stream, status_ptr=st_ptr)
-                else:
-                    self.ctx.decode_chunks_schedule_post(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs,
-                                                         post.struct(*post.window(dst, dst_tok0, n, chunk_tokens)),
-                                                         stream=cur.cuda_stream, status_ptr=st_ptr)
-                events = list(zip(ends, evs))
-            return DecodeJob(evs[-1], events if layers_per_launch else None, table, status_idx=st, pool=self._status)
+                events = self._run_schedule(schedule, table, bound, n, dst, dst_tok0, chunk_tokens, layers_per_launch, post,
+                                            cur, st_ptr)
+            return DecodeJob(events[-1][1], events if layers_per_launch else None, table, status_idx=st, pool=self._status)
+
+    @staticmethod
+    def _run_schedule(schedule, table: torch.Tensor, bound: int, n: int, dst: native.KVLayout, dst_tok0: int, chunk_tokens: int,
+                      layers_per_launch, post: Optional[native.RangePost], cur, st_ptr: int) -> list:
+        """ONE C-ABI call (`schedule`) launches every range of layers over the n blobs `table` addresses, none larger than
+        `bound`, and records the range's event behind it, `post` in between -> [(first layer after the range, event)]."""
+        ends = [l1 for _, l1 in layer_ranges(dst.L, layers_per_launch)]
+        evs = [native.NativeEvent() for _ in ends]
+        kw = {} if post is None else {"post": post.struct(*post.window(dst, dst_tok0, n, chunk_tokens))}
+        schedule(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs, stream=cur.cuda_stream, status_ptr=st_ptr, **kw)
+        return list(zip(ends, evs))
 
     @staticmethod
     def _range_events(L: int, step: int):
@@ -979,12 +985,11 @@ class CacheGenDeviceCodec:
         """Blobs in pinned host DRAM that are no pack (a store of a single chunk, LMCACHE_AMD_PINNED_PACKS=0) with a
         post-op: lmc_load_chunks has no post-op, so the blobs cross PCIe whole into the decode slots, as decode() moves
         them, and ONE lmc_decode_chunks_schedule_post over the slots decodes them range by range with `post` in front
-        of every range's event, as decode_device does for blobs that live in HBM."""
+        of every range's event (_run_schedule: the step decode_device takes for blobs that live in HBM)."""
         n = len(host_blobs)
         if n == 0:
             return None
         stride = native.r16(max(hb.nbytes for hb in host_blobs))
-        ranges = layer_ranges(dst.L, layers_per_launch)
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             arena = self._dec_slots(n, stride, cur)
@@ -998,15 +1003,12 @@ class CacheGenDeviceCodec:
                 cur.wait_event(ready)
                 table = torch.tensor([arena.data_ptr() + i * stride for i in range(n)],
                                      dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-                ends = [l1 for _, l1 in ranges]
-                evs = [native.NativeEvent() for _ in ranges]
-                self.ctx.decode_chunks_schedule_post(table.data_ptr(), stride, n, dst, dst_tok0, chunk_tokens, ends, evs,
-                                                     post.struct(*post.window(dst, dst_tok0, n, chunk_tokens)),
-                                                     stream=cur.cuda_stream, status_ptr=st_ptr)
+                events = self._run_schedule(self.ctx.decode_chunks_schedule_post, table, stride, n, dst, dst_tok0, chunk_tokens,
+                                            layers_per_launch, post, cur, st_ptr)
                 last = torch.cuda.Event()
                 last.record(cur)
                 self._dec_free = last
-            return DecodeJob(evs[-1], list(zip(ends, evs)), table, status_idx=st, pool=self._status)
+            return DecodeJob(events[-1][1], events, table, status_idx=st, pool=self._status)
 
     # ---- packs: the plane-major pinned tier ---------------------------------------------------------------
     def store_pack(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins: Sequence[int],
@@ -1020,7 +1022,7 @@ class CacheGenDeviceCodec:
         direct: see _readable; a split source is coded by the two kernels, so its pack leaves as ONE part."""
         src, tok_begin, tok_end = self._readable(src, tok_begin, tok_end, direct)
         L, H, D = src.L, src.H, src.D
-        n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
+        n, _ = self._job_size(src, tok_begin, tok_end, chunk_tokens)
         with self._lock, torch.cuda.device(self.device):
             cap = pack_cap(n, L, chunk_tokens, H, D, bins)
             cur = torch.cuda.current_stream(self.device)

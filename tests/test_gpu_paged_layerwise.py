@@ -44,6 +44,74 @@ class _Count:
         native.Context.rope_shift, native.Context.copy_kv = self.saved
 
 
+@pytest.mark.parametrize("backend", ["cachegen-hbm", "cachegen-host"])
+def test_retrieve_into_paged_queues_each_post_op_once_behind_the_decode(backend, monkeypatch):
+    """What retrieve_into_paged (not layer-wise) launches from Python behind its decode: at most one lmc_rope_shift over
+    tokens [0, got) of the rows, then at most one lmc_copy_kv of [0, got) into the cache at token 0, neither on a miss.
+    (The cache contents are held by the test below and by tests/test_gpu_rope_shift.py.)"""
+    nl, H, D, bs, skip = 2, 2, 128, 16, 40
+    dt = torch.bfloat16
+    nb = 2 * ((NTOK + 5 + bs - 1) // bs) + 2
+    g = torch.Generator().manual_seed(73)
+    tokens = generate_tokens(NTOK, DEV)  # three chunks of CS tokens, the last one short
+    kv = tuple((torch.rand((NTOK, H, D), generator=g).to(dt).to(DEV), torch.rand((NTOK, H, D), generator=g).to(dt).to(DEV))
+               for _ in range(nl))
+    uniform = RopeShift.from_base(10000.0, D, 128, DEV, delta=37)
+    per_tok = torch.randint(-127, 128, (NTOK,), generator=g, dtype=torch.int32).to(DEV)
+    by_token = RopeShift(uniform.cos_sin, D, True, per_tok)
+    tail = torch.ones(NTOK, dtype=torch.bool, device=DEV)
+    tail[:skip] = False  # cuts into the second chunk
+    engine = LMCacheEngine(make_cfg(backend, CS), dumb_metadata("vllm", "Llama-3-8B"))
+    ctx = native.get_context(0)
+    calls = []
+
+    def recording(name, real):
+        def f(*a, **k):
+            calls.append((name, a, k))
+            return real(*a, **k)
+        return f
+
+    try:
+        engine.store(tokens, kv)
+        for name in ("rope_shift", "copy_kv"):  # on the context instance: the engine reaches both through its attributes
+            monkeypatch.setattr(ctx, name, recording(name, getattr(ctx, name)))
+
+        def run(layout, toks=tokens, **kw):
+            shape = {"NBHD": (2, nb, bs, H, D), "NHDB": (2, nb, H, D, bs)}[layout]
+            caches = [_random_bits(shape, dt, g).to(DEV) for _ in range(nl)]
+            del calls[:]
+            m = engine.retrieve_into_paged(toks, caches, _mapping("random", NTOK, nb, bs, g).to(DEV), bs, layout, **kw)
+            torch.cuda.synchronize()
+            return int(m.sum())
+
+        def is_rows(layout):  # a chunk of token rows: not paged at all
+            return layout.struct.paged_kind == native.PAGED_ROWS and not layout.struct.slot_mapping
+
+        # staged "NHDB", a per-token delta, a suffix mask: one rotation of the staged rows, then their one scatter
+        got = run("NHDB", mask=tail, rope=by_token)
+        assert got == NTOK - skip
+        assert [c[0] for c in calls] == ["rope_shift", "copy_kv"], calls
+        (_, a, k), (_, b, kb) = calls
+        assert is_rows(a[0]) and a[1:3] == (0, got) and a[3].data_ptr() == uniform.cos_sin.data_ptr() and a[4:6] == (D, True)
+        assert k["delta"] == 0 and torch.equal(k["deltas"], per_tok[skip:skip + got])
+        assert is_rows(b[0]) and b[1:3] == (0, got) and b[3].struct.paged_kind == native.PAGED_SPLIT and b[4] == 0 and not kb
+        assert b[0].struct.base == a[0].struct.base  # the chunk that was rotated is the one that is scattered
+        # direct, no rope: the decoder writes the split blocks, nothing is queued from Python
+        assert run("NHDB", direct=True) == NTOK and calls == []
+        # a row layout with a rope: the one rotation is on the paged cache itself, and nothing is scattered
+        got = run("NBHD", mask=tail, rope=uniform)
+        assert got == NTOK - skip and [c[0] for c in calls] == ["rope_shift"], calls
+        _, a, k = calls[0]
+        assert a[0].struct.paged_kind == native.PAGED_ROWS and a[0].struct.slot_mapping and a[1:3] == (0, got)
+        assert k["delta"] == 37 and k["deltas"] is None
+        # a miss: neither
+        assert run("NHDB", toks=tokens + 10000, rope=by_token) == 0 and calls == []
+        assert run("NBHD", toks=tokens + 10000, rope=uniform) == 0 and calls == []
+        assert ctx.status(clear=True) == 0
+    finally:
+        engine.close()
+
+
 @pytest.mark.parametrize("geom", [(2, 128, 16), (1, 64, 8)], ids=lambda g: "H%d_D%d_bs%d" % g)
 @pytest.mark.parametrize("backend", ["cachegen-host", "cachegen-hbm", "cuda"])
 def test_layerwise_equals_retrieve_into_paged_and_every_event_means_final(backend, geom):
