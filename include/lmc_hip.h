@@ -628,6 +628,31 @@ int lmc_unpack_blobs(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int3
                      void* const* blob_ptrs_h, const uint32_t* blob_caps_h, uint32_t* job_status, lmc_stream_t stream);
 int lmc_pack_chunk_bytes(const void* pack_h, uint64_t nbytes, int32_t chunk, uint32_t* size_out);
 
+/*
+ * lmc_transcode_fixed -- the fixed-width tier's way to a pack: n LMC_MODEL_FIXED blobs that lie ANYWHERE in device memory
+ *   -> the blobs lmc_encode_chunks would have written from the KV they were stored from, byte for byte and with equal
+ *   size words, without that KV.  Replaces nothing in the reference (it has no second coder model).  Two kernels on
+ *   `stream`: k_fixed_expand re-addresses the fixed streams into the symbol workspace, copies the scales and clears the
+ *   job's words -- what k_quantize leaves -- and the coder launch of the two-kernel encode follows, chosen as
+ *   lmc_encode_chunks chooses it (counts-only or general, ragged last chunk and one-token tail included).  Never the
+ *   fused kernel, whatever lmc_ctx_set_encode_path says.  The workspace is the encode jobs' (two, by stream).
+ *   blob_ptrs    device array [nchunks] of blob addresses, each 16-byte aligned
+ *   blob_bytes   device-accessible uint32 [nchunks]: the room each pointer may be read for (0 = no blob there)
+ *   L, H, D, dtype   the geometry and the 16-bit KV dtype the blobs were stored with (no fp8: the fixed tier has none);
+ *                    planes of up to LMC_MAX_CHANNELS channels
+ *   ntokens      tokens of all chunks together (every chunk chunk_tokens long but, possibly, the last)
+ *   bins_h       host int32 [2 L]: must be the bins the blobs hold
+ *   blobs_out, blob_stride, sizes, job_status   as lmc_encode_chunks takes them (blob_stride >= lmc_blob_bound, both
+ *                    16-byte aligned); header word 23 of the new blobs is 0
+ *   Refusals are lmc_encode_chunks's: LMC_ERR_INVALID with nothing queued.  On the device a blob is held against
+ *   everything lmc_decode_chunks_fixed_schedule holds it against, in its order, and against the call (L, H, D, dtype,
+ *   the chunk's length, the bins): LMC_STATUS_BAD_HEADER / BAD_STREAM / BAD_SCALES in the job's word, no read outside
+ *   blob_bytes[i], and the chunk's output is no blob of its KV (the other chunks of the job are not touched by that).
+ */
+int lmc_transcode_fixed(lmc_ctx* ctx, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks, int32_t L,
+                        int32_t H, int32_t D, int32_t dtype, int32_t chunk_tokens, uint32_t ntokens, const int32_t* bins_h,
+                        void* blobs_out, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
+
 
 int lmc_stream_create(lmc_stream_t* out);
 int lmc_stream_destroy(lmc_stream_t s);

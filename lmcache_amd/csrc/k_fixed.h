@@ -40,6 +40,9 @@
 // The split stores carry no non-temporal hint: 16-byte pieces whose neighbours arrive later want L2 to merge them
 // (k_decode.h, LMC_DEC_SPLIT_NT: 1.47 against 3.11 ms there).  A V store of 32 contiguous bytes per channel (two octs of
 // a 16-slot block regrouped through LDS) was not built, so not compared.
+//
+// k_fixed_expand (at the end of this file) -- fixed-width blobs back into the symbol workspace, scales and job words that
+// k_quantize leaves for the coder: the first kernel of lmc_transcode_fixed, the fixed-width tier's demotion.
 #pragma once
 #include "k_encode.h"
 #include "k_quantize.h"
@@ -403,6 +406,176 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
       }
     }
     wave_lds_fence();  // the tile has been read: the next one may take its place
+  }
+  const u32 got = wave_sum_u32(acc);
+  const u32 tw = lane < 4 ? ((const LMC_GLOBAL u32*)(sbytes + ssize - LMC_FIXED_TAIL_BYTES))[lane] : 0u;
+  if (__ballot(lane < 4 && tw != (lane == 0 ? got : 0u)) != 0ull) fail(LMC_ST_BAD_STREAM);
+}
+
+// ---- k_fixed_expand: fixed-width blobs -> what k_quantize<true> leaves for the same chunks ----------------------------
+// The first kernel of lmc_transcode_fixed (lmc_api.hip): it stands where k_quantize stands in the two-kernel encode and
+// k_cdf_encode runs behind it unchanged, so a fixed-width blob becomes the entropy-coded blob of the same KV without the
+// KV.  Per (chunk, plane) it fills the symbol workspace, copies the plane's scales into the output blob, and clears the
+// job's look-back granules and size words.
+// Mapping: k_fixed_decode's -- a wave takes a stream and walks it in tiles of four octs, lane = (oct tile * 4 + lane / 16,
+// channels 4 (lane & 15) .. + 3): one 16-byte non-temporal load of `lo`, a dword of `hi`, the next tile's loads in flight
+// while this one is stored.  No LDS: the lane that loaded a dword owns every bit of its four channels for the oct.
+//   narrow plane   the `lo` vector IS the workspace's four dwords of (oct, channels): one 16-byte store
+//   wide plane     byte k of quad dword 2 oct + j = nibble of token 4 j + k | bit 4 from `hi`: two 16-byte stores
+// Plain stores: the coder reads the workspace next (k_quantize's stores carry no hint either).  The SET of dwords written
+// is quantize_task's: every oct below ceil(TQ / 2), those past the chunk's own (a ragged last chunk in a job of longer
+// chunks) as zeros, and quad 2 oct + 1 only where it lies below TQ.  Bytes of tokens at or past T -- inside the last oct
+// whatever the blob holds there, zeros in the octs behind it -- are never read by the coder (k_quantize.h says the same
+// of its own), so they are not part of what the two kernels have to agree on.
+// Validation: k_fixed_decode's checks in its order, plus what a transcode adds -- pointer and room before the header is
+// read (lmc_pack_blobs's rule), L / H / D / dtype and T against the call's (the coder writes the new header from the
+// call's), the blob's bins against the call's (the coder takes them from BinsArg).  A wave that fails sets the job's
+// status word and stores ZEROS for its whole stream: the coder behind it must never meet bytes nobody wrote (a fresh
+// workspace) or a symbol of 32 and more -- its histogram is [32][lane].
+struct FixedExpandArgs {
+  const u8* const* blob_ptrs;  // device [nchunks]: the fixed-width blob of chunk i
+  const u32* blob_bytes;       // device [nchunks]: how far it may be read
+  int tok_begin, tok_end, chunk_tokens, nchunks;
+  int P, C, G, TQ;
+  int L, H, D, dtype;
+  u32* sym4;             // symbol workspace, region (chunk, plane) at (chunk * P + plane) * sym_stride
+  long long sym_stride;
+  u8* scale_base;        // QuantArgs: scale of (chunk, p, t) at scale_base + chunk * scale_stride + 2 * (p * Tc + t)
+  long long scale_stride;
+  unsigned long long* agg;  // QuantArgs: zeroed here, [agg_n]
+  long long agg_n;
+  u32* sizes;               // ... and the job's size words [nchunks]
+  u32* status;
+  BinsArg bins;
+};
+
+#define FIXED_EXP_WAVES 4
+
+// bit r of the low four bits of n -> bit 0 of byte r (7 r + r = 8 r; the products' bit positions are all distinct)
+__device__ __forceinline__ u32 fixed_spread4(u32 n) { return ((n & 15u) * 0x00204081u) & 0x01010101u; }
+
+__global__ __launch_bounds__(64 * FIXED_EXP_WAVES) void k_fixed_expand(FixedExpandArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const u32 gid = blockIdx.x * (u32)FIXED_EXP_WAVES + (u32)wave;  // (the grid is below 2^30 workgroups: lmc_api.hip)
+  const int n = a.P * a.G;  // streams of a chunk
+  if ((unsigned long long)gid >= (unsigned long long)a.nchunks * (unsigned long long)n) return;
+  if (lane == 0) {  // the job words k_quantize clears: a launch has a wave per granule
+    if (a.agg && (long long)gid < a.agg_n) a.agg[gid] = 0ull;
+    if (a.sizes && gid < (u32)a.nchunks) a.sizes[gid] = 0u;
+  }
+  const int chunk = (int)(gid / (u32)n);
+  const int r = (int)(gid - (u32)chunk * (u32)n);
+  const int p = r / a.G, g = r - p * a.G;
+  const u32 Tc = (u32)min(a.chunk_tokens, a.tok_end - (a.tok_begin + chunk * a.chunk_tokens));
+  const u32 TQ = (u32)a.TQ, TO = (TQ + 1u) >> 1;
+  const bool wide = !lmc_sym_nibbles((int)a.bins.b[p]);  // (wave-uniform; the blob's bins are held against these below)
+  u32* const ws = a.sym4 + ((long long)chunk * a.P + p) * a.sym_stride;
+  const u32 c4 = (u32)g * 64u + 4u * ((u32)lane & 15u);
+  const bool cok = c4 < (u32)a.C;
+  const u32 ntile = (TO + 3u) >> 2;
+  // the lane's oct of a tile into the workspace
+  auto store_oct = [&](u32 o, const u32x4_t& lo, u32 hi) {
+    if (!cok || o >= TO) return;
+    if (!wide) {
+      *(LMC_GLOBAL u32x4_t*)(ws + (size_t)o * (u32)a.C + c4) = lo;
+      return;
+    }
+    const u32 w[4] = {lo.x, lo.y, lo.z, lo.w};
+    u32 q0[4], q1[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const u32 hb = hi >> (8 * e);
+      q0[e] = (w[e] & 0x0f0f0f0fu) | (fixed_spread4(hb) << 4);
+      q1[e] = ((w[e] >> 4) & 0x0f0f0f0fu) | (fixed_spread4(hb >> 4) << 4);
+    }
+    *(LMC_GLOBAL u32x4_t*)(ws + (size_t)(2u * o) * (u32)a.C + c4) = u32x4_t{q0[0], q0[1], q0[2], q0[3]};
+    if (2u * o + 1u < TQ) *(LMC_GLOBAL u32x4_t*)(ws + (size_t)(2u * o + 1u) * (u32)a.C + c4) = u32x4_t{q1[0], q1[1], q1[2], q1[3]};
+  };
+  auto fail = [&](u32 bit) {
+    if (lane == 0) atomicOr(a.status, bit);
+    for (u32 tile = 0; tile < ntile; tile++) store_oct(tile * 4u + ((u32)lane >> 4), u32x4_t{0u, 0u, 0u, 0u}, 0u);
+  };
+
+  // ---- pointer and room, then the header ------------------------------------------------------------------------------
+  const u8* const blob = (const u8*)uniform_ptr(a.blob_ptrs[chunk]);
+  const u32 room = (u32)__builtin_amdgcn_readfirstlane((int)a.blob_bytes[chunk]);
+  if (!blob || ((u64)(uintptr_t)blob & 15ull) || room < LMC_HEADER_BYTES) return fail(LMC_ST_BAD_HEADER);
+  const u32 hv = ((const LMC_GLOBAL u32*)blob)[lane & 31];
+  auto hdw = [&](int i) { return (u32)__builtin_amdgcn_readlane((int)hv, i); };
+  const u32 T = hdw(4);
+  const BlobOff bo = lmc_blob_off((u32)a.P, T, (u32)a.G);
+  if (hdw(0) != LMC_BLOB_MAGIC || (hdw(1) & 0xffffu) != LMC_BLOB_VERSION || hdw(7) != (u32)a.C || T == 0u || T > 65535u ||
+      T != Tc || hdw(8) != (u32)a.P || hdw(22) != LMC_MODEL_FIXED || hdw(15) != bo.streams || hdw(2) != (u32)a.dtype ||
+      hdw(3) != (u32)a.L || hdw(5) != (u32)a.H || hdw(6) != (u32)a.D ||
+      (unsigned long long)hdw(15) + (unsigned long long)hdw(16) != (unsigned long long)hdw(17) ||
+      (unsigned long long)hdw(17) > (unsigned long long)room) {
+    return fail(LMC_ST_BAD_HEADER);
+  }
+  // ---- the bins (they lie in front of off_streams <= total_bytes <= room): the call's, and the layout they give ---------
+  const u32 O = (T + 7u) >> 3;
+  const u32 bw = 4 * lane < a.P ? ((const LMC_GLOBAL u32*)(blob + LMC_HEADER_BYTES))[lane] : 0u;  // lane = four planes' bins
+  bool bad = false;
+  for (int j = 0; 4 * j < a.P; j++) {  // (wave-uniform: scalar loads of the call's, a readlane of the blob's)
+    u32 want;
+    __builtin_memcpy(&want, a.bins.b + 4 * j, 4);
+    const u32 mask = a.P - 4 * j >= 4 ? 0xffffffffu : (1u << (8 * (a.P - 4 * j))) - 1u;
+    bad = bad || (((u32)__builtin_amdgcn_readlane((int)bw, j) ^ want) & mask) != 0u;
+  }
+  u32 nwide = 0, nwide_before = 0;
+  for (int q0 = 0; q0 < a.P; q0 += 64) {
+    const int q = q0 + lane;
+    const u32 b = ((u32)__shfl((int)bw, q >> 2) >> (8 * (q & 3))) & 0xffu;
+    const u64 m = __ballot(q < a.P && b > LMC_FIXED_NARROW_BINS);
+    const int below = p - q0;  // planes of this round that lie in front of p
+    nwide += (u32)__builtin_popcountll(m);
+    nwide_before += (u32)__builtin_popcountll(below >= 64 ? m : below <= 0 ? 0ull : m & ((1ull << below) - 1ull));
+  }
+  // lmc_fixed_stream_bytes summed: 256 O + 16 per stream, 64 O more per wide one (the host has seen to it that the
+  // call's geometry and bins stay below 2^32)
+  const u32 total = (u32)a.G * ((256u * O + LMC_FIXED_TAIL_BYTES) * (u32)a.P + 64u * O * nwide);
+  const u32 pbeg = (u32)a.G * ((256u * O + LMC_FIXED_TAIL_BYTES) * (u32)p + 64u * O * nwide_before);
+  const u32 ssize = (wide ? 320u : 256u) * O + LMC_FIXED_TAIL_BYTES;
+  const u32 beg = pbeg + (u32)g * ssize;
+  if (bad || total != hdw(16)) return fail(LMC_ST_BAD_HEADER);  // (the directory lies in front of off_streams too)
+  const u32x2_t gd = *(const LMC_GLOBAL u32x2_t*)(blob + bo.gdir + 8u * (u32)(p * a.G + g));
+  if ((u32)__builtin_amdgcn_readfirstlane((int)gd.x) != beg || (u32)__builtin_amdgcn_readfirstlane((int)gd.y) != beg + ssize)
+    return fail(LMC_ST_BAD_HEADER);
+  const u8* const sbytes = blob + bo.streams + beg;  // beg + ssize <= total: inside the blob
+
+  if (g == 0) {  // the plane's first wave: the scales into the new blob, summed on the way
+    const u16* const scl = reinterpret_cast<const u16*>(blob + bo.scales) + (size_t)p * T;
+    u16* const out = reinterpret_cast<u16*>(a.scale_base + (long long)chunk * a.scale_stride) + (size_t)p * T;
+    const u32 want = (u32)__builtin_amdgcn_readfirstlane((int)((const LMC_GLOBAL u32*)(blob + bo.scsum))[p]);
+    u32 acc = 0;
+    for (u32 t = (u32)lane; t < T; t += 64) {
+      const u32 v = (u32)scl[t];
+      acc += (t + 1u) * (v + 1u);  // lmc_scale_checksum_term
+      out[t] = (u16)v;
+    }
+    if (wave_sum_u32(acc) != want) return fail(LMC_ST_BAD_SCALES);
+  }
+
+  // ---- the stream -------------------------------------------------------------------------------------------------------
+  const LMC_GLOBAL u32x4_t* const lo_g = (const LMC_GLOBAL u32x4_t*)sbytes;
+  const LMC_GLOBAL u32* const hi_g = (const LMC_GLOBAL u32*)(sbytes + 256u * (size_t)O);
+  struct Tile { u32x4_t lo; u32 hi; };
+  auto load_tile = [&](u32 tile) -> Tile {
+    Tile t;
+    const bool in = tile * 4u + ((u32)lane >> 4) < O;
+    t.lo = in ? __builtin_nontemporal_load(lo_g + (tile * 64u + (u32)lane)) : u32x4_t{0u, 0u, 0u, 0u};
+    t.hi = (wide && in) ? __builtin_nontemporal_load(hi_g + (tile * 64u + (u32)lane)) : 0u;
+    return t;
+  };
+  u32 acc = 0;
+  Tile cur = load_tile(0);
+  for (u32 tile = 0; tile < ntile; tile++) {  // (O <= TO: the octs behind the chunk's own are stored as zeros)
+    const Tile mine = cur;
+    if (tile + 1u < ntile) cur = load_tile(tile + 1u);  // in flight while this tile is stored
+    const u32 i0 = tile * 256u + 4u * (u32)lane;  // the check word over exactly what was loaded
+    acc += (2u * i0 + 1u) * mine.lo.x + (2u * i0 + 3u) * mine.lo.y + (2u * i0 + 5u) * mine.lo.z + (2u * i0 + 7u) * mine.lo.w;
+    acc += (2u * (64u * O + tile * 64u + (u32)lane) + 1u) * mine.hi;
+    store_oct(tile * 4u + ((u32)lane >> 4), mine.lo, mine.hi);
   }
   const u32 got = wave_sum_u32(acc);
   const u32 tw = lane < 4 ? ((const LMC_GLOBAL u32*)(sbytes + ssize - LMC_FIXED_TAIL_BYTES))[lane] : 0u;

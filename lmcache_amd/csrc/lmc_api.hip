@@ -554,21 +554,44 @@ int lmc_encode_chunks_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_be
                              nullptr, true);
 }
 
+// What stands in front of the coder in a job that has no KV to quantise: fixed-width blobs of earlier stores
+// (lmc_transcode_fixed; k_fixed.h, k_fixed_expand).
+struct FixedSrc {
+  const void* const* blob_ptrs;  // device [nchunks]
+  const uint32_t* blob_bytes;    // device [nchunks]
+  int L, H, D, dtype;
+};
+static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, int nchunks, int32_t tok_begin, int32_t tok_end,
+                      int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes,
+                      uint32_t* job_status, lmc_stream_t stream, int nparts, const AfterPart* after_part);
+
 static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
                                const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
                                lmc_stream_t stream, int nparts, const AfterPart* after_part, bool split_ok) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok) || !blobs || !sizes || ((uintptr_t)blobs & 15) ||
-      (blob_stride & 15))
-    return LMC_ERR_INVALID;
-  const int L = src->num_layers, H = src->num_heads, D = src->head_size;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok)) return LMC_ERR_INVALID;
+  return encode_job(c, src, nullptr, nchunks, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream,
+                    nparts, after_part);
+}
+
+// The encode job behind its source's own checks: the refusals every source shares, the workspace, the launches.  `src`: the
+// KV that k_quantize or the fused kernel reads, or NULL and `fx`: k_fixed_expand in k_quantize's place -- always the two
+// kernels, and behind the first one the job is the same job.
+static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, int nchunks, int32_t tok_begin, int32_t tok_end,
+                      int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes,
+                      uint32_t* job_status, lmc_stream_t stream, int nparts, const AfterPart* after_part) {
+  if (!blobs || !sizes || ((uintptr_t)blobs & 15) || (blob_stride & 15)) return LMC_ERR_INVALID;
+  const int L = src ? src->num_layers : fx->L, H = src ? src->num_heads : fx->H, D = src ? src->head_size : fx->D;
+  const int kv_dtype = src ? src->dtype : fx->dtype;
   const int P = 2 * L, C = H * D, G = (C + 63) / 64;  // (C <= LMC_MAX_CHANNELS: layout_ok)
   if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
   // an LMC_PAGED_SPLIT source (at most 1024 channels per plane: encode_job_ok): k_quantize's split instances, then
   // k_cdf_encode -- never the fused kernel, so the job is one part
-  const bool nhdb = src->paged_kind == LMC_PAGED_SPLIT;
+  const bool nhdb = src && src->paged_kind == LMC_PAGED_SPLIT;
   BinsArg bins;
   if (!bins_ok(bins_h, P, &bins)) return LMC_ERR_INVALID;
+  // (fixed-width blobs of this geometry and these bins stay below 2^32 bytes, as their encoder saw to: k_fixed_expand's sums)
+  if (fx && lmc_fixed_blob_bytes((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, bins.b) > 0xffffffffull) return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
 
@@ -591,7 +614,7 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   // 64 planes of 1024 channels, 4 / 8 / 12 / 16 / 32 / 64 chunks: fused / two-kernel time = 1.27 / 1.16 / 1.05 / 1.00 /
   // 0.91 / 0.90 (tools/probes/encode_ab.hip)
   const long long auto_min = 4ll * c->num_cus;
-  const bool fused = !nhdb && fused_fits && (c->enc_path == LMC_ENCODE_PATH_FUSED ||
+  const bool fused = !nhdb && !fx && fused_fits && (c->enc_path == LMC_ENCODE_PATH_FUSED ||
                                     (c->enc_path == LMC_ENCODE_PATH_AUTO && (long long)nfull * ipc >= auto_min));
   // chunks that go through the general coder launch (scratch slots): every chunk of a job whose chunks are longer than
   // 256 tokens or whose streams do not fill 8-wave workgroups, a ragged last chunk of a single token
@@ -638,7 +661,7 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   ea.bins = bins;
   ea.agg = w->agg; ea.sizes = sizes;
   ea.L = L; ea.H = H; ea.D = D;
-  ea.dtype = lmc_math_dtype(src->dtype);  // the header's dtype word: an fp8 chunk is coded as its bf16 images (lmc_format.h)
+  ea.dtype = lmc_math_dtype(kv_dtype);  // the header's dtype word: an fp8 chunk is coded as its bf16 images (lmc_format.h)
   u8* const scale_base = (u8*)blobs + hl.off_scales;  // off_scales does not depend on T
 
   if (!w->ticket) {
@@ -663,19 +686,37 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
     e2.scratch = w->scratch;  // (at most one launch of a job codes into scratch: its slots are counted from its first chunk)
     e2.agg = w->agg + (size_t)c0 * PG;
     e2.sizes = sizes + c0;
-    QuantArgs qa;
-    memset(&qa, 0, sizeof qa);
-    qa.src = to_addr(src); qa.bins = bins;
-    qa.tok_begin = e2.tok_begin; qa.tok_end = tok_end; qa.chunk_tokens = chunk_tokens; qa.nchunks = n;
-    qa.P = P; qa.C = C; qa.TQ = TQ; qa.pc_limit = n * P; qa.sym_stride = ea.sym_stride;
-    qa.sym4 = const_cast<u32*>(e2.sym4);
-    qa.scale_base = scale_base + (size_t)c0 * blob_stride;
-    qa.scale_stride = (long long)blob_stride;
-    qa.agg = e2.agg; qa.agg_n = (long long)n * PG;  // zeroed by the quantiser: one dispatch less per job
-    qa.sizes = e2.sizes;
     int r;
     if ((r = prof_mark(c, s))) return r;
-    if ((r = launch_quant<true>(qa, s, nhdb))) return r;
+    if (fx) {  // the same workspace, scales and job words from the chunks' fixed-width blobs
+      FixedExpandArgs xa;
+      memset(&xa, 0, sizeof xa);
+      xa.blob_ptrs = (const u8* const*)fx->blob_ptrs + c0; xa.blob_bytes = fx->blob_bytes + c0;
+      xa.tok_begin = e2.tok_begin; xa.tok_end = tok_end; xa.chunk_tokens = chunk_tokens; xa.nchunks = n;
+      xa.P = P; xa.C = C; xa.G = G; xa.TQ = TQ;
+      xa.L = L; xa.H = H; xa.D = D; xa.dtype = kv_dtype;
+      xa.sym4 = const_cast<u32*>(e2.sym4); xa.sym_stride = ea.sym_stride;
+      xa.scale_base = scale_base + (size_t)c0 * blob_stride; xa.scale_stride = (long long)blob_stride;
+      xa.agg = e2.agg; xa.agg_n = (long long)n * PG;
+      xa.sizes = e2.sizes;
+      xa.status = e2.status;
+      xa.bins = bins;
+      const long long nwaves = (long long)n * PG;  // a wave per stream
+      hipLaunchKernelGGL(k_fixed_expand, dim3((unsigned)((nwaves + FIXED_EXP_WAVES - 1) / FIXED_EXP_WAVES)), dim3(64 * FIXED_EXP_WAVES), 0, s, xa);
+      HIP_TRY(hipGetLastError());
+    } else {
+      QuantArgs qa;
+      memset(&qa, 0, sizeof qa);
+      qa.src = to_addr(src); qa.bins = bins;
+      qa.tok_begin = e2.tok_begin; qa.tok_end = tok_end; qa.chunk_tokens = chunk_tokens; qa.nchunks = n;
+      qa.P = P; qa.C = C; qa.TQ = TQ; qa.pc_limit = n * P; qa.sym_stride = ea.sym_stride;
+      qa.sym4 = const_cast<u32*>(e2.sym4);
+      qa.scale_base = scale_base + (size_t)c0 * blob_stride;
+      qa.scale_stride = (long long)blob_stride;
+      qa.agg = e2.agg; qa.agg_n = (long long)n * PG;  // zeroed by the quantiser: one dispatch less per job
+      qa.sizes = e2.sizes;
+      if ((r = launch_quant<true>(qa, s, nhdb))) return r;
+    }
     if ((r = prof_mark(c, s))) return r;
     const long long ngroups = (long long)n * PG;
     // launches whose chunks all have 2 .. 256 tokens (a ragged last chunk included) take the counts-only coder: 8 waves
@@ -690,9 +731,9 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { g_last_hip = (int)le; tickets_reset(); return LMC_ERR_HIP; }
     w->tickets_drawn += nwg;  // only a launch that went out has drawn
-    if (lmc_dtype_fp8(src->dtype)) {  // the coder wrote header word 23 as 0: the KV's dtype goes there
+    if (lmc_dtype_fp8(kv_dtype)) {  // the coder wrote header word 23 as 0: the KV's dtype goes there
       hipLaunchKernelGGL(k_set_kv_dtype, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, e2.blobs, e2.blob_stride, n,
-                         (u32)src->dtype);
+                         (u32)kv_dtype);
       HIP_TRY(hipGetLastError());
     }
     return prof_mark(c, s);
@@ -740,6 +781,27 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
   w->ws_used = true;
   w->last_stream = s;
   return LMC_OK;
+}
+
+// Fixed-width blobs of earlier stores -> the entropy-coded blobs of the same KV: k_fixed_expand, then the coder launch
+// lmc_encode_chunks would have made behind k_quantize (encode_job).  The blobs are read where they lie, through the pointer
+// table; a chunk that does not check out sets the job's status word (its slot then holds the coded blob of a chunk of zero
+// symbols, with a size word to match: the status word is the verdict, as for every job).
+int lmc_transcode_fixed(lmc_ctx* c, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks, int32_t L, int32_t H,
+                        int32_t D, int32_t dtype, int32_t chunk_tokens, uint32_t ntokens, const int32_t* bins_h, void* blobs_out,
+                        uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream) {
+  if (!c || !blob_ptrs || !blob_bytes || nchunks < 1 || nchunks > 65535 || L < 1 || 2 * L > LMC_MAX_PLANES || H < 1 || D < 1 ||
+      chunk_tokens < 1 || chunk_tokens > 65535 || (dtype != LMC_DTYPE_BF16 && dtype != LMC_DTYPE_FP16))
+    return LMC_ERR_INVALID;
+  const long long C = (long long)H * D;
+  if (C < 8 || (C & 7) || C > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
+  // every chunk is chunk_tokens long but, possibly, the last (lmc_pack_blobs's rule); token indices are 32-bit and signed
+  if ((uint64_t)ntokens > (uint64_t)nchunks * (uint32_t)chunk_tokens || (uint64_t)ntokens <= (uint64_t)(nchunks - 1) * (uint32_t)chunk_tokens ||
+      ntokens > 0x7fffffffu)
+    return LMC_ERR_INVALID;
+  const FixedSrc fx = {blob_ptrs, blob_bytes, L, H, D, dtype};
+  return encode_job(c, nullptr, &fx, nchunks, 0, (int32_t)ntokens, chunk_tokens, bins_h, blobs_out, blob_stride, sizes, job_status, stream,
+                    1, nullptr);
 }
 
 }  // extern "C"

@@ -184,6 +184,8 @@ SYMBOLS = {
     "lmc_load_pack_post": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _PL, _i32, _i32, _vp, _vp, _vp,
                                           ctypes.POINTER(RangePostStruct)]),
     "lmc_pack_blobs": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _u64, _vp, _vp]),
+    "lmc_transcode_fixed": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _u64, _vp, _vp,
+                                           _vp]),
     "lmc_unpack_blobs": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "lmc_pack_chunk_bytes": (ctypes.c_int, [_vp, _u64, _i32, ctypes.POINTER(ctypes.c_uint32)]),
     "lmc_copy_kv": (ctypes.c_int, [_vp, _PL, _i32, _i32, _PL, _i32, _vp]),
@@ -820,11 +822,16 @@ class Context:
         self._call("lmc_calculate_cdf", sym.device, stream, sym.data_ptr(), P, T, C, max_bins, out.data_ptr())
         return out
 
-    def _encode_job(self, symbol: str, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, blobs_ptr: int,
-                    blob_stride: int, sizes_ptr: int, stream: Optional[int], status_ptr: Optional[int]) -> int:
-        """The marshalling of the lmc_encode_chunks* exports and lmc_store_pack (one argument list) -> the job's chunks."""
-        self._call(symbol, src.device, stream, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens, self._bins(bins),
-                   blobs_ptr, blob_stride, sizes_ptr, status_ptr)
+    def _encode_job(self, symbol: str, src, tok_begin: int, tok_end: int, chunk_tokens: int, bins, blobs_ptr: int,
+                    blob_stride: int, sizes_ptr: int, stream: Optional[int], status_ptr: Optional[int], device=None) -> int:
+        """The marshalling of the lmc_encode_chunks* exports and lmc_store_pack (one argument list) -> the job's chunks.
+        `src`: the KVLayout the job reads; or, for lmc_transcode_fixed, which reads blobs instead, the tuple of its own
+        leading arguments (with `device`) -- behind the source the argument list is the same."""
+        if isinstance(src, KVLayout):
+            head, device = (ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens), src.device
+        else:
+            head = tuple(src)
+        self._call(symbol, device, stream, *head, self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr)
         return self._nchunks(tok_begin, tok_end, chunk_tokens)
 
     def encode_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
@@ -988,6 +995,17 @@ class Context:
         device-accessible uint32 [n], the room of each) -> one pack in the DEVICE region at pack_ptr.  No encode."""
         self._call("lmc_pack_blobs", device, stream, blob_ptrs, blob_bytes_ptr, nchunks, L, H, D, chunk_tokens, ntokens,
                    pack_ptr, pack_cap, status_ptr)
+
+    def transcode_fixed(self, blob_ptrs: int, blob_bytes_ptr: int, nchunks: int, L: int, H: int, D: int, dtype: int,
+                        chunk_tokens: int, ntokens: int, bins, blobs_ptr: int, blob_stride: int, sizes_ptr: int, device,
+                        stream: Optional[int] = None, status_ptr: Optional[int] = None) -> int:
+        """lmc_transcode_fixed: nchunks fixed-width blobs anywhere in device memory (blob_ptrs: device int64 [n];
+        blob_bytes_ptr: device-accessible uint32 [n], the room of each) -> the blobs encode_chunks would have written from
+        the same KV, at blobs_ptr + i * blob_stride, sizes at sizes_ptr.  `dtype`: dtype_code of the stored KV."""
+        n = self._encode_job("lmc_transcode_fixed", (blob_ptrs, blob_bytes_ptr, nchunks, L, H, D, dtype, chunk_tokens, ntokens),
+                             0, ntokens, chunk_tokens, bins, blobs_ptr, blob_stride, sizes_ptr, stream, status_ptr, device=device)
+        assert n == nchunks, "ntokens does not make nchunks chunks"
+        return n
 
     def unpack_blobs(self, pack_ptr: int, pack_bytes: int, chunk_begin: int, nchunks: int, dst_ptrs: Sequence[int],
                      dst_caps: Sequence[int], device, stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:

@@ -22,8 +22,10 @@ Three storage modes, chosen by the config:
   local_device="cuda", local_serde="cachegen-fixed"
                                            the same tier (mode "hbm-cachegen", model "fixed") with FIXED-WIDTH blobs
                                            (LMC_MODEL_FIXED: 3.8x instead of 4.6x, no entropy coder on either leg).
-                                           Rows only: an "NHDB" cache is staged; no layer-wise store; an HBM budget
-                                           drops its LRU groups, never demotes them.  ValueError with any other device.
+                                           No layer-wise store.  With both budgets its LRU groups are dropped, as
+                                           they always were -- or, with LMCACHE_AMD_FIXED_DEMOTE=1, demoted like the
+                                           coded tier's, as entropy-coded packs (below); a demoted group is not
+                                           promoted back.  ValueError with any other device.
 
 Bounded tiers.  LMCACHE_AMD_HBM_BYTES / LMCACHE_AMD_PINNED_BYTES (integers, optional K / M / G suffix; read at
 construction, unset = unbounded) or set_capacity() give the HBM and the pinned tier a byte budget.  The unit of
@@ -32,7 +34,18 @@ chain -- in LRU order (a hit touches the groups it read from the last to the fir
 Over budget, the LRU groups are dropped; an "hbm-cachegen" backend with BOTH budgets is tiered instead: its LRU group
 is demoted -- two or more chunks repacked on the GPU into one pinned pack (lmc_pack_blobs, then DMA), a single chunk
 copied as it is -- and a group that is hit in the pinned tier is served where it lies and afterwards promoted on the
-worker thread (lmc_unpack_blobs), demoting colder groups to make room.  What holds:
+worker thread (lmc_unpack_blobs), demoting colder groups to make room.
+The fixed-width tier ("cachegen-fixed") is tiered only where LMCACHE_AMD_FIXED_DEMOTE=1 was set when the backend was
+built (backend.fixed_demotes; the default keeps what the tier did before it could demote: with both budgets its LRU groups
+are dropped).  It demotes by TRANSCODING: its blobs hold the symbols and scales the entropy-coded
+blobs of the same KV hold, so lmc_transcode_fixed turns a group -- one chunk or many -- into those blobs in the codec's
+transient HBM staging (outside both budgets), and from there the leg is the coded tier's: lmc_pack_blobs, DMA, the check
+of the landed pack.  Each tier keeps the format it wants: fixed width where the bytes stay in HBM, entropy-coded where
+they cross PCIe.  The pack's size is known only after the transcode: room in the pinned tier is made for the pack's
+BOUND and the group is filed at the size that landed.  A demoted group is served where it lies, by the rANS decoder
+(every retrieve goes by what an entry IS, never by the backend's model: a prefix half in HBM and half demoted is a
+fixed-width run and a pack run).  PROMOTION of such a group is not built -- it needs the reverse transcode -- so a hit
+does not queue one (logged once) and the group stays in the pinned tier until it is evicted.  What holds:
   1. A key is in exactly one tier, and `contains` never reads False during a demotion or promotion: the new entry is
      published before the old memory is released.  Every change of `dict` bumps `_gen`, so neither the kept prefix
      answer nor the codec's table of a kept entry list can be served stale.
@@ -89,6 +102,7 @@ class _DevChunk:
     blob: torch.Tensor                 # uint8 view of the backend's HBM arena: one encoded chunk
     shape: Tuple[int, ...]
     dtype: torch.dtype
+    model: Optional[str] = None        # the blob's coder model as the codec names it: None (entropy-coded) or "fixed"
 
 
 @dataclass
@@ -245,9 +259,12 @@ class LMCLocalBackend(LMCBackendInterface):
         self._next_gid = 0
         self._promoting: set = set()
         self._oversize_logged = False
-        # (fixed-width blobs are not repacked: with both budgets set their LRU groups are dropped, not demoted)
-        self._tiers = Tiers(self._lru, self._demote_group if self.mode == "hbm-cachegen" and self.model != "fixed" else None,
-                            self._drop_group, self._demoted_size)
+        self._promotion_off_logged = False
+        # both coder models can demote, the fixed-width one by transcoding its blobs (_demote_group) -- but only where it is
+        # asked to: a fixed-width backend with both budgets has always DROPPED its LRU groups, and keeps doing so unless
+        # LMCACHE_AMD_FIXED_DEMOTE=1 says otherwise (read here, once)
+        self.fixed_demotes = self.model == "fixed" and os.environ.get("LMCACHE_AMD_FIXED_DEMOTE", "0") == "1"
+        self._tiers = Tiers(self._lru, self._demote_group if self._demotes() else None, self._drop_group, self._demoted_size)
         self.put_queue: "queue.Queue" = queue.Queue()
         self.put_thread = threading.Thread(target=self.put_worker, daemon=True)
         self.put_thread.start()
@@ -305,13 +322,18 @@ class LMCLocalBackend(LMCBackendInterface):
             self._tiers.budget["hbm"], self._tiers.budget["pinned"] = hbm_bytes, pinned_bytes
             if _keep_unset and hbm_bytes is None and pinned_bytes is None:
                 return
-            if self.mode == "hbm-cachegen" and self.model != "fixed" and pinned_bytes is not None and self.host_arena is None:
+            if self._demotes() and pinned_bytes is not None and self.host_arena is None:
                 self.host_arena = PinnedArena()
             if self.host_arena is not None:
                 self.host_arena.set_budget(pinned_bytes)
             if self.dev_arena is not None:
                 self.dev_arena.set_budget(hbm_bytes)
             self._tiers.enforce()
+
+    def _demotes(self) -> bool:
+        """Whether this backend's HBM tier has a pinned tier under it: the coded HBM tier, and the fixed-width one where
+        fixed_demotes is set."""
+        return self.mode == "hbm-cachegen" and (self.model != "fixed" or self.fixed_demotes)
 
     def tier_of(self, key: CacheEngineKey) -> Optional[str]:
         e = self.dict.get(key)
@@ -376,9 +398,14 @@ class LMCLocalBackend(LMCBackendInterface):
             self._lru.remove(old_gid)
 
     def _demoted_size(self, gid: int) -> int:
-        """Bytes group `gid` of the HBM tier takes in the pinned tier: its pack's exact size, or its one blob's."""
+        """Bytes group `gid` of the HBM tier takes in the pinned tier: its pack's exact size, or its one blob's.  A
+        fixed-width group's pack is known only once it has been transcoded: its BOUND (_demote_group files the group at
+        the size that landed)."""
         g = self._groups[gid]
-        sizes = [self.dict[k].blob.numel() for k in self._own_keys(g) if isinstance(self.dict.get(k), _DevChunk)]
+        devs = [self.dict[k] for k in self._own_keys(g) if isinstance(self.dict.get(k), _DevChunk)]
+        if devs and g.geometry is not None and any(e.model == "fixed" for e in devs):
+            return r16(native.pack_bound(len(devs), g.geometry[0], g.chunk_tokens, g.geometry[1], g.geometry[2]))
+        sizes = [e.blob.numel() for e in devs]
         if len(sizes) >= 2 and len(sizes) == len(g.keys) and g.geometry is not None:
             return r16(self._codec().demoted_bytes(sizes, g.geometry, g.chunk_tokens, g.ntokens))
         return sum(r16(n) for n in sizes) or g.nbytes
@@ -425,8 +452,17 @@ class LMCLocalBackend(LMCBackendInterface):
         if len(keys) != len(g.keys) or not all(isinstance(e, _DevChunk) for e in old):
             return False  # (a group that lost a key to a later store is no whole chain link any more)
         codec = self._codec()
+        fixed = any(e.model == "fixed" for e in old)
+        if fixed and (g.geometry is None or not all(e.model == "fixed" for e in old)):
+            return False
 
         def move():
+            if fixed:
+                # fixed-width blobs cross PCIe entropy-coded: transcoded, then the same pack leg -- a single chunk too (its
+                # blob as it is would be a fixed-width blob in the tier the rANS decoder serves)
+                pack = codec.demote_blobs([e.blob for e in old], g.geometry, g.chunk_tokens, g.ntokens, self.host_arena,
+                                          ready=g.readers[:1], model="fixed", bins=self.cachegen_config.plane_bins(g.geometry[0]))
+                return [_PackChunk(pack, i, e.shape, e.dtype) for i, e in enumerate(old)], r16(pack.blob.nbytes)
             if len(old) >= 2:
                 pack = codec.demote_blobs([e.blob for e in old], g.geometry, g.chunk_tokens, g.ntokens, self.host_arena,
                                           ready=g.readers[:1])
@@ -523,6 +559,13 @@ class LMCLocalBackend(LMCBackendInterface):
             if events:
                 g.readers = g.live_readers() + list(events)
             if self._lru.tier_of(gid) == "pinned" and self._tiers.tiered() and gid not in self._promoting:
+                if self.model == "fixed":
+                    # promotion would have to turn the pack's coded blobs back into fixed-width ones (the reverse
+                    # transcode, not built): the group is served where it lies and stays there
+                    if not self._promotion_off_logged:
+                        self._promotion_off_logged = True
+                        logger.info("fixed-width tier: a demoted group that is hit stays in the pinned tier (no promotion; logged once)")
+                    continue
                 self._promoting.add(gid)
                 self.put_queue.put(lambda gid=gid: self._promote_group(gid))
 
@@ -601,6 +644,14 @@ class LMCLocalBackend(LMCBackendInterface):
         """The codec's `model` argument for this tier's encode / decode_device calls."""
         return {"model": "fixed"} if self.model == "fixed" else {}
 
+    @staticmethod
+    def _run_model(entries: Sequence) -> Optional[str]:
+        """The coder model of a run of HBM entries, read off the entries (one decode job is one model)."""
+        models = {e.model for e in entries}
+        if len(models) != 1:
+            raise ValueError("one decode job over HBM blobs of two coder models")
+        return models.pop()
+
     def _group_of(self, geometry: tuple, chunk_tokens: int, shapes) -> dict:
         """What _store keeps about a CacheGen group beside its entries (the repack legs of demotion and promotion need it)."""
         tok = _token_axis(self.fmt or "vllm")
@@ -616,15 +667,29 @@ class LMCLocalBackend(LMCBackendInterface):
                 blobs = codec.keep_on_device(job, self.dev_arena)
                 ready = torch.cuda.Event()
                 ready.record(torch.cuda.current_stream(self._cuda_device))
-                return [_DevChunk(t, shp, dtype) for t, shp in zip(blobs, shapes)], sum(r16(t.numel()) for t in blobs), ready
+                return ([_DevChunk(t, shp, dtype, self._coder().get("model")) for t, shp in zip(blobs, shapes)],
+                        sum(r16(t.numel()) for t in blobs), ready)
             if self._tiers.budget["hbm"] is None:
                 self._store("hbm", 0, keep, keys, **group)
                 return
             sizes = codec.sizes_of(job)
             nbytes = sum(r16(n) for n in sizes)
-            where = self._tiers.place(nbytes)
+            fixed = self.model == "fixed"
+            L, H, D = group["geometry"]
+            bound = r16(native.pack_bound(len(sizes), L, group["chunk_tokens"], H, D)) if fixed else None
+            where = self._tiers.place(nbytes, bound)
             if where == "hbm":
                 ok = self._store("hbm", nbytes, keep, keys, **group)
+            elif where == "pinned" and fixed:
+                # larger than the whole HBM budget: straight to the pinned tier, transcoded from the encode arena into one
+                # entropy-coded pack (room is made for its bound, the group is filed at the size that landed)
+                def to_pack():
+                    views = [job.arena[i * job.stride:i * job.stride + nb] for i, nb in enumerate(sizes)]
+                    pack = codec.demote_blobs(views, group["geometry"], group["chunk_tokens"], group["ntokens"], self.host_arena,
+                                              ready=[job.done], model="fixed", bins=self.cachegen_config.plane_bins(L))
+                    job.offload_issued = True
+                    return [_PackChunk(pack, i, shp, dtype) for i, shp in enumerate(shapes)], r16(pack.blob.nbytes), None
+                ok = self._store("pinned", bound, to_pack, keys, **group)
             elif where == "pinned":  # larger than the whole HBM budget: straight to the pinned tier, a blob per chunk
                 ok = self._store("pinned", nbytes, lambda: self._offload_entries(job, sizes, shapes, dtype), keys, **group)
             else:
@@ -760,7 +825,7 @@ class LMCLocalBackend(LMCBackendInterface):
             T = entry.shape[2] if fmt == "vllm" else entry.shape[3]
             codec = self._codec()
             try:
-                codec.finish_decode(codec.decode_device([entry.blob], native.KVLayout.from_chunk(out, fmt), 0, T, **self._coder()))
+                codec.finish_decode(codec.decode_device([entry.blob], native.KVLayout.from_chunk(out, fmt), 0, T, model=entry.model))
             except native.NativeError:
                 logger.exception("stored chunk does not decode: treated as a miss")
                 return None
@@ -986,7 +1051,7 @@ class LMCLocalBackend(LMCBackendInterface):
             return 0
         ctx = native.get_context(self._cuda_device)
         dev = dst.device
-        if self.mode == "hbm-cachegen" and all(isinstance(e, _DevChunk) for e in entries):
+        if self.mode == "hbm-cachegen" and all(isinstance(e, _DevChunk) for e in entries) and len({e.model for e in entries}) == 1:
             # blobs in HBM: one decode launch per range of layers, an event after each; with jobs_out the call
             # returns at once and the caller finishes the job (engine.retrieve_layerwise)
             codec = self._codec()
@@ -994,7 +1059,7 @@ class LMCLocalBackend(LMCBackendInterface):
                 # (`entries` is the SAME list object for a repeated lookup of one prefix -- _prefix_entries -- and the codec
                 # keeps the uploaded address table of the last few lists it has seen)
                 job = codec.decode_device([e.blob for e in entries], dst, dst_tok0, chunk_tokens, layers_per_launch,
-                                          same_blobs_as=entries, post=post, **self._coder())
+                                          same_blobs_as=entries, post=post, model=self._run_model(entries))
             self._touch(keys[:len(entries)], [job.done])
             if jobs_out is not None:
                 jobs_out.append((codec, job))
@@ -1014,7 +1079,7 @@ class LMCLocalBackend(LMCBackendInterface):
 
             def kind_of(e):
                 if isinstance(e, _DevChunk):
-                    return "dev"
+                    return "dev-fixed" if e.model == "fixed" else "dev"
                 return "pack" if isinstance(e, _PackChunk) and e.pack.chunk_tokens == chunk_tokens else "blobs"
             while i < len(entries):
                 e = entries[i]
@@ -1035,9 +1100,9 @@ class LMCLocalBackend(LMCBackendInterface):
             for kind, i, j in runs:
                 tok0 = dst_tok0 + i * chunk_tokens
                 with torch.cuda.device(dev):
-                    if kind == "dev":
+                    if kind in ("dev", "dev-fixed"):
                         job = codec.decode_device([e.blob for e in entries[i:j]], dst, tok0, chunk_tokens, layers_per_launch,
-                                                  post=post, **self._coder())
+                                                  post=post, model=self._run_model(entries[i:j]))
                     elif kind == "pack":
                         job = codec.load_pack(entries[i].pack, entries[i].index, j - i, dst, tok0, layers_per_launch, post=post)
                     else:
@@ -1053,7 +1118,7 @@ class LMCLocalBackend(LMCBackendInterface):
                         else:
                             job = codec.decode(blobs, dst, tok0, chunk_tokens)
                 events.append(job.done)
-                if layerwise or (kind == "dev" and jobs_out is not None):
+                if layerwise or (kind in ("dev", "dev-fixed") and jobs_out is not None):
                     jobs_out.append((codec, job))
                 else:
                     codec.finish_decode(job)  # this decode's event, then its own status word

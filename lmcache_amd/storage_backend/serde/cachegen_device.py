@@ -630,6 +630,7 @@ class CacheGenDeviceCodec:
         self.decode_batch_chunks = 8                         # chunks per H2D/decode pipeline stage
         self._pack_dev: Optional[torch.Tensor] = None        # HBM staging of a pack on its way to pinned memory (store_pack)
         self._pack_dev_free: Optional[torch.cuda.Event] = None
+        self._xcode_dev: Optional[torch.Tensor] = None       # HBM staging of a fixed-width group's coded blobs (transcode_fixed)
         self._pack_prev = None                               # weak reference to the last PackJob that took _pack_dev
         # plane ranges a pack's encode is launched in (store_pack): LMCACHE_AMD_PACK_PARTS=1 is the round-5 behaviour
         # (the whole encode, then the pack, then its copies), for A/B
@@ -668,6 +669,10 @@ class CacheGenDeviceCodec:
     _ENCODERS = {(None, False): "encode_chunks", (None, True): "encode_chunks_split",
                  ("fixed", False): "encode_chunks_fixed", ("fixed", True): "encode_chunks_fixed_split"}
     _SCHEDULES = {("fixed", False): "decode_chunks_fixed_schedule", ("fixed", True): "decode_chunks_fixed_split_schedule"}
+
+    # coder model of a group's HBM blobs -> the codec's method that turns them into entropy-coded blobs in front of the pack
+    # leg of a demotion (None: they are coded already)
+    _DEMOTERS = {None: None, "fixed": "transcode_fixed"}
 
     def _entry(self, names: dict, model: Optional[str], layout: native.KVLayout, default: Optional[str] = None):
         """self.ctx's method, looked up at call time, for an encode from / a decode into `layout` in coder `model`: the one
@@ -1151,14 +1156,70 @@ class CacheGenDeviceCodec:
             return DecodeJob(events[-1][1], events, status_idx=st, pool=self._status)
 
     # ---- bounded tiers: HBM blobs <-> pinned pack, no re-encode ---------------------------------------------------------
+    def transcode_fixed(self, blobs: Sequence[torch.Tensor], geometry: tuple, chunk_tokens: int, ntokens: int,
+                        bins: Sequence[int], ready: Sequence = ()) -> List[torch.Tensor]:
+        """Fixed-width HBM blobs of one store group (exact-size uint8 tensors, anywhere) -> the entropy-coded blobs
+        encode() would have written from the same KV (lmc_transcode_fixed), as exact-size views of the codec's transcode
+        staging: a transient HBM region at blob_bound stride, codec-owned, grown on demand and OUTSIDE every tier's
+        budget (it holds a group only while that group is on its way out of HBM).  The views are good until the next
+        transcode_fixed; the caller holds the codec's lock across their use (demote_blobs does).  Blocks until the sizes
+        are there; NativeError if the job's status word is set -- a fixed blob that does not check out."""
+        L, H, D = geometry
+        n = len(blobs)
+        stride = native.r16(native.blob_bound(L, chunk_tokens, H, D))
+        with self._lock, torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            if self._xcode_dev is None or self._xcode_dev.numel() < n * stride:
+                cur.synchronize()  # (whoever read the views of the region that goes)
+                self._xcode_dev = None
+                self._xcode_dev = torch.empty(n * stride, dtype=torch.uint8, device=self.device)
+            out = self._xcode_dev
+            _stream_waits(cur, ready)
+            # the stored KV's dtype is the blobs' own header word (a group is one store: one dtype)
+            dtype = int(blobs[0][8:12].view(torch.int32).item())
+            words = [b.data_ptr() for b in blobs]
+            room = [b.numel() for b in blobs]
+            words += [room[i] | (room[i + 1] << 32 if i + 1 < n else 0) for i in range(0, n, 2)]  # uint32 pairs
+            table = torch.tensor(words, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+            loans = []
+            with self._launch(cur, loans) as (st, st_ptr):
+                sizes = _borrow(loans, self._size_pool, 4 * n, 4 * max(n, 256))
+                self.ctx.transcode_fixed(table.data_ptr(), table.data_ptr() + 8 * n, n, L, H, D, dtype, chunk_tokens, ntokens,
+                                         bins, out.data_ptr(), stride, sizes.ptr, self.device, stream=cur.cuda_stream,
+                                         status_ptr=st_ptr)
+                done = torch.cuda.Event()
+                done.record(cur)
+            job = Job(done, status_idx=st, pool=self._status, loans=loans)
+            done.synchronize()
+            got = sizes.tensor[:4 * n].view(torch.int32).tolist()  # before the words go back
+            _raise_on(job.retire(), "CacheGen demotion (lmc_transcode_fixed)")
+            if any(nb <= 0 or nb > stride for nb in got):
+                raise native.NativeError("CacheGen demotion (lmc_transcode_fixed): a chunk was not coded")
+            return [out[i * stride:i * stride + nb] for i, nb in enumerate(got)]
+
     def demote_blobs(self, blobs: Sequence[torch.Tensor], geometry: tuple, chunk_tokens: int, ntokens: int,
-                     arena: PinnedArena, ready: Sequence = ()) -> HostPack:
+                     arena: PinnedArena, ready: Sequence = (), model: Optional[str] = None,
+                     bins: Optional[Sequence[int]] = None) -> HostPack:
         """The demotion leg: the HBM blobs of one store group (exact-size uint8 tensors, anywhere) -> one pack in pinned
         host DRAM, byte for byte the pack store_pack would have written.  lmc_pack_blobs repacks them on the GPU into the
         HBM pack staging, two DMA copies move the pack into a region of `arena` taken at its exact size (the blobs'
         sizes say what it is), and lmc_pack_info checks it where it landed.  Blocks until the pack is there (a worker's
         call, or set_capacity's); raises NativeError -- nothing kept -- if the job's status word or the check says no,
-        ArenaFull if `arena` has no room.  ready: events behind the writes of the blobs."""
+        ArenaFull if `arena` has no room.  ready: events behind the writes of the blobs.
+        model "fixed" (with the planes' `bins`): the blobs are LMC_MODEL_FIXED and are transcoded first (transcode_fixed:
+        into the codec's transient HBM staging, which no budget counts); the coded blobs' sizes are read, and from there
+        the leg is the same leg -- the pack holds entropy-coded streams, whichever model the HBM tier keeps."""
+        if model not in self._DEMOTERS:
+            raise ValueError(f"unknown coder model {model!r} (None or 'fixed')")
+        first = self._DEMOTERS[model]
+        with self._lock:  # (re-entrant: the staging's views stay the group's until the pack has left)
+            if first is not None:
+                blobs, ready = getattr(self, first)(blobs, geometry, chunk_tokens, ntokens, bins, ready), ()
+            return self._pack_out(blobs, geometry, chunk_tokens, ntokens, arena, ready)
+
+    def _pack_out(self, blobs: Sequence[torch.Tensor], geometry: tuple, chunk_tokens: int, ntokens: int,
+                  arena: PinnedArena, ready: Sequence = ()) -> HostPack:
+        """demote_blobs behind its model: entropy-coded blobs -> the pack in `arena`."""
         L, H, D = geometry
         n = len(blobs)
         total = self.demoted_bytes([b.numel() for b in blobs], geometry, chunk_tokens, ntokens)
@@ -1356,7 +1417,7 @@ class CacheGenDeviceCodec:
             if self._stage is not None:
                 self._stage.free()
                 self._stage = None
-            self._enc_arena = self._dec_arena = self._pack_dev = None
+            self._enc_arena = self._dec_arena = self._pack_dev = self._xcode_dev = None
             self._table_cache, self._same_blobs = {}, {}
 
 
