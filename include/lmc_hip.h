@@ -653,6 +653,37 @@ int lmc_transcode_fixed(lmc_ctx* ctx, const void* const* blob_ptrs, const uint32
                         int32_t H, int32_t D, int32_t dtype, int32_t chunk_tokens, uint32_t ntokens, const int32_t* bins_h,
                         void* blobs_out, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream);
 
+/*
+ * lmc_transcode_to_fixed -- the way back, a demoted fixed-width group's promotion: n entropy-coded blobs (LMC_MODEL_COUNTS
+ *   or LMC_MODEL_CDF16) that lie ANYWHERE in device memory -> the LMC_MODEL_FIXED blobs lmc_encode_chunks_fixed would have
+ *   written from the KV they were stored from, byte for byte, without that KV:
+ *       lmc_transcode_to_fixed(lmc_encode_chunks(x)) == lmc_encode_chunks_fixed(x)
+ *   over every byte of [0, lmc_fixed_blob_bytes), pads included.  Replaces nothing in the reference (it has no second
+ *   coder model).  ONE launch on `stream`: the rANS decoder with a fixed-width sink (k_decode.h, DEC_SINK_FIXED) -- the
+ *   two formats share the stream geometry, so the wave that decodes a coded stream writes one fixed-width stream, a plane's
+ *   first wave copies the scales, the chunk's first wave writes header, bins and pads.  No workspace (neither KV nor
+ *   symbols are staged), no host wait.
+ *   blob_ptrs    device array [nchunks] of blob addresses, each 16-byte aligned
+ *   blob_bytes   device-accessible uint32 [nchunks]: the room each pointer may be read for (0 = no blob there)
+ *   L, H, D, dtype   the geometry and the 16-bit KV dtype the blobs were stored with (no fp8: the fixed tier has none);
+ *                    planes of up to LMC_MAX_CHANNELS channels
+ *   ntokens      tokens of all chunks together (every chunk chunk_tokens long but, possibly, the last)
+ *   bins_h       host int32 [2 L]: must be the bins the blobs hold
+ *   out_ptrs     device array [nchunks]: where chunk i's fixed-width blob goes, 16-byte aligned, anywhere
+ *   out_bytes    device-accessible uint32 [nchunks]: the room there, >= lmc_fixed_blob_bytes for the chunk's length
+ *   Refusals are lmc_transcode_fixed's: LMC_ERR_INVALID with nothing queued (geometry, dtype, bins, a fixed-width blob of
+ *   2^32 bytes or more, 2^31 streams or more).  On the device a blob is held against everything lmc_decode_chunks holds it
+ *   against, in its order, and against the call: pointer, alignment and room before the header is read, total_bytes
+ *   against blob_bytes[i], L / H / D / dtype / the chunk's length, the bins, a coded model (an LMC_MODEL_FIXED input is a
+ *   bad header), header word 23 == 0, and the output's pointer and room: LMC_STATUS_BAD_HEADER, and nothing is written for
+ *   that stream.  LMC_STATUS_BAD_SCALES / BAD_STREAM are known only once scales or stream have been consumed: that
+ *   chunk's output is then unspecified, but nothing is written outside its [out_ptrs[i], + lmc_fixed_blob_bytes), and the
+ *   other chunks of the job are not touched by it.
+ */
+int lmc_transcode_to_fixed(lmc_ctx* ctx, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks,
+                           int32_t L, int32_t H, int32_t D, int32_t dtype, int32_t chunk_tokens, uint32_t ntokens,
+                           const int32_t* bins_h, void* const* out_ptrs, const uint32_t* out_bytes,
+                           uint32_t* job_status, lmc_stream_t stream);
 
 int lmc_stream_create(lmc_stream_t* out);
 int lmc_stream_destroy(lmc_stream_t s);

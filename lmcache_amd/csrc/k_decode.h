@@ -27,6 +27,7 @@
 // descriptor's range).  4.9 KiB of LDS per wave -> 8 waves per SIMD.
 #pragma once
 #include "k_head.h"
+#include "k_encode.h"  // write_blob_static: the fixed-width sink writes a blob's static sections
 
 // lmc_tok_off for the decoder's scatter: a block size that is a power of two (every one vLLM offers) costs a shift and a
 // mask instead of a 32-bit division per lane and 64 tokens (wave-uniform branch).  Kept apart from lmc_tok_off: the same
@@ -76,6 +77,14 @@ struct DecodeArgs {
   const unsigned long long* seg_off;
   const u8* seg_streams;
   int seg_n;
+  // SINK == DEC_SINK_FIXED (lmc_transcode_to_fixed): chunk i's coded blob may be read for blob_bytes[i] bytes, its
+  // LMC_MODEL_FIXED blob goes to out_ptrs[i] (out_bytes[i] bytes of room); the call's geometry, dtype and bins, which the
+  // blob must hold and the new header is written from; tok_end = tokens of all chunks together
+  const u32* blob_bytes;
+  u8* const* out_ptrs;
+  const u32* out_bytes;
+  int L, H, D, dtype, tok_end;
+  BinsArg bins;
 };
 
 // LDS of a workgroup: the four waves' dequantisation LUTs (32 x f32 = 128 B each) FIRST -- their byte addresses stay
@@ -135,8 +144,21 @@ __device__ unsigned long long g_decode_timeline[65536 * 4];
 // value plane), and the eight tokens of a block of the block path are, in a value plane, 16 (fp8: 8) CONTIGUOUS bytes of
 // the lane: one wide store where the rows take eight narrow ones.
 enum { DEC_ROWS = 0, DEC_PAGED_ROWS = 1, DEC_PAGED_SPLIT = 2 };
-template <bool SYMOUT, int DT_OUT, int KIND>
+// SINK: what a decoded symbol becomes.  DEC_SINK_KV: the dequantised element in the caller's KV (DT_OUT, KIND).
+// DEC_SINK_SYM: an int8 in sym_out (lmc_decode_symbols).  DEC_SINK_FIXED: its 4 or 5 bits in the LMC_MODEL_FIXED blob of
+// the same chunk (lmc_format.h; lmc_transcode_to_fixed, the fixed-width tier's promotion): the two formats share the
+// stream geometry -- (plane, 64-channel group), lane = channel -- so the wave that decodes a coded stream writes exactly
+// one fixed-width stream: per oct of eight tokens a `lo` dword per lane (one coalesced 256-byte store) and, where the
+// plane has more than 17 bins, a `hi` byte per lane (64 bytes); the check word is summed on the way, lane by lane (it
+// is linear mod 2^32), and one wave_sum_u32 at the end gives the tail.  The same wave writes its directory entry; a
+// plane's first wave copies the scales (it sums them anyway) and scsum; the chunk's first wave header, bins and pads.
+// Every byte of [0, lmc_fixed_blob_bytes) is written, as k_fixed_encode writes it.  DT_OUT and KIND are unused there.
+enum { DEC_SINK_KV = 0, DEC_SINK_SYM = 1, DEC_SINK_FIXED = 2 };
+template <int SINK, int DT_OUT, int KIND>
 __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(8))) void k_decode(DecodeArgs a) {
+  constexpr bool FIXOUT = SINK == DEC_SINK_FIXED;
+  constexpr bool SYMOUT = SINK != DEC_SINK_KV;  // no KV destination: no dequantisation LUT, no scales, no rows
+  static_assert(!FIXOUT || (DT_OUT == LMC_DTYPE_BF16 && KIND == DEC_ROWS), "one fixed-width instance");
   __shared__ __attribute__((aligned(16))) u8 lds_all[DEC_WAVES * (DEC_LUT_BYTES + DEC_WAVE_BYTES)];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform -> SGPRs
@@ -179,6 +201,14 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   const int p = pidx < a.layer_count ? a.layer_begin + pidx : (a.P >> 1) + a.layer_begin + pidx - a.layer_count;
   const int pg = p * a.G + g;
   const u8* blob = a.blob_ptrs ? (const u8*)uniform_ptr(a.blob_ptrs[chunk]) : a.blobs + (long long)chunk * a.blob_stride;
+  u32 room = 0;  // FIXOUT: how far this chunk's blob may be read
+  if constexpr (FIXOUT) {  // pointer and room before the header is read (k_fixed_expand's rule)
+    room = (u32)__builtin_amdgcn_readfirstlane((int)a.blob_bytes[chunk]);
+    if (!blob || ((u64)(uintptr_t)blob & 15ull) || room < LMC_HEADER_BYTES) {
+      if (lane == 0) atomicOr(a.status, LMC_ST_BAD_HEADER);
+      return;
+    }
+  }
   // The header's 32 words with ONE coalesced load (lane i holds word i), handed out by v_readlane: all control flow
   // below is scalar, and the validity test -- a chain of || over nine header words -- no longer walks through nine
   // dependent round trips to memory (round 6: the prologue was 15 us of a wave's 95, most of it this chain).
@@ -188,7 +218,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   // length turns out to be -- the directory entry at the offset a chunk of chunk_tokens tokens has it at.  A shorter
   // chunk (a ragged last one) reads its entry again below.  (Blobs behind a pointer table end where they end: no
   // speculative read there.)
-  const u32 bins_p = (u32)((const LMC_GLOBAL u8*)blob)[LMC_HEADER_BYTES + p];
+  // (FIXOUT: a blob behind a pointer is read for its header alone until that has been checked; the bins are the call's)
+  const u32 bins_p = FIXOUT ? (u32)a.bins.b[p] : (u32)((const LMC_GLOBAL u8*)blob)[LMC_HEADER_BYTES + p];
   const BlobOff bo_spec = lmc_blob_off((u32)a.P, (u32)a.chunk_tokens, (u32)a.G);
   const bool spec = !SYMOUT && !a.blob_ptrs && (unsigned long long)bo_spec.streams <= (unsigned long long)a.blob_stride;
   u32x2_t gd_spec = {0u, 0u};
@@ -213,6 +244,52 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   }
   const int c = g * 64 + lane;
   const bool active = c < a.C;
+
+  // ---- FIXOUT: what a transcode adds (k_fixed_expand's list), then where the chunk's fixed-width blob puts this stream --
+  u8* fx_out = nullptr;      // the output blob
+  u32 fx_O = 0, fx_beg = 0, fx_ssize = 0, fx_total = 0;  // octs; the stream's place in, its size, and the size of the streams section
+  if constexpr (FIXOUT) {
+    const u32 Tc = (u32)min(a.chunk_tokens, a.tok_end - chunk * a.chunk_tokens);
+    // the call's geometry, dtype and chunk length (the new header is written from the call's); a 16-bit KV (word 23); the
+    // sections in front of the streams and the streams themselves inside total_bytes, and that inside the room
+    if (T != Tc || src_dtype != (u32)a.dtype || hdw(3) != (u32)a.L || hdw(5) != (u32)a.H || hdw(6) != (u32)a.D || hdw(23) != 0u ||
+        (unsigned long long)hdw(15) + (unsigned long long)hdw(16) != (unsigned long long)hdw(17) ||
+        (unsigned long long)hdw(17) > (unsigned long long)room) {
+      if (lane == 0) atomicOr(a.status, LMC_ST_BAD_HEADER);
+      return;
+    }
+    // the blob's bins (in front of off_streams <= total_bytes <= room) against the call's: lane = four planes' bins
+    const u32 bw = 4 * lane < a.P ? ((const LMC_GLOBAL u32*)(blob + LMC_HEADER_BYTES))[lane] : 0u;
+    bool bad = false;
+    for (int j = 0; 4 * j < a.P; j++) {  // (wave-uniform: scalar loads of the call's, a readlane of the blob's)
+      u32 want;
+      __builtin_memcpy(&want, a.bins.b + 4 * j, 4);
+      const u32 mask = a.P - 4 * j >= 4 ? 0xffffffffu : (1u << (8 * (a.P - 4 * j))) - 1u;
+      bad = bad || (((u32)__builtin_amdgcn_readlane((int)bw, j) ^ want) & mask) != 0u;
+    }
+    // lmc_fixed_stream_bytes summed, as k_fixed_expand sums it: 256 O + 16 per stream, 64 O more per plane of more than
+    // 17 bins (the host has seen to it that the call's geometry and bins stay below 2^32)
+    u32 nwide = 0, nwide_before = 0;
+    for (int q0 = 0; q0 < a.P; q0 += 64) {
+      const int q = q0 + lane;
+      const u32 b = ((u32)__shfl((int)bw, q >> 2) >> (8 * (q & 3))) & 0xffu;
+      const u64 m = __ballot(q < a.P && b > LMC_FIXED_NARROW_BINS);
+      const int below = p - q0;  // planes of this round that lie in front of p
+      nwide += (u32)__builtin_popcountll(m);
+      nwide_before += (u32)__builtin_popcountll(below >= 64 ? m : below <= 0 ? 0ull : m & ((1ull << below) - 1ull));
+    }
+    fx_O = (T + 7u) >> 3;
+    fx_total = (u32)a.G * ((256u * fx_O + LMC_FIXED_TAIL_BYTES) * (u32)a.P + 64u * fx_O * nwide);
+    fx_ssize = (bins_p > LMC_FIXED_NARROW_BINS ? 320u : 256u) * fx_O + LMC_FIXED_TAIL_BYTES;
+    fx_beg = (u32)a.G * ((256u * fx_O + LMC_FIXED_TAIL_BYTES) * (u32)p + 64u * fx_O * nwide_before) + (u32)g * fx_ssize;
+    fx_out = (u8*)uniform_ptr(a.out_ptrs[chunk]);
+    const u32 out_room = (u32)__builtin_amdgcn_readfirstlane((int)a.out_bytes[chunk]);
+    if (bad || !fx_out || ((u64)(uintptr_t)fx_out & 15ull) ||
+        (unsigned long long)bo.streams + (unsigned long long)fx_total > (unsigned long long)out_room) {
+      if (lane == 0) atomicOr(a.status, LMC_ST_BAD_HEADER);
+      return;
+    }
+  }
 
   // ---- where the stream lies (directory entry {beg, end}, lmc_format.h v6) ------------------------------------------
   const u32* gdir = reinterpret_cast<const u32*>(blob + bo.gdir);
@@ -364,6 +441,30 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
       return;
     }
   }
+  if constexpr (FIXOUT) {
+    // Everything of the new blob that is not this stream's lo / hi / tail, here: in front of the ring's first request, so
+    // that none of these stores falls between a request and its take (block_take's vmcnt(N) counts the oct stores alone).
+    if (g == 0) {  // the plane's first wave: the scales into the new blob, summed on the way, and scsum
+      u16* const so = reinterpret_cast<u16*>(fx_out + bo.scales) + (long long)p * T;
+      const u32 want = (u32)__builtin_amdgcn_readfirstlane((int)reinterpret_cast<const u32*>(blob + bo.scsum)[p]);
+      u32 sacc = 0;
+      for (u32 t = (u32)lane; t < T; t += 64) {
+        const u32 v = (u32)scl[t];
+        sacc += (t + 1u) * (v + 1u);  // lmc_scale_checksum_term
+        so[t] = (u16)v;
+      }
+      if (wave_sum_u32(sacc) != want) {
+        if (lane == 0) atomicOr(a.status, LMC_ST_BAD_SCALES);
+        return;
+      }
+      if (lane == 0) reinterpret_cast<u32*>(fx_out + bo.scsum)[p] = want;
+      if (p == 0) {  // the chunk's first wave: header, bins and pads, as k_fixed_encode writes them
+        write_blob_static(fx_out, bo, a, T, fx_total, lane);
+        if (lane == 22) reinterpret_cast<u32*>(fx_out)[22] = LMC_MODEL_FIXED;  // (the lane that wrote the coded models' word)
+      }
+    }
+    if (lane == 0) *(LMC_GLOBAL u32x2_t*)(fx_out + bo.gdir + 8u * (u32)pg) = u32x2_t{fx_beg, fx_beg + fx_ssize};
+  }
   if (!SYMOUT && lane < 32) {
     const float Cf = (float)((int)bins_p / 2 - 1);
     const float v = (float)lane - Cf;
@@ -500,6 +601,10 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   }
   const int tdst0 = a.dst_tok0 + chunk * a.chunk_tokens;
   const u32 fp8_lim = OUT8 ? fp8_fast_scale_limit<OUT8 ? DT_OUT : LMC_DTYPE_FP8_E4M3>(nsym + 1u) : 0u;  // (wave-uniform)
+
+  // FIXOUT: the oct being gathered (lo dword, hi byte), the lane's share of the stream's check word, the output stream
+  u32 fx_lo = 0, fx_hi = 0, fx_acc = 0;
+  u8* const fx_sb = FIXOUT ? fx_out + bo.streams + fx_beg : nullptr;  // (wave-uniform)
 
   // the ring bookkeeping is wave-uniform (SGPRs: its tests are scalar branches); runs when e <= trig
   auto ring_event = [&]() {
@@ -782,6 +887,55 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     // block that is not (slots in any order, a first token in the middle of a group of eight of its block) sends the
     // whole stream through the one-token loop.
     u32 tgen = nskip;
+    // FIXOUT: a symbol (as decode_token returns it) into the oct being gathered, token k of the oct; every field masked
+    // to its width, so that a damaged stream -- flagged at the end -- cannot spill into a neighbour's bits
+    auto fx_put = [&](u32 sa, u32 k) {
+      const u32 sym = WIDE ? (sa - lut_addr) >> 2 : (sa - col_addr) >> 7;
+      fx_lo |= (sym & 15u) << (8u * (k & 3u) + 4u * (k >> 2));
+      if constexpr (!WIDE) fx_hi |= ((sym >> 4) & 1u) << k;  // (16 symbols at most <=> bins <= 17: no hi section)
+    };
+    // ... and oct o into the stream.  EVERY lane stores (a lane without a channel its zeros: the format defines them,
+    // the memory is not pre-zeroed), unconditionally: nst counts vector memory operations that were really issued
+    auto fx_flush = [&](u32 o) {
+      const u32 lo = active ? fx_lo : 0u;
+      const u32 li = o * 64u + (u32)lane;
+      __builtin_nontemporal_store(lo, (LMC_GLOBAL u32*)fx_sb + li);  // 256 bytes, coalesced
+      fx_acc += (2u * li + 1u) * lo;
+      if constexpr (!WIDE) {
+        const u32 hi = active ? fx_hi : 0u;
+        __builtin_nontemporal_store((u8)hi, (LMC_GLOBAL u8*)fx_sb + (256u * fx_O + li));  // 64 bytes
+        // the byte's dword is number 64 O + 16 o + lane / 4 of the stream, the byte its lane % 4 -th
+        fx_acc += (2u * (64u * fx_O + (li >> 2)) + 1u) * (hi << (8u * ((u32)lane & 3u)));
+        fx_hi = 0u;
+      }
+      fx_lo = 0u;
+#if LMC_DEC_RING_AGPR
+      nst += WIDE ? 1u : 2u;  // (exactly the vector memory operations issued above: block_take's vmcnt(N) counts on it)
+#endif
+    };
+    if constexpr (FIXOUT) {
+      // Whole octs, as the rows' block path takes its eight tokens: four pairs, the ring looked after behind every second
+      // token, the shift counts compile-time numbers and the loop's scalar work once per oct.  (Token by token -- the
+      // loop below, which keeps the ragged last oct -- the transcode of a 16 k context took 0.95 ms where the plain decode
+      // takes 0.77: profiles/fixed_model.md.)
+      const u32 nblk = (u32)__builtin_amdgcn_readfirstlane((int)(T >> 3));
+      for (u32 o = 0; o < nblk; o++) {
+        auto pair = [&](auto k_tag) {
+          constexpr u32 K = (u32)decltype(k_tag)::value;
+          float lv_unused;
+          const u32 sa = decode_token(top_tag, model_tag, lv_unused, BoolTag<false>{});
+          fx_put(sa, K);
+          const u32 sb = decode_token(top_tag, model_tag, lv_unused, BoolTag<true>{});
+          fx_put(sb, K + 1u);
+        };
+        pair(IntTag<0>{});
+        pair(IntTag<2>{});
+        pair(IntTag<4>{});
+        pair(IntTag<6>{});
+        fx_flush(o);
+      }
+      tgen = 8u * nblk;
+    }
     // fp8 destinations take the same blocks: two tokens' bytes leave as buffer_store_byte + buffer_store_byte_d16_hi.
     if constexpr (!SYMOUT && SRC_BF16 && (DT_OUT == LMC_DTYPE_BF16 || OUT8) && decltype(model_tag)::value) {
       typedef u32x4_t __attribute__((aligned(4))) u32x4_a4;
@@ -956,7 +1110,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
       auto one_token = [&](u32 i) {
         float lv = 0.0f;
         const u32 sa = decode_token(top_tag, model_tag, lv, BoolTag<true>{});
-        if (SYMOUT) {
+        if constexpr (FIXOUT) {  // the ragged last oct: the token's place in it is wave-uniform (scalar shift counts)
+          const u32 k = (t0 + i) & 7u;
+          fx_put(sa, k);
+          if (k == 7u || t0 + i + 1u == T) fx_flush((t0 + i) >> 3);  // (tokens >= T of the last oct stay 0)
+        } else if (SYMOUT) {
           const u32 sym = WIDE ? (sa - lut_addr) >> 2 : (sa - col_addr) >> 7;
           if (active) *((LMC_GLOBAL int8_t*)(ubase + (u64)(t0 + i) * a.C) + lane_off) = (int8_t)sym;
         } else {
@@ -1010,7 +1168,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
       else run(src_tag, IntTag<8>{}, BoolTag<false>{});
     }
   };
-  if (src_dtype == (u32)LMC_DTYPE_BF16) run_src(BoolTag<true>{});
+  if constexpr (FIXOUT) run_src(BoolTag<true>{});  // (symbols and scale bits are the same whatever the 16-bit dtype: one body)
+  else if (src_dtype == (u32)LMC_DTYPE_BF16) run_src(BoolTag<true>{});
   else run_src(BoolTag<false>{});
 
 #ifdef LMC_EXP_TIMELINE
@@ -1025,5 +1184,9 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   const bool state_bad = active && x != rans_l;
   if (e != 0 || __ballot(state_bad)) {
     if (lane == 0) atomicOr(a.status, LMC_ST_BAD_STREAM);
+  }
+  if constexpr (FIXOUT) {  // the tail: the check word, then 12 zero bytes
+    const u32 chk = wave_sum_u32(fx_acc);
+    if (lane < 4) ((LMC_GLOBAL u32*)(fx_sb + fx_ssize - LMC_FIXED_TAIL_BYTES))[lane] = lane == 0 ? chk : 0u;
   }
 }

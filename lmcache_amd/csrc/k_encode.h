@@ -101,8 +101,9 @@ __global__ __launch_bounds__(64) void k_set_kv_dtype(u8* blobs, long long stride
 // Header, bins and the zero pads between sections (what the oracle memsets): by one wave.  KV_DT: the header's kv_dtype
 // word (lmc_format.h), 0 but in the fused encoder's fp8 instances (the two-kernel path's coder does not know the KV
 // dtype: lmc_api.hip sets the word behind it, k_set_kv_dtype).
-template <int KV_DT = 0>
-__device__ __forceinline__ void write_blob_static(u8* blob, const BlobOff& bo, const EncodeArgs& a, u32 T,
+// (ARGS: EncodeArgs, or the decoder's DecodeArgs when it writes a fixed-width blob: P, C, G, L, H, D, dtype and bins)
+template <int KV_DT = 0, class ARGS = EncodeArgs>
+__device__ __forceinline__ void write_blob_static(u8* blob, const BlobOff& bo, const ARGS& a, u32 T,
                                                   u32 stream_bytes, int lane) {
   const u32 P = (u32)a.P, n = (u32)(a.P * a.G);
   for (u32 i = lane; i < bo.scales - bo.bins; i += 64) blob[bo.bins + i] = i < P ? a.bins.b[i] : (u8)0;

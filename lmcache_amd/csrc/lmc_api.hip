@@ -1060,9 +1060,9 @@ static bool decode_blobs(DecodeArgs& a, const void* blobs, uint64_t stride, cons
 static void launch_decode(int dtype, int kind, dim3 grid, hipStream_t s, const DecodeArgs& a) {
   with_kv_dtype(dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
-    if (kind == DEC_PAGED_SPLIT) hipLaunchKernelGGL((k_decode<false, DT, DEC_PAGED_SPLIT>), grid, dim3(64 * DEC_WAVES), 0, s, a);
-    else if (kind == DEC_PAGED_ROWS) hipLaunchKernelGGL((k_decode<false, DT, DEC_PAGED_ROWS>), grid, dim3(64 * DEC_WAVES), 0, s, a);
-    else hipLaunchKernelGGL((k_decode<false, DT, DEC_ROWS>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+    if (kind == DEC_PAGED_SPLIT) hipLaunchKernelGGL((k_decode<DEC_SINK_KV, DT, DEC_PAGED_SPLIT>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+    else if (kind == DEC_PAGED_ROWS) hipLaunchKernelGGL((k_decode<DEC_SINK_KV, DT, DEC_PAGED_ROWS>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+    else hipLaunchKernelGGL((k_decode<DEC_SINK_KV, DT, DEC_ROWS>), grid, dim3(64 * DEC_WAVES), 0, s, a);
   });
 }
 
@@ -1216,9 +1216,46 @@ int lmc_decode_symbols(lmc_ctx* c, const void* blob, int32_t L, int32_t H, int32
   a.sym_out = sym_out;
   HIP_TRY(hipSetDevice(c->device));
   const long long n = (long long)a.P * a.G;  // every layer (decode_geometry set the full range)
-  hipLaunchKernelGGL((k_decode<true, LMC_DTYPE_BF16, DEC_ROWS>), dim3((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((k_decode<DEC_SINK_SYM, LMC_DTYPE_BF16, DEC_ROWS>), dim3((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return LMC_OK;
+}
+
+// Entropy-coded blobs of earlier stores -> the fixed-width blobs of the same KV: ONE launch of the rANS decoder with its
+// fixed-width sink (k_decode.h, DEC_SINK_FIXED), a wave per stream over all layers.  No workspace (neither the KV nor the
+// symbols are staged) and no host wait.  The refusals are lmc_transcode_fixed's.
+int lmc_transcode_to_fixed(lmc_ctx* c, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks, int32_t L, int32_t H,
+                           int32_t D, int32_t dtype, int32_t chunk_tokens, uint32_t ntokens, const int32_t* bins_h,
+                           void* const* out_ptrs, const uint32_t* out_bytes, uint32_t* job_status, lmc_stream_t stream) {
+  if (!c || !blob_ptrs || !blob_bytes || !out_ptrs || !out_bytes || nchunks < 1 || nchunks > 65535 || L < 1 ||
+      2 * L > LMC_MAX_PLANES || H < 1 || D < 1 || chunk_tokens < 1 || chunk_tokens > 65535 ||
+      (dtype != LMC_DTYPE_BF16 && dtype != LMC_DTYPE_FP16))
+    return LMC_ERR_INVALID;
+  const long long C = (long long)H * D;
+  if (C < 8 || (C & 7) || C > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
+  // every chunk is chunk_tokens long but, possibly, the last (lmc_pack_blobs's rule); token indices are 32-bit and signed
+  if ((uint64_t)ntokens > (uint64_t)nchunks * (uint32_t)chunk_tokens || (uint64_t)ntokens <= (uint64_t)(nchunks - 1) * (uint32_t)chunk_tokens ||
+      ntokens > 0x7fffffffu)
+    return LMC_ERR_INVALID;
+  DecodeArgs a;
+  if (decode_geometry(c, nchunks, L, H, D, job_status, a)) return LMC_ERR_INVALID;  // (2^31 streams or more)
+  if (!bins_ok(bins_h, 2 * L, &a.bins)) return LMC_ERR_INVALID;
+  // the header's size words, and the kernel's sums of stream sizes, are 32 bits
+  if (lmc_fixed_blob_bytes((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, a.bins.b) > 0xffffffffull) return LMC_ERR_INVALID;
+  a.blob_ptrs = (const u8* const*)blob_ptrs; a.blob_bytes = blob_bytes;
+  a.out_ptrs = (u8* const*)out_ptrs; a.out_bytes = out_bytes;
+  a.chunk_tokens = chunk_tokens; a.tok_end = (int)ntokens;
+  a.L = L; a.H = H; a.D = D; a.dtype = dtype;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);  // (the profiling marks are the context's)
+  c->pn = 0;
+  int rc;
+  if ((rc = prof_mark(c, s))) return rc;
+  const long long n = (long long)nchunks * a.P * a.G;  // every layer (decode_geometry set the full range)
+  hipLaunchKernelGGL((k_decode<DEC_SINK_FIXED, LMC_DTYPE_BF16, DEC_ROWS>), dim3((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return prof_mark(c, s);
 }
 
 }  // extern "C"

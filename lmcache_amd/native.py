@@ -186,6 +186,8 @@ SYMBOLS = {
     "lmc_pack_blobs": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _u64, _vp, _vp]),
     "lmc_transcode_fixed": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _u64, _vp, _vp,
                                            _vp]),
+    "lmc_transcode_to_fixed": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp,
+                                              _vp]),
     "lmc_unpack_blobs": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "lmc_pack_chunk_bytes": (ctypes.c_int, [_vp, _u64, _i32, ctypes.POINTER(ctypes.c_uint32)]),
     "lmc_copy_kv": (ctypes.c_int, [_vp, _PL, _i32, _i32, _PL, _i32, _vp]),
@@ -1006,6 +1008,19 @@ class Context:
                              0, ntokens, chunk_tokens, bins, blobs_ptr, blob_stride, sizes_ptr, stream, status_ptr, device=device)
         assert n == nchunks, "ntokens does not make nchunks chunks"
         return n
+
+    def transcode_to_fixed(self, blob_ptrs: int, blob_bytes_ptr: int, nchunks: int, L: int, H: int, D: int, dtype: int,
+                           chunk_tokens: int, ntokens: int, bins, out_ptrs: int, out_bytes_ptr: int, device,
+                           stream: Optional[int] = None, status_ptr: Optional[int] = None) -> int:
+        """lmc_transcode_to_fixed, transcode_fixed's inverse: nchunks entropy-coded blobs anywhere in device memory
+        (blob_ptrs: device int64 [n]; blob_bytes_ptr: device-accessible uint32 [n], the room of each) -> the blobs
+        encode_chunks_fixed would have written from the same KV, chunk i at the device address out_ptrs[i] (device int64
+        [n]; out_bytes_ptr: device-accessible uint32 [n], the room there, at least fixed_blob_bytes of the chunk's length).
+        One launch, no workspace.  `dtype`: dtype_code of the stored KV."""
+        assert self._nchunks(0, ntokens, chunk_tokens) == nchunks, "ntokens does not make nchunks chunks"
+        self._call("lmc_transcode_to_fixed", device, stream, blob_ptrs, blob_bytes_ptr, nchunks, L, H, D, dtype, chunk_tokens,
+                   ntokens, self._bins(bins), out_ptrs, out_bytes_ptr, status_ptr)
+        return nchunks
 
     def unpack_blobs(self, pack_ptr: int, pack_bytes: int, chunk_begin: int, nchunks: int, dst_ptrs: Sequence[int],
                      dst_caps: Sequence[int], device, stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:

@@ -24,7 +24,8 @@ Three storage modes, chosen by the config:
                                            (LMC_MODEL_FIXED: 3.8x instead of 4.6x, no entropy coder on either leg).
                                            No layer-wise store.  With both budgets its LRU groups are dropped, as
                                            they always were -- or, with LMCACHE_AMD_FIXED_DEMOTE=1, demoted like the
-                                           coded tier's, as entropy-coded packs (below); a demoted group is not
+                                           coded tier's, as entropy-coded packs (below), and with
+                                           LMCACHE_AMD_FIXED_PROMOTE=1 as well a demoted group that is hit is
                                            promoted back.  ValueError with any other device.
 
 Bounded tiers.  LMCACHE_AMD_HBM_BYTES / LMCACHE_AMD_PINNED_BYTES (integers, optional K / M / G suffix; read at
@@ -44,8 +45,14 @@ of the landed pack.  Each tier keeps the format it wants: fixed width where the 
 they cross PCIe.  The pack's size is known only after the transcode: room in the pinned tier is made for the pack's
 BOUND and the group is filed at the size that landed.  A demoted group is served where it lies, by the rANS decoder
 (every retrieve goes by what an entry IS, never by the backend's model: a prefix half in HBM and half demoted is a
-fixed-width run and a pack run).  PROMOTION of such a group is not built -- it needs the reverse transcode -- so a hit
-does not queue one (logged once) and the group stays in the pinned tier until it is evicted.  What holds:
+fixed-width run and a pack run).  PROMOTION of such a group is the reverse transcode and has a switch of its own,
+LMCACHE_AMD_FIXED_PROMOTE=1 (read at construction, backend.fixed_promotes; it takes effect only where fixed_demotes
+holds).  Without it a hit does not queue a promotion (logged once) and the group stays in the pinned tier until it is
+evicted.  With it a hit queues one as the coded tier does: on the worker thread the pack -- of one chunk or many -- is
+unpacked into the codec's transient HBM staging (lmc_unpack_blobs), room is made in the HBM tier for the group's
+fixed-width size (native.fixed_blob_bytes per chunk: a function of geometry, bins and chunk lengths, known beforehand),
+and lmc_transcode_to_fixed -- the rANS decoder with a fixed-width sink, one launch, no KV and no symbol workspace --
+writes the blobs lmc_encode_chunks_fixed would have written into the arena's regions.  What holds:
   1. A key is in exactly one tier, and `contains` never reads False during a demotion or promotion: the new entry is
      published before the old memory is released.  Every change of `dict` bumps `_gen`, so neither the kept prefix
      answer nor the codec's table of a kept entry list can be served stale.
@@ -264,6 +271,10 @@ class LMCLocalBackend(LMCBackendInterface):
         # asked to: a fixed-width backend with both budgets has always DROPPED its LRU groups, and keeps doing so unless
         # LMCACHE_AMD_FIXED_DEMOTE=1 says otherwise (read here, once)
         self.fixed_demotes = self.model == "fixed" and os.environ.get("LMCACHE_AMD_FIXED_DEMOTE", "0") == "1"
+        # ... and a demoted fixed-width group is promoted back -- the pack's coded blobs transcoded into fixed-width ones
+        # (_promote_group) -- only where LMCACHE_AMD_FIXED_PROMOTE=1 is set as well: without it a hit serves such a group
+        # where it lies and leaves it there, as before the reverse transcode existed
+        self.fixed_promotes = self.fixed_demotes and os.environ.get("LMCACHE_AMD_FIXED_PROMOTE", "0") == "1"
         self._tiers = Tiers(self._lru, self._demote_group if self._demotes() else None, self._drop_group, self._demoted_size)
         self.put_queue: "queue.Queue" = queue.Queue()
         self.put_thread = threading.Thread(target=self.put_worker, daemon=True)
@@ -504,14 +515,25 @@ class LMCLocalBackend(LMCBackendInterface):
                 return
             keys = self._own_keys(g)
             old = [self.dict[k] for k in keys]
-            packed = len(old) >= 2 and all(isinstance(e, _PackChunk) and e.pack is old[0].pack and e.index == i
-                                           for i, e in enumerate(old)) and old[0].pack.nchunks == len(old)
-            single = len(old) == 1 and isinstance(old[0], _HostChunk) and old[0].encoded
+            # a fixed-width backend's pinned groups are packs of entropy-coded blobs whatever their length (_demote_group
+            # makes a pack of a single chunk too) and go back as fixed-width blobs: the reverse transcode
+            fixed = self.model == "fixed"
+            if fixed and (not self.fixed_promotes or g.geometry is None):
+                return
+            packed = len(old) >= (1 if fixed else 2) and all(isinstance(e, _PackChunk) and e.pack is old[0].pack and e.index == i
+                                                             for i, e in enumerate(old)) and old[0].pack.nchunks == len(old)
+            single = not fixed and len(old) == 1 and isinstance(old[0], _HostChunk) and old[0].encoded
             if len(keys) != len(g.keys) or not (packed or single):
                 return
             codec = self._codec()
+            bins = self.cachegen_config.plane_bins(g.geometry[0]) if fixed else None
             try:
-                if packed:
+                if fixed:
+                    pack = old[0].pack
+                    L, H, D = g.geometry
+                    lens = [g.chunk_tokens] * (len(old) - 1) + [g.ntokens - (len(old) - 1) * g.chunk_tokens]
+                    sizes = [native.fixed_blob_bytes(L, T, H, D, bins) for T in lens]
+                elif packed:
                     pack = old[0].pack
                     sizes = [native.pack_chunk_bytes(pack.blob.ptr, pack.blob.nbytes, i) for i in range(len(old))]
                 else:
@@ -524,7 +546,9 @@ class LMCLocalBackend(LMCBackendInterface):
                 if self.dev_arena is None:
                     self.dev_arena = DeviceArena(torch.device("cuda", self._cuda_device), budget=self._tiers.budget["hbm"])
                 with torch.cuda.device(self._cuda_device):
-                    if packed:
+                    if fixed:
+                        blobs = codec.promote_pack(pack, self.dev_arena, model="fixed", bins=bins)
+                    elif packed:
                         blobs = codec.promote_pack(pack, self.dev_arena)
                     else:
                         cur = torch.cuda.current_stream()
@@ -536,7 +560,7 @@ class LMCLocalBackend(LMCBackendInterface):
                 logger.exception("promotion failed: the group stays in the pinned tier")
                 return
             for k, e, t in zip(keys, old, blobs):
-                self._publish(k, _DevChunk(t, e.shape, e.dtype))
+                self._publish(k, _DevChunk(t, e.shape, e.dtype, model="fixed" if fixed else None))
             self._release(old, g.live_readers())
             g.readers, g.nbytes = [], nbytes
             self._lru.add("hbm", gid, nbytes)
@@ -559,9 +583,9 @@ class LMCLocalBackend(LMCBackendInterface):
             if events:
                 g.readers = g.live_readers() + list(events)
             if self._lru.tier_of(gid) == "pinned" and self._tiers.tiered() and gid not in self._promoting:
-                if self.model == "fixed":
-                    # promotion would have to turn the pack's coded blobs back into fixed-width ones (the reverse
-                    # transcode, not built): the group is served where it lies and stays there
+                if self.model == "fixed" and not self.fixed_promotes:
+                    # promotion turns the pack's coded blobs back into fixed-width ones (the reverse transcode); without
+                    # LMCACHE_AMD_FIXED_PROMOTE=1 the group is served where it lies and stays there
                     if not self._promotion_off_logged:
                         self._promotion_off_logged = True
                         logger.info("fixed-width tier: a demoted group that is hit stays in the pinned tier (no promotion; logged once)")

@@ -673,6 +673,9 @@ class CacheGenDeviceCodec:
     # coder model of a group's HBM blobs -> the codec's method that turns them into entropy-coded blobs in front of the pack
     # leg of a demotion (None: they are coded already)
     _DEMOTERS = {None: None, "fixed": "transcode_fixed"}
+    # ... and the way back: the codec's method that turns a pack's entropy-coded blobs into the model's HBM blobs behind
+    # the unpack leg of a promotion (None: the HBM tier keeps them coded)
+    _PROMOTERS = {None: None, "fixed": "transcode_to_fixed"}
 
     def _entry(self, names: dict, model: Optional[str], layout: native.KVLayout, default: Optional[str] = None):
         """self.ctx's method, looked up at call time, for an encode from / a decode into `layout` in coder `model`: the one
@@ -1281,27 +1284,87 @@ class CacheGenDeviceCodec:
             total += nb - native.blob_static_bytes(L, T, H, D)
         return total
 
-    def promote_pack(self, pack: HostPack, arena: "DeviceArena") -> List[torch.Tensor]:
+    def transcode_to_fixed(self, blobs: Sequence[torch.Tensor], geometry: tuple, chunk_tokens: int, ntokens: int,
+                           bins: Sequence[int], outs: Sequence[torch.Tensor], ready: Sequence = ()) -> None:
+        """transcode_fixed's inverse: the entropy-coded blobs of one store group (uint8 tensors, anywhere in HBM) -> the
+        fixed-width blobs encode(model="fixed") would have written from the same KV (lmc_transcode_to_fixed: one launch
+        of the rANS decoder with its fixed-width sink, no workspace), chunk i into outs[i] -- a uint8 tensor of at least
+        native.fixed_blob_bytes of that chunk's length, 16-byte aligned, anywhere.  Blocks until the blobs are there;
+        NativeError if the job's status word is set -- a coded blob that does not check out; outs then hold nothing."""
+        L, H, D = geometry
+        n = len(blobs)
+        assert len(outs) == n
+        with self._lock, torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            _stream_waits(cur, ready)
+            # the stored KV's dtype is the blobs' own header word (a group is one store: one dtype)
+            dtype = int(blobs[0][8:12].view(torch.int32).item())
+
+            def pairs(v):  # uint32 pairs in int64 words
+                return [v[i] | (v[i + 1] << 32 if i + 1 < n else 0) for i in range(0, n, 2)]
+            h = (n + 1) // 2
+            words = [b.data_ptr() for b in blobs] + [o.data_ptr() for o in outs]
+            words += pairs([b.numel() for b in blobs]) + pairs([o.numel() for o in outs])
+            table = torch.tensor(words, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+            base = table.data_ptr()
+            with self._launch(cur) as (st, st_ptr):
+                self.ctx.transcode_to_fixed(base, base + 16 * n, n, L, H, D, dtype, chunk_tokens, ntokens, bins,
+                                            base + 8 * n, base + 16 * n + 8 * h, self.device, stream=cur.cuda_stream,
+                                            status_ptr=st_ptr)
+                done = torch.cuda.Event()
+                done.record(cur)
+            job = Job(done, status_idx=st, pool=self._status)
+            done.synchronize()
+            _raise_on(job.retire(), "CacheGen promotion (lmc_transcode_to_fixed)")
+
+    def promote_pack(self, pack: HostPack, arena: "DeviceArena", model: Optional[str] = None,
+                     bins: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
         """The promotion leg: every chunk of a pack in pinned host DRAM -> the blob it was made of, each in a region of
         its own size in the HBM arena (lmc_unpack_blobs: DMA into the context's load staging, one kernel that scatters
         static slots and segments).  Blocks until the blobs are there; NativeError (nothing kept) if the job's status
-        word says no, ArenaFull if `arena` has no room."""
+        word says no, ArenaFull if `arena` has no room.
+        model "fixed" (with the planes' `bins`): the HBM tier keeps LMC_MODEL_FIXED blobs.  The pack is unpacked into the
+        codec's transient HBM staging instead (transcode_fixed's, in the other direction: no budget counts it, it is
+        grown on demand and held under the codec's lock), the arena's regions are taken at native.fixed_blob_bytes per
+        chunk -- the last one may be shorter -- and transcode_to_fixed writes the fixed-width blobs into them."""
+        if model not in self._PROMOTERS:
+            raise ValueError(f"unknown coder model {model!r} (None or 'fixed')")
+        last = self._PROMOTERS[model]
         n = pack.nchunks
         sizes = [native.pack_chunk_bytes(pack.blob.ptr, pack.blob.nbytes, i) for i in range(n)]
         out: List[torch.Tensor] = []
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             try:
-                for nb in sizes:
-                    out.append(arena.alloc(nb, stream=cur))
+                if last is None:
+                    dst = out
+                    for nb in sizes:
+                        out.append(arena.alloc(nb, stream=cur))
+                else:
+                    h = native.pack_info(pack.blob.ptr, pack.blob.nbytes)
+                    L, H, D, ntokens = int(h.num_layers), int(h.num_heads), int(h.head_size), int(h.ntokens)
+                    geometry = (L, H, D)
+                    offs = [0]
+                    for nb in sizes:
+                        offs.append(offs[-1] + native.r16(nb))
+                    if self._xcode_dev is None or self._xcode_dev.numel() < offs[-1]:
+                        cur.synchronize()  # (whoever read the views of the region that goes)
+                        self._xcode_dev = None
+                        self._xcode_dev = torch.empty(offs[-1], dtype=torch.uint8, device=self.device)
+                    dst = [self._xcode_dev[offs[i]:offs[i] + nb] for i, nb in enumerate(sizes)]
+                    for i in range(n):
+                        T = pack.chunk_tokens if i < n - 1 else ntokens - (n - 1) * pack.chunk_tokens
+                        out.append(arena.alloc(native.fixed_blob_bytes(L, T, H, D, bins), stream=cur))
                 with self._launch(cur) as (st, st_ptr):
-                    self.ctx.unpack_blobs(pack.blob.ptr, pack.blob.nbytes, 0, n, [t.data_ptr() for t in out], sizes,
+                    self.ctx.unpack_blobs(pack.blob.ptr, pack.blob.nbytes, 0, n, [t.data_ptr() for t in dst], sizes,
                                           self.device, stream=cur.cuda_stream, status_ptr=st_ptr)
                     done = torch.cuda.Event()
                     done.record(cur)
                 job = Job(done, status_idx=st, pool=self._status)
                 done.synchronize()
                 _raise_on(job.retire(), "CacheGen promotion (lmc_unpack_blobs)")
+                if last is not None:
+                    getattr(self, last)(dst, geometry, pack.chunk_tokens, ntokens, bins, out)
             except BaseException:
                 ev = torch.cuda.Event()
                 ev.record(cur)
