@@ -187,6 +187,15 @@ int lmc_device_status(lmc_ctx* ctx, int clear);
 #define LMC_ENCODE_PATH_FUSED 2
 int lmc_ctx_set_encode_path(lmc_ctx* ctx, int path);
 
+/* Into how many slices a layer's launch of a fixed-width layer-wise job (lmc_encode_layers_begin_fixed, which reads
+ * this) cuts each plane of a chunk; additive in ABI 6.  A slice is a run of whole passes of k_fixed_encode's eight
+ * waves over the plane's row octs (8, 16 or 32 octs a pass for planes of more than 256, more than 128, at most 128
+ * channels), so n is clipped to the passes of a whole chunk's plane.
+ *   n >= 1  that many;    0 (default)  the smallest power of two that gives a layer's launch (2 planes x nchunks x
+ *                                      slices workgroups) a workgroup per CU, else as many as there are passes.
+ * The blobs do not depend on it; the switch exists for A/B timing and for the tests.  n < 0: LMC_ERR_INVALID. */
+int lmc_ctx_set_fixed_layer_slices(lmc_ctx* ctx, int n);
+
 /* Per-kernel timing of the NEXT lmc_encode_chunks / lmc_decode_chunks calls:
  * when enabled the call brackets each of its kernels with hipEvents on the
  * caller's stream.  lmc_ctx_profile_read (after the caller has synchronised
@@ -305,6 +314,27 @@ typedef struct lmc_layer_job lmc_layer_job;
 int lmc_encode_layers_begin(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
                             int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
                             uint32_t* sizes, uint32_t* job_status, lmc_layer_job** job_out);
+/*
+ * The layer-wise form of lmc_encode_chunks_fixed_split (additive in ABI 6; csrc/k_fixed.h): the same lmc_layer_job, tagged
+ * with its model -- lmc_encode_layer, lmc_encode_layers_finish and lmc_encode_layers_abort take it as they take the coded
+ * job, with the same ordering rules and the same LMC_ERR_INVALID for a repeated, skipped or out-of-range layer or an early
+ * finish, nothing queued.  Arguments and refusals are lmc_encode_chunks_fixed_split's (fp8 KV and blob_stride <
+ * lmc_blob_bound are LMC_ERR_INVALID); LMC_NOT_LAYERWISE only for planes of more than 1024 channels: every chunk length
+ * of the one-piece call is eligible, a ragged last chunk of one token included.
+ * A fixed-width stream's place is a function of (bins, T) alone, so there is no placement chain, no V region and no
+ * move at the end: lmc_encode_layer is ONE launch of k_fixed_encode over planes `layer` and L + `layer`, each plane of a
+ * chunk cut into slices (lmc_ctx_set_fixed_layer_slices) so that a launch of few chunks still fills the chip; the
+ * workgroups store streams and scales where they belong and their partial check sums into the job's own workspace
+ * ([nchunks][2L][slices][G + 1] dwords, plain stores, nothing zeroed in front).  lmc_encode_layers_finish is
+ * k_fixed_layers_finish: it sums the partials and writes each stream's 16-byte tail and directory entry, the planes'
+ * scale checksums, header, bins, pads and the size word.  sizes[i] is written 0 by layer 0's launch and
+ * lmc_fixed_blob_bytes by the finish; afterwards bytes [0, sizes[i]) of every blob are byte for byte what
+ * lmc_encode_chunks_fixed / _fixed_split writes and nothing beyond them is touched.  The job takes neither of the
+ * context's encode workspaces.
+ */
+int lmc_encode_layers_begin_fixed(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
+                                  int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
+                                  uint32_t* sizes, uint32_t* job_status, lmc_layer_job** job_out);
 int lmc_encode_layer(lmc_ctx* ctx, lmc_layer_job* job, int32_t layer, lmc_stream_t stream);
 int lmc_encode_layers_finish(lmc_ctx* ctx, lmc_layer_job* job, lmc_stream_t stream);
 int lmc_encode_layers_abort(lmc_ctx* ctx, lmc_layer_job* job);

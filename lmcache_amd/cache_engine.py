@@ -211,6 +211,10 @@ class LMCacheEngine:
         planes on a side stream of the job -- never on the model's -- and layer_event(l) fires once layer l's KV has been
         read; finish() is one pass at HBM speed plus the tier's copies, and leaves what store_paged leaves: the same keys,
         byte for byte the same blobs (and the same pack on the pinned tier).
+        The fixed-width HBM tier (local_serde="cachegen-fixed") is layer-wise where LMCACHE_AMD_FIXED_LAYERWISE=1 was set
+        when the engine was built (lmc_encode_layers_begin_fixed; k_fixed.h): the same layouts -- "NHDB" with direct=True
+        -- and planes, chunks of any length the tier stores; save_layer(l) is one sliced launch of its one kernel, finish()
+        a few words per stream.  Without the switch it falls back, as it always has.
         Everything else FALLS BACK: the raw tiers, remote, hybrid and chunk-tensor backends, a job the layer-wise encoder
         does not take, and an "NHDB" cache without `direct` -- it has no token rows to read per layer, and its staging
         gather needs every layer.  save_layer is then a no-op, layer_event(l) is None (nothing has been read: the cache

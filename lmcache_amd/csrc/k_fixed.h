@@ -15,6 +15,14 @@
 // workgroups that live as long as a plane takes (FIXED_ENC_WAVES below).
 // The workgroup of plane 0 also writes header, bins and pads; every workgroup its plane's directory entries and scsum.
 //
+// k_fixed_encode<..., LAYER = true> + k_fixed_layers_finish -- the layer-wise job (lmc_encode_layers_begin_fixed): a launch
+// covers the two planes of one layer, which a workgroup per (plane, chunk) would leave at 2 x nchunks workgroups, so the
+// work item there is (chunk, plane, SLICE): a run of whole passes of the plane's row octs.  Loads, `lo` / `hi` stores and
+// scales are the one-piece kernel's.  The sums stay on chip per slice as above; check word and scsum are linear mod 2^32
+// over absolute dword / token indices, so a slice's LDS sums are partials: stored once, plainly, into a slot of the job's
+// workspace that only this workgroup writes, and added up by the finish kernel, which also writes what is per stream,
+// per plane and per chunk.  Still no memset, no pre-zeroed word, no global atomic.
+//
 // k_fixed_decode -- a wave takes a stream and walks it in tiles of four octs (32 tokens): 16-byte loads of `lo` (lane =
 // 4 channels of one oct) and a dword of `hi`, staged in 1.3 KiB of LDS and read back transposed -- lane = (8 channels,
 // one token) -- so that every lane dequantises one 16-byte row vector per oct: t = ((q - C) / C) * max1 from k_decode.h's
@@ -54,7 +62,15 @@ __device__ __forceinline__ u32 fixed_stream_bytes_dev(u32 bins, u32 O) {  // lmc
 
 struct FixedEncArgs {
   KvAddr src;
-  EncodeArgs e;  // tok_begin .. nchunks, P, C, G, blobs, blob_stride, bins, sizes, L, H, D, dtype
+  EncodeArgs e;  // tok_begin .. nchunks, P, C, G, blobs, blob_stride, bins, sizes, L, H, D, dtype; plane0, plane_step
+  // ---- a layer's launch of a layer-wise job (lmc_encode_layers_begin_fixed): the LAYER instances alone read these ----
+  // grid = (planes of the launch, nchunks, slices): workgroup (x, chunk, z) quantises passes [z * slice_passes, + slice_passes)
+  // of plane e.plane0 + x * e.plane_step and leaves its LDS sums -- NG check words and the scsum term, PARTIALS of the
+  // plane's (both are sums mod 2^32 over the absolute dword / token index) -- at part[((chunk * P + p) * gridDim.z + z) *
+  // (NG + 1)], plain stores, each slot written by exactly this workgroup (zeros by a slice that lies behind a ragged
+  // chunk's last oct).  Tails, directory, scsum, the static sections and the size word are k_fixed_layers_finish's.
+  u32* part;
+  u32 slice_passes;
 };
 
 // What quantize_task hands over (k_quantize.h, SINK).  o0 / o1: byte r of dword e = symbol of (token 8 oct + r / + 4 + r,
@@ -103,10 +119,16 @@ struct FixedSink {
 #define FIXED_ENC_WAVES 8  // 8 waves walk a 256-token plane in 4 passes: measured against 4 waves (8 passes, workgroups that
                            // live twice as long) on a 16 k Llama-3-8B context, same box, alternating: 0.557 against 0.614 ms
 #endif
-template <int G, int NITER, int DT, int SPLIT, bool NHDB = false>
+// LAYER: the sliced launch over a layer's planes (FixedEncArgs).  A template flag and not run-time fields read by every
+// instance: with the flag off the kernel is the code it was, and the one-piece encode of a 16 k context cannot be told
+// from the parent library's (0.6344 / 0.6351 against 0.6346 / 0.6352 ms, alternating in one process).  The build with
+// run-time fields came out 0.002 ms behind this one, though only across two runs of a comparison whose sides did not
+// share a host path: profiles/fixed_layerwise_store.md has both.  Price: 16 instances, half a minute of compile.
+template <int G, int NITER, int DT, int SPLIT, bool NHDB = false, bool LAYER = false>
 __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncArgs a) {
   constexpr int NW = FIXED_ENC_WAVES;
   static_assert(!NHDB || SPLIT == 1, "a split source: planes of up to 1024 channels");
+  static_assert(!LAYER || SPLIT == 1, "layer launches: planes of up to 1024 channels (the split tasks meet at barriers)");
   static_assert(SPLIT == 1 || (G == LMC_WAVE && NITER == 2 && (SPLIT == 2 || SPLIT == 4)), "split tasks: whole waves");
   constexpr int RPW = LMC_WAVE / G;
   constexpr int PER_PASS = SPLIT > 1 ? NW / SPLIT : NW * RPW;  // row octs a workgroup takes at a time
@@ -116,8 +138,8 @@ __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncA
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int sub = lane / G, sl = lane % G;
-  const int p = (int)blockIdx.x, chunk = (int)blockIdx.y;
   const EncodeArgs& e = a.e;
+  const int p = LAYER ? e.plane0 + (int)blockIdx.x * e.plane_step : (int)blockIdx.x, chunk = (int)blockIdx.y;
   const int tok0 = e.tok_begin + chunk * e.chunk_tokens;
   const int Tc = min(e.chunk_tokens, e.tok_end - tok0);
   const u32 O = ((u32)Tc + 7u) >> 3, NG = (u32)e.G;
@@ -144,7 +166,9 @@ __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncA
   const int slice = SPLIT > 1 ? wave % SPLIT : 0;
   u32* const xm = xmax + (SPLIT > 1 ? (wave / SPLIT) * 8 * SPLIT : 0);
   const u32 npass = (O + PER_PASS - 1u) / PER_PASS;  // the same for every wave: the split tasks meet at barriers
-  for (u32 pass = 0; pass < npass; pass++) {
+  const u32 pass0 = LAYER ? blockIdx.z * a.slice_passes : 0u;  // a slice: a run of whole passes
+  const u32 pass1 = LAYER ? min(npass, pass0 + a.slice_passes) : npass;
+  for (u32 pass = pass0; pass < pass1; pass++) {
     int oct = SPLIT > 1 ? (int)pass * PER_PASS + wave / SPLIT : ((int)pass * NW + wave) * RPW + sub;
     const bool ovalid = (u32)oct < O;
     if (!ovalid) oct = 0;
@@ -160,6 +184,12 @@ __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncA
   }
   if (sink.scs) __hip_atomic_fetch_add((LdsU32*)&scs_all, sink.scs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   __syncthreads();
+  if constexpr (LAYER) {  // a slice of a layer-wise job: its sums are partials, and the first layer's launch clears the size word
+    u32* const out = a.part + (((size_t)chunk * (u32)e.P + (u32)p) * gridDim.z + blockIdx.z) * (NG + 1u);
+    if ((u32)tid <= NG) out[tid] = (u32)tid < NG ? chk[tid] : scs_all;
+    if (tid == 0 && e.sizes && blockIdx.x == 0 && blockIdx.z == 0) e.sizes[chunk] = 0u;
+    return;
+  }
   if ((u32)tid < NG) {  // tails and directory entries of the plane's streams
     u8* const sb = sink.plane_streams + (size_t)tid * ssize;
     *(LMC_GLOBAL u32x4_t*)(sb + ssize - LMC_FIXED_TAIL_BYTES) = u32x4_t{chk[tid], 0u, 0u, 0u};
@@ -172,6 +202,55 @@ __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncA
     if (lane == 22) reinterpret_cast<u32*>(blob)[22] = LMC_MODEL_FIXED;  // (the lane that wrote the coded models' word)
     if (lane == 0 && e.sizes) e.sizes[chunk] = bo.streams + total;
   }
+}
+
+// ---- k_fixed_layers_finish: the tail of a layer-wise job, a workgroup per chunk ------------------------------------------
+// Sums the slices' partials of every (plane, stream) and writes what k_fixed_encode writes behind its plane loop: the
+// 16-byte tail {check, 0, 0, 0} and the directory entry of each stream, scsum[p], header, bins and pads, the model word
+// and -- last, behind a barrier -- sizes[chunk].  P * (G + 1) * slices dwords read and a few tens of bytes per stream
+// written: nothing of the streams or the scales moves.
+struct FixedFinishArgs {
+  EncodeArgs e;
+  const u32* part;  // [nchunks][P][nslices][G + 1]
+  u32 nslices;
+};
+
+#define FIXED_FIN_THREADS 256
+__global__ __launch_bounds__(FIXED_FIN_THREADS) void k_fixed_layers_finish(FixedFinishArgs a) {
+  __shared__ u32 pbeg[LMC_MAX_PLANES + 1];  // a plane's first stream in the streams section; [P]: the section's bytes
+  const EncodeArgs& e = a.e;
+  const int tid = (int)threadIdx.x, lane = tid & 63, chunk = (int)blockIdx.x;
+  const int Tc = min(e.chunk_tokens, e.tok_end - (e.tok_begin + chunk * e.chunk_tokens));
+  const u32 O = ((u32)Tc + 7u) >> 3, NG = (u32)e.G, P = (u32)e.P;
+  const BlobOff bo = lmc_blob_off(P, (u32)Tc, NG);
+  u8* const blob = e.blobs + (long long)chunk * e.blob_stride;
+  for (u32 q = (u32)tid; q <= P; q += FIXED_FIN_THREADS) {
+    u32 beg = 0;
+    for (u32 r = 0; r < q; r++) beg += NG * fixed_stream_bytes_dev((u32)e.bins.b[r], O);
+    pbeg[q] = beg;
+  }
+  __syncthreads();
+  const u32 total = pbeg[P];
+  for (u32 i = (u32)tid; i < P * (NG + 1u); i += FIXED_FIN_THREADS) {
+    const u32 p = i / (NG + 1u), k = i - p * (NG + 1u);
+    const u32* const in = a.part + ((size_t)chunk * P + p) * a.nslices * (NG + 1u) + k;
+    u32 sum = 0;
+    for (u32 s = 0; s < a.nslices; s++) sum += in[(size_t)s * (NG + 1u)];
+    if (k < NG) {
+      const u32 ssize = fixed_stream_bytes_dev((u32)e.bins.b[p], O);
+      const u32 b0 = pbeg[p] + k * ssize;
+      *(LMC_GLOBAL u32x4_t*)(blob + bo.streams + b0 + ssize - LMC_FIXED_TAIL_BYTES) = u32x4_t{sum, 0u, 0u, 0u};
+      *(LMC_GLOBAL u32x2_t*)(blob + bo.gdir + 8u * (p * NG + k)) = u32x2_t{b0, b0 + ssize};
+    } else {
+      reinterpret_cast<u32*>(blob + bo.scsum)[p] = sum;
+    }
+  }
+  if (tid >= FIXED_FIN_THREADS - 64) {  // the last wave
+    write_blob_static(blob, bo, e, (u32)Tc, total, lane);
+    if (lane == 22) reinterpret_cast<u32*>(blob)[22] = LMC_MODEL_FIXED;  // (the lane that wrote the coded models' word)
+  }
+  __syncthreads();
+  if (tid == 0) e.sizes[chunk] = bo.streams + total;
 }
 
 struct FixedDecArgs {

@@ -39,12 +39,14 @@ static thread_local int g_last_hip = 0;
   } while (0)
 
 // What a layer-wise encode job (lmc_encode_layers_*) owns from begin to finish: look-back granules that live across the
-// job's launches, a ticket counter, the symbol workspace of ONE layer's two planes and the region its V streams wait in.
+// job's launches, a ticket counter, the symbol workspace of ONE layer's two planes and the region its V streams wait in;
+// a job of the fixed-width model (lmc_encode_layers_begin_fixed) the slices' partial sums alone.
 // Kept by the context between jobs and handed to the next one behind `free_ev`.
 struct lmc_layer_bufs {
   unsigned long long* agg = nullptr; size_t agg_bytes = 0;
   u32* sym4 = nullptr; size_t sym4_bytes = 0;
   u8* vregion = nullptr; size_t v_bytes = 0;
+  u32* part = nullptr; size_t part_bytes = 0;  // k_fixed.h: [nchunks][P][slices][G + 1]
   u32* ticket = nullptr;
   hipEvent_t free_ev = nullptr;  // recorded behind the last launch of the job that had them last
   bool used = false;             // ... if any
@@ -61,6 +63,8 @@ struct lmc_layer_job {
   u32* sizes; u32* status;
   int chain_gran;            // granules of a plane: G / 8 (a granule per workgroup) or G (per wave)
   long long vstride;         // bytes of a chunk's slot in the V region
+  bool fixed = false;        // LMC_MODEL_FIXED: k_fixed_encode per layer, k_fixed_layers_finish
+  u32 slices = 1, slice_passes = 0;  // ... in `slices` workgroups per (chunk, plane) of `slice_passes` passes each
   int next_layer = 0;
   u32 tickets_drawn = 0;
   hipStream_t last_stream = nullptr;  // of the last launch that went out
@@ -90,6 +94,7 @@ struct lmc_ctx {
   Workspace ws[2];
   int num_cus = 256;
   int enc_path = LMC_ENCODE_PATH_AUTO;  // lmc_ctx_set_encode_path
+  int fixed_slices = 0;                 // lmc_ctx_set_fixed_layer_slices
   int fused_pl = 0;                     // LMC_FUSED_PL at lmc_ctx_create (A/B switch of tools/probes: planes per work item of narrow planes; 0 = the built-in choice)
   u32 epoch = 0;                        // of the last fused launch (tags its look-back granules)
   unsigned long long* pack_table = nullptr;  // device copy of a pack's offset table while it is written (lmc_store_pack)
@@ -187,6 +192,7 @@ int lmc_ctx_destroy(lmc_ctx* c) {
     if (b->agg) (void)hipFree(b->agg);
     if (b->sym4) (void)hipFree(b->sym4);
     if (b->vregion) (void)hipFree(b->vregion);
+    if (b->part) (void)hipFree(b->part);
     if (b->ticket) (void)hipFree(b->ticket);
     if (b->free_ev) (void)hipEventDestroy(b->free_ev);
     delete b;
@@ -219,6 +225,13 @@ int lmc_ctx_set_encode_path(lmc_ctx* c, int path) {
   if (!c || path < LMC_ENCODE_PATH_AUTO || path > LMC_ENCODE_PATH_FUSED) return LMC_ERR_INVALID;
   std::lock_guard<std::mutex> lk(c->mu);
   c->enc_path = path;
+  return LMC_OK;
+}
+
+int lmc_ctx_set_fixed_layer_slices(lmc_ctx* c, int n) {
+  if (!c || n < 0) return LMC_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->fixed_slices = n;
   return LMC_OK;
 }
 
@@ -466,20 +479,23 @@ static int reserve_locked(lmc_ctx::Workspace* c, int L, int H, int D, int chunk_
 // the profiling marks ------------------------------------------------------------------------------------------------
 // NHDB: the source is an LMC_PAGED_SPLIT cache (k_quantize.h, split_load_oct): instances of their own, planes of up to
 // 1024 channels (encode_job_ok)
-template <int DT>
-static int launch_fixed_encode(const FixedEncArgs& fa, hipStream_t s, bool nhdb) {
+// LAYER: a layer's launch of a layer-wise job (FixedEncArgs): e.nplanes planes of every chunk in `slices` workgroups each,
+// instances of their own (16: the one-piece instances stay the code they were), planes of up to 1024 channels.
+template <int DT, bool LAYER = false>
+static int launch_fixed_encode(const FixedEncArgs& fa, hipStream_t s, bool nhdb, unsigned slices = 1) {
   const int C = fa.e.C;
-  const dim3 grid((unsigned)fa.e.P, (unsigned)fa.e.nchunks), block(64 * FIXED_ENC_WAVES);
+  const dim3 grid((unsigned)(LAYER ? fa.e.nplanes : fa.e.P), (unsigned)fa.e.nchunks, slices), block(64 * FIXED_ENC_WAVES);
+  if (LAYER && C > 1024) return LMC_ERR_INVALID;
   if (nhdb) {
-    if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1, true>), grid, block, 0, s, fa);
-    else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1, true>), grid, block, 0, s, fa);
-    else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1, true>), grid, block, 0, s, fa);
-    else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1, true>), grid, block, 0, s, fa);
+    if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1, true, LAYER>), grid, block, 0, s, fa);
+    else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1, true, LAYER>), grid, block, 0, s, fa);
+    else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1, true, LAYER>), grid, block, 0, s, fa);
+    else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1, true, LAYER>), grid, block, 0, s, fa);
     else return LMC_ERR_INVALID;
-  } else if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1>), grid, block, 0, s, fa);
-  else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1>), grid, block, 0, s, fa);
-  else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1>), grid, block, 0, s, fa);
-  else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1>), grid, block, 0, s, fa);
+  } else if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1, false, LAYER>), grid, block, 0, s, fa);
+  else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1, false, LAYER>), grid, block, 0, s, fa);
+  else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1, false, LAYER>), grid, block, 0, s, fa);
+  else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1, false, LAYER>), grid, block, 0, s, fa);
   else if (C <= 2048) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 2>), grid, block, 0, s, fa);
   else hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 4>), grid, block, 0, s, fa);  // C <= LMC_MAX_CHANNELS: layout_ok
   HIP_TRY(hipGetLastError());
@@ -866,37 +882,57 @@ static void layer_job_release(lmc_layer_job* j) {
   delete j;
 }
 
-int lmc_encode_layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
-                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
-                            lmc_layer_job** job_out) {
+// One body for the two models' begin.  `fixed`: lmc_encode_layers_begin_fixed.
+static int layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                        const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                        lmc_layer_job** job_out, bool fixed) {
   int nchunks;
   if (!job_out) return LMC_ERR_INVALID;
   *job_out = nullptr;
   if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true) || !blobs || !sizes || ((uintptr_t)blobs & 15) ||
-      (blob_stride & 15))
+      (blob_stride & 15) || (fixed && lmc_dtype_fp8(src->dtype)))
     return LMC_ERR_INVALID;
   const int L = src->num_layers, H = src->num_heads, D = src->head_size;
   const int P = 2 * L, C = H * D, G = (C + 63) / 64;
   if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
   BinsArg bins;
   if (!bins_ok(bins_h, P, &bins)) return LMC_ERR_INVALID;
+  if (fixed && lmc_fixed_blob_bytes((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, bins.b) > 0xffffffffull)
+    return LMC_ERR_INVALID;  // (encode_fixed's refusal: the header's size words are 32 bits)
   // eligible: the counts-only coder takes every chunk (2 .. 256 tokens, a ragged last one included) and k_quantize's
-  // one-wave-per-oct instances every plane (at most 1024 channels)
+  // one-wave-per-oct instances every plane (at most 1024 channels); the fixed-width model has no coder: every chunk
+  // length of the one-piece call, the same planes
   const int tail = (tok_end - tok_begin) % chunk_tokens;
-  if (chunk_tokens < (int)LMC_COUNTS_T_MIN || chunk_tokens > (int)LMC_COUNTS_T || (tail && tail < (int)LMC_COUNTS_T_MIN) || C > 1024)
+  if (C > 1024 ||
+      (!fixed && (chunk_tokens < (int)LMC_COUNTS_T_MIN || chunk_tokens > (int)LMC_COUNTS_T || (tail && tail < (int)LMC_COUNTS_T_MIN))))
     return LMC_NOT_LAYERWISE;
   HIP_TRY(hipSetDevice(c->device));
   const int gran = G % 8 == 0 ? G / 8 : G;
   const size_t TQ = ((size_t)chunk_tokens + 3) / 4;
-  const size_t need_agg = (size_t)nchunks * 2 * L * gran * 8;
-  const size_t need_sym = (size_t)nchunks * 2 * TQ * C * 4;
+  const size_t need_agg = fixed ? 0 : (size_t)nchunks * 2 * L * gran * 8;
+  const size_t need_sym = fixed ? 0 : (size_t)nchunks * 2 * TQ * C * 4;
   const size_t vstride = ((size_t)L * G * lmc_group_cap_bytes((uint32_t)chunk_tokens) + 255) & ~(size_t)255;
-  const size_t need_v = (size_t)nchunks * vstride;
+  const size_t need_v = fixed ? 0 : (size_t)nchunks * vstride;
 
   std::lock_guard<std::mutex> lk(c->mu);
+  // fixed-width: the passes of a whole chunk's plane (k_fixed_encode: 8 waves take 8, 16 or 32 row octs at a time) are
+  // cut into `slices` runs of `slice_passes`: as many as lmc_ctx_set_fixed_layer_slices says, else the smallest power of
+  // two that gives a layer's launch a workgroup per CU -- never more slices than passes, and no slice without a pass
+  u32 slices = 1, slice_passes = 0;
+  if (fixed) {
+    const u32 per_pass = C <= 128 ? 32u : C <= 256 ? 16u : 8u;
+    const u32 npass = (((u32)chunk_tokens + 7u) / 8u + per_pass - 1u) / per_pass;
+    u32 want = (u32)c->fixed_slices;
+    if (!want)
+      for (want = 1; 2u * want <= npass && (unsigned long long)want * 2u * (u32)nchunks < (unsigned long long)c->num_cus;) want *= 2u;
+    want = std::min(want, npass);
+    slice_passes = (npass + want - 1u) / want;
+    slices = (npass + slice_passes - 1u) / slice_passes;
+  }
+  const size_t need_part = fixed ? (size_t)nchunks * P * slices * (G + 1) * 4 : 0;
   lmc_layer_bufs* b = nullptr;
   for (lmc_layer_bufs* k : c->layer_pool)  // idle buffers that are large enough, else any idle ones (grown below)
-    if (!k->busy && k->agg_bytes >= need_agg && k->sym4_bytes >= need_sym && k->v_bytes >= need_v) { b = k; break; }
+    if (!k->busy && k->agg_bytes >= need_agg && k->sym4_bytes >= need_sym && k->v_bytes >= need_v && k->part_bytes >= need_part) { b = k; break; }
   for (lmc_layer_bufs* k : c->layer_pool)
     if (!b && !k->busy) b = k;
   if (!b) {
@@ -912,13 +948,14 @@ int lmc_encode_layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_be
     }
     c->layer_pool.push_back(b);
   }
-  if (b->agg_bytes < need_agg || b->sym4_bytes < need_sym || b->v_bytes < need_v) {
+  if (b->agg_bytes < need_agg || b->sym4_bytes < need_sym || b->v_bytes < need_v || b->part_bytes < need_part) {
     // growing frees memory that the previous job's kernels may still use: wait for them (this call only)
     if (b->used) HIP_TRY(hipEventSynchronize(b->free_ev));
     int rc;
     if ((rc = ws_grow((void**)&b->agg, &b->agg_bytes, need_agg))) return rc;
     if ((rc = ws_grow((void**)&b->sym4, &b->sym4_bytes, need_sym))) return rc;
     if ((rc = ws_grow((void**)&b->vregion, &b->v_bytes, need_v))) return rc;
+    if ((rc = ws_grow((void**)&b->part, &b->part_bytes, need_part))) return rc;
   }
   lmc_layer_job* j = new (std::nothrow) lmc_layer_job();
   if (!j) return LMC_ERR_NOMEM;
@@ -927,9 +964,22 @@ int lmc_encode_layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_be
   j->blobs = (u8*)blobs; j->blob_stride = blob_stride; j->sizes = sizes;
   j->status = job_status ? job_status : c->status_h;
   j->chain_gran = gran; j->vstride = (long long)vstride;
+  j->fixed = fixed; j->slices = slices; j->slice_passes = slice_passes;
   b->busy = true;
   *job_out = j;
   return LMC_OK;
+}
+
+int lmc_encode_layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                            lmc_layer_job** job_out) {
+  return layers_begin(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, job_out, false);
+}
+
+int lmc_encode_layers_begin_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                                  const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                                  lmc_layer_job** job_out) {
+  return layers_begin(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, job_out, true);
 }
 
 // the coder's view of the job (EncodeArgs of every launch but for its planes)
@@ -962,6 +1012,24 @@ int lmc_encode_layer(lmc_ctx* c, lmc_layer_job* j, int32_t layer, lmc_stream_t s
   lmc_layer_bufs* b = j->b;
   EncodeArgs ea = layer_encode_args(j);
   const int L = ea.L;
+  if (j->fixed) {  // one launch: planes `layer` and L + `layer` in slices; nothing to zero (k_fixed.h, FixedEncArgs)
+    if (layer == 0 && b->used) HIP_TRY(hipStreamWaitEvent(s, b->free_ev, 0));
+    FixedEncArgs fa;
+    memset(&fa, 0, sizeof fa);
+    fa.src = to_addr(&j->src);
+    fa.e = ea;
+    fa.e.dtype = j->src.dtype;
+    fa.e.sizes = layer == 0 ? j->sizes : nullptr;  // 0 = "this chunk's encode did not finish" until k_fixed_layers_finish
+    fa.e.plane0 = layer; fa.e.plane_step = L; fa.e.nplanes = 2;
+    fa.part = b->part; fa.slice_passes = j->slice_passes;
+    const bool nhdb = j->src.paged_kind == LMC_PAGED_SPLIT;
+    const int rc = j->src.dtype == LMC_DTYPE_BF16 ? launch_fixed_encode<LMC_DTYPE_BF16, true>(fa, s, nhdb, j->slices)
+                                                  : launch_fixed_encode<LMC_DTYPE_FP16, true>(fa, s, nhdb, j->slices);
+    j->queued = true; j->last_stream = s;
+    if (rc) return rc;
+    j->next_layer = layer + 1;
+    return LMC_OK;
+  }
   if (layer == 0) {
     // the job's first launch: behind the buffers' previous job; granules and tickets start from zero ONCE -- the later
     // layers' look-backs read the prefixes this and every earlier layer leave
@@ -1002,6 +1070,19 @@ int lmc_encode_layers_finish(lmc_ctx* c, lmc_layer_job* j, lmc_stream_t stream) 
   if (!layer_job_ok(c, j) || j->next_layer != j->src.num_layers) return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
+  if (j->fixed) {
+    FixedFinishArgs ff;
+    memset(&ff, 0, sizeof ff);
+    ff.e = layer_encode_args(j);
+    ff.e.dtype = j->src.dtype;
+    ff.part = j->b->part; ff.nslices = j->slices;
+    hipLaunchKernelGGL(k_fixed_layers_finish, dim3((unsigned)j->nchunks), dim3(FIXED_FIN_THREADS), 0, s, ff);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) { g_last_hip = (int)le; return LMC_ERR_HIP; }
+    j->queued = true; j->last_stream = s;
+    layer_job_release(j);
+    return LMC_OK;
+  }
   LayersFinishArgs fa;
   memset(&fa, 0, sizeof fa);
   fa.e = layer_encode_args(j);

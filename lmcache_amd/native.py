@@ -54,7 +54,24 @@ def build(force: bool = False) -> str:
             sys.stderr.write("\n".join(l for l in proc.stderr.splitlines() if "[-Rpass-analysis=kernel-resource-usage]" not in l) + "\n")
         _write_kernel_resources(proc.stderr)
         _check_decoder_registers()
+        _check_fixed_registers()
     return SO_PATH
+
+
+def _check_fixed_registers() -> None:
+    """k_fixed_encode's instances -- the one-piece encode's and the LAYER ones of the sliced per-layer launches (k_fixed.h,
+    FixedEncArgs) -- and k_fixed_layers_finish must not spill: a build in which one of them uses scratch is refused here,
+    as the decoder's is above."""
+    import json
+    res = json.load(open(RESOURCES_PATH))
+    bad = {k: v.get("ScratchSize") for k, v in res.items()
+           if ("k_fixed_encode" in k or "k_fixed_layers_finish" in k) and v.get("ScratchSize") != 0}
+    if bad:
+        try:
+            os.remove(SO_PATH)
+        except OSError:
+            pass
+        raise RuntimeError(f"k_fixed_encode / k_fixed_layers_finish must not use scratch (k_fixed.h); got {bad}")
 
 
 def _check_decoder_registers() -> None:
@@ -152,6 +169,7 @@ SYMBOLS = {
     "lmc_ctx_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "lmc_device_status": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmc_ctx_set_encode_path": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lmc_ctx_set_fixed_layer_slices": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmc_ctx_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmc_ctx_profile_read": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.c_int]),
     "lmc_quantize": (ctypes.c_int, [_vp, _PL, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -161,6 +179,7 @@ SYMBOLS = {
     "lmc_encode_chunks_fixed": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_encode_chunks_fixed_split": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "lmc_encode_layers_begin": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, ctypes.POINTER(_vp)]),
+    "lmc_encode_layers_begin_fixed": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, ctypes.POINTER(_vp)]),
     "lmc_encode_layer": (ctypes.c_int, [_vp, _vp, _i32, _vp]),
     "lmc_encode_layers_finish": (ctypes.c_int, [_vp, _vp, _vp]),
     "lmc_encode_layers_abort": (ctypes.c_int, [_vp, _vp]),
@@ -872,12 +891,31 @@ class Context:
         """lmc_encode_layers_begin: the layer-wise form of encode_chunks_split -> the job's handle, or None when the job
         is not eligible (LMC_NOT_LAYERWISE: the caller encodes in one piece).  `src` is kept alive by the handle."""
         h = ctypes.c_void_p()
-        rc = lib().lmc_encode_layers_begin(self.handle, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
-                                           self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr, ctypes.byref(h))
+        return self._layers_begin("lmc_encode_layers_begin", src, tok_begin, tok_end, chunk_tokens, bins, blobs_ptr, blob_stride,
+                                  sizes_ptr, status_ptr)
+
+    def encode_layers_begin_fixed(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
+                                  blobs_ptr: int, blob_stride: int, sizes_ptr: int, status_ptr: Optional[int] = None
+                                  ) -> Optional["LayerEncodeHandle"]:
+        """lmc_encode_layers_begin_fixed: the layer-wise form of encode_chunks_fixed_split -> the same handle as
+        encode_layers_begin's, or None for planes of more than 1024 channels."""
+        return self._layers_begin("lmc_encode_layers_begin_fixed", src, tok_begin, tok_end, chunk_tokens, bins, blobs_ptr,
+                                  blob_stride, sizes_ptr, status_ptr)
+
+    def _layers_begin(self, symbol: str, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
+                      blobs_ptr: int, blob_stride: int, sizes_ptr: int, status_ptr: Optional[int]) -> Optional["LayerEncodeHandle"]:
+        h = ctypes.c_void_p()
+        rc = getattr(lib(), symbol)(self.handle, ctypes.byref(src.struct), tok_begin, tok_end, chunk_tokens,
+                                    self._bins(bins), blobs_ptr, blob_stride, sizes_ptr, status_ptr, ctypes.byref(h))
         if rc == NOT_LAYERWISE:
             return None
-        check(rc, "lmc_encode_layers_begin")
+        check(rc, symbol)
         return LayerEncodeHandle(self, h, src)
+
+    def set_fixed_layer_slices(self, n: int) -> None:
+        """lmc_ctx_set_fixed_layer_slices: slices per plane of a chunk in the layer launches of the fixed-width layer-wise
+        jobs begun from now on; 0: the library's own rule.  Blobs do not depend on it."""
+        check(lib().lmc_ctx_set_fixed_layer_slices(self.handle, int(n)), "lmc_ctx_set_fixed_layer_slices")
 
     def decode_chunks(self, blobs_ptr: int, blob_stride: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                       chunk_tokens: int, stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
@@ -1065,7 +1103,7 @@ class Context:
 
 
 class LayerEncodeHandle:
-    """A live lmc_layer_job: encode_layer(l) for l = 0 .. L-1 in order, then finish() -- or abort() at any point.  The raw
+    """A live lmc_layer_job of either coder model: encode_layer(l) for l = 0 .. L-1 in order, then finish() -- or abort() at any point.  The raw
     return codes are available (`*_rc`) for callers that test the refusals; the plain methods raise NativeError."""
 
     def __init__(self, ctx: "Context", handle, src: KVLayout):

@@ -275,6 +275,10 @@ class LMCLocalBackend(LMCBackendInterface):
         # (_promote_group) -- only where LMCACHE_AMD_FIXED_PROMOTE=1 is set as well: without it a hit serves such a group
         # where it lies and leaves it there, as before the reverse transcode existed
         self.fixed_promotes = self.fixed_demotes and os.environ.get("LMCACHE_AMD_FIXED_PROMOTE", "0") == "1"
+        # the fixed-width tier stores layer by layer (begin_put_kv_layers: lmc_encode_layers_begin_fixed) only where
+        # LMCACHE_AMD_FIXED_LAYERWISE=1 is set (read here, once): the default keeps what the tier has always done with a
+        # layer-wise store -- one encode of the whole context behind the last layer
+        self.fixed_layerwise = self.model == "fixed" and os.environ.get("LMCACHE_AMD_FIXED_LAYERWISE", "0") == "1"
         self._tiers = Tiers(self._lru, self._demote_group if self._demotes() else None, self._drop_group, self._demoted_size)
         self.put_queue: "queue.Queue" = queue.Queue()
         self.put_thread = threading.Thread(target=self.put_worker, daemon=True)
@@ -1003,8 +1007,10 @@ class LMCLocalBackend(LMCBackendInterface):
         """put_kv_range whose encode is issued layer by layer, while the forward pass that writes `src` is still running:
         -> a LayerwisePut (encode_layer(l) for l = 0 .. L-1, layer_event(l), finish(blocking)), or None -- the caller
         then stores in one piece with put_kv_range once every layer is there.  None is returned by the raw tiers (their
-        gather IS the store) and for a job the layer-wise encoder does not take (CacheGenDeviceCodec.encode_layers: a
-        layout it cannot read in place, chunks outside 2 .. 256 tokens, planes of more than 1024 channels).
+        gather IS the store), for a job the layer-wise encoder does not take (CacheGenDeviceCodec.encode_layers: a
+        layout it cannot read in place, chunks outside 2 .. 256 tokens, planes of more than 1024 channels) and by the
+        fixed-width tier unless LMCACHE_AMD_FIXED_LAYERWISE=1 was set when the backend was built (fixed_layerwise; then
+        CacheGenDeviceCodec.encode_layers_fixed: any chunk length, the same layouts and planes).
         Replaces the store of the reference behind the forward pass (cache_engine.py:268-282) and the connector's gather
         of every layer in front of it (docs/source/developer_tutorial/LLM_Engine.rst:91-122).
         After finish() the backend holds what put_kv_range leaves for the same arguments -- the same keys, the same blob
@@ -1013,11 +1019,13 @@ class LMCLocalBackend(LMCBackendInterface):
         are put_kv_range's.  Nothing is published before finish()."""
         n = (tok_end - tok_begin + chunk_tokens - 1) // chunk_tokens
         assert n == len(keys), "one key per chunk"
-        if n == 0 or self.mode not in ("cachegen", "hbm-cachegen") or self.model == "fixed":  # (no layer-wise store of the fixed-width model yet)
+        if n == 0 or self.mode not in ("cachegen", "hbm-cachegen") or (self.model == "fixed" and not self.fixed_layerwise):
             return None
         L, H, D = src.L, src.H, src.D
+        codec = self._codec()
+        encode_layers = codec.encode_layers_fixed if self.model == "fixed" else codec.encode_layers
         with torch.cuda.device(src.device):
-            job = self._codec().encode_layers(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L))
+            job = encode_layers(src, tok_begin, tok_end, chunk_tokens, self.cachegen_config.plane_bins(L))
         if job is None:
             return None
         shapes = [_chunk_shape(fmt, L, min(chunk_tokens, tok_end - (tok_begin + i * chunk_tokens)), H, D) for i in range(n)]

@@ -341,7 +341,8 @@ class EncodeJob(Job):
 
 
 class LayerwiseEncodeJob(EncodeJob):
-    """An encode issued layer by layer (CacheGenDeviceCodec.encode_layers; lmc_encode_layers_*, csrc/k_layers.h):
+    """An encode issued layer by layer (CacheGenDeviceCodec.encode_layers / encode_layers_fixed; lmc_encode_layers_*,
+    csrc/k_layers.h, and for the fixed-width model csrc/k_fixed.h):
     encode_layer(l) for l = 0 .. L-1 in order, then finish().  After finish() it IS an EncodeJob -- arena at blob_bound
     stride, pinned size words, its own status word, `done` behind its last kernel -- whose blobs are byte for byte those
     of CacheGenDeviceCodec.encode() for the same source, range, chunk length and bins: sizes_of, offload and
@@ -368,7 +369,8 @@ class LayerwiseEncodeJob(EncodeJob):
             self.layer_events.append(ev)
 
     def finish(self) -> "LayerwiseEncodeJob":
-        """k_layers_finish behind the last layer; `done` is recorded behind it.  No host wait."""
+        """The finish kernel (k_layers_finish, k_fixed_layers_finish) behind the last layer; `done` is recorded behind it.
+        No host wait."""
         with torch.cuda.device(self.arena.device):
             self.handle.finish(self.stream.cuda_stream)
             self.done.record(self.stream)
@@ -747,6 +749,23 @@ class CacheGenDeviceCodec:
         2 .. 256 tokens, planes of more than 1024 channels (lmc_encode_layers_begin).  Nothing is queued here.
         The job has an arena of its own and a side stream: it spans a forward pass and must not hold the shared encode
         arena, nor the model's stream."""
+        return self._encode_layers(src, tok_begin, tok_end, chunk_tokens, bins, None)
+
+    def encode_layers_fixed(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int,
+                            bins: Sequence[int]) -> Optional[LayerwiseEncodeJob]:
+        """encode(model="fixed") issued layer by layer (lmc_encode_layers_begin_fixed, csrc/k_fixed.h): the same job
+        object as encode_layers', and after finish() an EncodeJob of the fixed-width model -- sizes_of and keep_on_device
+        take it as they take encode(model="fixed")'s.  None: a source the encoders do not read in place, or planes of
+        more than 1024 channels; every chunk length is eligible.  fp8 KV raises, as in encode()."""
+        return self._encode_layers(src, tok_begin, tok_end, chunk_tokens, bins, "fixed")
+
+    # coder model -> the context's begin of a layer-wise job
+    _LAYER_BEGINS = {None: "encode_layers_begin", "fixed": "encode_layers_begin_fixed"}
+
+    def _encode_layers(self, src: native.KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int,
+                       bins: Sequence[int], model: Optional[str]) -> Optional[LayerwiseEncodeJob]:
+        """The one body of encode_layers / encode_layers_fixed."""
+        begin = self._entry({}, model, src, self._LAYER_BEGINS.get(model))  # (one entry per model: it takes either layout)
         split = src.struct.paged_kind == native.PAGED_SPLIT
         if not (src.vector_readable() or (split and src.H * src.D <= 1024)):
             return None
@@ -759,8 +778,7 @@ class CacheGenDeviceCodec:
             loans = []
             with self._launch(side, loans) as (st, st_ptr):
                 sizes = _borrow(loans, self._size_pool, 4 * n, 4 * max(n, 256))
-                handle = self.ctx.encode_layers_begin(src, tok_begin, tok_end, chunk_tokens, bins, arena.data_ptr(), stride,
-                                                      sizes.ptr, status_ptr=st_ptr)
+                handle = begin(src, tok_begin, tok_end, chunk_tokens, bins, arena.data_ptr(), stride, sizes.ptr, status_ptr=st_ptr)
             if handle is None:  # not eligible: nothing was queued, the words go back as they came
                 self._status.read_release(st)
                 for buf, words in loans:
