@@ -10,6 +10,7 @@
 #include <functional>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -38,15 +39,34 @@ static thread_local int g_last_hip = 0;
     }                                      \
   } while (0)
 
+// A device buffer that only grows.  grow(need): at least `need` bytes -- the old block is freed first, then a block of
+// `need` rounded up to 1 MiB is taken; whoever grows a buffer that queued kernels may still use waits for them first.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t bytes = 0;
+  int grow(size_t need) {
+    if (bytes >= need) return LMC_OK;
+    if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) { g_last_hip = (int)e; return LMC_ERR_HIP; } p = nullptr; bytes = 0; }
+    need = (need + (size_t)(1 << 20)) & ~(size_t)((1 << 20) - 1);
+    hipError_t e = hipMalloc(&p, need);
+    if (e != hipSuccess) { g_last_hip = (int)e; return e == hipErrorOutOfMemory ? LMC_ERR_NOMEM : LMC_ERR_HIP; }
+    bytes = need;
+    return LMC_OK;
+  }
+  void free() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+
 // What a layer-wise encode job (lmc_encode_layers_*) owns from begin to finish: look-back granules that live across the
 // job's launches, a ticket counter, the symbol workspace of ONE layer's two planes and the region its V streams wait in;
 // a job of the fixed-width model (lmc_encode_layers_begin_fixed) the slices' partial sums alone.
 // Kept by the context between jobs and handed to the next one behind `free_ev`.
 struct lmc_layer_bufs {
-  unsigned long long* agg = nullptr; size_t agg_bytes = 0;
-  u32* sym4 = nullptr; size_t sym4_bytes = 0;
-  u8* vregion = nullptr; size_t v_bytes = 0;
-  u32* part = nullptr; size_t part_bytes = 0;  // k_fixed.h: [nchunks][P][slices][G + 1]
+  DevBuf<unsigned long long> agg;
+  DevBuf<u32> sym4;
+  DevBuf<u8> vregion;
+  DevBuf<u32> part;  // k_fixed.h: [nchunks][P][slices][G + 1]
+  template <typename F> void each_buf(F&& f) { f(agg); f(sym4); f(vregion); f(part); }
   u32* ticket = nullptr;
   hipEvent_t free_ev = nullptr;  // recorded behind the last launch of the job that had them last
   bool used = false;             // ... if any
@@ -81,9 +101,10 @@ struct lmc_ctx {
   // on their two streams instead of one behind the other: a job takes the slot its stream used last, else an idle one
   // (the second is allocated when the first is found busy by another stream for the first time), else the first.
   struct Workspace {
-    u32* sym4 = nullptr;  size_t sym4_bytes = 0;       // symbols between the quantise stage and the coder
-    u8* scratch = nullptr; size_t scratch_bytes = 0;   // two-kernel path: the streams before they are placed
-    unsigned long long* agg = nullptr; size_t agg_bytes = 0;  // look-back granules of the in-kernel compaction
+    DevBuf<u32> sym4;               // symbols between the quantise stage and the coder
+    DevBuf<u8> scratch;             // two-kernel path: the streams before they are placed
+    DevBuf<unsigned long long> agg; // look-back granules of the in-kernel compaction
+    template <typename F> void each_buf(F&& f) { f(sym4); f(scratch); f(agg); }
     hipEvent_t ws_free = nullptr;  // recorded after the last kernel that touches the workspace
     bool ws_used = false;
     hipStream_t last_stream = nullptr;
@@ -97,11 +118,11 @@ struct lmc_ctx {
   int fixed_slices = 0;                 // lmc_ctx_set_fixed_layer_slices
   int fused_pl = 0;                     // LMC_FUSED_PL at lmc_ctx_create (A/B switch of tools/probes: planes per work item of narrow planes; 0 = the built-in choice)
   u32 epoch = 0;                        // of the last fused launch (tags its look-back granules)
-  unsigned long long* pack_table = nullptr;  // device copy of a pack's offset table while it is written (lmc_store_pack)
-  size_t pack_table_bytes = 0;
+  DevBuf<unsigned long long> pack_table;  // device copy of a pack's offset table while it is written (lmc_store_pack)
   // store / load legs (lmc_store_chunks, lmc_load_chunks)
-  u8* store_arena = nullptr; size_t store_bytes = 0;  // blobs of the job being offloaded
-  u8* load_slots = nullptr; size_t load_bytes = 0;    // HBM slots the gather kernel fills
+  DevBuf<u8> store_arena;  // blobs of the job being offloaded
+  DevBuf<u8> load_slots;   // HBM slots the gather kernel fills
+  template <typename F> void each_buf(F&& f) { f(pack_table); f(store_arena); f(load_slots); }
   hipStream_t copy_stream = nullptr, copy_stream2 = nullptr;  // the PCIe side of both legs (two DMA queues for the load)
   hipEvent_t store_free = nullptr, load_free = nullptr;  // the arena / the slots may be reused behind these
   bool store_used = false, load_used = false;
@@ -158,7 +179,7 @@ int lmc_ctx_create(int device, lmc_ctx** out) {
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0) c->num_cus = v;
     if (const char* e = getenv("LMC_FUSED_PL")) c->fused_pl = atoi(e);  // read ONCE: never in the encode path
   }
-  hipError_t e = hipHostMalloc((void**)&c->status_h, 64, hipHostMallocMapped | hipHostMallocPortable);
+  hipError_t e = hipHostMalloc(&c->status_h, 64, hipHostMallocMapped | hipHostMallocPortable);
   if (e != hipSuccess) { g_last_hip = (int)e; delete c; return LMC_ERR_HIP; }
   memset(c->status_h, 0, 64);
   for (int k = 0; k < 2; k++) {
@@ -172,27 +193,21 @@ int lmc_ctx_create(int device, lmc_ctx** out) {
 int lmc_ctx_destroy(lmc_ctx* c) {
   if (!c) return LMC_OK;
   (void)hipSetDevice(c->device);
+  const auto free_buf = [](auto& buf) { buf.free(); };
   for (lmc_ctx::Workspace& w : c->ws) {
     if (w.ws_used) (void)hipEventSynchronize(w.ws_free);
-    if (w.sym4) (void)hipFree(w.sym4);
-    if (w.scratch) (void)hipFree(w.scratch);
-    if (w.agg) (void)hipFree(w.agg);
+    w.each_buf(free_buf);
     if (w.ticket) (void)hipFree(w.ticket);
     if (w.ws_free) (void)hipEventDestroy(w.ws_free);
   }
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
   if (c->copy_stream2) { (void)hipStreamSynchronize(c->copy_stream2); (void)hipStreamDestroy(c->copy_stream2); }
-  if (c->store_arena) (void)hipFree(c->store_arena);
-  if (c->load_slots) (void)hipFree(c->load_slots);
-  if (c->pack_table) (void)hipFree(c->pack_table);
+  c->each_buf(free_buf);
   if (c->store_free) (void)hipEventDestroy(c->store_free);
   if (c->load_free) (void)hipEventDestroy(c->load_free);
   for (lmc_layer_bufs* b : c->layer_pool) {  // (a job still live at this point is the caller's leak: its handle dangles)
     if (b->used) (void)hipEventSynchronize(b->free_ev);
-    if (b->agg) (void)hipFree(b->agg);
-    if (b->sym4) (void)hipFree(b->sym4);
-    if (b->vregion) (void)hipFree(b->vregion);
-    if (b->part) (void)hipFree(b->part);
+    b->each_buf(free_buf);
     if (b->ticket) (void)hipFree(b->ticket);
     if (b->free_ev) (void)hipEventDestroy(b->free_ev);
     delete b;
@@ -339,15 +354,43 @@ static bool bins_ok(const int32_t* bins_h, int P, BinsArg* out) {
   return true;
 }
 
-// f(IntTag<DT>) for the KV dtype code `dtype` (one that layout_ok has passed): where a run-time dtype picks a kernel instance.
+// ---- where a run-time value picks a kernel instance: f is a generic lambda that takes the value as a tag type ------------
+// f(IntTag<V>) for the first of V, Vs... that equals v, else for the last of them.
+template <int V, int... Vs, typename F>
+static auto with_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) return f(IntTag<V>{});
+  else return v == V ? f(IntTag<V>{}) : with_int<Vs...>(v, f);
+}
+template <typename F>
+static auto with_bool(bool b, F&& f) { return b ? f(BoolTag<true>{}) : f(BoolTag<false>{}); }
+// The KV dtype code `dtype` (one that layout_ok has passed) for the kernels that have an instance per dtype ...
 template <typename F>
 static auto with_kv_dtype(int dtype, F&& f) {
-  switch (dtype) {
-    case LMC_DTYPE_BF16: return f(IntTag<LMC_DTYPE_BF16>{});
-    case LMC_DTYPE_FP16: return f(IntTag<LMC_DTYPE_FP16>{});
-    case LMC_DTYPE_FP8_E4M3: return f(IntTag<LMC_DTYPE_FP8_E4M3>{});
-    default: return f(IntTag<LMC_DTYPE_FP8_E5M2>{});
-  }
+  return with_int<LMC_DTYPE_BF16, LMC_DTYPE_FP16, LMC_DTYPE_FP8_E4M3, LMC_DTYPE_FP8_E5M2>(dtype, f);
+}
+// ... and for the ones that have 16-bit instances only (k_fixed_*, k_rope_*: their callers have refused fp8).  Never
+// with_kv_dtype there: it would build fp8 instances nobody launches.
+template <typename F>
+static auto with_kv_dtype16(int dtype, F&& f) {
+  return with_int<LMC_DTYPE_BF16, LMC_DTYPE_FP16>(dtype, f);
+}
+// How a destination's tokens are found (k_decode.h, KIND).
+template <typename F>
+static auto with_decode_kind(const lmc_kv_layout* dst, F&& f) {
+  const int kind = dst->paged_kind == LMC_PAGED_SPLIT ? DEC_PAGED_SPLIT : dst->slot_mapping ? DEC_PAGED_ROWS : DEC_ROWS;
+  return with_int<DEC_PAGED_SPLIT, DEC_PAGED_ROWS, DEC_ROWS>(kind, f);
+}
+// f(IntTag<G>, IntTag<NITER>) for a plane of C <= 1024 channels: G lanes take a row, NITER runs of 8 channels each (the
+// rungs every plane-wide kernel has: k_quantize, k_encode_fused, k_fixed_encode).  false, and f not called: the plane is
+// wider -- the caller has its own instances for that, or none.
+template <typename F>
+static bool with_plane_width(int C, F&& f) {
+  if (C <= 128) f(IntTag<16>{}, IntTag<1>{});
+  else if (C <= 256) f(IntTag<32>{}, IntTag<1>{});
+  else if (C <= 512) f(IntTag<64>{}, IntTag<1>{});
+  else if (C <= 1024) f(IntTag<64>{}, IntTag<2>{});
+  else return false;
+  return true;
 }
 
 // What k_quantize's loads can address in an LMC_PAGED_SPLIT source that layout_ok(src, false, true) has passed
@@ -377,6 +420,29 @@ static bool encode_job_ok(const lmc_ctx* c, const lmc_kv_layout* src, int32_t to
   return *nchunks <= 65535;
 }
 
+// ... and of the arena its blobs go to, a slot of `blob_stride` bytes per chunk, and of its bins (-> *bins): 16-byte slots
+// that hold the largest blob of the geometry, a size word per chunk.  `fixed_blobs`: the job writes or reads fixed-width
+// blobs, whose exact size must fit the header's 32-bit size words (the coded models' bound is blob_stride's: checked by
+// whoever sized the arena).
+static bool encode_dst_ok(const void* blobs, uint64_t blob_stride, const uint32_t* sizes, int L, int H, int D, int32_t chunk_tokens,
+                          const int32_t* bins_h, bool fixed_blobs, BinsArg* bins) {
+  if (!blobs || !sizes || ((uintptr_t)blobs & 15) || (blob_stride & 15)) return false;
+  if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return false;
+  if (!bins_ok(bins_h, 2 * L, bins)) return false;
+  return !fixed_blobs || lmc_fixed_blob_bytes((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, bins->b) <= 0xffffffffull;
+}
+
+// What a job over blobs of earlier stores asks of the geometry it is told (the transcodes, lmc_pack_blobs): `nchunks`
+// chunks of L layers x H heads x D, planes of a multiple of 8 channels up to LMC_MAX_CHANNELS, and `ntokens` tokens that
+// fill every chunk but, possibly, the last.
+static bool chunk_geometry_ok(int32_t nchunks, int32_t L, int32_t H, int32_t D, int32_t chunk_tokens, uint32_t ntokens) {
+  if (nchunks < 1 || nchunks > 65535 || L < 1 || 2 * L > LMC_MAX_PLANES || H < 1 || D < 1 || chunk_tokens < 1 || chunk_tokens > 65535)
+    return false;
+  const long long C = (long long)H * D;
+  if (C < 8 || (C & 7) || C > LMC_MAX_CHANNELS) return false;
+  return (uint64_t)ntokens <= (uint64_t)nchunks * (uint32_t)chunk_tokens && (uint64_t)ntokens > (uint64_t)(nchunks - 1) * (uint32_t)chunk_tokens;
+}
+
 // NHDB: the source is an LMC_PAGED_SPLIT cache (k_quantize.h: instances of their own, planes of up to 1024 channels)
 template <int DT, bool QUAD, bool NHDB = false>
 static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
@@ -384,29 +450,26 @@ static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
   if (a.pc_limit < 1) return LMC_OK;
   const unsigned nz = (unsigned)((a.pc_limit + a.P - 1) / a.P);  // chunks that hold the plane-chunks to do
   const unsigned ny = (unsigned)(a.nplanes ? a.nplanes : a.P);   // planes of the launch (QuantArgs::plane0)
-#define LQ(G, N)                                                                                   \
-  do {                                                                                             \
-    const int per_wg = 4 * (64 / (G)), TO = (a.TQ + 1) / 2; /* row octs per plane-chunk */         \
-    dim3 grid((unsigned)((TO + per_wg - 1) / per_wg), ny, nz);                                    \
-    hipLaunchKernelGGL((k_quantize<G, N, DT, QUAD, 1, NHDB>), grid, dim3(256), 0, s, a);           \
-  } while (0)
-  // wide planes, workspace output: SPLIT waves share a row oct, 1024 channels each (k_quantize.h)
-#define LQS(SPLIT)                                                                                 \
-  do {                                                                                             \
-    const int TO = (a.TQ + 1) / 2, per_wg = 4 / (SPLIT);                                           \
-    dim3 grid((unsigned)((TO + per_wg - 1) / per_wg), ny, nz);                                    \
-    hipLaunchKernelGGL((k_quantize<64, 2, DT, QUAD, QUAD ? SPLIT : 1>), grid, dim3(256), 0, s, a); \
-  } while (0)
-  if (C <= 128) LQ(16, 1);
-  else if (C <= 256) LQ(32, 1);
-  else if (C <= 512) LQ(64, 1);
-  else if (C <= 1024) LQ(64, 2);
-  else if constexpr (NHDB) return LMC_ERR_INVALID;
-  else if (C <= 2048) { if (QUAD) LQS(2); else LQ(64, 4); }
-  else if (C <= 4096) { if (QUAD) LQS(4); else LQ(64, 8); }
-  else return LMC_ERR_INVALID;
-#undef LQ
-#undef LQS
+  // SPLIT > 1 (wide planes, workspace output): SPLIT waves share a row oct, 1024 channels each (k_quantize.h)
+  const auto launch = [&](auto g, auto n, auto split) {
+    constexpr int G = decltype(g)::value, N = decltype(n)::value, SPLIT = decltype(split)::value;
+    const int per_wg = 4 * (64 / G) / SPLIT, TO = (a.TQ + 1) / 2;  // row octs per plane-chunk
+    const dim3 grid((unsigned)((TO + per_wg - 1) / per_wg), ny, nz);
+    hipLaunchKernelGGL((k_quantize<G, N, DT, QUAD, SPLIT, NHDB>), grid, dim3(256), 0, s, a);
+  };
+  const IntTag<64> g64;
+  if (with_plane_width(C, [&](auto g, auto n) { launch(g, n, IntTag<1>{}); })) {
+  } else if constexpr (NHDB) {
+    return LMC_ERR_INVALID;
+  } else if (C > 4096) {
+    return LMC_ERR_INVALID;
+  } else if (QUAD) {  // (a plain `if`, here and below: either QUAD builds both arms, as it always has -- the set of kernels stays)
+    if (C <= 2048) launch(g64, IntTag<2>{}, IntTag<QUAD ? 2 : 1>{});
+    else launch(g64, IntTag<2>{}, IntTag<QUAD ? 4 : 1>{});
+  } else {
+    if (C <= 2048) launch(g64, IntTag<4>{}, IntTag<1>{});
+    else launch(g64, IntTag<8>{}, IntTag<1>{});
+  }
   HIP_TRY(hipGetLastError());
   return LMC_OK;
 }
@@ -426,31 +489,20 @@ static uint64_t blob_stride(int L, int chunk_tokens, int H, int D) {
   return (lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D) + 15) & ~(uint64_t)15;
 }
 
-static int ws_grow(void** p, size_t* have, size_t need) {
-  if (*have >= need) return LMC_OK;
-  if (*p) { hipError_t e = hipFree(*p); if (e != hipSuccess) { g_last_hip = (int)e; return LMC_ERR_HIP; } *p = nullptr; *have = 0; }
-  need = (need + (size_t)(1 << 20)) & ~(size_t)((1 << 20) - 1);
-  hipError_t e = hipMalloc(p, need);
-  if (e != hipSuccess) { g_last_hip = (int)e; return e == hipErrorOutOfMemory ? LMC_ERR_NOMEM : LMC_ERR_HIP; }
-  *have = need;
-  return LMC_OK;
-}
-
 // The fused encode for a plane width (k_fused.h: lanes per quantise task, channel runs per lane, waves per row).
-template <int DT, bool PSRC>
-static void launch_fused_src(int C, dim3 grid, dim3 block, hipStream_t s, const FusedArgs& fa) {
-  if (C <= 128) hipLaunchKernelGGL((k_encode_fused<16, 1, DT, FUSED_WAVES, PSRC>), grid, block, 0, s, fa);
-  else if (C <= 256) hipLaunchKernelGGL((k_encode_fused<32, 1, DT, FUSED_WAVES, PSRC>), grid, block, 0, s, fa);
-  else if (C <= 512) hipLaunchKernelGGL((k_encode_fused<64, 1, DT, FUSED_WAVES, PSRC>), grid, block, 0, s, fa);
-  else hipLaunchKernelGGL((k_encode_fused<64, 2, DT, FUSED_WAVES, PSRC>), grid, block, 0, s, fa);  // C <= LMC_FUSED_MAX_CHANNELS
-}
-template <int DT>
+// C <= LMC_FUSED_MAX_CHANNELS = 1024 (encode_job's fused_fits): the common rungs are all the kernel has.
 static void launch_fused(int C, dim3 grid, dim3 block, hipStream_t s, const FusedArgs& fa) {
   // a paged source with a block size that is a power of two (every one vLLM offers) has kernel instances of its own: the
   // tokens' slots by scalar loads (k_fused.h, fused_tok_off)
   const u32 bs = (u32)fa.src.block_size;
-  if (fa.src.slot_mapping && bs != 0u && (bs & (bs - 1u)) == 0u) launch_fused_src<DT, true>(C, grid, block, s, fa);
-  else launch_fused_src<DT, false>(C, grid, block, s, fa);
+  with_kv_dtype(fa.src.dtype, [&](auto dt) {
+    with_bool(fa.src.slot_mapping && bs != 0u && (bs & (bs - 1u)) == 0u, [&](auto psrc) {
+      with_plane_width(C, [&](auto g, auto n) {
+        hipLaunchKernelGGL((k_encode_fused<decltype(g)::value, decltype(n)::value, decltype(dt)::value, FUSED_WAVES, decltype(psrc)::value>),
+                           grid, block, 0, s, fa);
+      });
+    });
+  });
 }
 
 // caller holds ctx->mu.  The symbol workspace and the look-back granules of `max_chunks` chunks, stream scratch for
@@ -461,17 +513,15 @@ static int reserve_locked(lmc_ctx::Workspace* c, int L, int H, int D, int chunk_
   const size_t need_sym = (size_t)max_chunks * P * TQ * C * 4;
   const size_t need_scr = (size_t)scratch_chunks * P * G * lmc_group_cap_bytes((uint32_t)chunk_tokens);
   const size_t need_agg = (size_t)max_chunks * P * G * 8;
-  if (need_sym <= c->sym4_bytes && need_scr <= c->scratch_bytes && need_agg <= c->agg_bytes)
+  if (need_sym <= c->sym4.bytes && need_scr <= c->scratch.bytes && need_agg <= c->agg.bytes)
     return LMC_OK;
   // growing frees memory that queued kernels may still use: wait for them (this call only)
   if (c->ws_used) HIP_TRY(hipEventSynchronize(c->ws_free));
   int rc;
-  if ((rc = ws_grow((void**)&c->sym4, &c->sym4_bytes, need_sym))) return rc;
-  if ((rc = ws_grow((void**)&c->scratch, &c->scratch_bytes, need_scr))) return rc;
-  const size_t agg_before = c->agg_bytes;
-  if ((rc = ws_grow((void**)&c->agg, &c->agg_bytes, need_agg))) return rc;
+  const size_t agg_before = c->agg.bytes;
+  if ((rc = c->sym4.grow(need_sym)) || (rc = c->scratch.grow(need_scr)) || (rc = c->agg.grow(need_agg))) return rc;
   // fresh granules must not look like a published value of some epoch (k_fused.h)
-  if (c->agg_bytes != agg_before) HIP_TRY(hipMemset(c->agg, 0, c->agg_bytes));
+  if (c->agg.bytes != agg_before) HIP_TRY(hipMemset(c->agg.p, 0, c->agg.bytes));
   return LMC_OK;
 }
 
@@ -485,19 +535,17 @@ template <int DT, bool LAYER = false>
 static int launch_fixed_encode(const FixedEncArgs& fa, hipStream_t s, bool nhdb, unsigned slices = 1) {
   const int C = fa.e.C;
   const dim3 grid((unsigned)(LAYER ? fa.e.nplanes : fa.e.P), (unsigned)fa.e.nchunks, slices), block(64 * FIXED_ENC_WAVES);
-  if (LAYER && C > 1024) return LMC_ERR_INVALID;
-  if (nhdb) {
-    if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1, true, LAYER>), grid, block, 0, s, fa);
-    else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1, true, LAYER>), grid, block, 0, s, fa);
-    else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1, true, LAYER>), grid, block, 0, s, fa);
-    else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1, true, LAYER>), grid, block, 0, s, fa);
-    else return LMC_ERR_INVALID;
-  } else if (C <= 128) hipLaunchKernelGGL((k_fixed_encode<16, 1, DT, 1, false, LAYER>), grid, block, 0, s, fa);
-  else if (C <= 256) hipLaunchKernelGGL((k_fixed_encode<32, 1, DT, 1, false, LAYER>), grid, block, 0, s, fa);
-  else if (C <= 512) hipLaunchKernelGGL((k_fixed_encode<64, 1, DT, 1, false, LAYER>), grid, block, 0, s, fa);
-  else if (C <= 1024) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 1, false, LAYER>), grid, block, 0, s, fa);
-  else if (C <= 2048) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 2>), grid, block, 0, s, fa);
-  else hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 4>), grid, block, 0, s, fa);  // C <= LMC_MAX_CHANNELS: layout_ok
+  const bool common = with_bool(nhdb, [&](auto split) {
+    return with_plane_width(C, [&](auto g, auto n) {
+      hipLaunchKernelGGL((k_fixed_encode<decltype(g)::value, decltype(n)::value, DT, 1, decltype(split)::value, LAYER>), grid, block, 0, s, fa);
+    });
+  });
+  if (!common) {  // wider than 1024 channels: rows in one piece only, SPLIT waves to a row oct
+    if constexpr (LAYER) return LMC_ERR_INVALID;
+    else if (nhdb) return LMC_ERR_INVALID;
+    else if (C <= 2048) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 2>), grid, block, 0, s, fa);
+    else hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 4>), grid, block, 0, s, fa);  // C <= LMC_MAX_CHANNELS: layout_ok
+  }
   HIP_TRY(hipGetLastError());
   return LMC_OK;
 }
@@ -547,29 +595,6 @@ int lmc_calculate_cdf(lmc_ctx* c, const int8_t* sym, int32_t P, int32_t T, int32
   return LMC_OK;
 }
 
-// lmc_encode_chunks, optionally launched in `nparts` ranges of PLANES (all chunks of the job): after part r,
-// after_part(r, planes coded so far, last part?) runs with the context lock held (lmc_store_pack_parts packs the range
-// there).  Only a job that takes the fused kernel for every chunk is split; any other job is one part.
-typedef std::function<int(int, int, bool)> AfterPart;
-static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
-                               const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
-                               lmc_stream_t stream, int nparts, const AfterPart* after_part, bool split_ok);
-
-int lmc_encode_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
-                      const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
-                      lmc_stream_t stream) {
-  return encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream, 1,
-                             nullptr, false);
-}
-
-// ... and from any source: an LMC_PAGED_SPLIT cache is read in place by k_quantize's split instances (never fused)
-int lmc_encode_chunks_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
-                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
-                            lmc_stream_t stream) {
-  return encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream, 1,
-                             nullptr, true);
-}
-
 // What stands in front of the coder in a job that has no KV to quantise: fixed-width blobs of earlier stores
 // (lmc_transcode_fixed; k_fixed.h, k_fixed_expand).
 struct FixedSrc {
@@ -577,37 +602,23 @@ struct FixedSrc {
   const uint32_t* blob_bytes;    // device [nchunks]
   int L, H, D, dtype;
 };
-static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, int nchunks, int32_t tok_begin, int32_t tok_end,
-                      int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes,
-                      uint32_t* job_status, lmc_stream_t stream, int nparts, const AfterPart* after_part);
-
-static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
-                               const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
-                               lmc_stream_t stream, int nparts, const AfterPart* after_part, bool split_ok) {
-  int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok)) return LMC_ERR_INVALID;
-  return encode_job(c, src, nullptr, nchunks, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream,
-                    nparts, after_part);
-}
-
+typedef std::function<int(int, int, bool)> AfterPart;
 // The encode job behind its source's own checks: the refusals every source shares, the workspace, the launches.  `src`: the
 // KV that k_quantize or the fused kernel reads, or NULL and `fx`: k_fixed_expand in k_quantize's place -- always the two
 // kernels, and behind the first one the job is the same job.
 static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, int nchunks, int32_t tok_begin, int32_t tok_end,
                       int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes,
                       uint32_t* job_status, lmc_stream_t stream, int nparts, const AfterPart* after_part) {
-  if (!blobs || !sizes || ((uintptr_t)blobs & 15) || (blob_stride & 15)) return LMC_ERR_INVALID;
   const int L = src ? src->num_layers : fx->L, H = src ? src->num_heads : fx->H, D = src ? src->head_size : fx->D;
   const int kv_dtype = src ? src->dtype : fx->dtype;
   const int P = 2 * L, C = H * D, G = (C + 63) / 64;  // (C <= LMC_MAX_CHANNELS: layout_ok)
-  if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
   // an LMC_PAGED_SPLIT source (at most 1024 channels per plane: encode_job_ok): k_quantize's split instances, then
   // k_cdf_encode -- never the fused kernel, so the job is one part
   const bool nhdb = src && src->paged_kind == LMC_PAGED_SPLIT;
   BinsArg bins;
-  if (!bins_ok(bins_h, P, &bins)) return LMC_ERR_INVALID;
-  // (fixed-width blobs of this geometry and these bins stay below 2^32 bytes, as their encoder saw to: k_fixed_expand's sums)
-  if (fx && lmc_fixed_blob_bytes((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, bins.b) > 0xffffffffull) return LMC_ERR_INVALID;
+  // (fixed-width blobs READ here: of this geometry and these bins they stay below 2^32 bytes, as their encoder saw to --
+  // k_fixed_expand's sums)
+  if (!encode_dst_ok(blobs, blob_stride, sizes, L, H, D, chunk_tokens, bins_h, /*fixed_blobs=*/fx != nullptr, &bins)) return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
 
@@ -667,21 +678,21 @@ static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, 
 
   EncodeArgs ea;
   memset(&ea, 0, sizeof ea);
-  ea.sym4 = w->sym4;
+  ea.sym4 = w->sym4.p;
   ea.tok_begin = tok_begin; ea.tok_end = tok_end; ea.chunk_tokens = chunk_tokens; ea.nchunks = nchunks;
   ea.P = P; ea.C = C; ea.G = G; ea.TQ = TQ;
   ea.sym_stride = (long long)TQ * C;
   ea.blobs = (u8*)blobs; ea.blob_stride = (long long)blob_stride;
-  ea.scratch = w->scratch; ea.cap = cap;
+  ea.scratch = w->scratch.p; ea.cap = cap;
   ea.status = job_status ? job_status : c->status_h;
   ea.bins = bins;
-  ea.agg = w->agg; ea.sizes = sizes;
+  ea.agg = w->agg.p; ea.sizes = sizes;
   ea.L = L; ea.H = H; ea.D = D;
   ea.dtype = lmc_math_dtype(kv_dtype);  // the header's dtype word: an fp8 chunk is coded as its bf16 images (lmc_format.h)
   u8* const scale_base = (u8*)blobs + hl.off_scales;  // off_scales does not depend on T
 
   if (!w->ticket) {
-    HIP_TRY(hipMalloc((void**)&w->ticket, 64));
+    HIP_TRY(hipMalloc(&w->ticket, 64));
     HIP_TRY(hipMemsetAsync(w->ticket, 0, 64, s));  // ordered in front of the first launch that draws from it
     w->tickets_drawn = 0;
   }
@@ -697,10 +708,10 @@ static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, 
   auto two_kernels = [&](int c0, int n) -> int {
     EncodeArgs e2 = ea;
     e2.tok_begin = tok_begin + c0 * chunk_tokens; e2.nchunks = n;
-    e2.sym4 = w->sym4 + (size_t)c0 * P * (size_t)ea.sym_stride;
+    e2.sym4 = w->sym4.p + (size_t)c0 * P * (size_t)ea.sym_stride;
     e2.blobs = (u8*)blobs + (size_t)c0 * blob_stride;
-    e2.scratch = w->scratch;  // (at most one launch of a job codes into scratch: its slots are counted from its first chunk)
-    e2.agg = w->agg + (size_t)c0 * PG;
+    e2.scratch = w->scratch.p;  // (at most one launch of a job codes into scratch: its slots are counted from its first chunk)
+    e2.agg = w->agg.p + (size_t)c0 * PG;
     e2.sizes = sizes + c0;
     int r;
     if ((r = prof_mark(c, s))) return r;
@@ -777,7 +788,7 @@ static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, 
       const dim3 grid((unsigned)((long long)nfull * (it1 - it0)));
       fa.item_base = (u32)((long long)it0 * nfull);
       fa.e.ticket_base = w->tickets_drawn;
-      with_kv_dtype(src->dtype, [&](auto dt) { launch_fused<decltype(dt)::value>(C, grid, block, s, fa); });
+      launch_fused(C, grid, block, s, fa);
       const hipError_t le = hipGetLastError();
       if (le != hipSuccess) { g_last_hip = (int)le; tickets_reset(); return LMC_ERR_HIP; }
       w->tickets_drawn += grid.x;
@@ -799,6 +810,33 @@ static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, 
   return LMC_OK;
 }
 
+// lmc_encode_chunks, optionally launched in `nparts` ranges of PLANES (all chunks of the job): after part r,
+// after_part(r, planes coded so far, last part?) runs with the context lock held (lmc_store_pack_parts packs the range
+// there).  Only a job that takes the fused kernel for every chunk is split; any other job is one part.
+static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                               const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                               lmc_stream_t stream, int nparts, const AfterPart* after_part, bool split_ok) {
+  int nchunks;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok)) return LMC_ERR_INVALID;
+  return encode_job(c, src, nullptr, nchunks, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream,
+                    nparts, after_part);
+}
+
+int lmc_encode_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                      const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                      lmc_stream_t stream) {
+  return encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream, 1,
+                             nullptr, false);
+}
+
+// ... and from any source: an LMC_PAGED_SPLIT cache is read in place by k_quantize's split instances (never fused)
+int lmc_encode_chunks_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
+                            const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
+                            lmc_stream_t stream) {
+  return encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream, 1,
+                             nullptr, true);
+}
+
 // Fixed-width blobs of earlier stores -> the entropy-coded blobs of the same KV: k_fixed_expand, then the coder launch
 // lmc_encode_chunks would have made behind k_quantize (encode_job).  The blobs are read where they lie, through the pointer
 // table; a chunk that does not check out sets the job's status word (its slot then holds the coded blob of a chunk of zero
@@ -806,14 +844,9 @@ static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, 
 int lmc_transcode_fixed(lmc_ctx* c, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks, int32_t L, int32_t H,
                         int32_t D, int32_t dtype, int32_t chunk_tokens, uint32_t ntokens, const int32_t* bins_h, void* blobs_out,
                         uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status, lmc_stream_t stream) {
-  if (!c || !blob_ptrs || !blob_bytes || nchunks < 1 || nchunks > 65535 || L < 1 || 2 * L > LMC_MAX_PLANES || H < 1 || D < 1 ||
-      chunk_tokens < 1 || chunk_tokens > 65535 || (dtype != LMC_DTYPE_BF16 && dtype != LMC_DTYPE_FP16))
-    return LMC_ERR_INVALID;
-  const long long C = (long long)H * D;
-  if (C < 8 || (C & 7) || C > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
-  // every chunk is chunk_tokens long but, possibly, the last (lmc_pack_blobs's rule); token indices are 32-bit and signed
-  if ((uint64_t)ntokens > (uint64_t)nchunks * (uint32_t)chunk_tokens || (uint64_t)ntokens <= (uint64_t)(nchunks - 1) * (uint32_t)chunk_tokens ||
-      ntokens > 0x7fffffffu)
+  // (token indices are 32-bit and signed; fixed-width blobs hold 16-bit KV)
+  if (!c || !blob_ptrs || !blob_bytes || !chunk_geometry_ok(nchunks, L, H, D, chunk_tokens, ntokens) || ntokens > 0x7fffffffu ||
+      (dtype != LMC_DTYPE_BF16 && dtype != LMC_DTYPE_FP16))
     return LMC_ERR_INVALID;
   const FixedSrc fx = {blob_ptrs, blob_bytes, L, H, D, dtype};
   return encode_job(c, nullptr, &fx, nchunks, 0, (int32_t)ntokens, chunk_tokens, bins_h, blobs_out, blob_stride, sizes, job_status, stream,
@@ -827,16 +860,11 @@ static int encode_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin,
                         const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
                         lmc_stream_t stream, bool split_ok) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok) || lmc_dtype_fp8(src->dtype) || !blobs || !sizes ||
-      ((uintptr_t)blobs & 15) || (blob_stride & 15))
-    return LMC_ERR_INVALID;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok) || lmc_dtype_fp8(src->dtype)) return LMC_ERR_INVALID;
   const int L = src->num_layers, H = src->num_heads, D = src->head_size;
-  if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
   FixedEncArgs fa;
   memset(&fa, 0, sizeof fa);
-  if (!bins_ok(bins_h, 2 * L, &fa.e.bins)) return LMC_ERR_INVALID;
-  // the header's size words are 32 bits (the coded models' bound is checked by whoever sized the arena: blob_stride)
-  if (lmc_fixed_blob_bytes((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, fa.e.bins.b) > 0xffffffffull) return LMC_ERR_INVALID;
+  if (!encode_dst_ok(blobs, blob_stride, sizes, L, H, D, chunk_tokens, bins_h, /*fixed_blobs=*/true, &fa.e.bins)) return LMC_ERR_INVALID;
   fa.src = to_addr(src);
   fa.e.tok_begin = tok_begin; fa.e.tok_end = tok_end; fa.e.chunk_tokens = chunk_tokens; fa.e.nchunks = nchunks;
   fa.e.P = 2 * L; fa.e.C = H * D; fa.e.G = (fa.e.C + 63) / 64;
@@ -851,9 +879,7 @@ static int encode_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin,
   int rc;
   if ((rc = prof_mark(c, s))) return rc;
   const bool nhdb = src->paged_kind == LMC_PAGED_SPLIT;
-  if (src->dtype == LMC_DTYPE_BF16) rc = launch_fixed_encode<LMC_DTYPE_BF16>(fa, s, nhdb);
-  else rc = launch_fixed_encode<LMC_DTYPE_FP16>(fa, s, nhdb);
-  if (rc) return rc;
+  if ((rc = with_kv_dtype16(src->dtype, [&](auto dt) { return launch_fixed_encode<decltype(dt)::value>(fa, s, nhdb); }))) return rc;
   return prof_mark(c, s);
 }
 
@@ -889,17 +915,12 @@ static int layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin,
   int nchunks;
   if (!job_out) return LMC_ERR_INVALID;
   *job_out = nullptr;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true) || !blobs || !sizes || ((uintptr_t)blobs & 15) ||
-      (blob_stride & 15) || (fixed && lmc_dtype_fp8(src->dtype)))
-    return LMC_ERR_INVALID;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true) || (fixed && lmc_dtype_fp8(src->dtype))) return LMC_ERR_INVALID;
   const int L = src->num_layers, H = src->num_heads, D = src->head_size;
   const int P = 2 * L, C = H * D, G = (C + 63) / 64;
-  if (blob_stride < lmc_blob_bound((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D)) return LMC_ERR_INVALID;
   BinsArg bins;
-  if (!bins_ok(bins_h, P, &bins)) return LMC_ERR_INVALID;
-  if (fixed && lmc_fixed_blob_bytes((uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, bins.b) > 0xffffffffull)
-    return LMC_ERR_INVALID;  // (encode_fixed's refusal: the header's size words are 32 bits)
-  // eligible: the counts-only coder takes every chunk (2 .. 256 tokens, a ragged last one included) and k_quantize's
+  if (!encode_dst_ok(blobs, blob_stride, sizes, L, H, D, chunk_tokens, bins_h, fixed, &bins)) return LMC_ERR_INVALID;
+  // (every refusal is made before this: a job that is refused is refused whether or not it is) eligible: the counts-only coder takes every chunk (2 .. 256 tokens, a ragged last one included) and k_quantize's
   // one-wave-per-oct instances every plane (at most 1024 channels); the fixed-width model has no coder: every chunk
   // length of the one-piece call, the same planes
   const int tail = (tok_end - tok_begin) % chunk_tokens;
@@ -930,16 +951,19 @@ static int layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin,
     slices = (npass + slice_passes - 1u) / slice_passes;
   }
   const size_t need_part = fixed ? (size_t)nchunks * P * slices * (G + 1) * 4 : 0;
+  const auto fits = [&](const lmc_layer_bufs* k) {
+    return k->agg.bytes >= need_agg && k->sym4.bytes >= need_sym && k->vregion.bytes >= need_v && k->part.bytes >= need_part;
+  };
   lmc_layer_bufs* b = nullptr;
   for (lmc_layer_bufs* k : c->layer_pool)  // idle buffers that are large enough, else any idle ones (grown below)
-    if (!k->busy && k->agg_bytes >= need_agg && k->sym4_bytes >= need_sym && k->v_bytes >= need_v && k->part_bytes >= need_part) { b = k; break; }
+    if (!k->busy && fits(k)) { b = k; break; }
   for (lmc_layer_bufs* k : c->layer_pool)
     if (!b && !k->busy) b = k;
   if (!b) {
     b = new (std::nothrow) lmc_layer_bufs();
     if (!b) return LMC_ERR_NOMEM;
     hipError_t e = hipEventCreateWithFlags(&b->free_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&b->ticket, 64);
+    if (e == hipSuccess) e = hipMalloc(&b->ticket, 64);
     if (e != hipSuccess) {
       g_last_hip = (int)e;
       if (b->free_ev) (void)hipEventDestroy(b->free_ev);
@@ -948,14 +972,11 @@ static int layers_begin(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin,
     }
     c->layer_pool.push_back(b);
   }
-  if (b->agg_bytes < need_agg || b->sym4_bytes < need_sym || b->v_bytes < need_v || b->part_bytes < need_part) {
+  if (!fits(b)) {
     // growing frees memory that the previous job's kernels may still use: wait for them (this call only)
     if (b->used) HIP_TRY(hipEventSynchronize(b->free_ev));
     int rc;
-    if ((rc = ws_grow((void**)&b->agg, &b->agg_bytes, need_agg))) return rc;
-    if ((rc = ws_grow((void**)&b->sym4, &b->sym4_bytes, need_sym))) return rc;
-    if ((rc = ws_grow((void**)&b->vregion, &b->v_bytes, need_v))) return rc;
-    if ((rc = ws_grow((void**)&b->part, &b->part_bytes, need_part))) return rc;
+    if ((rc = b->agg.grow(need_agg)) || (rc = b->sym4.grow(need_sym)) || (rc = b->vregion.grow(need_v)) || (rc = b->part.grow(need_part))) return rc;
   }
   lmc_layer_job* j = new (std::nothrow) lmc_layer_job();
   if (!j) return LMC_ERR_NOMEM;
@@ -987,7 +1008,7 @@ static EncodeArgs layer_encode_args(const lmc_layer_job* j) {
   const lmc_kv_layout* src = &j->src;
   EncodeArgs ea;
   memset(&ea, 0, sizeof ea);
-  ea.sym4 = j->b->sym4;
+  ea.sym4 = j->b->sym4.p;
   ea.tok_begin = j->tok_begin; ea.tok_end = j->tok_end; ea.chunk_tokens = j->chunk_tokens; ea.nchunks = j->nchunks;
   ea.L = src->num_layers; ea.H = src->num_heads; ea.D = src->head_size;
   ea.P = 2 * ea.L; ea.C = ea.H * ea.D; ea.G = (ea.C + 63) / 64; ea.TQ = (j->chunk_tokens + 3) / 4;
@@ -995,49 +1016,39 @@ static EncodeArgs layer_encode_args(const lmc_layer_job* j) {
   ea.blobs = j->blobs; ea.blob_stride = (long long)j->blob_stride;
   ea.status = j->status;
   ea.bins = j->bins;
-  ea.agg = j->b->agg; ea.sizes = j->sizes;
+  ea.agg = j->b->agg.p; ea.sizes = j->sizes;
   ea.dtype = lmc_math_dtype(src->dtype);
   ea.ticket = j->b->ticket;
   ea.chain_gran = j->chain_gran;
-  ea.vregion = j->b->vregion; ea.vstride = j->vstride;
+  ea.vregion = j->b->vregion.p; ea.vstride = j->vstride;
   return ea;
 }
 
-int lmc_encode_layer(lmc_ctx* c, lmc_layer_job* j, int32_t layer, lmc_stream_t stream) {
-  if (!c) return LMC_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!layer_job_ok(c, j) || layer != j->next_layer || layer >= j->src.num_layers) return LMC_ERR_INVALID;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
+// One layer of a job, per model; the caller (lmc_encode_layer) has ordered `s` behind the buffers' previous job.
+// Fixed-width: one launch -- planes `layer` and L + `layer` in slices; nothing to zero (k_fixed.h, FixedEncArgs).
+static int encode_layer_fixed(lmc_layer_job* j, int layer, hipStream_t s) {
+  FixedEncArgs fa;
+  memset(&fa, 0, sizeof fa);
+  fa.src = to_addr(&j->src);
+  fa.e = layer_encode_args(j);
+  fa.e.dtype = j->src.dtype;
+  fa.e.sizes = layer == 0 ? j->sizes : nullptr;  // 0 = "this chunk's encode did not finish" until k_fixed_layers_finish
+  fa.e.plane0 = layer; fa.e.plane_step = fa.e.L; fa.e.nplanes = 2;
+  fa.part = j->b->part.p; fa.slice_passes = j->slice_passes;
+  const bool nhdb = j->src.paged_kind == LMC_PAGED_SPLIT;
+  return with_kv_dtype16(j->src.dtype, [&](auto dt) { return launch_fixed_encode<decltype(dt)::value, true>(fa, s, nhdb, j->slices); });
+}
+// Coded: k_quantize of the layer's two planes, then the counts-only coder over their streams.
+static int encode_layer_coded(lmc_layer_job* j, int layer, hipStream_t s) {
   lmc_layer_bufs* b = j->b;
   EncodeArgs ea = layer_encode_args(j);
   const int L = ea.L;
-  if (j->fixed) {  // one launch: planes `layer` and L + `layer` in slices; nothing to zero (k_fixed.h, FixedEncArgs)
-    if (layer == 0 && b->used) HIP_TRY(hipStreamWaitEvent(s, b->free_ev, 0));
-    FixedEncArgs fa;
-    memset(&fa, 0, sizeof fa);
-    fa.src = to_addr(&j->src);
-    fa.e = ea;
-    fa.e.dtype = j->src.dtype;
-    fa.e.sizes = layer == 0 ? j->sizes : nullptr;  // 0 = "this chunk's encode did not finish" until k_fixed_layers_finish
-    fa.e.plane0 = layer; fa.e.plane_step = L; fa.e.nplanes = 2;
-    fa.part = b->part; fa.slice_passes = j->slice_passes;
-    const bool nhdb = j->src.paged_kind == LMC_PAGED_SPLIT;
-    const int rc = j->src.dtype == LMC_DTYPE_BF16 ? launch_fixed_encode<LMC_DTYPE_BF16, true>(fa, s, nhdb, j->slices)
-                                                  : launch_fixed_encode<LMC_DTYPE_FP16, true>(fa, s, nhdb, j->slices);
-    j->queued = true; j->last_stream = s;
-    if (rc) return rc;
-    j->next_layer = layer + 1;
-    return LMC_OK;
-  }
   if (layer == 0) {
-    // the job's first launch: behind the buffers' previous job; granules and tickets start from zero ONCE -- the later
-    // layers' look-backs read the prefixes this and every earlier layer leave
-    if (b->used) HIP_TRY(hipStreamWaitEvent(s, b->free_ev, 0));
-    HIP_TRY(hipMemsetAsync(b->agg, 0, (size_t)j->nchunks * 2 * L * j->chain_gran * 8, s));
+    // the job's first launch: granules and tickets start from zero ONCE -- the later layers' look-backs read the prefixes
+    // this and every earlier layer leave
+    HIP_TRY(hipMemsetAsync(b->agg.p, 0, (size_t)j->nchunks * 2 * L * j->chain_gran * 8, s));
     HIP_TRY(hipMemsetAsync(b->ticket, 0, 64, s));
     j->tickets_drawn = 0;
-    j->queued = true; j->last_stream = s;
   }
   ea.plane0 = layer; ea.plane_step = L; ea.nplanes = 2;
   lmc_blob_header hl;
@@ -1047,12 +1058,11 @@ int lmc_encode_layer(lmc_ctx* c, lmc_layer_job* j, int32_t layer, lmc_stream_t s
   qa.src = to_addr(&j->src); qa.bins = j->bins;
   qa.tok_begin = j->tok_begin; qa.tok_end = j->tok_end; qa.chunk_tokens = j->chunk_tokens; qa.nchunks = j->nchunks;
   qa.P = ea.P; qa.C = ea.C; qa.TQ = ea.TQ; qa.pc_limit = j->nchunks * ea.P; qa.sym_stride = ea.sym_stride;
-  qa.sym4 = b->sym4;
+  qa.sym4 = b->sym4.p;
   qa.scale_base = j->blobs + hl.off_scales; qa.scale_stride = (long long)j->blob_stride;
   qa.sizes = layer == 0 ? j->sizes : nullptr;  // 0 = "this chunk's encode did not finish" until k_layers_finish
   qa.plane0 = layer; qa.plane_step = L; qa.nplanes = 2;
-  int rc = launch_quant<true>(qa, s, j->src.paged_kind == LMC_PAGED_SPLIT);
-  j->queued = true; j->last_stream = s;
+  const int rc = launch_quant<true>(qa, s, j->src.paged_kind == LMC_PAGED_SPLIT);
   if (rc) return rc;
   const long long ngroups = (long long)j->nchunks * 2 * ea.G;
   const unsigned nwg = (unsigned)((ngroups + 7) / 8);
@@ -1060,8 +1070,40 @@ int lmc_encode_layer(lmc_ctx* c, lmc_layer_job* j, int32_t layer, lmc_stream_t s
   hipLaunchKernelGGL((k_cdf_encode<true, true, 8, true>), dim3(nwg), dim3(64 * 8), 0, s, ea);
   HIP_TRY(hipGetLastError());
   j->tickets_drawn += nwg;
+  return LMC_OK;
+}
+
+int lmc_encode_layer(lmc_ctx* c, lmc_layer_job* j, int32_t layer, lmc_stream_t stream) {
+  if (!c) return LMC_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!layer_job_ok(c, j) || layer != j->next_layer || layer >= j->src.num_layers) return LMC_ERR_INVALID;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (layer == 0 && j->b->used) HIP_TRY(hipStreamWaitEvent(s, j->b->free_ev, 0));  // behind the buffers' previous job
+  const int rc = j->fixed ? encode_layer_fixed(j, layer, s) : encode_layer_coded(j, layer, s);
+  j->queued = true; j->last_stream = s;  // (a failed launch too: what went out before it is on that stream)
+  if (rc) return rc;
   j->next_layer = layer + 1;
   return LMC_OK;
+}
+
+// The job's last launch, per model: the headers, sizes and -- coded -- the move of the V streams behind the K streams.
+static void layers_finish_fixed(const lmc_layer_job* j, hipStream_t s) {
+  FixedFinishArgs ff;
+  memset(&ff, 0, sizeof ff);
+  ff.e = layer_encode_args(j);
+  ff.e.dtype = j->src.dtype;
+  ff.part = j->b->part.p; ff.nslices = j->slices;
+  hipLaunchKernelGGL(k_fixed_layers_finish, dim3((unsigned)j->nchunks), dim3(FIXED_FIN_THREADS), 0, s, ff);
+}
+static void layers_finish_coded(const lmc_layer_job* j, hipStream_t s) {
+  LayersFinishArgs fa;
+  memset(&fa, 0, sizeof fa);
+  fa.e = layer_encode_args(j);
+  fa.kv_dtype = lmc_dtype_fp8(j->src.dtype) ? (u32)j->src.dtype : 0u;
+  // the move of a chunk's V streams in pieces of 16 KiB per pass of a workgroup
+  const unsigned nx = (unsigned)std::min<long long>(64, std::max<long long>(1, j->vstride / (16 * 256 * 4)));
+  hipLaunchKernelGGL(k_layers_finish, dim3(nx, (unsigned)j->nchunks), dim3(256), 0, s, fa);
 }
 
 int lmc_encode_layers_finish(lmc_ctx* c, lmc_layer_job* j, lmc_stream_t stream) {
@@ -1070,28 +1112,9 @@ int lmc_encode_layers_finish(lmc_ctx* c, lmc_layer_job* j, lmc_stream_t stream) 
   if (!layer_job_ok(c, j) || j->next_layer != j->src.num_layers) return LMC_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
-  if (j->fixed) {
-    FixedFinishArgs ff;
-    memset(&ff, 0, sizeof ff);
-    ff.e = layer_encode_args(j);
-    ff.e.dtype = j->src.dtype;
-    ff.part = j->b->part; ff.nslices = j->slices;
-    hipLaunchKernelGGL(k_fixed_layers_finish, dim3((unsigned)j->nchunks), dim3(FIXED_FIN_THREADS), 0, s, ff);
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) { g_last_hip = (int)le; return LMC_ERR_HIP; }
-    j->queued = true; j->last_stream = s;
-    layer_job_release(j);
-    return LMC_OK;
-  }
-  LayersFinishArgs fa;
-  memset(&fa, 0, sizeof fa);
-  fa.e = layer_encode_args(j);
-  fa.kv_dtype = lmc_dtype_fp8(j->src.dtype) ? (u32)j->src.dtype : 0u;
-  // the move of a chunk's V streams in pieces of 16 KiB per pass of a workgroup
-  const unsigned nx = (unsigned)std::min<long long>(64, std::max<long long>(1, j->vstride / (16 * 256 * 4)));
-  hipLaunchKernelGGL(k_layers_finish, dim3(nx, (unsigned)j->nchunks), dim3(256), 0, s, fa);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) { g_last_hip = (int)le; return LMC_ERR_HIP; }
+  if (j->fixed) layers_finish_fixed(j, s);
+  else layers_finish_coded(j, s);
+  HIP_TRY(hipGetLastError());  // (the job stays live: the caller aborts it)
   j->queued = true; j->last_stream = s;
   layer_job_release(j);
   return LMC_OK;
@@ -1137,13 +1160,13 @@ static bool decode_blobs(DecodeArgs& a, const void* blobs, uint64_t stride, cons
   return true;
 }
 
-// k_decode for a destination dtype: the destination's dtype decides what a blob decodes to (any blob, any of the four)
-static void launch_decode(int dtype, int kind, dim3 grid, hipStream_t s, const DecodeArgs& a) {
-  with_kv_dtype(dtype, [&](auto dt) {
-    constexpr int DT = decltype(dt)::value;
-    if (kind == DEC_PAGED_SPLIT) hipLaunchKernelGGL((k_decode<DEC_SINK_KV, DT, DEC_PAGED_SPLIT>), grid, dim3(64 * DEC_WAVES), 0, s, a);
-    else if (kind == DEC_PAGED_ROWS) hipLaunchKernelGGL((k_decode<DEC_SINK_KV, DT, DEC_PAGED_ROWS>), grid, dim3(64 * DEC_WAVES), 0, s, a);
-    else hipLaunchKernelGGL((k_decode<DEC_SINK_KV, DT, DEC_ROWS>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+// k_decode for a destination: its dtype decides what a blob decodes to (any blob, any of the four), its kind how the
+// tokens are found
+static void launch_decode(const lmc_kv_layout* dst, dim3 grid, hipStream_t s, const DecodeArgs& a) {
+  with_kv_dtype(dst->dtype, [&](auto dt) {
+    with_decode_kind(dst, [&](auto kind) {
+      hipLaunchKernelGGL((k_decode<DEC_SINK_KV, decltype(dt)::value, decltype(kind)::value>), grid, dim3(64 * DEC_WAVES), 0, s, a);
+    });
   });
 }
 
@@ -1156,19 +1179,13 @@ static void launch_fixed_decode(const lmc_kv_layout* dst, long long nstreams, hi
   FixedDecArgs fa;
   fa.d = a;
   fa.vec = layout_ok(dst) ? 1 : 0;  // rows that take 16-byte vectors of 8 channels: what the encoders ask of a source
+  if (dst->paged_kind == LMC_PAGED_SPLIT) fa.vec = 0;  // (the kernel looks at the plane's own alignment: k_fixed.h)
   const dim3 grid((unsigned)((nstreams + FIXED_DEC_WAVES - 1) / FIXED_DEC_WAVES)), block(64 * FIXED_DEC_WAVES);
-  const bool paged = dst->slot_mapping != nullptr;
-  if (dst->paged_kind == LMC_PAGED_SPLIT) {
-    fa.vec = 0;  // (the kernel looks at the plane's own alignment: k_fixed.h)
-    if (dst->dtype == LMC_DTYPE_BF16) hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_BF16, DEC_PAGED_SPLIT>), grid, block, 0, s, fa);
-    else hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_FP16, DEC_PAGED_SPLIT>), grid, block, 0, s, fa);
-  } else if (dst->dtype == LMC_DTYPE_BF16) {
-    if (paged) hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_BF16, DEC_PAGED_ROWS>), grid, block, 0, s, fa);
-    else hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_BF16, DEC_ROWS>), grid, block, 0, s, fa);
-  } else {
-    if (paged) hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_FP16, DEC_PAGED_ROWS>), grid, block, 0, s, fa);
-    else hipLaunchKernelGGL((k_fixed_decode<LMC_DTYPE_FP16, DEC_ROWS>), grid, block, 0, s, fa);
-  }
+  with_kv_dtype16(dst->dtype, [&](auto dt) {
+    with_decode_kind(dst, [&](auto kind) {
+      hipLaunchKernelGGL((k_fixed_decode<decltype(dt)::value, decltype(kind)::value>), grid, block, 0, s, fa);
+    });
+  });
 }
 
 static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev,
@@ -1176,9 +1193,8 @@ static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, 
   a.layer_begin = l0; a.layer_count = nl;
   const long long n = (long long)a.nchunks * 2 * nl * a.G;
   const dim3 grid((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES));
-  const int kind = dst->paged_kind == LMC_PAGED_SPLIT ? DEC_PAGED_SPLIT : dst->slot_mapping ? DEC_PAGED_ROWS : DEC_ROWS;
   if (fixed) launch_fixed_decode(dst, n, s, a);
-  else launch_decode(dst->dtype, kind, grid, s, a);
+  else launch_decode(dst, grid, s, a);
   HIP_TRY(hipGetLastError());
   if (post) {  // (none of its launches needs the lock)
     const int rc = range_post(c, dst, post, l0, nl, s);
@@ -1308,15 +1324,8 @@ int lmc_decode_symbols(lmc_ctx* c, const void* blob, int32_t L, int32_t H, int32
 int lmc_transcode_to_fixed(lmc_ctx* c, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks, int32_t L, int32_t H,
                            int32_t D, int32_t dtype, int32_t chunk_tokens, uint32_t ntokens, const int32_t* bins_h,
                            void* const* out_ptrs, const uint32_t* out_bytes, uint32_t* job_status, lmc_stream_t stream) {
-  if (!c || !blob_ptrs || !blob_bytes || !out_ptrs || !out_bytes || nchunks < 1 || nchunks > 65535 || L < 1 ||
-      2 * L > LMC_MAX_PLANES || H < 1 || D < 1 || chunk_tokens < 1 || chunk_tokens > 65535 ||
-      (dtype != LMC_DTYPE_BF16 && dtype != LMC_DTYPE_FP16))
-    return LMC_ERR_INVALID;
-  const long long C = (long long)H * D;
-  if (C < 8 || (C & 7) || C > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
-  // every chunk is chunk_tokens long but, possibly, the last (lmc_pack_blobs's rule); token indices are 32-bit and signed
-  if ((uint64_t)ntokens > (uint64_t)nchunks * (uint32_t)chunk_tokens || (uint64_t)ntokens <= (uint64_t)(nchunks - 1) * (uint32_t)chunk_tokens ||
-      ntokens > 0x7fffffffu)
+  if (!c || !blob_ptrs || !blob_bytes || !out_ptrs || !out_bytes || !chunk_geometry_ok(nchunks, L, H, D, chunk_tokens, ntokens) ||
+      ntokens > 0x7fffffffu || (dtype != LMC_DTYPE_BF16 && dtype != LMC_DTYPE_FP16))
     return LMC_ERR_INVALID;
   DecodeArgs a;
   if (decode_geometry(c, nchunks, L, H, D, job_status, a)) return LMC_ERR_INVALID;  // (2^31 streams or more)
@@ -1342,14 +1351,6 @@ int lmc_transcode_to_fixed(lmc_ctx* c, const void* const* blob_ptrs, const uint3
 }  // extern "C"
 
 // One side of lmc_copy_kv is LMC_PAGED_SPLIT (k_copy_split.h): a wave per (plane, head, tile of TT tokens).
-template <typename E, bool GATHER>
-static void launch_copy_split(const SplitCopyArgs& a, int tt, unsigned blocks, size_t lds, hipStream_t s) {
-  const dim3 g(blocks), b(64 * SPLIT_WAVES);
-  if (tt == 32) hipLaunchKernelGGL((k_copy_split<E, GATHER, 32>), g, b, lds, s, a);
-  else if (tt == 16) hipLaunchKernelGGL((k_copy_split<E, GATHER, 16>), g, b, lds, s, a);
-  else hipLaunchKernelGGL((k_copy_split<E, GATHER, 8>), g, b, lds, s, a);
-}
-
 static int copy_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst,
                       int32_t dst_tok0, hipStream_t stream) {
   const bool gather = src->paged_kind == LMC_PAGED_SPLIT;
@@ -1375,11 +1376,14 @@ static int copy_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, i
   long long blocks = (items + SPLIT_WAVES - 1) / SPLIT_WAVES;
   if (blocks > 8LL * c->num_cus) blocks = 8LL * c->num_cus;  // grid-stride beyond eight workgroups per CU
   const size_t lds = a.fast ? SPLIT_WAVES * image : 0;
-  if (b8) {
-    if (gather) launch_copy_split<u8, true>(a, tt, (unsigned)blocks, lds, stream);
-    else launch_copy_split<u8, false>(a, tt, (unsigned)blocks, lds, stream);
-  } else if (gather) launch_copy_split<u16, true>(a, tt, (unsigned)blocks, lds, stream);
-  else launch_copy_split<u16, false>(a, tt, (unsigned)blocks, lds, stream);
+  with_bool(b8, [&](auto e8) {
+    with_bool(gather, [&](auto g) {
+      with_int<32, 16, 8>(tt, [&](auto t) {
+        using E = std::conditional_t<decltype(e8)::value, u8, u16>;
+        hipLaunchKernelGGL((k_copy_split<E, decltype(g)::value, decltype(t)::value>), dim3((unsigned)blocks), dim3(64 * SPLIT_WAVES), lds, stream, a);
+      });
+    });
+  });
   HIP_TRY(hipGetLastError());
   return LMC_OK;
 }
@@ -1420,11 +1424,12 @@ static bool rope_ok(const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, co
 // Re-rotate the keys of tokens [tok_begin, +ntok) by a position difference, in place (k_rope.h).  The access form is
 // chosen as lmc_copy_kv chooses `vec`: 16-byte vectors where the rows, the head and the pair halves are whole vectors
 // (and the table's rows are), one pair per thread for everything else.
-template <int DT>
-static void launch_rope(bool vec, bool neox, dim3 grid, size_t lds, hipStream_t s, const RopeArgs& a) {
-  if (!vec) hipLaunchKernelGGL((k_rope_elem<DT>), grid, dim3(256), 0, s, a);
-  else if (neox) hipLaunchKernelGGL((k_rope_vec<DT, true>), grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((k_rope_vec<DT, false>), grid, dim3(256), lds, s, a);
+static void launch_rope(int dtype, bool vec, bool neox, dim3 grid, size_t lds, hipStream_t s, const RopeArgs& a) {
+  with_kv_dtype16(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (!vec) hipLaunchKernelGGL((k_rope_elem<DT>), grid, dim3(256), 0, s, a);
+    else with_bool(neox, [&](auto nx) { hipLaunchKernelGGL((k_rope_vec<DT, decltype(nx)::value>), grid, dim3(256), lds, s, a); });
+  });
 }
 
 // lmc_rope_shift behind its checks (rope_ok).
@@ -1447,8 +1452,7 @@ static int rope_launch(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, i
   if (blocks > cap) blocks = cap;
   const dim3 grid((unsigned)blocks, (unsigned)kv->num_layers);
   const size_t lds = vec && !r.deltas ? (size_t)rot_dim * sizeof(float) : 0;  // the one table row of a uniform delta
-  if (kv->dtype == LMC_DTYPE_BF16) launch_rope<LMC_DTYPE_BF16>(vec, neox, grid, lds, stream, a);
-  else launch_rope<LMC_DTYPE_FP16>(vec, neox, grid, lds, stream, a);
+  launch_rope(kv->dtype, vec, neox, grid, lds, stream, a);
   HIP_TRY(hipGetLastError());
   return LMC_OK;
 }
@@ -1607,12 +1611,38 @@ static int store_acquire(lmc_ctx* c, hipStream_t s, size_t arena_bytes, size_t t
   int rc;
   std::lock_guard<std::mutex> lk(c->mu);
   if ((rc = legs_init(c))) return rc;
-  if (c->store_bytes < arena_bytes || c->pack_table_bytes < table_bytes) {
+  if (c->store_arena.bytes < arena_bytes || c->pack_table.bytes < table_bytes) {
     if (c->store_used) HIP_TRY(hipEventSynchronize(c->store_free));  // growing frees the buffers: this call only
-    if ((rc = ws_grow((void**)&c->store_arena, &c->store_bytes, arena_bytes))) return rc;
-    if ((rc = ws_grow((void**)&c->pack_table, &c->pack_table_bytes, table_bytes))) return rc;
+    if ((rc = c->store_arena.grow(arena_bytes)) || (rc = c->pack_table.grow(table_bytes))) return rc;
   }
   if (c->store_used) HIP_TRY(hipStreamWaitEvent(s, c->store_free, 0));  // the previous job's copies have read the arena
+  return LMC_OK;
+}
+// caller holds c->mu: the next job may take the arena and the table behind what `last` has queued so far
+static int store_release(lmc_ctx* c, hipStream_t last) {
+  HIP_TRY(hipEventRecord(c->store_free, last));
+  c->store_used = true;
+  return LMC_OK;
+}
+// The load side, caller holds c->mu.  The load staging (c->load_slots) of at least `bytes` for a job that copies into it
+// on `queues` (1 or 2) copy queues -> cs[]: the host waits for the previous load only when the staging must grow, the
+// queues always do, before their first copy (its decodes have read the staging).
+static int load_acquire(lmc_ctx* c, size_t bytes, int queues, hipStream_t cs[2]) {
+  int rc;
+  if ((rc = legs_init(c))) return rc;
+  if (queues > 1 && !c->copy_stream2) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking));
+  if (c->load_slots.bytes < bytes) {
+    if (c->load_used) HIP_TRY(hipEventSynchronize(c->load_free));
+    if ((rc = c->load_slots.grow(bytes))) return rc;
+  }
+  cs[0] = c->copy_stream; cs[1] = c->copy_stream2;
+  for (int q = 0; q < queues && c->load_used; q++) HIP_TRY(hipStreamWaitEvent(cs[q], c->load_free, 0));
+  return LMC_OK;
+}
+// ... and behind the job's last reader of the staging, on `s`
+static int load_release(lmc_ctx* c, hipStream_t s) {
+  HIP_TRY(hipEventRecord(c->load_free, s));
+  c->load_used = true;
   return LMC_OK;
 }
 
@@ -1634,22 +1664,21 @@ int lmc_store_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, in
   for (int c0 = 0; c0 < nchunks; c0 += per) {
     const int c1 = c0 + per < nchunks ? c0 + per : nchunks;
     const int t1 = tok_begin + c1 * chunk_tokens < tok_end ? tok_begin + c1 * chunk_tokens : tok_end;
-    if ((rc = encode_chunks_parts(c, src, tok_begin + c0 * chunk_tokens, t1, chunk_tokens, bins_h, c->store_arena + (size_t)c0 * stride,
+    if ((rc = encode_chunks_parts(c, src, tok_begin + c0 * chunk_tokens, t1, chunk_tokens, bins_h, c->store_arena.p + (size_t)c0 * stride,
                                   stride, sizes_h + c0, job_status, stream, 1, nullptr, true)))
       return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = stream_follows(c, c->copy_stream, s))) return rc;
     OffloadArgs oa;
     memset(&oa, 0, sizeof oa);
-    oa.blobs = c->store_arena; oa.stride = (long long)stride; oa.sizes_d = sizes_h; oa.nchunks = nchunks; oa.chunk0 = c0;
+    oa.blobs = c->store_arena.p; oa.stride = (long long)stride; oa.sizes_d = sizes_h; oa.nchunks = nchunks; oa.chunk0 = c0;
     oa.host = (u8*)host_arena_h; oa.cap = host_cap; oa.offsets_h = (unsigned long long*)offsets_h; oa.sizes_h = sizes_h;
     oa.status = st;
     hipLaunchKernelGGL(k_offload, dim3(8, (unsigned)(c1 - c0)), dim3(256), 0, c->copy_stream, oa);
     HIP_TRY(hipGetLastError());
   }
   std::lock_guard<std::mutex> lk(c->mu);
-  HIP_TRY(hipEventRecord(c->store_free, c->copy_stream));
-  c->store_used = true;
+  if ((rc = store_release(c, c->copy_stream))) return rc;
   HIP_TRY(hipStreamWaitEvent(s, c->store_free, 0));  // the caller's stream is done when the blobs have landed
   return LMC_OK;
 }
@@ -1677,17 +1706,8 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
   hipStream_t s = (hipStream_t)stream;
   const int step = layers_per_range > 0 && layers_per_range < L ? layers_per_range : L;
   std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = legs_init(c))) return rc;
-  if (!c->copy_stream2) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking));
-  if (c->load_bytes < (size_t)nchunks * stride) {
-    if (c->load_used) HIP_TRY(hipEventSynchronize(c->load_free));
-    if ((rc = ws_grow((void**)&c->load_slots, &c->load_bytes, (size_t)nchunks * stride))) return rc;
-  }
-  hipStream_t cs[2] = {c->copy_stream, c->copy_stream2};  // two DMA queues (tools/probes/d2h_streams.py)
-  if (c->load_used) {  // the previous load's decodes have read the slots
-    HIP_TRY(hipStreamWaitEvent(cs[0], c->load_free, 0));
-    HIP_TRY(hipStreamWaitEvent(cs[1], c->load_free, 0));
-  }
+  hipStream_t cs[2];  // two DMA queues (tools/probes/d2h_streams.py)
+  if ((rc = load_acquire(c, (size_t)nchunks * stride, 2, cs))) return rc;
   // The blobs lie in pinned HOST memory: their headers are checked right here, by the CPU (a blob that does not check
   // out fails the call before anything is queued), and every blob travels as ONE hipMemcpyAsync, alternating between
   // two DMA queues.  Layer-range-major copies (the K run and the V run of every chunk, per range) were built first and
@@ -1703,19 +1723,17 @@ int lmc_load_chunks(lmc_ctx* c, const void* const* host_blob_ptrs_h, const uint3
       return LMC_ERR_INVALID;
   }
   for (int i = 0; i < nchunks; i++)
-    HIP_TRY(hipMemcpyAsync(c->load_slots + (size_t)i * stride, host_blob_ptrs_h[i], (sizes_h[i] + 15u) & ~15u,
+    HIP_TRY(hipMemcpyAsync(c->load_slots.p + (size_t)i * stride, host_blob_ptrs_h[i], (sizes_h[i] + 15u) & ~15u,
                            hipMemcpyHostToDevice, cs[i & 1]));
   for (int q = 0; q < 2; q++)  // the decodes wait for both queues
     if ((rc = stream_follows(c, s, cs[q]))) return rc;
-  da.blobs = c->load_slots; da.blob_stride = (long long)stride;
+  da.blobs = c->load_slots.p; da.blob_stride = (long long)stride;
   int r = 0;
   for (int l0 = 0; l0 < L; l0 += step, r++) {
     const int n = l0 + step <= L ? step : L - l0;
     if ((rc = decode_range_locked(da, dst, l0, n, s, range_events ? range_events[r] : nullptr))) return rc;
   }
-  HIP_TRY(hipEventRecord(c->load_free, s));
-  c->load_used = true;
-  return LMC_OK;
+  return load_release(c, s);
 }
 
 // ---- packs (lmc_format.h): the layer-major form of the pinned host tier ---------------------------------------------
@@ -1743,24 +1761,27 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
   int rc;
   const size_t table_bytes = 8 * ((size_t)P * nchunks + 2);  // the table, and the running total of the parts
   if ((rc = store_acquire(c, s, (size_t)nchunks * stride, table_bytes))) return rc;
-  pa.blobs = c->store_arena; pa.stride = (long long)stride; pa.sizes_d = sizes_h;
+  pa.blobs = c->store_arena.p; pa.stride = (long long)stride; pa.sizes_d = sizes_h;
   pa.n = nchunks; pa.L = L; pa.G = (int)pa.hdr.ngroups;
-  pa.host = (u8*)pack_h; pa.cap = pack_cap; pa.table_d = c->pack_table;
+  pa.host = (u8*)pack_h; pa.cap = pack_cap; pa.table_d = c->pack_table.p;
   pa.status = job_status ? job_status : c->status_h;
+  const auto pack_range = [](const PackArgs& q, hipStream_t on) -> int {  // planes [q.p_begin, q.p_end) of the arena's blobs
+    hipLaunchKernelGGL(k_pack_scan<false>, dim3(1), dim3(256), 0, on, q);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_pack_copy<false>, dim3(64), dim3(256), 0, on, q);  // PCIe-bound: 64 workgroups fill the link
+    HIP_TRY(hipGetLastError());
+    return LMC_OK;
+  };
   if (nparts == 0) {
     // the whole job is encoded (1 ms per 16 k tokens) before the first byte leaves: the pack kernels on the copy stream
-    if ((rc = encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, c->store_arena, stride, sizes_h, job_status, stream,
+    if ((rc = encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, c->store_arena.p, stride, sizes_h, job_status, stream,
                                   1, nullptr, true)))
       return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = stream_follows(c, c->copy_stream, s))) return rc;
     pa.p_begin = 0; pa.p_end = P; pa.last = 1; pa.part_h = nullptr;
-    hipLaunchKernelGGL(k_pack_scan<false>, dim3(1), dim3(256), 0, c->copy_stream, pa);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_pack_copy<false>, dim3(64), dim3(256), 0, c->copy_stream, pa);  // PCIe-bound: 64 workgroups fill the link
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->store_free, c->copy_stream));
-    c->store_used = true;
+    if ((rc = pack_range(pa, c->copy_stream))) return rc;
+    if ((rc = store_release(c, c->copy_stream))) return rc;
     HIP_TRY(hipStreamWaitEvent(s, c->store_free, 0));  // the caller's stream is done when the pack has landed
     return LMC_OK;
   }
@@ -1776,25 +1797,21 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
       PackArgs q = pa;
       q.p_begin = packed; q.p_end = upto; q.last = last ? 1 : 0;
       q.part_h = (unsigned long long*)(part_info_h + 2 * parts_out);
-      hipLaunchKernelGGL(k_pack_scan<false>, dim3(1), dim3(256), 0, s, q);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_pack_copy<false>, dim3(64), dim3(256), 0, s, q);
-      HIP_TRY(hipGetLastError());
+      const int prc = pack_range(q, s);
+      if (prc) return prc;
       packed = upto;
     }
     if (part_events && part_events[parts_out]) HIP_TRY(hipEventRecord((hipEvent_t)part_events[parts_out], s));
     parts_out++;
     return LMC_OK;
   };
-  if ((rc = encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, c->store_arena, stride, sizes_h, job_status,
+  if ((rc = encode_chunks_parts(c, src, tok_begin, tok_end, chunk_tokens, bins_h, c->store_arena.p, stride, sizes_h, job_status,
                                 stream, nparts, &after, true)))
     return rc;
   std::lock_guard<std::mutex> lk(c->mu);
   for (; parts_out < nparts; parts_out++)  // a job that could not be split: the unused parts' events fire behind the only one
     if (part_events && part_events[parts_out]) HIP_TRY(hipEventRecord((hipEvent_t)part_events[parts_out], s));
-  HIP_TRY(hipEventRecord(c->store_free, s));
-  c->store_used = true;
-  return LMC_OK;
+  return store_release(c, s);
 }
 
 int lmc_store_pack(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
@@ -1894,15 +1911,11 @@ int lmc_load_pack_post(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int3
   hipStream_t s = (hipStream_t)stream;
   const int step = layers_per_range > 0 && layers_per_range < L ? layers_per_range : L;
   std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = legs_init(c))) return rc;
-  if (c->load_bytes < h.total_bytes) {
-    if (c->load_used) HIP_TRY(hipEventSynchronize(c->load_free));
-    if ((rc = ws_grow((void**)&c->load_slots, &c->load_bytes, (size_t)h.total_bytes))) return rc;
-  }
-  hipStream_t cs = c->copy_stream;  // ONE queue: the ranges must arrive in layer order
-  if (c->load_used) HIP_TRY(hipStreamWaitEvent(cs, c->load_free, 0));  // the previous load's decodes have read the buffer
+  hipStream_t queues[2];
+  if ((rc = load_acquire(c, (size_t)h.total_bytes, 1, queues))) return rc;
+  hipStream_t cs = queues[0];  // ONE queue: the ranges must arrive in layer order
   // the device copy keeps the pack's offsets: table, static slots and segments land where they lie in the pack
-  u8* dev = c->load_slots;
+  u8* dev = c->load_slots.p;
   HIP_TRY(hipMemcpyAsync(dev + h.off_table, b + h.off_table, 8 * (2 * (size_t)L * n + 1), hipMemcpyHostToDevice, cs));
   HIP_TRY(hipMemcpyAsync(dev + h.off_static + (size_t)c0 * h.static_stride, b + h.off_static + (size_t)c0 * h.static_stride,
                          (size_t)m * h.static_stride, hipMemcpyHostToDevice, cs));
@@ -1929,9 +1942,7 @@ int lmc_load_pack_post(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int3
     if ((rc = stream_follows(c, s, cs))) return rc;
     if ((rc = decode_range_locked(da, dst, l0, nl, s, range_events ? range_events[r] : nullptr, c, post))) return rc;
   }
-  HIP_TRY(hipEventRecord(c->load_free, s));
-  c->load_used = true;
-  return LMC_OK;
+  return load_release(c, s);
 }
 
 int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
@@ -1945,15 +1956,11 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
 int lmc_pack_blobs(lmc_ctx* c, const void* const* blob_ptrs, const uint32_t* blob_bytes, int32_t nchunks, int32_t L, int32_t H,
                    int32_t D, int32_t chunk_tokens, uint32_t ntokens, void* pack_d, uint64_t pack_cap, uint32_t* job_status,
                    lmc_stream_t stream) {
-  if (!c || !blob_ptrs || !blob_bytes || nchunks < 1 || nchunks > 65535 || L < 1 || 2 * L > LMC_MAX_PLANES || H < 1 || D < 1 ||
-      chunk_tokens < 1 || chunk_tokens > 65535 || !pack_d || ((uintptr_t)pack_d & 15))
+  // (P * nchunks: lmc_store_pack's bound on a pack's table)
+  if (!c || !blob_ptrs || !blob_bytes || !pack_d || ((uintptr_t)pack_d & 15) || !chunk_geometry_ok(nchunks, L, H, D, chunk_tokens, ntokens) ||
+      2ll * L * nchunks > (1ll << 22))
     return LMC_ERR_INVALID;
-  const long long C = (long long)H * D;
   const int P = 2 * L;
-  if (C < 8 || (C & 7) || C > LMC_MAX_CHANNELS || (long long)P * nchunks > (1ll << 22)) return LMC_ERR_INVALID;
-  // every chunk is chunk_tokens long but, possibly, the last
-  if ((uint64_t)ntokens > (uint64_t)nchunks * (uint32_t)chunk_tokens || (uint64_t)ntokens <= (uint64_t)(nchunks - 1) * (uint32_t)chunk_tokens)
-    return LMC_ERR_INVALID;
   PackArgs pa;
   memset(&pa, 0, sizeof pa);
   lmc_pack_layout((uint32_t)nchunks, (uint32_t)L, (uint32_t)chunk_tokens, (uint32_t)H, (uint32_t)D, &pa.hdr);
@@ -1967,7 +1974,7 @@ int lmc_pack_blobs(lmc_ctx* c, const void* const* blob_ptrs, const uint32_t* blo
   if ((rc = store_acquire(c, s, 0, 8 * ((size_t)P * nchunks + 2)))) return rc;
   pa.blob_ptrs = (const u8* const*)blob_ptrs; pa.blob_bytes = blob_bytes;
   pa.n = nchunks; pa.L = L; pa.G = (int)pa.hdr.ngroups;
-  pa.host = (u8*)pack_d; pa.cap = pack_cap; pa.table_d = c->pack_table;
+  pa.host = (u8*)pack_d; pa.cap = pack_cap; pa.table_d = c->pack_table.p;
   pa.status = job_status ? job_status : c->status_h;
   pa.p_begin = 0; pa.p_end = P; pa.last = 1; pa.part_h = nullptr;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -1980,9 +1987,7 @@ int lmc_pack_blobs(lmc_ctx* c, const void* const* blob_ptrs, const uint32_t* blo
   hipLaunchKernelGGL(k_pack_copy<true>, dim3((unsigned)std::max(1, std::min(items, c->num_cus))), dim3(256), 0, s, pa);
   HIP_TRY(hipGetLastError());
   if ((rc = prof_mark(c, s))) return rc;
-  HIP_TRY(hipEventRecord(c->store_free, s));  // the next job may rewrite the table behind this
-  c->store_used = true;
-  return LMC_OK;
+  return store_release(c, s);  // the next job may rewrite the table behind this
 }
 
 int lmc_pack_chunk_bytes(const void* pack_h, uint64_t nbytes, int32_t chunk, uint32_t* size_out) {
@@ -2017,22 +2022,13 @@ int lmc_unpack_blobs(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_
   hipStream_t s = (hipStream_t)stream;
   int rc;
   std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = legs_init(c))) return rc;
-  if (!c->copy_stream2) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking));
   // the load staging holds the pack at its own offsets (as for lmc_load_pack), and behind it the destinations' addresses
   // and their room
   const size_t meta_off = (size_t)lmc_r16_64(h.total_bytes), caps_off = meta_off + (size_t)lmc_r16_64(8 * (uint64_t)m);
   const size_t need = caps_off + (size_t)lmc_r16_64(4 * (uint64_t)m);
-  if (c->load_bytes < need) {
-    if (c->load_used) HIP_TRY(hipEventSynchronize(c->load_free));
-    if ((rc = ws_grow((void**)&c->load_slots, &c->load_bytes, need))) return rc;
-  }
-  hipStream_t cs[2] = {c->copy_stream, c->copy_stream2};  // the order of arrival does not matter here: two DMA queues
-  if (c->load_used) {  // the previous load's kernels have read the buffer
-    HIP_TRY(hipStreamWaitEvent(cs[0], c->load_free, 0));
-    HIP_TRY(hipStreamWaitEvent(cs[1], c->load_free, 0));
-  }
-  u8* dev = c->load_slots;
+  hipStream_t cs[2];  // the order of arrival does not matter here: two DMA queues
+  if ((rc = load_acquire(c, need, 2, cs))) return rc;
+  u8* dev = c->load_slots.p;
   // (the two arrays are the caller's pageable memory: hipMemcpyAsync has read them when it returns)
   HIP_TRY(hipMemcpyAsync(dev + meta_off, blob_ptrs_h, 8 * (size_t)m, hipMemcpyHostToDevice, cs[0]));
   HIP_TRY(hipMemcpyAsync(dev + caps_off, blob_caps_h, 4 * (size_t)m, hipMemcpyHostToDevice, cs[0]));
@@ -2064,9 +2060,7 @@ int lmc_unpack_blobs(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_
   hipLaunchKernelGGL(k_unpack, dim3((unsigned)std::max(1, std::min(items, c->num_cus))), dim3(256), 0, s, ua);
   HIP_TRY(hipGetLastError());
   if ((rc = prof_mark(c, s))) return rc;
-  HIP_TRY(hipEventRecord(c->load_free, s));
-  c->load_used = true;
-  return LMC_OK;
+  return load_release(c, s);
 }
 
 int lmc_blob_info(const void* blob_h, size_t nbytes, lmc_blob_header* out) {
