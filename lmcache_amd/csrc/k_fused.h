@@ -277,12 +277,42 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
   __shared__ __attribute__((aligned(16))) u32 rtab_lds[RTAB_LDS_DWORDS];  // reciprocals of the counts model's frequencies, bound table
   __shared__ u32 st_alloc[FUSED_MAX_NS];  // allocation of the item's group streams
   __shared__ u32 wg_excl;
+  __shared__ u32 wg_ticket;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+#ifdef LMC_EXP_TIMELINE
+  const unsigned long long tl_pre = wall_clock64();  // the workgroup's first instruction, in front of the ticket
+#endif
+  // ---- item start: the ticket, and under its round trip what does not depend on it ---------------------------------
   // consecutive work items are the same planes of consecutive chunks (see k_cdf_encode): an item's predecessors
   // in the look-back were taken at least nchunks workgroups earlier.  The item comes from a ticket, not from
   // blockIdx (EncodeArgs::ticket): a predecessor's workgroup has started, whatever order the hardware dispatches in.
-  const u32 tick = (u32)__builtin_amdgcn_readfirstlane((int)draw_ticket(a.ticket, a.ticket_base));
+  // The ticket is an agent-scope atomic: a round trip to L2, behind which draw_ticket (k_encode.h) has a barrier and
+  // nothing else of the workgroup in flight.  Here it is issued first; the histogram's zero fill and the copy of the
+  // constant tables (3 KB from L2: a second round trip) run while it is under way, and ONE barrier publishes the
+  // ticket and the zeroed counters (until then: draw_ticket's barrier, the copy's loads, the zero fill, a second
+  // barrier: bench ms_per_step 0.785 - 0.791 against 0.800 - 0.807, alternating runs on one box,
+  // profiles/fused_serial_part.md).
+  // GL == 32 keeps the old order: whether its items take the histogram in phase A depends on the item.
+  typedef __attribute__((address_space(3))) u32* lds_u32w;
+  constexpr bool EARLY = GL != 32;
+  u32 tick;
+  if constexpr (EARLY) {
+    u32 tk = 0;
+    if (threadIdx.x == 0) tk = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (HISTA) {
+      if ((u32)(size_t)(lds_u32w)lds_all != 0u) __builtin_trap();  // (static layout: plane_hist_row builds addresses from 0)
+      uint4* z = reinterpret_cast<uint4*>(lds_all);  // (every item of these instances takes its histogram in phase A)
+#pragma unroll
+      for (int i = 0; i < PLANE_HIST_DWORDS / 4 / (64 * NW); i++) z[i * 64 * NW + threadIdx.x] = make_uint4(0, 0, 0, 0);
+    }
+    rtab_to_lds(rtab_lds);  // (read by the coder waves: behind the barrier that ends phase A as well)
+    if (threadIdx.x == 0) wg_ticket = tk - a.ticket_base;
+    __syncthreads();  // the ticket; the counters are zero before any wave adds (every wave adds everywhere)
+    tick = (u32)__builtin_amdgcn_readfirstlane((int)wg_ticket);
+  } else {
+    tick = (u32)__builtin_amdgcn_readfirstlane((int)draw_ticket(a.ticket, a.ticket_base));
+  }
   const u32 item = fa.item_base + tick;
   LMC_TL(0);
 #ifdef LMC_EXP_TIMELINE
@@ -291,6 +321,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     g_fused_timeline[tick * 8u + 6u] = ((unsigned long long)xcc << 32) | hwid;
+    g_fused_timeline[tick * 8u + 7u] = tl_pre;
   }
 #endif
   const int chunk = (int)(item % (unsigned)a.nchunks), it = (int)(item / (unsigned)a.nchunks);
@@ -301,22 +332,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
   u32* const hist = lds_all + wave * CNT_TAB_DWORDS;  // this wave's table slice ...
   u16* const ring = reinterpret_cast<u16*>(lds_all + NW * CNT_TAB_DWORDS + wave * CNT_RING_DWORDS);  // ... and staging buffer
 
-  rtab_to_lds(rtab_lds);  // visible to the coder waves behind the barrier that ends phase A
+  if constexpr (!EARLY) rtab_to_lds(rtab_lds);  // visible to the coder waves behind the barrier that ends phase A
   // the item's planes take their histogram while they are quantised.  GL == 64: always; GL == 32: when the item's planes
   // fit the 128 virtual quantising lanes (wave-uniform; false only with an LMC_FUSED_PL override that packs more planes
   // into an item)
   const bool hist_a = HISTA || (HISTN && np * GL <= 128);
-  if constexpr (HISTA || HISTN) {
-    typedef __attribute__((address_space(3))) u32* lds_u32w;
+  if constexpr (!EARLY) {
     if ((u32)(size_t)(lds_u32w)lds_all != 0u) __builtin_trap();  // (static layout: plane_hist_row builds addresses from 0)
-    // (An unused read of the plane's bin count, left over from the time when byte planes could go without the histogram.
-    // The compiler drops it, but the GL == 64 instances come out scheduled differently without it -- 7 instructions in
-    // 50 000 -- and the change that retired that switch promised the same machine code.  It goes with the next change
-    // to this kernel that is timed on the GPU.)
-    if constexpr (HISTA) {
-      const int bins0 = (int)a.bins.b[p0];
-      (void)bins0;
-    }
     if (hist_a) {
       uint4* z = reinterpret_cast<uint4*>(lds_all);
 #pragma unroll

@@ -1,6 +1,6 @@
 // fused_timeline.hip -- phase time stamps of every work item of one k_encode_fused launch (a library built with
 // -DLMC_EXP_TIMELINE: tools/build_variants.sh tl "-DLMC_EXP_TIMELINE=1").  Writes gpurun_out/fused_timeline.bin:
-// [items][8] u64 = {start, phase A done, pass 1 done, look-back done, wave 0 coded, all coded, hw id, -} (100 MHz ticks).
+// [items][8] u64 = {start, phase A done, pass 1 done, look-back done, wave 0 coded, all coded, hw id, the workgroup's first instruction -- in front of the ticket} (100 MHz ticks).
 //   hipcc --offload-arch=gfx950 -O2 -o tools/probes/fused_timeline tools/probes/fused_timeline.hip -Iinclude -ldl
 //   tools/probes/fused_timeline build_alt/tl/liblmc_hip.so [ctx_tokens] [out.bin]
 #include <dlfcn.h>

@@ -11,14 +11,22 @@ t0 = ts[:, 0].min()
 us = (ts - t0) / 100.0  # 100 MHz ticks -> microseconds
 end = us[:, 5].max()
 print(f"{n} items; launch span {end:.1f} us (first start to last end)")
-names = ["wait+phase A", "pass 1", "look-back", "pass 2 (wave 0)", "pass 2 (rest)"]
+names = ["ticket", "start+phase A", "pass 1", "look-back", "pass 2 (wave 0)", "pass 2 (rest)"]
 dur = np.diff(us, axis=1)
+# column 7: the workgroup's first instruction, in front of the ticket (0 in a library built before the stamp existed)
+pre = t[:, 7].astype(np.int64)
+tick_us = np.where(pre > 0, (ts[:, 0] - pre) / 100.0, np.nan)
+dur = np.concatenate([tick_us[:, None], dur], axis=1)
 order = np.argsort(us[:, 0])
-print("\nphase durations (us) by start order (quartiles of the launch's items)")
+print("\nphase durations (us) by start order (eighths of the launch's items)")
 print("%-18s" % "items" + "".join("%18s" % nm for nm in names) + "%12s" % "total")
 for q in range(8):
     sel = order[q * n // 8:(q + 1) * n // 8]
-    print("%-18s" % f"{q * n // 8}..{(q + 1) * n // 8 - 1}" + "".join("%18.1f" % dur[sel, k].mean() for k in range(5)) + "%12.1f" % (us[sel, 5] - us[sel, 0]).mean())
+    print("%-18s" % f"{q * n // 8}..{(q + 1) * n // 8 - 1}" + "".join("%18.2f" % dur[sel, k].mean() for k in range(6)) + "%12.1f" % (us[sel, 5] - us[sel, 0] + np.nan_to_num(tick_us[sel])).mean())
+# the steady state: items that started while the machine was full and ended before the tail (the middle half by start order)
+mid = order[n // 4:3 * n // 4]
+print("%-18s" % "middle half" + "".join("%18.2f" % dur[mid, k].mean() for k in range(6)) + "%12.1f" % (us[mid, 5] - us[mid, 0] + np.nan_to_num(tick_us[mid])).mean())
+print("%-18s" % "  ... median" + "".join("%18.2f" % np.median(dur[mid, k]) for k in range(6)))
 print("\nitems in each phase over time (every %d us)" % max(1, int(end / 40)))
 step = max(1.0, end / 40)
 print("%8s %8s %8s %8s %8s %8s %8s" % ("t us", "resident", "phase A", "pass 1", "lookback", "pass 2", "started"))

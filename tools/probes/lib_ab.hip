@@ -212,6 +212,13 @@ int main(int argc, char** argv) {
     }
   }
   printf("%-8s %9s %9s %9s %9s %9s %9s %9s %9s %9s %9s %9s %9s  (ms per 16 k context, %d rounds x %d jobs; pdec = decode + scatter into a paged cache, every token at a slot of its own; bdec = the same with vLLM's mapping: blocks anywhere, a block's tokens in order; benc / penc = encode reading the paged cache through those two mappings)\n", "library", "enc min", "enc med", "dec min", "dec med", "pdec min", "pdec med", "bdec min", "bdec med", "benc min", "benc med", "penc min", "penc med", rounds, reps);
+  // every round's fused encode, in the order the rounds ran (a comparison of two builds rests on the RANGES not
+  // overlapping, not on the minima)
+  for (Lib& l : libs) {
+    printf("%-8s enc by round:", l.name.c_str());
+    for (double x : l.enc) printf(" %.4f", x);
+    printf("\n");
+  }
   for (Lib& l : libs) {
     std::vector<double>* v[6] = {&l.enc, &l.dec, &l.pdec, &l.bdec, &l.benc, &l.penc};
     printf("%-8s", l.name.c_str());
