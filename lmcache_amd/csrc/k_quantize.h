@@ -49,7 +49,9 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 // [-MAX 2^-23, 2 MAX + ...] and round-half-even gives 0 .. 2*MAX.  Two elements per instruction with the
 // packed fp32 multiply and add (each rounded on its own: no FMA), and v_cvt_pk_u8_f32 does the RNE
 // conversion, the clamp at 0 (-0.x -> 0) and the byte insertion in one op (probed on gfx950:
-// tools/probes/cvt_pk_u8.hip -- RNE, saturating, NaN -> 0).
+// tools/probes/cvt_pk_u8.hip -- RNE, saturating, NaN -> 0).  The three functions below, compiled with the library's
+// flags, are held against round(fl(fl(x * factor) + MAX)) for every x of chosen rows -- rows picked so that a fused
+// multiply-add or a factor one ulp off would show -- by tests/test_gpu_device_arith.py::test_quantise_step_*.
 __device__ __forceinline__ f32x2_t quant_z2(float xlo, float xhi, f32x2_t factor2, f32x2_t maxf2) {
   f32x2_t x = {xlo, xhi};
   f32x2_t y = x * factor2;  // v_pk_mul_f32, rounded

@@ -99,7 +99,8 @@ __device__ __forceinline__ BlobOff lmc_blob_off(u32 P, u32 T, u32 G) {
 }
 
 // e / R and e % R for small uniform R (2..30) and e < 2^15: exact through one float multiply
-// ((e + 0.5) / R is never within 1/60 of an integer; checked exhaustively on the host).
+// ((e + 0.5) / R is never within 1/60 of an integer; checked exhaustively on the host --
+// tests/test_device_arith_host.py -- and on the device, tests/test_gpu_device_arith.py).
 __device__ __forceinline__ void divmod_small(u32 e, u32 R, float rcpR, u32& q, u32& r) {
   q = (u32)(((float)e + 0.5f) * rcpR);
   r = e - q * R;
@@ -241,7 +242,10 @@ __device__ __forceinline__ u32 f2fp16(float f) {  // v_cvt_f16_f32, RNE
 // the division over every 16-bit max x MAX 1 .. 15: 0 mismatches inside row_div_in_range for bf16 and fp16
 // (profiles/r03_row_div.log; outside it -- bf16 maxes that are fp32 denormals or whose reciprocal is -- 4014 of
 // 491 520 differ, which is why the range test exists).  The test is on the row max, wave-uniform: a scalar branch;
-// zero / inf / NaN maxes fail it and keep the division.
+// zero / inf / NaN maxes fail it and keep the division.  The probe explores and times; what HOLDS the claim is
+// tests/test_gpu_device_arith.py::test_row_factor_every_max_pattern, which runs these two functions themselves, built
+// with the library's flags, over the same domain in every GPU run of the suite -- and the plain division next to them,
+// every pattern, denormal quotients included.
 __device__ __forceinline__ bool row_div_in_range(u32 max_bits, int dtype) {
   if (dtype == LMC_DTYPE_BF16) {
     const u32 e = (max_bits >> 7) & 0xffu;  // bf16 carries fp32's exponent field
@@ -407,7 +411,9 @@ __device__ __forceinline__ u32 lane_rank(u64 mask) {  // # set bits of mask belo
 }
 
 // RNE(v / T) for wave-uniform T; magic = floor(2^32 / T) (0xffffffff for T == 1).
-// v = n * 65504 with n <= T < 65536, so v < 2^32.
+// v = n * 65504 with n <= T < 65536, so v < 2^32.  The estimate is short by at most one T (the integer emulation in
+// tests/test_device_arith_host.py never needs the second correction); every T with its ties, and the two column
+// builders below, are held against integer RNE by tests/test_gpu_device_arith.py.
 __device__ __forceinline__ u32 rne_div_u32(u32 v, u32 T, u32 magic) {
   u32 q = __umulhi(v, magic);
   u32 r = v - q * T;
@@ -423,7 +429,8 @@ __device__ __forceinline__ u32 rne_div_u32(u32 v, u32 T, u32 magic) {
 // (cvt 2^-24, v_rcp_f32 1 ulp = 2^-23, two multiplies 2^-24 each) add up to
 // < 2^-21.6 relative, so the biased estimate never exceeds the true quotient
 // and is short of it by < 2^16 * 2^-20.3 < 1: qe is q or q-1, one branch-free
-// correction (re >= f) finishes it.
+// correction (re >= f) finishes it.  (Held on the device, with rans_put below, for every f at the quotient steps of
+// chosen and seeded x: tests/test_gpu_device_arith.py::test_divmod_est_and_rans_put.)
 __device__ __forceinline__ void divmod_est(u32 x, u32 f, u32& q, u32& r) {
   const float rf = __builtin_amdgcn_rcpf((float)f) * 0.99999952316284f;  // 1 - 2^-21
   const u32 qe = (u32)((float)x * rf);

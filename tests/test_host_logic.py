@@ -280,9 +280,9 @@ def test_blob_counts_section_rebuilds_the_reference_cdf(oracle, T):
 
 def test_divmod_small_is_exact_for_every_row_length():
     """The kernels split e into (e / R, e % R) with one float multiply (lmc_device.h divmod_small); R is the
-    number of counts per channel, 3 .. 31, e < 64 * R."""
+    number of counts per channel, 3 .. 31, e over the whole stated domain e < 2^15."""
     for R in range(2, 32):
-        e = np.arange(64 * R, dtype=np.uint32)
+        e = np.arange(1 << 15, dtype=np.uint32)
         q = ((e.astype(np.float32) + np.float32(0.5)) * (np.float32(1.0) / np.float32(R))).astype(np.uint32)
         assert np.array_equal(q, e // R), R
 
