@@ -510,6 +510,48 @@ int lmc_rope_shift(lmc_ctx* ctx, const lmc_kv_layout* kv, int32_t tok_begin, int
                    uint32_t* job_status, lmc_stream_t stream);
 
 /* ------------------------------------------------------------------ */
+/* CacheBlend token selection: KV deviation and top-k                  */
+/* ------------------------------------------------------------------ */
+/*
+ * The selection step of CacheBlend (BASELINE.json configs[4]; additive in ABI 6; csrc/k_blend.h): segments that were
+ * prefilled on their own sit in the paged cache (retrieve + lmc_rope_shift), the model recomputes ONE check layer over all
+ * tokens, and the tokens whose fresh K/V deviates most from what the cache holds are the ones it recomputes in the deeper
+ * layers.  Replaces nothing in the reference v0.1.2 (it has no blending); stands where a connector-side CacheBlend executor
+ * gathers the cached layer by slot mapping in torch, subtracts, squares, sums over (head, channel), runs torch.topk (tie
+ * order unspecified) and sorts -- a gather per cache layout, three element-wise passes with temporaries the size of the
+ * layer's KV -- in the TTFT path of every blended request.
+ *
+ * lmc_kv_deviation: for token i in [0, ntok)
+ *     dev_k[i] = sum over (h, d) of (K_a(a_layer, a_tok0 + i, h, d) - K_b(b_layer, b_tok0 + i, h, d))^2
+ *     dev_v[i] = the same sum over the V planes
+ *   dev_k, dev_v   device fp32 [ntok]; either may be NULL (that plane is skipped), not both
+ *   Tokens are addressed through each layout's own slot_mapping and strides, exactly as lmc_copy_kv addresses its two
+ *   sides, and the layouts follow lmc_copy_kv's rules: any strides, any LMC_PAGED_ROWS layout, at most one side
+ *   LMC_PAGED_SPLIT; num_heads, head_size and dtype equal on both sides -- num_layers may differ (`a` is typically the
+ *   model's fresh [T,H,D] pair of one layer, `b` the whole cache).  bf16 and fp16 only: fp8 is refused as lmc_rope_shift
+ *   refuses it (a blended fp8 cache cannot be position-shifted in the first place).
+ *   LMC_ERR_INVALID, nothing launched and nothing written: a layout lmc_copy_kv would refuse, a mismatch of H, D or dtype,
+ *   fp8, both sides split, a layer out of range, ntok < 1, a negative token offset, both outputs NULL.
+ *   Both KV sides are only read.  Elements are widened exactly to fp32; difference, square and sum are fp32.  No float
+ *   atomics: for given layouts and shapes the order of the additions is fixed by the code, so a token's sum is the same
+ *   bits on every run.  One plain store per token and plane.
+ *
+ * lmc_select_topk: the min(k, n) tokens with the largest key, key = bits(dev[i]) & 0x7fffffff compared as unsigned -- the
+ *   float order of the non-negative values lmc_kv_deviation writes, with NaN above +inf (a token whose KV holds a NaN is
+ *   recomputed first).  Ties go to the lower index.
+ *   dev       device fp32 [n]
+ *   idx_out   device int32: receives min(k, n) indices in ASCENDING order (the order the model recomputes in); nothing
+ *             beyond them is written
+ *   k comes from the host: no count to read back, no host wait, no allocation.  1 <= n <= 2^20 and k >= 0 (k == 0 writes
+ *   nothing and launches nothing); anything else is LMC_ERR_INVALID.  Deterministic.
+ * The two calls stay apart on purpose: under tensor parallelism a rank sees its own heads only, and the connector must
+ * all-reduce `dev` across the ranks before it selects, or the ranks pick different tokens.
+ */
+int lmc_kv_deviation(lmc_ctx* ctx, const lmc_kv_layout* a, int32_t a_layer, int32_t a_tok0, const lmc_kv_layout* b,
+                     int32_t b_layer, int32_t b_tok0, int32_t ntok, float* dev_k, float* dev_v, lmc_stream_t stream);
+int lmc_select_topk(lmc_ctx* ctx, const float* dev, int32_t n, int32_t k, int32_t* idx_out, lmc_stream_t stream);
+
+/* ------------------------------------------------------------------ */
 /* host DRAM offload plumbing                                          */
 /* ------------------------------------------------------------------ */
 /* Pinned, device-accessible host memory (hipHostMalloc).  Replaces the

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/lmc_hip.h"
+#include "k_blend.h"
 #include "k_copy.h"
 #include "k_copy_split.h"
 #include "k_decode.h"
@@ -1527,6 +1528,87 @@ int lmc_rope_shift(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, int32
   const RopeSpec r = {cos_sin, table_rows, rot_dim, is_neox, delta, deltas};
   if (!c || !rope_ok(kv, tok_begin, ntok, r)) return LMC_ERR_INVALID;
   return rope_launch(c, kv, tok_begin, ntok, r, job_status, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- CacheBlend token selection (k_blend.h) -------------------------------------------------------------------------
+// What lmc_kv_deviation asks of its two layouts and its range: lmc_copy_kv's rules with the layer count free, 16-bit
+// elements only (every refusal LMC_ERR_INVALID, nothing launched).
+static bool deviation_ok(const lmc_kv_layout* a, int32_t a_layer, int32_t a_tok0, const lmc_kv_layout* b, int32_t b_layer,
+                         int32_t b_tok0, int32_t ntok, const float* dev_k, const float* dev_v) {
+  if (!layout_ok(a, false, true) || !layout_ok(b, false, true) || ntok < 1 || a_tok0 < 0 || b_tok0 < 0) return false;
+  if (a->num_heads != b->num_heads || a->head_size != b->head_size || a->dtype != b->dtype || lmc_dtype_fp8(a->dtype)) return false;
+  if (a->paged_kind == LMC_PAGED_SPLIT && b->paged_kind == LMC_PAGED_SPLIT) return false;  // one side is rows
+  if (a_layer < 0 || a_layer >= a->num_layers || b_layer < 0 || b_layer >= b->num_layers) return false;
+  if ((long long)a_tok0 + ntok > INT32_MAX || (long long)b_tok0 + ntok > INT32_MAX) return false;
+  return dev_k || dev_v;
+}
+// One side of the comparison: its layer's two planes, and whether its strides let it be read 16 bytes at a time -- rows:
+// lmc_copy_kv's `vec` rule; split: every stride a whole granule (the kernel looks at the plane base itself).
+static DevSide deviation_side(const lmc_kv_layout* l, int32_t layer, int32_t tok0) {
+  DevSide s;
+  memset(&s, 0, sizeof s);
+  s.kv = to_addr(l);
+  s.tok0 = tok0; s.plane_k = layer; s.plane_v = l->num_layers + layer;
+  s.split = l->paged_kind == LMC_PAGED_SPLIT;
+  auto mult = [](int64_t v) { return v % 8 == 0; };
+  s.vec = s.split ? mult(l->stride_block) && mult(l->stride_head) && (l->plane_ptrs || (mult(l->stride_layer) && mult(l->stride_kv)))
+                  : layout_ok(l);
+  return s;
+}
+
+extern "C" {
+
+int lmc_kv_deviation(lmc_ctx* c, const lmc_kv_layout* a, int32_t a_layer, int32_t a_tok0, const lmc_kv_layout* b,
+                     int32_t b_layer, int32_t b_tok0, int32_t ntok, float* dev_k, float* dev_v, lmc_stream_t stream) {
+  if (!c || !deviation_ok(a, a_layer, a_tok0, b, b_layer, b_tok0, ntok, dev_k, dev_v)) return LMC_ERR_INVALID;
+  DeviationArgs g;
+  memset(&g, 0, sizeof g);
+  // the kernel's tile form wants the split side second: the squared difference does not care
+  const bool swap = a->paged_kind == LMC_PAGED_SPLIT;
+  g.a = swap ? deviation_side(b, b_layer, b_tok0) : deviation_side(a, a_layer, a_tok0);
+  g.b = swap ? deviation_side(a, a_layer, a_tok0) : deviation_side(b, b_layer, b_tok0);
+  g.ntok = ntok; g.C = a->num_heads * a->head_size;
+  g.lpt = 1;
+  while (g.lpt < g.C / 8 && g.lpt < 64) g.lpt <<= 1;
+  g.ntiles = (int)(((long long)ntok + 14) / 8);  // the first tile may begin 7 positions in front of the range
+  g.out[0] = dev_k; g.out[1] = dev_v;
+  if (dev_k) g.plane_kv[g.nplanes++] = 0;
+  if (dev_v) g.plane_kv[g.nplanes++] = 1;
+  HIP_TRY(hipSetDevice(c->device));
+  // a wave of the group form takes 64 / lpt tokens, a wave of the tile form a tile; grid-stride beyond 32 workgroups per CU
+  auto launch = [&](bool tile, long long items) {
+    long long blocks = (items + BLEND_WAVES - 1) / BLEND_WAVES;
+    if (blocks > 32LL * c->num_cus) blocks = 32LL * c->num_cus;
+    with_kv_dtype16(a->dtype, [&](auto dt) {
+      with_bool(tile, [&](auto tl) {
+        hipLaunchKernelGGL((k_kv_deviation<decltype(dt)::value, decltype(tl)::value>), dim3((unsigned)blocks, (unsigned)g.nplanes),
+                           dim3(64 * BLEND_WAVES), 0, (hipStream_t)stream, g);
+      });
+    });
+  };
+  const long long tpw = 64 / g.lpt, groups = (ntok + tpw - 1) / tpw;
+  if (!g.b.split) launch(false, groups);  // both planes in one launch
+  else {  // a split side: the K plane in the group form, the V plane in the tile form, a launch each
+    const int want_k = dev_k != nullptr, want_v = dev_v != nullptr;
+    g.nplanes = 1;
+    if (want_k) { g.plane_kv[0] = 0; launch(false, groups); }
+    if (want_v) { g.plane_kv[0] = 1; launch(true, g.ntiles); }
+  }
+  HIP_TRY(hipGetLastError());
+  return LMC_OK;
+}
+
+int lmc_select_topk(lmc_ctx* c, const float* dev, int32_t n, int32_t k, int32_t* idx_out, lmc_stream_t stream) {
+  if (!c || !dev || n < 1 || n > (1 << 20) || k < 0 || (k > 0 && !idx_out)) return LMC_ERR_INVALID;
+  if (k == 0) return LMC_OK;  // nothing to write
+  TopkArgs t;
+  t.dev = dev; t.idx_out = idx_out; t.n = (u32)n; t.kk = (u32)(k < n ? k : n);
+  HIP_TRY(hipSetDevice(c->device));
+  hipLaunchKernelGGL(k_select_topk, dim3(1), dim3(TOPK_THREADS), 0, (hipStream_t)stream, t);
+  HIP_TRY(hipGetLastError());
+  return LMC_OK;
 }
 
 // ---- host DRAM offload plumbing ---------------------------------------------

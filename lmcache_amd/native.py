@@ -211,6 +211,8 @@ SYMBOLS = {
     "lmc_pack_chunk_bytes": (ctypes.c_int, [_vp, _u64, _i32, ctypes.POINTER(ctypes.c_uint32)]),
     "lmc_copy_kv": (ctypes.c_int, [_vp, _PL, _i32, _i32, _PL, _i32, _vp]),
     "lmc_rope_shift": (ctypes.c_int, [_vp, _PL, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "lmc_kv_deviation": (ctypes.c_int, [_vp, _PL, _i32, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "lmc_select_topk": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "lmc_pinned_alloc": (ctypes.c_int, [_sz, ctypes.POINTER(_vp)]),
     "lmc_pinned_free": (ctypes.c_int, [_vp]),
     "lmc_memcpy_async": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, _vp]),
@@ -1091,6 +1093,31 @@ class Context:
         self._call("lmc_rope_shift", layout.device, stream, ctypes.byref(layout.struct), tok_begin, ntok, cos_sin.data_ptr(),
                    cos_sin.shape[0], rot_dim, 1 if is_neox else 0, int(delta), None if deltas is None else deltas.data_ptr(),
                    job_status)
+
+    def kv_deviation(self, a: KVLayout, a_layer: int, a_tok0: int, b: KVLayout, b_layer: int, b_tok0: int, ntok: int,
+                     dev_k: Optional[torch.Tensor] = None, dev_v: Optional[torch.Tensor] = None,
+                     stream: Optional[int] = None) -> None:
+        """lmc_kv_deviation: dev_k[i] / dev_v[i] = the squared distance, summed over heads and channels in fp32, between
+        the K / V of token a_tok0 + i of layer a_layer of `a` and token b_tok0 + i of layer b_layer of `b`.  dev_k, dev_v:
+        contiguous device float32 tensors of at least ntok entries; either may be None (that plane is skipped)."""
+        for name, t in (("dev_k", dev_k), ("dev_v", dev_v)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= ntok):
+                raise ValueError(f"{name} must be a contiguous device float32 tensor of at least ntok = {ntok} entries")
+        self._call("lmc_kv_deviation", a.device, stream, ctypes.byref(a.struct), a_layer, a_tok0, ctypes.byref(b.struct), b_layer,
+                   b_tok0, ntok, None if dev_k is None else dev_k.data_ptr(), None if dev_v is None else dev_v.data_ptr())
+
+    def select_topk(self, dev: torch.Tensor, k: int, idx_out: torch.Tensor, stream: Optional[int] = None) -> int:
+        """lmc_select_topk: the min(k, n) entries of `dev` (device float32 [n]) with the largest magnitude bits, NaN above
+        +inf, ties to the lower index -> their indices in ascending order in idx_out (device int32, at least min(k, n)
+        entries).  Returns min(k, n); nothing is read back."""
+        n = dev.numel()
+        kk = min(int(k), n)
+        if not (dev.is_cuda and dev.dtype == torch.float32 and dev.is_contiguous()):
+            raise ValueError("dev must be a contiguous device float32 tensor")
+        if not (idx_out.is_cuda and idx_out.dtype == torch.int32 and idx_out.is_contiguous() and idx_out.numel() >= max(kk, 0)):
+            raise ValueError(f"idx_out must be a contiguous device int32 tensor of at least min(k, n) = {kk} entries")
+        self._call("lmc_select_topk", dev.device, stream, dev.data_ptr(), n, int(k), idx_out.data_ptr())
+        return kk
 
     @staticmethod
     def _check_rope_args(cos_sin: torch.Tensor, rot_dim: int, deltas: Optional[torch.Tensor], ntok: Optional[int]) -> None:
