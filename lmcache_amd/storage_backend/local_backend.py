@@ -549,17 +549,29 @@ class LMCLocalBackend(LMCBackendInterface):
                     return
                 if self.dev_arena is None:
                     self.dev_arena = DeviceArena(torch.device("cuda", self._cuda_device), budget=self._tiers.budget["hbm"])
-                with torch.cuda.device(self._cuda_device):
+
+                def move():
                     if fixed:
-                        blobs = codec.promote_pack(pack, self.dev_arena, model="fixed", bins=bins)
-                    elif packed:
-                        blobs = codec.promote_pack(pack, self.dev_arena)
-                    else:
-                        cur = torch.cuda.current_stream()
-                        t = self.dev_arena.alloc(sizes[0], stream=cur)
-                        native.memcpy_async(t.data_ptr(), old[0].blob.ptr, sizes[0], "h2d", cur.cuda_stream)
-                        cur.synchronize()
-                        blobs = [t]
+                        return codec.promote_pack(pack, self.dev_arena, model="fixed", bins=bins)
+                    if packed:
+                        return codec.promote_pack(pack, self.dev_arena)
+                    cur = torch.cuda.current_stream()
+                    t = self.dev_arena.alloc(sizes[0], stream=cur)
+                    native.memcpy_async(t.data_ptr(), old[0].blob.ptr, sizes[0], "h2d", cur.cuda_stream)
+                    cur.synchronize()
+                    return [t]
+
+                blobs = None
+                with torch.cuda.device(self._cuda_device):
+                    while blobs is None:
+                        try:
+                            blobs = move()
+                        except ArenaFull:
+                            # the byte count allowed it, the holes did not: the HBM tier's LRU group goes down, and again
+                            # (its demotion may have pushed THIS group out of a fragmented pinned tier: then nothing is left
+                            # to promote)
+                            if not self._tiers.take_lru("hbm", keep=[gid]) or self._lru.tier_of(gid) != "pinned":
+                                return
             except Exception:
                 logger.exception("promotion failed: the group stays in the pinned tier")
                 return

@@ -53,8 +53,9 @@ class PinnedArena:
     (the reference never evicts, hybrid_backend.py:24): free() only counts.  With a byte budget (constructor, or
     set_budget() later) regions come from a first-fit free list with coalescing (storage_backend/tiering.py), free()
     gives them back, and the bytes reserved from the system -- the sum of the slab sizes -- never exceed the budget
-    (an arena that was unbounded before keeps the slabs it has; it takes no new one while it is over).  A freed
-    region carries the events of whoever may still read it; alloc() makes the streams of the next owner wait for them."""
+    (an arena that was unbounded before keeps the slabs it has that still hold live bytes; it takes no new one while it
+    is over, and what it was given back while unbounded becomes holes).  A freed region carries the events of whoever may
+    still read it; alloc() makes the streams of the next owner wait for them."""
 
     def __init__(self, slab_bytes: int = 256 << 20, budget: Optional[int] = None, buffer_factory=None):
         self.slab_bytes = slab_bytes
@@ -66,6 +67,11 @@ class PinnedArena:
         self._lock = threading.Lock()
         self.total_allocated = 0
         self._fl: Optional[FreeList] = None
+        # unbounded: the regions given back so far, (slab, offset, size, events) -- only counted while the arena is a bump
+        # allocator, holes of the free list once it turns bounded -- and how many of their bytes are tails that shrink()
+        # could not return to the bump pointer (total_allocated still counts those)
+        self._freed: List[tuple] = []
+        self.cut_bytes = 0
         if budget is not None:
             self.set_budget(budget)
 
@@ -76,7 +82,9 @@ class PinnedArena:
 
     def set_budget(self, budget: Optional[int]) -> None:
         """Bound the arena from now on (None on an unbounded arena: nothing changes; a bounded arena stays a free list
-        and only loses its limit).  What the bump allocator has handed out so far counts as live."""
+        and only loses its limit).  What the bump allocator has handed out so far and not been given back counts as
+        live; what was given back meanwhile becomes holes.  Slabs that are one hole go back to the system while the
+        arena is over the new budget."""
         with self._lock:
             if self._fl is None:
                 if budget is None:
@@ -87,10 +95,15 @@ class PinnedArena:
                     fl.add_slab(b, b.nbytes, self._used if last else self._tops[k])
                 for b in self._spare:
                     fl.add_slab(b, b.nbytes, 0)
+                for slab, off, size, events in self._freed:
+                    fl.free(slab, off, size, events)
+                self._freed, self.cut_bytes = [], 0
                 self._slabs, self._spare = self._slabs + self._spare, []
                 self._fl = fl
+                self.total_allocated = fl.live
             else:
                 self._fl.budget = budget
+            self._release_empty_locked()
 
     @property
     def live_bytes(self) -> int:
@@ -132,6 +145,7 @@ class PinnedArena:
         with self._lock:
             if self._fl is None:
                 self.total_allocated -= size
+                self._freed.append((hb.slab, hb.offset, size, list(events)))
                 return
             self._fl.free(hb.slab, hb.offset, size, events)
             self.total_allocated = self._fl.live
@@ -195,6 +209,11 @@ class PinnedArena:
             elif self._slabs and hb.slab is self._slabs[-1] and hb.offset + native.r16(max(hb.nbytes, 16)) == self._used:
                 self.total_allocated -= self._used - (hb.offset + keep)
                 self._used = hb.offset + keep
+            elif native.r16(max(hb.nbytes, 16)) > keep:
+                # (another allocation lies behind it: the tail stays unused and counted; a hole once the arena is bounded)
+                tail = native.r16(max(hb.nbytes, 16)) - keep
+                self._freed.append((hb.slab, hb.offset + keep, tail, []))
+                self.cut_bytes += tail
         return HostBlob(hb.slab, hb.offset, nbytes)
 
     def reserve(self, nbytes: int, slab_bytes: int = 0) -> None:
@@ -219,6 +238,7 @@ class PinnedArena:
             self._tops = []
             self._used = 0
             self.total_allocated = 0
+            self._freed, self.cut_bytes = [], 0
             if self._fl is not None:
                 budget = self._fl.budget
                 self._fl = FreeList(budget, _event_done)
@@ -230,6 +250,7 @@ class PinnedArena:
             for s in self._slabs + self._spare:
                 s.free()
             self._slabs, self._spare, self._tops = [], [], []
+            self._freed, self.cut_bytes = [], 0
             if self._fl is not None:
                 self._fl = FreeList(self._fl.budget, _event_done)
 
@@ -491,6 +512,7 @@ class DeviceArena:
         self._lock = threading.Lock()
         self._fl: Optional[FreeList] = None
         self._live = 0
+        self._freed: List[tuple] = []  # unbounded: (slab index, offset, size, events) given back so far (PinnedArena._freed)
         self._ids: List[int] = []    # bounded: the free list's id of each slab
         self._next_id = 0
         if budget is not None:
@@ -536,12 +558,15 @@ class DeviceArena:
                 fl = FreeList(budget, _event_done)
                 for k, t in enumerate(self._slabs):
                     fl.add_slab(k, t.numel(), self._used if k == len(self._slabs) - 1 else self._tops[k])
-                # (what was freed while unbounded was only counted: those bytes stay lost to the old slabs)
+                for k, off, size, events in self._freed:  # (what was given back while unbounded: holes from now on)
+                    fl.free(k, off, size, events)
+                self._freed = []
                 self._ids = list(range(len(self._slabs)))
                 self._next_id = len(self._slabs)
                 self._fl = fl
             else:
                 self._fl.budget = budget
+            self._release_empty_locked()
 
     def alloc(self, nbytes: int, stream=None) -> torch.Tensor:
         """stream: who writes the region (bounded arena: it waits for the events of the previous owner; None: the
@@ -585,22 +610,23 @@ class DeviceArena:
         """Give the blob `t` (a view alloc() returned) back; `events`: what may still read it."""
         size = native.r16(max(t.numel(), 16))
         with self._lock:
-            if self._fl is None:
-                self._live -= size
-                return
             p = t.data_ptr()
             for k, slab in enumerate(self._slabs):
                 base = slab.data_ptr()
                 if base <= p < base + slab.numel():
-                    self._fl.free(self._ids[k], p - base, size, events)
                     break
             else:
                 raise ValueError("DeviceArena.free: not a region of this arena")
+            if self._fl is None:
+                self._live -= size
+                self._freed.append((k, p - base, size, list(events)))
+                return
+            self._fl.free(self._ids[k], p - base, size, events)
             self._release_empty_locked()  # over budget (bounded after the fact): empty slabs go back
 
     def close(self):
         with self._lock:
-            self._slabs, self._tops, self._used, self._live = [], [], 0, 0
+            self._slabs, self._tops, self._used, self._live, self._freed = [], [], 0, 0, []
             if self._fl is not None:
                 self._fl = FreeList(self._fl.budget, _event_done)
                 self._ids, self._next_id = [], 0

@@ -195,15 +195,16 @@ def test_an_arena_bounded_later_keeps_what_it_handed_out():
     assert a.live_bytes == 1008
     h3 = a.alloc(500)
     assert h3.slab is h2.slab and h3.offset == 3200  # ... the bump allocator reuses nothing
-    a.set_budget(2048)
-    assert a.live_bytes == 1008 + 3200 + 512  # what the bump pointers cover counts as live
+    a.set_budget(1530)
+    # what the bump pointers cover and nobody has given back counts as live; what was given back is a hole again (it
+    # used to stay counted for good: a tier bounded after a key was stored twice lost that much of its budget)
+    assert a.live_bytes == 1008 + 512
     with pytest.raises(ArenaFull):
         a.alloc(16)
     slab2 = h3.slab
     a.free(h3)
-    a.free(type(h3)(slab2, 0, 3200))
     assert slab2.freed and a.reserved_bytes == 4096  # over budget: the empty slab went back to the system
-    assert a.alloc(1000).offset == 1008
+    assert a.alloc(500).offset == 1008
 
 
 def test_a_bounded_arena_whose_groups_have_gone_takes_a_region_larger_than_any_slab():
