@@ -114,6 +114,8 @@ int lmc_abi_version(void);
  *   - NOT lmc_encode_chunks and lmc_quantize: they stand for the reference's to_bytes / torch_quant_vectorized, whose
  *     caller holds a tensor of rows.  NOT lmc_encode_chunks_fixed and lmc_decode_chunks_fixed_schedule either: their
  *     _split twins are the ones that take it.
+ *   - lmc_rope_shift_split (16-bit elements): the keys re-rotated in the split blocks themselves, under the decoders'
+ *     rule for the 32-bit offsets; NOT lmc_rope_shift, which rotates rows.
  * Every other entry point -- lmc_rope_shift among them -- reads and writes rows and returns LMC_ERR_INVALID for it: bring
  * the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot read.  Any other paged_kind is
  * LMC_ERR_INVALID; a caller that zeroes the struct gets LMC_PAGED_ROWS.
@@ -403,6 +405,13 @@ int lmc_decode_chunks_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint6
  * Per range:  rotation -- lmc_rope_shift's kernels in place on the window of `dst` (rows);  scatter -- lmc_copy_kv's
  * scatter of the window;  both -- the rotation of the staged window, then its scatter, two launches (a scatter that
  * rotates the keys on their way was built and measured: slower than the two, profiles/paged_layerwise.md).  Neither: nothing.
+ * ONE more form, every condition required: `dst` is LMC_PAGED_SPLIT, cos_sin is set, scatter_dst describes the SAME cache
+ * as `dst` (every field of the two structs equal) and scatter_tok0 == tok_begin.  It says that the range's final place is
+ * where the decoder put it and the rotation is done there: per range ONE lmc_rope_shift_split launch on the range's layer
+ * window of `dst`, between its decode and its event; nothing is copied.  It is held against lmc_rope_shift_split's rules.
+ * (Both sides split was refused before this form existed, so no valid call changed its meaning; a rotation of a split
+ * `dst` with scatter_dst NULL, or with a scatter_dst that differs from `dst` in any field, or with
+ * scatter_tok0 != tok_begin, stays LMC_ERR_INVALID.)
  * The whole post-op is held against lmc_rope_shift's and lmc_copy_kv's rules before anything of the job is queued
  * (LMC_ERR_INVALID): a rotation of an LMC_PAGED_SPLIT `dst`, of fp8, a scatter_dst that is not LMC_PAGED_SPLIT or differs
  * from `dst` in geometry or dtype, ntok < 1, ...  A per-token |delta| outside the table is reported as lmc_rope_shift
@@ -417,7 +426,8 @@ typedef struct lmc_range_post {
   int32_t scatter_tok0;
 } lmc_range_post;
 /* lmc_decode_chunks_schedule with `post` done to every range between its launch and its event; post NULL IS
- * lmc_decode_chunks_schedule (one body). */
+ * lmc_decode_chunks_schedule (one body).  A split `dst` takes the in-place rotation form of lmc_range_post (`dst` named
+ * as its own scatter_dst): decoded into the split blocks, then lmc_rope_shift_split per range. */
 int lmc_decode_chunks_schedule_post(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
                                     const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
                                     const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
@@ -448,7 +458,8 @@ int lmc_decode_chunks_fixed_schedule(lmc_ctx* ctx, const void* const* blob_ptrs,
  * of dst_tok0 + ... = 0 or past the blob's count is neither written nor looked up in slot_mapping).  The decoded bits
  * are those the row decode leaves in a chunk.  The split destination's 32-bit offsets follow the rule stated at
  * lmc_kv_layout for the coded decoders (LMC_ERR_INVALID beyond it, as for fp8), and `post` follows
- * lmc_decode_chunks_schedule_post: a rotation of a split `dst` is LMC_ERR_INVALID.
+ * lmc_decode_chunks_schedule_post: a rotation of a split `dst` is LMC_ERR_INVALID unless the post names `dst` as its
+ * own scatter_dst (the in-place form of lmc_range_post: lmc_rope_shift_split per range, in front of the range's event).
  */
 int lmc_decode_chunks_fixed_split_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes,
                                            int32_t nchunks, const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens,
@@ -495,8 +506,8 @@ int lmc_copy_kv(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32
  * With c = row |d| cos and s = sign(d) * row |d| sin:  o1 = x1 c - x2 s,  o2 = x2 c + x1 s, every product and sum rounded
  * to fp32 by itself, then one round-to-nearest-even cast to the layout's dtype.  (The shifted key has then been rounded
  * to 16 bits twice: when it was stored and now.)
- * LMC_ERR_INVALID, with nothing launched: a layout the decoders would refuse; LMC_PAGED_SPLIT (no split addressing here: lmc_copy_kv takes
- * it: shift the chunk before it is scattered); an fp8 dtype (rotating fp8 would round the key to 3 or 2 mantissa bits a
+ * LMC_ERR_INVALID, with nothing launched: a layout the decoders would refuse; LMC_PAGED_SPLIT (no split addressing here: lmc_rope_shift_split
+ * below rotates such a cache in place, or shift the chunk before lmc_copy_kv scatters it); an fp8 dtype (rotating fp8 would round the key to 3 or 2 mantissa bits a
  * second time: not offered); rot_dim odd, < 2 or > head_size; table_rows < 1; a uniform |delta| >= table_rows; ntok < 1,
  * tok_begin < 0, a NULL table; ntok * num_heads * rot_dim / 2 >= 2^31 (split the range).
  * A per-token |deltas[i]| >= table_rows leaves that token untouched and raises LMC_STATUS_BAD_POSITION in job_status (or
@@ -508,6 +519,29 @@ int lmc_copy_kv(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32
 int lmc_rope_shift(lmc_ctx* ctx, const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const float* cos_sin,
                    int32_t table_rows, int32_t rot_dim, int32_t is_neox, int32_t delta, const int32_t* deltas,
                    uint32_t* job_status, lmc_stream_t stream);
+
+/*
+ * lmc_rope_shift IN an LMC_PAGED_SPLIT cache (additive in ABI 6; k_rope.h: k_rope_split_vec / k_rope_split_elem): the keys
+ * of tokens [tok_begin, +ntok) are re-rotated where the decoder stored them, in the split blocks of vLLM's ROCm
+ * paged-attention kernels -- behind a DIRECT decode (lmc_decode_chunks_schedule, lmc_decode_chunks_fixed_split_schedule,
+ * lmc_load_pack, a scatter by lmc_copy_kv) there is no staged chunk of rows to rotate first.  The NeoX partners of a pair
+ * lie in granules j and j + rot_dim/16 of one (block, head, slot), the GPT-J partners inside one granule.
+ *   `kv` must be LMC_PAGED_SPLIT with 16-bit elements (bf16 / fp16); every other argument, the arithmetic, the status
+ *   bit and every refusal are lmc_rope_shift's.  LMC_ERR_INVALID with nothing launched as well for: a rows layout
+ *   (lmc_rope_shift takes that), a split layout beyond the 32-bit offsets stated at lmc_kv_layout for the decoders, and
+ *   ntok * num_heads * (work items of a head) >= 2^31.
+ *   touches   channels [0, rot_dim) of the K planes at the slots of the named tokens; V planes, other slots and channels
+ *             >= rot_dim are not written at all
+ *   A window of layers is a layout of that many layers (plane_ptrs moved by two pointers per layer, or base by
+ *   stride_layer): what lmc_range_post does per range.
+ * 16-byte accesses (two loads, eight pairs, two stores per NeoX item; consecutive lanes take consecutive tokens, which
+ * in a block-ordered mapping are adjacent granules) where the K planes stand on 16-byte boundaries, stride_block and
+ * stride_head are multiples of 8 elements, the table is 16-byte aligned and rot_dim % 16 == 0 (NeoX) or % 8 == 0 (GPT-J);
+ * anything else one pair per thread (correct, not fast).
+ */
+int lmc_rope_shift_split(lmc_ctx* ctx, const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const float* cos_sin,
+                         int32_t table_rows, int32_t rot_dim, int32_t is_neox, int32_t delta, const int32_t* deltas,
+                         uint32_t* job_status, lmc_stream_t stream);
 
 /* ------------------------------------------------------------------ */
 /* CacheBlend token selection: KV deviation and top-k                  */
@@ -660,7 +694,8 @@ int lmc_load_pack(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t
                   uint32_t* job_status, lmc_stream_t stream);
 /* lmc_load_pack with `post` (lmc_range_post, above) done to every range between its decode and range_events[r]: the
  * pinned tier's layer-by-layer retrieve into a paged cache.  post NULL IS lmc_load_pack (one body); a post-op that does
- * not check out is LMC_ERR_INVALID with nothing queued, like a pack that does not. */
+ * not check out is LMC_ERR_INVALID with nothing queued, like a pack that does not.  A split `dst` takes the in-place
+ * rotation form of lmc_range_post (`dst` named as its own scatter_dst): lmc_rope_shift_split per range. */
 int lmc_load_pack_post(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
                        const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
                        uint32_t* job_status, lmc_stream_t stream, const lmc_range_post* post);

@@ -19,6 +19,7 @@ caller's per-layer tensors by the kernels (put_kv_range / get_kv_range), or by
 one lmc_copy_kv pass per chunk for backends that only speak chunk tensors.
 """
 import hashlib
+import os
 import time
 from typing import Dict, Iterable, List, Optional, Tuple, Union
 
@@ -49,6 +50,10 @@ class LMCacheEngine:
         self.chunk_size = config.chunk_size
         self.save_decode_cache = config.save_decode_cache
         self.engine_ = CreateStorageBackend(config, metadata)
+        # retrieve_into_paged(direct=True, rope=...) on an "NHDB" cache: decode into the split blocks and re-rotate the keys
+        # there (lmc_rope_shift_split) where LMCACHE_AMD_SPLIT_ROPE=1 is set (read here, once); the default keeps what the
+        # tiers have always done with that call -- the coded tiers raise, the fixed-width tier stages
+        self.split_rope = os.environ.get("LMCACHE_AMD_SPLIT_ROPE", "0") == "1"
         logger.debug("Current storage backend type %s", type(self.engine_))
 
     # ------------------------------------------------------------------ index (pure Python)
@@ -329,6 +334,13 @@ class LMCacheEngine:
                   (local_serde="cachegen-fixed") decodes into the split blocks the same way
                   (lmc_decode_chunks_fixed_split_schedule); asked for `direct` WITH `rope` it does not raise but takes
                   the staged path (logged once).
+                  Where LMCACHE_AMD_SPLIT_ROPE=1 was set when the engine was built (engine.split_rope), `direct` WITH
+                  `rope` is honoured by every tier that honours `direct` -- the coded HBM tier, the fixed-width tier,
+                  pinned packs and blobs, the raw tiers' per-chunk scatter: the KV goes straight into the split blocks
+                  and ONE lmc_rope_shift_split (k_rope.h: k_rope_split_*) behind it re-rotates the keys there.  No
+                  staged chunk; when everything has completed the caches hold, bit for bit, what the staged call
+                  leaves.  The side effect of `direct` stays: a blob that fails to decode is a miss, nothing is
+                  rotated, and the call's slots may hold garbage.
           rope  a lmcache_amd.rope.RopeShift: the keys of the retrieved tokens are re-rotated to new positions on the way
                 (a segment that was prefilled on its own and is placed at offset p: delta = p; a per-token delta tensor
                 has one entry per token of `tokens`).  One lmc_rope_shift (k_rope.h) on the current stream behind the
@@ -347,7 +359,10 @@ class LMCacheEngine:
     def _direct_retrieve(self, direct: bool, layout: str, rope: Optional[RopeShift] = None) -> bool:
         """`direct` as the backend honours it.  The fixed-width HBM tier (local_serde="cachegen-fixed") decodes straight
         into an "NHDB" cache (lmc_decode_chunks_fixed_split_schedule); asked for that together with a `rope` it does not
-        raise as the coded tiers do but takes the staged path, where the keys are rotated (logged once)."""
+        raise as the coded tiers do but takes the staged path, where the keys are rotated (logged once).  With
+        LMCACHE_AMD_SPLIT_ROPE=1 (self.split_rope) every tier honours it: the keys are rotated in the split blocks."""
+        if getattr(self, "split_rope", False):
+            return direct
         if direct and layout == "NHDB" and rope is not None and getattr(self.engine_, "model", None) == "fixed":
             if not getattr(self, "_fixed_direct_logged", False):
                 self._fixed_direct_logged = True
@@ -422,7 +437,11 @@ class LMCacheEngine:
         When everything has completed, every cache
         tensor holds, bit for bit, what retrieve_into_paged with the same arguments leaves.
         Staged "NHDB" (direct=False) keeps ONE staged chunk of the retrieved size; the returned object holds it until
-        finish().  direct=True sets no scatter: the decoder writes the split blocks.
+        finish().  direct=True sets no scatter: the decoder writes the split blocks.  direct=True with `rope` on "NHDB"
+        (LMCACHE_AMD_SPLIT_ROPE=1 when the engine was built; ValueError or the staged path otherwise, as for
+        retrieve_into_paged): each range is decoded into the split blocks and its keys are re-rotated there, one
+        lmc_rope_shift_split per range in front of the range's event (the in-place form of lmc_range_post); no staged chunk.
+        A blob that fails to decode may leave garbage in the call's slots, as for every `direct` retrieve.
         Tiers: the HBM-resident CacheGen tier and the pinned tier's packs are cut by layers as above.  Pinned blobs that
         are no pack (a store of one chunk, LMCACHE_AMD_PINNED_PACKS=0) cross PCIe whole, then decode range by range with
         the post-ops in front of the events: layer 0 waits for that transfer.  The raw tiers and remote backends queue
@@ -596,7 +615,7 @@ class _PagedTarget:
         self.num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
         direct = engine._direct_retrieve(direct, layout, rope)
         if rope is not None:
-            if direct and layout == "NHDB":
+            if direct and layout == "NHDB" and not getattr(engine, "split_rope", False):
                 raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
                                  "not address an \"NHDB\" cache); use the staged retrieve")
             engine._check_rope(rope, kv_caches, layout, len(tokens))
@@ -622,7 +641,9 @@ class _PagedTarget:
                 rot_dim=0 if rope is None else rope.rot_dim, is_neox=rope is None or rope.is_neox,
                 delta=0 if rope is None or isinstance(rope.delta, torch.Tensor) else rope.delta,
                 deltas=None if rope is None else rope.deltas_for(skip, nret, self.ntokens, dst.device),
-                scatter_dst=dst if self.staged else None)
+                # (a split cache that is filled directly names ITSELF: the keys are rotated where the decoder put them,
+                # native.RangePost.in_place / the in-place form of lmc_range_post)
+                scatter_dst=dst if self.staged or (rope is not None and layout == "NHDB") else None)
         self.hold = (chunk, self._post)
         return rows
 

@@ -1458,6 +1458,53 @@ static int rope_launch(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, i
   return LMC_OK;
 }
 
+// ---- the same rotation in an LMC_PAGED_SPLIT cache (lmc_rope_shift_split; k_rope.h: k_rope_split_*) -------------------
+// 16-byte accesses: every stride the kernel adds to a plane a whole granule, and what rope_vec_ok asks of the table and
+// of rot_dim.  A plane that comes out of a pointer table is looked at by the kernel (k_rope_split_vec goes element by
+// element through one that is off a 16-byte boundary).
+static bool rope_split_vec(const lmc_kv_layout* kv, const RopeSpec& r) {
+  if (!rope_vec_ok(r) || (kv->stride_block & 7) || (kv->stride_head & 7)) return false;
+  return kv->plane_ptrs || (!(kv->stride_layer & 7) && ((uintptr_t)kv->base & 15) == 0);
+}
+static int rope_split_per_head(const lmc_kv_layout* kv, const RopeSpec& r) {
+  return rope_split_vec(kv, r) ? r.rot_dim / (r.is_neox ? 16 : 8) : r.rot_dim / 2;
+}
+// What lmc_rope_shift_split asks: rope_ok's rules for a 16-bit split cache, whose 32-bit offsets follow the decoders' rule.
+static bool rope_split_ok(const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const RopeSpec& r) {
+  if (!layout_ok(kv, false, true) || kv->paged_kind != LMC_PAGED_SPLIT || lmc_dtype_fp8(kv->dtype) || !decode_dst_ok(kv, 0))
+    return false;
+  if (ntok < 1 || tok_begin < 0 || (long long)tok_begin + ntok > INT32_MAX || !r.cos_sin || r.table_rows < 1) return false;
+  if (r.rot_dim < 2 || (r.rot_dim & 1) || r.rot_dim > kv->head_size) return false;
+  if (!r.deltas && (r.delta <= -r.table_rows || r.delta >= r.table_rows)) return false;
+  return (long long)ntok * kv->num_heads * rope_split_per_head(kv, r) < (1ll << 31);
+}
+// lmc_rope_shift_split behind its checks (rope_split_ok); the grid is rope_launch's.
+static int rope_split_launch(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const RopeSpec& r,
+                             uint32_t* job_status, hipStream_t stream) {
+  const bool neox = r.is_neox != 0, vec = rope_split_vec(kv, r);
+  RopeArgs a;
+  memset(&a, 0, sizeof a);
+  a.kv = to_addr(kv);
+  a.cos_sin = r.cos_sin; a.deltas = r.deltas; a.status = job_status ? job_status : c->status_h;
+  a.tok_begin = tok_begin; a.ntok = ntok; a.rot = r.rot_dim; a.table_rows = r.table_rows; a.delta = r.delta; a.neox = neox;
+  a.per_head = (u32)rope_split_per_head(kv, r);
+  const long long nitems = (long long)ntok * kv->num_heads * a.per_head;  // of one layer (< 2^31: rope_split_ok)
+  a.nitems = (u32)nitems;
+  HIP_TRY(hipSetDevice(c->device));
+  long long blocks = (nitems + 255) / 256;
+  const long long cap = std::max(1ll, 64ll * c->num_cus / kv->num_layers);  // grid-stride beyond 64 blocks per CU
+  if (blocks > cap) blocks = cap;
+  const dim3 grid((unsigned)blocks, (unsigned)kv->num_layers);
+  const size_t lds = vec && !r.deltas ? (size_t)r.rot_dim * sizeof(float) : 0;  // the one table row of a uniform delta
+  with_kv_dtype16(kv->dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (!vec) hipLaunchKernelGGL((k_rope_split_elem<DT>), grid, dim3(256), 0, stream, a);
+    else with_bool(neox, [&](auto nx) { hipLaunchKernelGGL((k_rope_split_vec<DT, decltype(nx)::value>), grid, dim3(256), lds, stream, a); });
+  });
+  HIP_TRY(hipGetLastError());
+  return LMC_OK;
+}
+
 // ---- the post-op of a layer range (lmc_range_post): between a range's decode and its event --------------------------
 // Layers [l0, l0 + nl) of a layout as a layout of nl layers: the plane table is layer-major (lmc_plane_base), so the
 // window is a pointer into it, or the base moved by l0 layer strides.  The rope and copy kernels need nothing else.
@@ -1473,8 +1520,21 @@ static RopeSpec post_rope(const lmc_range_post* p) {
   return r;
 }
 // The whole post-op against lmc_copy_kv's and lmc_rope_shift's rules, before anything of the job is queued.
+// A rotation of a split `dst` that names ITSELF as the scatter target: the range's final place is where the decoder put
+// it, and the keys are rotated there (lmc_rope_shift_split per range; nothing is copied).  scatter_dst must describe the
+// same cache, every field equal, and token i of it be token i of `dst`.
+static bool post_in_place(const lmc_kv_layout* dst, const lmc_range_post* p) {
+  const lmc_kv_layout* s = p->scatter_dst;
+  if (!dst || dst->paged_kind != LMC_PAGED_SPLIT || !p->cos_sin || !s || p->scatter_tok0 != p->tok_begin) return false;
+  return s->dtype == dst->dtype && s->num_layers == dst->num_layers && s->num_heads == dst->num_heads &&
+         s->head_size == dst->head_size && s->base == dst->base && s->plane_ptrs == dst->plane_ptrs &&
+         s->stride_layer == dst->stride_layer && s->stride_kv == dst->stride_kv && s->stride_token == dst->stride_token &&
+         s->stride_head == dst->stride_head && s->slot_mapping == dst->slot_mapping && s->block_size == dst->block_size &&
+         s->paged_kind == dst->paged_kind && s->stride_block == dst->stride_block;
+}
 static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* p) {
   if (!p || (!p->cos_sin && !p->scatter_dst)) return true;
+  if (post_in_place(dst, p)) return rope_split_ok(dst, p->tok_begin, p->ntok, post_rope(p));
   if (p->scatter_dst && (p->scatter_dst->paged_kind != LMC_PAGED_SPLIT ||
                          !copy_kv_ok(dst, p->tok_begin, p->ntok, p->scatter_dst, p->scatter_tok0)))
     return false;
@@ -1485,6 +1545,7 @@ static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* p) {
 static int range_post(lmc_ctx* c, const lmc_kv_layout* dst, const lmc_range_post* p, int l0, int nl, hipStream_t s) {
   if (!p->cos_sin && !p->scatter_dst) return LMC_OK;
   const lmc_kv_layout rows = layer_window(dst, l0, nl);
+  if (post_in_place(dst, p)) return rope_split_launch(c, &rows, p->tok_begin, p->ntok, post_rope(p), nullptr, s);  // (`rows`: the split window)
   if (!p->scatter_dst) return rope_launch(c, &rows, p->tok_begin, p->ntok, post_rope(p), nullptr, s);
   // rotation and scatter: the staged rows are rotated in place, then scattered (a scatter that rotates on the way was built
   // and measured slower than these two launches: profiles/paged_layerwise.md)
@@ -1528,6 +1589,14 @@ int lmc_rope_shift(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, int32
   const RopeSpec r = {cos_sin, table_rows, rot_dim, is_neox, delta, deltas};
   if (!c || !rope_ok(kv, tok_begin, ntok, r)) return LMC_ERR_INVALID;
   return rope_launch(c, kv, tok_begin, ntok, r, job_status, (hipStream_t)stream);
+}
+
+int lmc_rope_shift_split(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const float* cos_sin,
+                         int32_t table_rows, int32_t rot_dim, int32_t is_neox, int32_t delta, const int32_t* deltas,
+                         uint32_t* job_status, lmc_stream_t stream) {
+  const RopeSpec r = {cos_sin, table_rows, rot_dim, is_neox, delta, deltas};
+  if (!c || !rope_split_ok(kv, tok_begin, ntok, r)) return LMC_ERR_INVALID;
+  return rope_split_launch(c, kv, tok_begin, ntok, r, job_status, (hipStream_t)stream);
 }
 
 }  // extern "C"

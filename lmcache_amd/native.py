@@ -211,6 +211,7 @@ SYMBOLS = {
     "lmc_pack_chunk_bytes": (ctypes.c_int, [_vp, _u64, _i32, ctypes.POINTER(ctypes.c_uint32)]),
     "lmc_copy_kv": (ctypes.c_int, [_vp, _PL, _i32, _i32, _PL, _i32, _vp]),
     "lmc_rope_shift": (ctypes.c_int, [_vp, _PL, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "lmc_rope_shift_split": (ctypes.c_int, [_vp, _PL, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "lmc_kv_deviation": (ctypes.c_int, [_vp, _PL, _i32, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp]),
     "lmc_select_topk": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "lmc_pinned_alloc": (ctypes.c_int, [_sz, ctypes.POINTER(_vp)]),
@@ -670,7 +671,9 @@ class RangePost:
     """Python owner of what becomes one lmc_range_post per decode job: a rotation as Context.rope_shift takes it and / or
     the LMC_PAGED_SPLIT cache the decode destination (then a staged chunk of rows) is scattered into.  Written in the
     decode destination's tokens: deltas[t] belongs to destination token t, and destination token t goes to token
-    scatter_tok0 + t of scatter_dst.  Keeps the tensors the kernels read alive."""
+    scatter_tok0 + t of scatter_dst.  A rotation whose scatter_dst is the (PAGED_SPLIT) decode destination ITSELF, with
+    scatter_tok0 0, is the in-place form: the decoder wrote the split blocks and the keys are rotated there
+    (lmc_rope_shift_split), nothing is copied.  Keeps the tensors the kernels read alive."""
 
     def __init__(self, cos_sin: Optional[torch.Tensor] = None, rot_dim: int = 0, is_neox: bool = True, delta: int = 0,
                  deltas: Optional[torch.Tensor] = None, scatter_dst: Optional["KVLayout"] = None, scatter_tok0: int = 0):
@@ -685,6 +688,13 @@ class RangePost:
         dropped, and the last chunk ends with the destination."""
         t0 = max(0, dst_tok0)
         return t0, min(dst.ntokens, dst_tok0 + nchunks * chunk_tokens) - t0
+
+    def in_place(self, dst: "KVLayout") -> bool:
+        """Whether this post rotates a PAGED_SPLIT `dst` where it lies: a rotation whose scatter target is `dst` itself
+        (the same cache, every field of the two lmc_kv_layout equal, token for token)."""
+        s = self.scatter_dst
+        return (self.cos_sin is not None and s is not None and self.scatter_tok0 == 0
+                and dst.struct.paged_kind == PAGED_SPLIT and (s is dst or bytes(s.struct) == bytes(dst.struct)))
 
     def struct(self, tok_begin: int, ntok: int) -> RangePostStruct:
         """The lmc_range_post of the job that fills destination tokens [tok_begin, +ntok): filled per call, nothing kept."""
@@ -703,7 +713,12 @@ class RangePost:
     def apply(self, ctx: "Context", dst: "KVLayout", tok_begin: int, ntok: int) -> None:
         """The same work from Python, for ALL layers of destination tokens [tok_begin, +ntok), on the current stream:
         lmc_rope_shift on the rows, then lmc_copy_kv into scatter_dst.  For retrieve_into_paged, and for the tiers whose
-        decode is not cut by the C side."""
+        decode is not cut by the C side.  A PAGED_SPLIT `dst` that the post names as its own scatter target (the in-place
+        form of lmc_range_post) was filled where it is: lmc_rope_shift_split there, and nothing is copied."""
+        if self.in_place(dst):
+            ctx.rope_shift_split(dst, tok_begin, ntok, self.cos_sin, self.rot_dim, self.is_neox, delta=self.delta,
+                                 deltas=None if self.deltas is None else self.deltas[tok_begin:tok_begin + ntok])
+            return
         if self.cos_sin is not None:
             ctx.rope_shift(dst, tok_begin, ntok, self.cos_sin, self.rot_dim, self.is_neox, delta=self.delta,
                            deltas=None if self.deltas is None else self.deltas[tok_begin:tok_begin + ntok])
@@ -1093,6 +1108,17 @@ class Context:
         self._call("lmc_rope_shift", layout.device, stream, ctypes.byref(layout.struct), tok_begin, ntok, cos_sin.data_ptr(),
                    cos_sin.shape[0], rot_dim, 1 if is_neox else 0, int(delta), None if deltas is None else deltas.data_ptr(),
                    job_status)
+
+    def rope_shift_split(self, layout: KVLayout, tok_begin: int, ntok: int, cos_sin: torch.Tensor, rot_dim: int,
+                         is_neox: bool = True, delta: int = 0, deltas: Optional[torch.Tensor] = None,
+                         job_status: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """lmc_rope_shift_split: rope_shift for a PAGED_SPLIT ("NHDB") layout of bf16 / fp16 -- the keys are re-rotated in
+        the split blocks themselves, behind a decode that stored into them directly.  Arguments as rope_shift's; a rows
+        layout is refused here (NativeError) as a split one is there."""
+        self._check_rope_args(cos_sin, rot_dim, deltas, ntok)
+        self._call("lmc_rope_shift_split", layout.device, stream, ctypes.byref(layout.struct), tok_begin, ntok,
+                   cos_sin.data_ptr(), cos_sin.shape[0], rot_dim, 1 if is_neox else 0, int(delta),
+                   None if deltas is None else deltas.data_ptr(), job_status)
 
     def kv_deviation(self, a: KVLayout, a_layer: int, a_tok0: int, b: KVLayout, b_layer: int, b_tok0: int, ntok: int,
                      dev_k: Optional[torch.Tensor] = None, dev_v: Optional[torch.Tensor] = None,
