@@ -78,7 +78,10 @@ __device__ __forceinline__ void rtab_to_lds(u32* rtab_lds) {
 // the coding pass reads a symbol dword for the last time: the load says so (non-temporal), so that what is touched
 // once does not push what is still needed out of L2 / Infinity Cache (same box: 1.017-1.027 -> 0.968-0.975 ms together
 // with the non-temporal raw-KV loads and stream stores of the fused kernel)
-#define LMC_SYM_LAST_LOAD(p) __builtin_nontemporal_load((const LMC_GLOBAL u32*)(p))
+// (through the stream's descriptor, SymBlocks below: the cache-policy operand 2 is the bit the stream stores pass as
+// `NT ? 2 : 0` -- slc in the intrinsic's numbering, which gfx950 prints as `nt`, what __builtin_nontemporal_load gave the
+// global_load this was until the symbol blocks moved to buffer loads)
+#define LMC_SYM_LAST_LOAD(rsrc, voff, soff) ((u32)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(voff), (int)(soff), 2 /* nt */))
 
 #define CNT_TAB_DWORDS 1024  // per wave: counters, then (aliased) the table: [16][64] u32, or [32][64] u16
 
@@ -158,6 +161,39 @@ __device__ __forceinline__ CountsStream counts_stream_of(const EncodeArgs& a, in
   s.nib = lmc_sym_nibbles((int)a.bins.b[s.p]);
   s.R = (u32)a.bins.b[s.p] - 1u;
   return s;
+}
+
+// The stream's symbol blocks as both passes fetch them: one wave-uniform buffer descriptor over the dword rows of the
+// stream's plane-chunk region that hold tokens (`rows` of C dwords: at most 256 KB, so every offset below fits its
+// 32-bit field whatever the context size), the lane's channel in the vector offset, the dword row in the scalar
+// offset.  Against the 64-bit per-lane pointer this replaces: no address arithmetic per load (row * C was a 64-bit
+// scalar multiply and a 64-bit vector add, with C re-read from the kernel arguments -- a wait for lgkmcnt(0), which also
+// drains the token pipeline's LDS reads), no pointer pair held in VGPRs, and no exec mask around the load: a lane
+// without a channel carries a vector offset past every range and reads 0 by the descriptor's range check.
+// Rows that may lie behind the last one (the partial block of a chunk that is no multiple of 32 tokens) go through
+// load_tail, the row in the VECTOR offset: the range check is documented for that operand on every target, and a row
+// at or past `rows` reads 0 without touching memory.
+struct SymBlocks {
+  __amdgpu_buffer_rsrc_t rsrc;
+  u32 voff;  // 4 * the lane's channel; a lane without a channel: 1 GiB, out of range with any row added
+  u32 rowb;  // bytes between consecutive dword rows, 4 * C (wave-uniform, in an SGPR)
+  // the row at byte offset `soff` (a multiple of rowb, wave-uniform) of a whole block: always below `rows`
+  __device__ __forceinline__ u32 load(u32 soff) const { return (u32)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, (int)soff, 0); }
+  __device__ __forceinline__ u32 load_last(u32 soff) const { return LMC_SYM_LAST_LOAD(rsrc, voff, soff); }
+  // row `row` (wave-uniform), which may be at or past `rows`: 0 then
+  __device__ __forceinline__ u32 load_tail(u32 row) const { return (u32)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(voff + row * rowb), 0, 0); }
+  __device__ __forceinline__ u32 load_tail_last(u32 row) const { return LMC_SYM_LAST_LOAD(rsrc, voff + row * rowb, 0); }
+};
+__device__ __forceinline__ SymBlocks sym_blocks_of(const EncodeArgs& a, const CountsStream& s, int rows) {
+  SymBlocks sb;
+  u32 rowb = (u32)__builtin_amdgcn_readfirstlane(4 * a.C);
+  // (opaque: otherwise the loops re-read C from the kernel arguments where they use it)
+  asm volatile("" : "+s"(rowb));
+  sb.rowb = rowb;
+  sb.voff = s.active ? 4u * (u32)s.c : 0x40000000u;
+  // built like the coder's out_rsrc below: from readfirstlane'd values, so that the compiler knows it uniform
+  sb.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)uniform_ptr64(s.symq - s.c), (short)0, (int)((u32)rows * rowb), 0x00020000);
+  return sb;
 }
 
 // A stream between its two passes: the lane's STORED counts (lmc_format.h: a count of 256 reads 255; a lane without
@@ -274,14 +310,23 @@ __device__ __forceinline__ u32 counts_hist_stream(const EncodeArgs& a, const Cou
     for (int i = 0; i < 16; i++) tabmem[i * 64 + lane] = 0;
     const u32 col = NIB ? tab_addr + 4u * (u32)lane : tab_addr + 4u * (u32)(lane >> 1);
     const u32 one = NIB ? 1u : 1u << ((lane & 1) * 16);
+    const SymBlocks sb = sym_blocks_of(a, s, rows);
     u32 w[DPB], wn[DPB];
 #pragma unroll
-    for (int j = 0; j < DPB; j++) w[j] = (s.active && j < rows) ? s.symq[(long long)j * a.C] : 0u;
+    for (int j = 0; j < DPB; j++) w[j] = sb.load_tail((u32)j);
+    u32 soff = 0;  // byte offset of block b's first row
     for (int b = 0; b < NB; b++) {
-      if (b + 1 < NB || rem) {
+      soff += (u32)DPB * sb.rowb;
+      if (b + 1 < NB) {  // a whole block: the rows step through the scalar offset
+        u32 so = soff;
 #pragma unroll
-        for (int j = 0; j < DPB; j++)
-          wn[j] = (s.active && (b + 1) * DPB + j < rows) ? s.symq[(long long)((b + 1) * DPB + j) * a.C] : 0u;
+        for (int j = 0; j < DPB; j++) {
+          wn[j] = sb.load(so);
+          so += sb.rowb;
+        }
+      } else if (rem) {  // the partial block behind the last whole one
+#pragma unroll
+        for (int j = 0; j < DPB; j++) wn[j] = sb.load_tail((u32)((b + 1) * DPB + j));
       }
       static_for<32>([&](auto itag) {
         constexpr int i = decltype(itag)::value;
@@ -503,24 +548,32 @@ __device__ __forceinline__ u32 counts_code_stream(const EncodeArgs& a, const Cou
     }
   };
   // state update x += (x / f) * (512 - f) + start, the quotient by the frequency's reciprocal {m, shc}
+  // (volatile, "memory": no arithmetic reason -- the blocks touch no memory.  They keep the step's two table reads where
+  // the source puts them, one on either side of this block.  The hazard pass takes any asm block that writes a register
+  // for a partial (dst_sel) write and wants one wait state in front of an asm block that reads it, and it counts an asm
+  // block in between as none: with nothing but the row-address block between this block's write of x and emit's read
+  // of it, it put an s_nop 0 there in every step that had no s_waitcnt in that place -- 13 of a nibble block's 32 steps,
+  // 30 of a byte block's.  A ds_read is an instruction it counts.)
   auto rans_put_nib = [&](u32 e, u32 m, u32 shc) {
     u32 q;
-    asm("v_mul_hi_u32 %[q], %[x], %[m]\n\t"
+    asm volatile("v_mul_hi_u32 %[q], %[x], %[m]\n\t"
         "v_lshrrev_b32_sdwa %[q], %[shc], %[q] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD\n\t"
         "v_mad_u32_u24 %[x], %[q], %[shc], %[x]\n\t"
         "v_add_u32_sdwa %[x], %[x], %[e] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
         : [x] "+v"(x), [q] "=&v"(q)
-        : [m] "v"(m), [shc] "v"(shc), [e] "v"(e));
+        : [m] "v"(m), [shc] "v"(shc), [e] "v"(e)
+        : "memory");
   };
   auto rans_put_byte = [&](_Float16 e, u32 m, u32 shc) {
     u32 q, st2;
-    asm("v_mul_hi_u32 %[q], %[x], %[m]\n\t"
+    asm volatile("v_mul_hi_u32 %[q], %[x], %[m]\n\t"
         "v_lshrrev_b32_sdwa %[q], %[shc], %[q] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD\n\t"
         "v_lshlrev_b32_sdwa %[st2], 1, %[e] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
         "v_mad_u32_u24 %[x], %[q], %[shc], %[x]\n\t"
         "v_add_u32_e32 %[x], %[x], %[st2]"
         : [x] "+v"(x), [q] "=&v"(q), [st2] "=&v"(st2)
-        : [m] "v"(m), [shc] "v"(shc), [e] "v"(e));
+        : [m] "v"(m), [shc] "v"(shc), [e] "v"(e)
+        : "memory");
   };
 
   auto pass2 = [&](auto nib_tag) {
@@ -585,12 +638,25 @@ __device__ __forceinline__ u32 counts_code_stream(const EncodeArgs& a, const Cou
       }
       wb = wbn;
     };
+    const SymBlocks sb = sym_blocks_of(a, s, rows);
+    const u32 blockb = (u32)DPB * sb.rowb;      // bytes of a block's DPB rows
+    u32 soff = (u32)max(NB - 1, 0) * blockb;    // byte offset of the current block's first row: steps down by scalar adds
     u32 w[DPB], wn[DPB];
-    // the last whole block (the first one coded), and in wn the partial block behind it
+    // the last whole block (the first one coded), and in wn the partial block behind it (all of this wave-uniform:
+    // scalar branches)
 #pragma unroll
-    for (int j = 0; j < DPB; j++) {
-      w[j] = (NB > 0 && s.active) ? LMC_SYM_LAST_LOAD(s.symq + (long long)((NB - 1) * DPB + j) * a.C) : 0u;
-      wn[j] = (rem && s.active && NB * DPB + j < rows) ? LMC_SYM_LAST_LOAD(s.symq + (long long)(NB * DPB + j) * a.C) : 0u;
+    for (int j = 0; j < DPB; j++) w[j] = wn[j] = 0u;
+    if (NB > 0) {
+      u32 so = soff;
+#pragma unroll
+      for (int j = 0; j < DPB; j++) {
+        w[j] = sb.load_last(so);
+        so += sb.rowb;
+      }
+    }
+    if (rem) {
+#pragma unroll
+      for (int j = 0; j < DPB; j++) wn[j] = sb.load_tail_last((u32)(NB * DPB + j));
     }
     // ---- the partial block of a chunk whose length is no multiple of 32 (tokens Tc - 1 .. 32 NB; round 5): a plain
     // loop -- the token's dword by wave-uniform selects, entry and reciprocal fetched where they are needed, the buffer
@@ -609,6 +675,10 @@ __device__ __forceinline__ u32 counts_code_stream(const EncodeArgs& a, const Cou
       if constexpr (NIB) rans_put_nib(E, R.x, R.y);
       else rans_put_byte(E, R.x, R.y);
     }
+    // (behind a single whole block the loop's last four steps read their look-ahead rows from wn: row 0 then, not whatever
+    // a partial dword holds behind the chunk's last token)
+#pragma unroll
+    for (int j = 0; j < DPB; j++) wn[j] = 0u;
 #ifdef LMC_EXP_SKIP_TOKEN_LOOP  // instruction-count experiments (tools/scripts/quick_pmc.sh): everything but pass 2's token loop
     return;
 #endif
@@ -618,17 +688,31 @@ __device__ __forceinline__ u32 counts_code_stream(const EncodeArgs& a, const Cou
     // leaves the previous step's three LDS operations in flight.  The step's asm block works out the address of the
     // reciprocal and appends the step's words -- under exec = emitting lanes: v_cmpx on the state's upper half against
     // the entry's (count << 7), mbcnt rank, ds_write_b16 into the staging buffer, x >>= 16, exec restored (`emit` above) --
-    // and the loads are plain loads the compiler tracks, issued right behind the block (behind the buffer store in the
-    // LDS queue).
+    // and the loads are plain loads the compiler tracks, issued behind the block (behind the buffer store in the
+    // LDS queue): the reciprocal's right behind it, the entry's behind the state update -- in front of the next step's
+    // block, see rans_put_nib.
+    // (the four entry reads stay in front of the two reciprocal reads -- sched_barrier: left to the scheduler, E2's read
+    // went behind them, the first step needs it, and the loop's header waited for lgkmcnt(0) in every block because of
+    // what its FIRST entry finds in the queue)
     ET E0 = entry_at(row_addr_cnt<NIB, 31, NT>(w, col));
     ET E1 = entry_at(row_addr_cnt<NIB, 30, NT>(w, col));
     ET E2 = entry_at(row_addr_cnt<NIB, 29, NT>(w, col));
     ET E3 = entry_at(row_addr_cnt<NIB, 28, NT>(w, col));
+    __builtin_amdgcn_sched_barrier(0);
     u32x2_t R0 = rtab_of(E0);
     u32x2_t R1 = rtab_of(E1);
     for (int b = NB - 1; b >= 0; b--) {
+      // the next block's DPB rows, under ONE scalar branch; behind the last block wn keeps what it holds -- symbols of
+      // this stream (or zeros), which the last four steps turn into table addresses that are read and never used
+      if (b > 0) {
+        soff -= blockb;
+        u32 so = soff;
 #pragma unroll
-      for (int j = 0; j < DPB; j++) wn[j] = (b > 0 && s.active) ? LMC_SYM_LAST_LOAD(s.symq + (long long)((b - 1) * DPB + j) * a.C) : 0u;
+        for (int j = 0; j < DPB; j++) {
+          wn[j] = sb.load_last(so);
+          so += sb.rowb;
+        }
+      }
       static_for<32>([&](auto itag) {
         constexpr int i = 31 - decltype(itag)::value;  // token of the block, descending
         u32 ad4;  // row address of the token four further on (past the last block: row 0, read and never used)
@@ -637,10 +721,10 @@ __device__ __forceinline__ u32 counts_code_stream(const EncodeArgs& a, const Cou
         u32 ra;
         emit(E0, E2, ra);  // (wb += 2 * words)
         const u32x2_t R2 = *(const __attribute__((address_space(3))) u32x2_t*)(size_t)(rtab_addr + ra);
-        const ET E4 = entry_at(ad4);
         if constexpr ((i & 1) == 0) flush_ring();  // every second token: the buffer holds 128 + 2 x 64 words
         if constexpr (NIB) rans_put_nib(E0, R0.x, R0.y);
         else rans_put_byte(E0, R0.x, R0.y);
+        const ET E4 = entry_at(ad4);
         E0 = E1; E1 = E2; E2 = E3; E3 = E4;
         R0 = R1; R1 = R2;
       });

@@ -463,6 +463,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     if (j < NS) {
       u32 beg = wg_excl;
       for (int k = 0; k < j; k++) beg += st_alloc[k];
+      // (wave-uniform, said so: summed from LDS it is a VGPR to the compiler, and with it `out` -- a 64-bit pointer per lane
+      // held across counts_open_stream, where the kernel is short of registers: 20 -> 12 bytes of scratch, GL = 64)
+      beg = (u32)__builtin_amdgcn_readfirstlane((int)beg);
       const u32 alloc = st_alloc[j];
       const CountsStream s = stream_of(j);
       u8* const out = blob + bo.streams + beg;
