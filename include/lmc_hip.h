@@ -466,6 +466,46 @@ int lmc_decode_chunks_fixed_split_schedule(lmc_ctx* ctx, const void* const* blob
                                            int32_t nranges, const int32_t* layer_ends_h, const lmc_event_t* events_h,
                                            const lmc_range_post* post, uint32_t* job_status, lmc_stream_t stream);
 
+/*
+ * A WINDOW OF HEADS out of every blob (additive in ABI 6): KV stored under one tensor-parallel degree, retrieved under
+ * another.  The blobs have src_heads heads; heads [src_head_begin, src_head_begin + nheads) of every blob are written to
+ * heads [dst_head_begin, dst_head_begin + nheads) of `dst`, whose num_heads is ITS OWN (a TP = 8 rank takes one eighth of
+ * a TP = 1 blob; a TP = 2 rank fills its destination from four TP = 8 blob sets with four calls).  The streams of a plane
+ * are independent per 64-channel group and the directory gives random access to them (lmc_format.h), so a launch reads
+ * only the streams of the groups the window touches -- the random access lmc_decode_chunks_layers uses along the layers,
+ * along the heads.  A channel that shares a group with the window but lies outside it is decoded and not stored.
+ *   dst->num_heads   the destination's head count;  dst->head_size must be the blobs' D (header word 6)
+ *   win              required.  LMC_ERR_INVALID, nothing queued: win NULL, src_heads < 1, nheads < 1, a window outside
+ *                    [0, src_heads) or outside [0, dst->num_heads), src_heads * D not a multiple of 8 or above
+ *                    LMC_MAX_CHANNELS, and whatever the twin refuses for `dst`
+ * Everything else is the twin's -- lmc_decode_chunks_schedule for the coded models (rows, paged rows, LMC_PAGED_SPLIT;
+ * 16-bit and fp8 elements), lmc_decode_chunks_fixed_split_schedule for LMC_MODEL_FIXED blobs (16-bit rows, paged rows,
+ * LMC_PAGED_SPLIT): blobs behind a pointer table, layer ranges with their events, the validation in front of every read.
+ * The decoders' 32-bit offset rule (lmc_kv_layout) is held against dst's own num_heads.  A blob whose header does not say
+ * num_heads == src_heads and head_size == dst->head_size is LMC_STATUS_BAD_HEADER; the scales of a plane are checked by
+ * the first group the window touches (LMC_STATUS_BAD_SCALES), the streams that are read by their own waves
+ * (LMC_STATUS_BAD_STREAM) -- damage in a stream outside the window's groups is not seen, it is not read.
+ * Only bytes of heads [dst_head_begin, dst_head_begin + nheads) of the call's own tokens are written.
+ * There is no `post`: a rotation or a scatter acts on all heads of `dst`, and a destination is typically filled by several
+ * window calls -- the caller queues lmc_rope_shift / lmc_copy_kv once, behind the last of them.
+ * A window that is the whole blob (src_heads == dst->num_heads, begins 0) launches exactly what the twin launches.
+ */
+typedef struct lmc_head_window {
+  int32_t src_heads;       /* H of the blobs (their header's num_heads)            */
+  int32_t src_head_begin;  /* first head taken out of every blob                    */
+  int32_t nheads;          /* heads taken                                           */
+  int32_t dst_head_begin;  /* head of dst that src_head_begin lands on              */
+} lmc_head_window;
+int lmc_decode_chunks_heads_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                     const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                     const int32_t* layer_ends_h, const lmc_event_t* events_h, const lmc_head_window* win,
+                                     uint32_t* job_status, lmc_stream_t stream);
+/* ... the same for LMC_MODEL_FIXED blobs (k_fixed_decode; one body with the call above). */
+int lmc_decode_chunks_fixed_heads_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes,
+                                           int32_t nchunks, const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens,
+                                           int32_t nranges, const int32_t* layer_ends_h, const lmc_event_t* events_h,
+                                           const lmc_head_window* win, uint32_t* job_status, lmc_stream_t stream);
+
 /* Entropy-decode only (debug / parity): blob -> sym_out int8 [P][T][C].
  * Stands where torchac_cuda.decode_fast_prefsum stands (cachegen_decoder.py:65-66). */
 int lmc_decode_symbols(lmc_ctx* ctx, const void* blob, int32_t L, int32_t H, int32_t D, int8_t* sym_out,

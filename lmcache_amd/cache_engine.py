@@ -25,7 +25,7 @@ from typing import Dict, Iterable, List, Optional, Tuple, Union
 
 import torch
 
-from lmcache_amd import native
+from lmcache_amd import native, resharding
 from lmcache_amd.config import LMCacheEngineConfig, LMCacheEngineMetadata
 from lmcache_amd.logging import init_logger
 from lmcache_amd.rope import RopeShift
@@ -57,9 +57,11 @@ class LMCacheEngine:
         logger.debug("Current storage backend type %s", type(self.engine_))
 
     # ------------------------------------------------------------------ index (pure Python)
-    def _make_key(self, chunk_hash: str, fmt: str) -> CacheEngineKey:
+    def _make_key(self, chunk_hash: str, fmt: str, shard: Optional[Tuple[int, int]] = None) -> CacheEngineKey:
+        """shard: (world_size, worker_id) of the store that wrote the chunk, where that is not this engine's own."""
         m = self.metadata
-        return CacheEngineKey(fmt, m.model_name, m.world_size, m.worker_id, chunk_hash)
+        ws, wid = (m.world_size, m.worker_id) if shard is None else shard
+        return CacheEngineKey(fmt, m.model_name, ws, wid, chunk_hash)
 
     def _num_tokens_in_kv(self, kv_tensors: Union[KVCache, torch.Tensor], fmt: str) -> int:
         return kv_tensors[0][0].shape[_token_dim(fmt)]
@@ -295,9 +297,17 @@ class LMCacheEngine:
     # ------------------------------------------------------------------ retrieve
     @_lmcache_nvtx_annotate
     @torch.no_grad()
-    def retrieve(self, tokens: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Tuple[KVCache, torch.Tensor]:
+    def retrieve(self, tokens: torch.Tensor, mask: Optional[torch.Tensor] = None, **resharding) -> Tuple[KVCache, torch.Tensor]:
         """Prefix hits only; `mask` (suffix mask) marks the tokens whose KV is wanted.
-        Returns (per-layer (K, V) tuple or (), ret_mask)."""
+        Returns (per-layer (K, V) tuple or (), ret_mask).
+        The named parameters are the reference's (tests/test_dropin_api.py holds this mirror to its signature); the one
+        keyword taken beyond them is stored_world_size: Optional[int] = None (anything else: TypeError):
+        retrieve(tokens, mask, stored_world_size=W) is stored_at(W).retrieve(tokens, mask) -- see stored_at."""
+        stored_world_size = resharding.pop("stored_world_size", None)
+        if resharding:
+            raise TypeError(f"retrieve() got an unexpected keyword argument {next(iter(resharding))!r}")
+        if stored_world_size is not None:
+            return self.stored_at(stored_world_size).retrieve(tokens, mask)
         target = _DenseTarget(self.metadata.fmt)
         got, ret_mask = self._retrieve_into(tokens, mask, target.make_dst)
         if got == 0:
@@ -350,11 +360,47 @@ class LMCacheEngine:
                 that token's keys as stored and raises LMC_STATUS_BAD_POSITION in the context's status word (a delta
                 tensor that lives on the CPU is checked here instead: ValueError).  A cos_sin that is not a contiguous
                 device fp32 table once moved to the cache's device is refused when the destination is made (ValueError
-                of native.RangePost), before the decode is queued."""
+                of native.RangePost), before the decode is queued.
+        On stored_at(W) -- the chunks were stored under another tensor-parallel degree -- the cache is still this rank's
+        own (its head count); the rotation and the staged scatter are queued ONCE, behind the last source's window.  With
+        direct=True the known caveat holds: slots of a miss may hold garbage."""
         target = _PagedTarget(self, tokens, kv_caches, slot_mapping, block_size, layout, mask, rope, direct)
         # (without jobs_out no decode job takes the post-ops: _retrieve_into queues them itself, native.RangePost.apply
         # over tokens [0, got) behind the last write, and only when the retrieve did not miss)
         return self._retrieve_into(tokens, mask, target.make_dst, post=target.post)[1]
+
+    def stored_at(self, stored_world_size: Optional[int]) -> "LMCacheEngine":
+        """This engine as it RETRIEVES chunks that an instance of another tensor-parallel degree stored: a view on the same
+        backend (same configuration and metadata; close the engine, not its views) whose retrieve() and
+        retrieve_into_paged() -- their signatures are the engine's, which tests/test_split_decode_host.py and
+        tests/test_paged_layerwise_host.py pin -- read across degrees:
+
+            engine.stored_at(1).retrieve_into_paged(tokens, kv_caches, slot_mapping, block_size, layout)
+
+        The keys are made with (stored_world_size, source rank) for every stored shard this rank's KV heads come from
+        (resharding.head_sources: contiguous head shards), a chunk is a hit only when ALL its shards are there (the usable
+        prefix is the minimum over the sources), and every source decodes its window of heads into the one destination,
+        whose head count is H_stored * stored_world_size / world_size.  None, or the engine's own world size: the engine
+        itself, today's path untouched.
+        ValueError, nothing queued: a backend without the window decode (the raw tiers, chunk-tensor backends) here; head
+        counts the two degrees do not divide once the stored geometry is known; retrieve_layerwise and
+        retrieve_into_paged_layerwise of a view (a window of heads has no per-range post-op)."""
+        if stored_world_size is None or int(stored_world_size) == self.metadata.world_size:
+            return self
+        if int(stored_world_size) < 1:
+            raise ValueError(f"stored_world_size must be a positive tensor-parallel degree, not {stored_world_size!r}")
+        if not (getattr(self.engine_, "supports_kv_layout", False) and getattr(self.engine_, "supports_head_window", False)):
+            raise ValueError("stored_world_size: this backend cannot take a window of heads out of a stored chunk (the "
+                             "CacheGen tiers of the local backend and the remote backends with remote_serde='cachegen' can)")
+        view = LMCacheEngine.__new__(LMCacheEngine)
+        view.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("_hash_chain", "_key_memo")})
+        view._stored_ws = int(stored_world_size)
+        return view
+
+    def _refuse_layerwise_view(self, what: str) -> None:
+        if getattr(self, "_stored_ws", None) is not None:
+            raise ValueError(f"{what} across tensor-parallel degrees is not built: a window of heads has no per-range "
+                             "post-op; use the one-piece call")
 
     def _direct_retrieve(self, direct: bool, layout: str, rope: Optional[RopeShift] = None) -> bool:
         """`direct` as the backend honours it.  The fixed-width HBM tier (local_serde="cachegen-fixed") decodes straight
@@ -404,7 +450,9 @@ class LMCacheEngine:
         model's layer l and a warm prefix costs the model almost nothing (bench.py: ttft_proxy).  Backends that
         cannot cut their retrieve by layer return one event that covers everything.  Call finish() before
         trusting the KV for good: it waits for the decode and raises if a stored blob was corrupt.
-        layers_per_launch: a range size, or a schedule of range sizes whose last entry repeats, e.g. (2, 6, 24)."""
+        layers_per_launch: a range size, or a schedule of range sizes whose last entry repeats, e.g. (2, 6, 24).
+        On a stored_at() view: ValueError, nothing queued."""
+        self._refuse_layerwise_view("retrieve_layerwise")
         target, jobs = _DenseTarget(self.metadata.fmt), []
         got, ret_mask = self._retrieve_into(tokens, mask, target.make_dst, layers_per_launch=layers_per_launch, jobs_out=jobs)
         if got == 0:
@@ -447,7 +495,9 @@ class LMCacheEngine:
         the post-ops in front of the events: layer 0 waits for that transfer.  The raw tiers and remote backends queue
         everything, then the post-ops for all layers behind it, and ONE event covers every layer: correct, not layer-wise.
         Call finish() before trusting the cache for good: it waits for the decode and raises NativeError if a stored
-        blob was corrupt -- the slots of the call's tokens may hold garbage then, as for retrieve_into_paged(direct=True)."""
+        blob was corrupt -- the slots of the call's tokens may hold garbage then, as for retrieve_into_paged(direct=True).
+        On a stored_at() view: ValueError, nothing queued."""
+        self._refuse_layerwise_view("retrieve_into_paged_layerwise")
         target, jobs = _PagedTarget(self, tokens, kv_caches, slot_mapping, block_size, layout, mask, rope, direct), []
         got, ret_mask = self._retrieve_into(tokens, mask, target.make_dst, layers_per_launch=layers_per_launch, jobs_out=jobs,
                                             post=target.post)
@@ -481,7 +531,11 @@ class LMCacheEngine:
         -> (got = tokens written, ret_mask).
         post: a callable, asked after make_dst, for the native.RangePost of this retrieve (or None).  The CacheGen tiers
         take it into their decode jobs (get_kv_range(post=...)); behind any other backend it is queued here (`pending`),
-        for all layers, once everything has been written."""
+        for all layers, once everything has been written.
+        A stored_at() view -- chunks stored under another tensor-parallel degree -- takes _retrieve_resharded."""
+        if getattr(self, "_stored_ws", None) is not None:
+            assert jobs_out is None and not layers_per_launch
+            return self._retrieve_resharded(tokens, mask, make_dst, post, self._stored_ws)
         t_start = time.perf_counter()
         fmt = self.metadata.fmt
         cs = self.chunk_size
@@ -582,6 +636,84 @@ class LMCacheEngine:
             ret_mask[num_skip_tok + nret:] = False
         logger.info("Retrieved %d chunks (%d tokens in total) -- elapsed time %.4f", hits, nret,
                     time.perf_counter() - t_start)
+        return nret, ret_mask
+
+    def _retrieve_resharded(self, tokens: torch.Tensor, mask: Optional[torch.Tensor], make_dst, post,
+                            stored_ws: int) -> Tuple[int, torch.Tensor]:
+        """_retrieve_into for chunks stored at tensor-parallel degree `stored_ws` (another than the engine's own): the
+        same prefix probe, first-chunk trim and ret_mask, with every hit chunk assembled from the stored shards this
+        rank's heads come from -- one get_kv_range(heads=...) per source into the one destination, the post-op queued
+        once behind the last."""
+        t_start = time.perf_counter()
+        fmt, cs, m = self.metadata.fmt, self.chunk_size, self.metadata
+        ret_mask = torch.ones_like(tokens, dtype=torch.bool)
+        num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
+        num_skip_chunk = num_skip_tok // cs
+        if num_skip_tok:
+            ret_mask[:num_skip_tok] = False
+        chunk_hashes = self._prefix_hashes_of(tokens, num_skip_chunk)
+
+        def miss():
+            ret_mask[:] = False
+            return 0, ret_mask
+
+        def keys_of(src_rank: int) -> List[CacheEngineKey]:
+            return [self._make_key(h, fmt, (stored_ws, src_rank)) for h in chunk_hashes]
+
+        def prefix(keys) -> int:
+            count = getattr(self.engine_, "contains_prefix", None)
+            if count is not None:
+                return count(keys)
+            hits = 0
+            for k in keys:
+                if not self.engine_.contains(k):
+                    break
+                hits += 1
+            return hits
+
+        # The geometry comes from the first source's first chunk; which rank that is does not depend on the head count
+        # (contiguous shards: rank floor(worker_id * stored_ws / world_size) holds this rank's first head).
+        first_rank = (m.worker_id * stored_ws) // m.world_size
+        first_keys = keys_of(first_rank)
+        if not first_keys or prefix(first_keys[:1]) == 0:
+            return miss()
+        try:
+            shape0, dtype = self.engine_.chunk_meta(first_keys[0])
+        except KeyError:  # gone since `contains`: a miss
+            return miss()
+        L = shape0[0]
+        H_src, D = (shape0[3], shape0[4]) if fmt == "vllm" else (shape0[2], shape0[4])
+        # (ValueError -- nothing has been queued yet -- where the two degrees do not both divide the model's KV heads)
+        sources = resharding.head_sources(H_src * stored_ws, m.world_size, m.worker_id, stored_ws)
+        H = H_src * stored_ws // m.world_size
+        src_keys = [first_keys if s == first_rank else keys_of(s) for s, _, _, _ in sources]
+        hits = min(prefix(keys) for keys in src_keys)  # a chunk counts only when all its shards are there
+        _, extra, nret = self.plan_retrieve(len(tokens), cs, num_skip_tok, hits)
+        if hits == 0 or nret <= 0:
+            return miss()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dst = make_dst(nret, L, H, D, dtype, dev)
+        pending = post() if post is not None else None
+        try:
+            for keys, (_, src_begin, nheads, dst_begin) in zip(src_keys, sources):
+                got = self.engine_.get_kv_range(keys[:hits], dst, fmt, -extra, cs,
+                                                heads=native.HeadWindow(H_src, src_begin, nheads, dst_begin))
+                hits = min(hits, hits if got is None else got)  # a shard that delivers fewer chunks shrinks the result
+                if hits == 0:
+                    break
+        except native.NativeError:
+            logger.exception("retrieve: a cached chunk failed to decode; treated as a miss")
+            hits = 0
+        _, extra, nret = self.plan_retrieve(len(tokens), cs, num_skip_tok, hits)
+        if hits == 0 or nret <= 0:
+            return miss()
+        if pending is not None:  # once, behind the last source's window: it acts on every head of dst
+            with torch.cuda.device(dst.device):
+                pending.apply(native.get_context(dst.device.index), dst, 0, nret)
+        if num_skip_tok + nret < len(ret_mask):
+            ret_mask[num_skip_tok + nret:] = False
+        logger.info("Retrieved %d chunks (%d tokens in total) from %d shards stored at TP = %d -- elapsed time %.4f", hits,
+                    nret, len(sources), stored_ws, time.perf_counter() - t_start)
         return nret, ret_mask
 
     def close(self):

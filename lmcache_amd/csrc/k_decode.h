@@ -85,6 +85,14 @@ struct DecodeArgs {
   const u32* out_bytes;
   int L, H, D, dtype, tok_end;
   BinsArg bins;
+  // Head window (lmc_decode_chunks_heads_schedule; k_fixed_decode reads the same fields): P, C, G above are the BLOB's, dst
+  // has a head count of its own, and of every blob the channels [wc_lo, wc_hi) -- whole heads -- are stored, head h of the
+  // blob as head h + wh_shift of dst.  A launch covers the groups the window touches, wg_lo .. wg_lo + wGw - 1, of every
+  // plane it takes: n = 2 layer_count wGw work items per chunk.  Every other call is the full window (decode_geometry):
+  // wc_lo = 0, wc_hi = C, wg_lo = 0, wGw = G, wh_shift = 0 and w_src_heads = 0, which asks nothing of header words 5 and 6
+  // (a window call holds them against w_src_heads and dst.D).  All of it is wave-uniform, and nothing of it is live in
+  // the token loop: the window is in the lane's voffset before the loop starts.
+  int wc_lo, wc_hi, wg_lo, wGw, wh_shift, w_src_heads;
 };
 
 // LDS of a workgroup: the four waves' dequantisation LUTs (32 x f32 = 128 B each) FIRST -- their byte addresses stay
@@ -170,7 +178,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   // (32-bit work-item arithmetic: lmc_api.hip rejects a launch of 2^31 streams or more, and a 64-bit division costs
   // more than a hundred instructions per stream)
   u32 gid = blockIdx.x * (u32)DEC_WAVES + (u32)wave;
-  const int n = 2 * a.layer_count * a.G;  // streams of a chunk in this launch
+  const int n = 2 * a.layer_count * a.wGw;  // streams of a chunk in this launch (wGw: the groups its head window touches)
   if (gid >= (u32)a.nchunks * (u32)n) return;
 #ifndef LMC_DEC_XCD_MAP
 #define LMC_DEC_XCD_MAP 1
@@ -182,10 +190,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     // plane's streams share one L2.  The launch's last, partial tile keeps the plain order.  Only where a token's row is
     // one run of bytes (heads back to back: contiguous decode -1.5 %); with the pieces of a row kilobytes apart -- paged
     // NHBD blocks -- the same map costs 3 - 5 % (profiles/r06_experiments.md section 13), so those keep the plain order.
-    const u32 tile = 8u * (u32)a.G, t0 = gid / tile * tile;
+    // (A head window launches wGw consecutive items per plane: the map runs on wGw, so a plane's streams still share an L2.)
+    const u32 tile = 8u * (u32)a.wGw, t0 = gid / tile * tile;
     if (a.dst.stride_head == (long long)a.dst.D && t0 + tile <= (u32)a.nchunks * (u32)n) {
       const u32 i = gid - t0;
-      gid = t0 + (i & 7u) * (u32)a.G + (i >> 3);
+      gid = t0 + (i & 7u) * (u32)a.wGw + (i >> 3);
     }
   }
   LMC_DTL(0, (unsigned long long)wall_clock64());
@@ -196,7 +205,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
 
   const int chunk = (int)(gid / (u32)n);
   const int r = (int)(gid - (u32)chunk * (u32)n);
-  const int pidx = r / a.G, g = r - pidx * a.G;
+  const int pidx = r / a.wGw, g = a.wg_lo + r - pidx * a.wGw;  // (the directory index stays p * G + g, G the blob's)
   // K planes of the layer range first, then their V planes (plane p = kv * L + layer)
   const int p = pidx < a.layer_count ? a.layer_begin + pidx : (a.P >> 1) + a.layer_begin + pidx - a.layer_count;
   const int pg = p * a.G + g;
@@ -236,6 +245,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   if (hdw(0) != LMC_BLOB_MAGIC || (hdw(1) & 0xffffu) != LMC_BLOB_VERSION || hdw(7) != (u32)a.C || T == 0u || T > 65535u ||
       !lmc_model_valid_dev(hdw(22), T) ||  // (the header's model is trusted: a round-3/4 blob of a short chunk is CDF16)
       hdw(8) != (u32)a.P || hdw(15) != bo.streams ||
+      (a.w_src_heads != 0 && (hdw(5) != (u32)a.w_src_heads || hdw(6) != (u32)a.dst.D)) ||  // a head window: the blob's heads
       // every section offset is a function of the fields checked above; the blob must also fit its slot
       (!SYMOUT && (T > (u32)a.chunk_tokens ||
                    (unsigned long long)hdw(a.seg_off ? 15 : 17) > (unsigned long long)a.blob_stride))) {
@@ -243,6 +253,9 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     return;
   }
   const int c = g * 64 + lane;
+  // `active`: the lane has a channel of the blob -- it decodes: its CDF column, its word pops (the 64 lanes share ONE
+  // interleaved word sequence, popped in ascending lane order) and the final-state check.  Whether it STORES is the head
+  // window's business alone (`stored`, in front of the token loop): a channel outside the window decodes exactly as ever.
   const bool active = c < a.C;
 
   // ---- FIXOUT: what a transcode adds (k_fixed_expand's list), then where the chunk's fixed-width blob puts this stream --
@@ -429,8 +442,9 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
   }
   // ---- dequantisation LUT; the per-token scales are fetched 64 tokens at a time inside the loop ----
   const u16* scl = reinterpret_cast<const u16*>(blob + bo.scales) + (long long)p * T;
-  if (!SYMOUT && g == 0) {  // the scales are the one section whose damage the coder cannot see: the plane's first wave
-                            // checks their checksum (every launch decodes all the groups of the planes it takes).
+  if (!SYMOUT && g == a.wg_lo) {  // the scales are the one section whose damage the coder cannot see: the plane's first wave
+                            // checks their checksum (every launch decodes all the groups of the planes it takes; with
+                            // a head window, the groups the window touches: the first of THOSE checks).
                             // The other G - 1 waves do not wait for the verdict: on LMC_ST_BAD_SCALES the destination's
                             // contents are UNDEFINED (include/lmc_hip.h says so; the engine turns any non-zero status
                             // into a miss and the caller recomputes those tokens).  Checking in every wave was measured
@@ -588,7 +602,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     ubase = (u64)(a.sym_out + (long long)p * T * a.C);
     lane_off = (u32)c;
   } else {
-    const int h = c / a.dst.D, d = c - h * a.dst.D;
+    const int hs = c / a.dst.D, d = c - hs * a.dst.D, h = hs + a.wh_shift;  // head of the blob -> head of dst
     if constexpr (SPLIT) {  // K: granule d / x of the head, element d % x of the granule; V: column d of the head
       constexpr u32 X = 16u / (u32)ESZ;
       const u32 bs = (u32)a.dst.block_size;
@@ -865,7 +879,10 @@ __global__ __launch_bounds__(64 * DEC_WAVES) __attribute__((amdgpu_waves_per_eu(
     const long long row_step = SPLIT ? (kv_v ? (long long)ESZ : 16ll) : a.dst.stride_token * ESZ;
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(ubase + (u64)((long long)(tdst0 + (int)nskip) * row_step)), (short)0, (int)0xfffffff0u, 0x00020000);
-    const u32 voff = active ? lane_off : 0xfffffff8u;
+    // (a channel outside the head window is parked with them: every store path below -- rows, paged rows, the split kind's
+    // wide V stores and K granules, the one-token loop -- takes its lane offset from voff)
+    const bool stored = active && c >= a.wc_lo && c < a.wc_hi;
+    const u32 voff = stored ? lane_off : 0xfffffff8u;
     u32 soff = 0;
     // per-token scales: lane i of `sc` holds the fp32 scale of token t0 + i (64 tokens per block), fetched with
     // one coalesced load a block ahead and handed to all lanes with v_readlane

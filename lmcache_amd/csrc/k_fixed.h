@@ -270,7 +270,7 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const u32 gid = blockIdx.x * (u32)FIXED_DEC_WAVES + (u32)wave;
-  const int n = 2 * a.layer_count * a.G;  // streams of a chunk in this launch
+  const int n = 2 * a.layer_count * a.wGw;  // streams of a chunk in this launch (wGw: the groups its head window touches)
   if (gid >= (u32)a.nchunks * (u32)n) return;
   u32* const lo_t = lds_all + wave * FIXED_DEC_WAVE_DWORDS;
   u32* const hi_t = lo_t + 256;
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
   float* const lut = sc_t + 32;
   const int chunk = (int)(gid / (u32)n);
   const int r = (int)(gid - (u32)chunk * (u32)n);
-  const int pidx = r / a.G, g = r - pidx * a.G;
+  const int pidx = r / a.wGw, g = a.wg_lo + r - pidx * a.wGw;  // (a.C, a.G and the directory index are the blob's)
   const int p = pidx < a.layer_count ? a.layer_begin + pidx : (a.P >> 1) + a.layer_begin + pidx - a.layer_count;
   const u8* const blob = a.blob_ptrs ? (const u8*)uniform_ptr(a.blob_ptrs[chunk]) : a.blobs + (long long)chunk * a.blob_stride;
   auto fail = [&](u32 bit) { if (lane == 0) atomicOr(a.status, bit); };
@@ -290,6 +290,7 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
   const BlobOff bo = lmc_blob_off((u32)a.P, T, (u32)a.G);
   if (hdw(0) != LMC_BLOB_MAGIC || (hdw(1) & 0xffffu) != LMC_BLOB_VERSION || hdw(7) != (u32)a.C || T == 0u || T > 65535u ||
       T > (u32)a.chunk_tokens || hdw(8) != (u32)a.P || hdw(22) != LMC_MODEL_FIXED || hdw(15) != bo.streams ||
+      (a.w_src_heads != 0 && (hdw(5) != (u32)a.w_src_heads || hdw(6) != (u32)a.dst.D)) ||  // a head window: the blob's heads
       (src_dtype != (u32)LMC_DTYPE_BF16 && src_dtype != (u32)LMC_DTYPE_FP16) ||
       (unsigned long long)hdw(15) + (unsigned long long)hdw(16) != (unsigned long long)hdw(17) ||
       (unsigned long long)hdw(17) > (unsigned long long)a.blob_stride) {
@@ -320,7 +321,7 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
   const bool wide = bins_p > LMC_FIXED_NARROW_BINS;  // (wave-uniform)
 
   const u16* const scl = reinterpret_cast<const u16*>(blob + bo.scales) + (long long)p * T;
-  if (g == 0) {  // the plane's first wave checks the scales (k_decode.h: the others do not wait for the verdict)
+  if (g == a.wg_lo) {  // the plane's first wave of the launch checks the scales (k_decode.h: the others do not wait for the verdict)
     const u32 want = (u32)__builtin_amdgcn_readfirstlane((int)((const LMC_GLOBAL u32*)(blob + bo.scsum))[p]);
     if (scale_checksum(scl, T, lane) != want) return fail(LMC_ST_BAD_SCALES);
   }
@@ -332,11 +333,17 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
 
   // ---- destination ---------------------------------------------------------------------------------------------------
   typedef typename KvElem<DT_OUT>::T E;
+  // Head window (DecodeArgs): channels [wc_lo, wc_hi) of the blob are stored, head h as head h + wh_shift of dst.  There is
+  // no dependency between lanes here, so a lane outside the window skips its stores; every lane still takes part in the
+  // loads, which the stream's check word is summed over.  The window's edges are multiples of D: where D % 8 == 0 a lane's
+  // 8 (V: 4) channels lie on one side of an edge and the 16-byte forms stay; otherwise the rows are not `vec` and the
+  // element path asks channel by channel.
   const int cj = lane & 7, tj = lane >> 3;
   const int c0 = g * 64 + 8 * cj;
-  const bool cok = c0 < a.C;
+  auto in_win = [&](int c) { return c >= a.wc_lo && c < a.wc_hi; };  // (wc_hi <= C)
+  const bool cok = (fa.vec || SPLIT) ? in_win(c0) : c0 < a.C;  // (element rows: per channel below; lmc_api.hip leaves `vec` off for a window of heads with D % 8 != 0)
   E* const pbase = const_cast<E*>(lmc_plane_base<E>(a.dst, p));
-  const int h0 = c0 / a.dst.D, d0 = c0 - h0 * a.dst.D;
+  const int h0s = c0 / a.dst.D, d0 = c0 - h0s * a.dst.D, h0 = h0s + a.wh_shift;
   const long long coff = (long long)h0 * a.dst.stride_head + d0;  // vec: the 8 channels are contiguous from here
   // LMC_PAGED_SPLIT (k_quantize.h has the two address forms): the block offset is 64-bit, the lane's part 32-bit (lmc_api.hip,
   // decode_dst_ok).  A key plane: the lane's 8 channels are one x-granule, x = 8 (head_size is whole granules).  A value
@@ -347,9 +354,9 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
   const bool aligned = SPLIT && ((((uintptr_t)pbase) & 15u) | (uintptr_t)((a.dst.stride_block | a.dst.stride_head) & 7)) == 0;
   const u32 k_in = (u32)h0 * (u32)a.dst.stride_head + ((u32)d0 >> 3) * (bs * 8u);
   const int vc0 = g * 64 + 4 * (lane & 15);
-  const bool vcok = vc0 < a.C;
-  const int vh = vc0 / a.dst.D;
-  const u32 v_in = (u32)vh * (u32)a.dst.stride_head + (u32)(vc0 - vh * a.dst.D) * bs;
+  const bool vcok = in_win(vc0);
+  const int vhs = vc0 / a.dst.D, vh = vhs + a.wh_shift;
+  const u32 v_in = (u32)vh * (u32)a.dst.stride_head + (u32)(vc0 - vhs * a.dst.D) * bs;
   const int tdst0 = a.dst_tok0 + chunk * a.chunk_tokens;
   const u32 sh = 8u * ((u32)tj & 3u) + 4u * ((u32)tj >> 2);
 
@@ -478,8 +485,8 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
         } else {
 #pragma unroll
           for (int e = 0; e < 8; e++) {
-            const int c = c0 + e, h = c / a.dst.D, d = c - h * a.dst.D;
-            *((LMC_GLOBAL u16*)(pbase + toff + (long long)h * a.dst.stride_head + d)) = (u16)bits[e];
+            const int c = c0 + e, hs = c / a.dst.D, d = c - hs * a.dst.D;
+            if (in_win(c)) *((LMC_GLOBAL u16*)(pbase + toff + (long long)(hs + a.wh_shift) * a.dst.stride_head + d)) = (u16)bits[e];
           }
         }
       }

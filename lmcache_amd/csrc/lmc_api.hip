@@ -1137,6 +1137,7 @@ static int decode_geometry(lmc_ctx* c, int nchunks, int L, int H, int D, uint32_
   if (!c || nchunks < 1) return LMC_ERR_INVALID;
   a.nchunks = nchunks; a.layer_count = L;
   a.P = 2 * L; a.C = H * D; a.G = (a.C + 63) / 64;
+  a.wc_hi = a.C; a.wGw = a.G;  // the full head window (k_decode.h): every channel stored, every group launched
   // k_decode numbers its streams (chunk, plane, group) in 32 bits: 2^31 of them would be > 10^11 tokens in one call
   if ((long long)nchunks * a.P * a.G >= (1ll << 31)) return LMC_ERR_INVALID;
   a.status = job_status ? job_status : c->status_h;
@@ -1180,6 +1181,7 @@ static void launch_fixed_decode(const lmc_kv_layout* dst, long long nstreams, hi
   FixedDecArgs fa;
   fa.d = a;
   fa.vec = layout_ok(dst) ? 1 : 0;  // rows that take 16-byte vectors of 8 channels: what the encoders ask of a source
+  if (a.w_src_heads && (dst->head_size & 7)) fa.vec = 0;  // a head window moves heads: a vector must lie inside one (k_fixed.h)
   if (dst->paged_kind == LMC_PAGED_SPLIT) fa.vec = 0;  // (the kernel looks at the plane's own alignment: k_fixed.h)
   const dim3 grid((unsigned)((nstreams + FIXED_DEC_WAVES - 1) / FIXED_DEC_WAVES)), block(64 * FIXED_DEC_WAVES);
   with_kv_dtype16(dst->dtype, [&](auto dt) {
@@ -1192,7 +1194,7 @@ static void launch_fixed_decode(const lmc_kv_layout* dst, long long nstreams, hi
 static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev,
                                lmc_ctx* c = nullptr, const lmc_range_post* post = nullptr, bool fixed = false) {
   a.layer_begin = l0; a.layer_count = nl;
-  const long long n = (long long)a.nchunks * 2 * nl * a.G;
+  const long long n = (long long)a.nchunks * 2 * nl * a.wGw;  // (wGw == G but for a head window: the groups it touches)
   const dim3 grid((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES));
   if (fixed) launch_fixed_decode(dst, n, s, a);
   else launch_decode(dst, grid, s, a);
@@ -1251,13 +1253,31 @@ static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* post);
 // which fills 16-bit rows and -- `fixed_split`: lmc_decode_chunks_fixed_split_schedule -- a 16-bit LMC_PAGED_SPLIT cache
 // (lmc_decode_chunks_fixed_schedule keeps refusing one: such a cache is filled through a staged chunk and
 // post->scatter_dst there).
+// `win` (lmc_decode_chunks_*_heads_schedule; NULL: none, the launches are the ones they were): the blobs have win->src_heads
+// heads of dst->head_size, and heads [src_head_begin, + nheads) of every blob go to heads [dst_head_begin, ...) of `dst`,
+// which keeps its own head count.  Everything asked of `dst` -- the 32-bit offset rule included -- is asked of dst's own
+// geometry by decode_common; the blob's C and G and the window's channels and groups replace what it derived from dst.
 static int decode_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
                            const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
                            const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
-                           lmc_stream_t stream, const lmc_range_post* post, bool fixed, bool fixed_split = false) {
+                           lmc_stream_t stream, const lmc_range_post* post, bool fixed, bool fixed_split = false,
+                           const lmc_head_window* win = nullptr) {
   DecodeArgs a;
   int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, !fixed || fixed_split);
   if (rc) return rc;
+  if (win) {
+    const long long D = dst->head_size, Cs = (long long)win->src_heads * D;
+    if (win->src_heads < 1 || win->nheads < 1 || win->src_head_begin < 0 || win->dst_head_begin < 0 ||
+        (long long)win->src_head_begin + win->nheads > win->src_heads ||
+        (long long)win->dst_head_begin + win->nheads > dst->num_heads || (Cs & 7) || Cs > LMC_MAX_CHANNELS)
+      return LMC_ERR_INVALID;
+    a.C = (int)Cs; a.G = (a.C + 63) / 64;
+    if ((long long)nchunks * a.P * a.G >= (1ll << 31)) return LMC_ERR_INVALID;  // decode_geometry's bound, on the blob's groups
+    a.wc_lo = win->src_head_begin * (int)D; a.wc_hi = a.wc_lo + win->nheads * (int)D;
+    a.wg_lo = a.wc_lo / 64; a.wGw = (a.wc_hi - 1) / 64 - a.wg_lo + 1;
+    a.wh_shift = win->dst_head_begin - win->src_head_begin;
+    a.w_src_heads = win->src_heads;
+  }
   if (fixed && (lmc_dtype_fp8(dst->dtype) || max_blob_bytes < LMC_HEADER_BYTES)) return LMC_ERR_INVALID;
   if (!decode_blobs(a, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, blob_ptrs) || nranges < 1 || !layer_ends_h)
     return LMC_ERR_INVALID;
@@ -1294,6 +1314,24 @@ int lmc_decode_chunks_fixed_split_schedule(lmc_ctx* c, const void* const* blob_p
                                            uint32_t* job_status, lmc_stream_t stream) {
   return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
                          job_status, stream, post, true, true);
+}
+
+int lmc_decode_chunks_heads_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                     const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                     const int32_t* layer_ends_h, const lmc_event_t* events_h, const lmc_head_window* win,
+                                     uint32_t* job_status, lmc_stream_t stream) {
+  if (!win) return LMC_ERR_INVALID;
+  return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
+                         job_status, stream, nullptr, false, false, win);
+}
+
+int lmc_decode_chunks_fixed_heads_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                           const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                           const int32_t* layer_ends_h, const lmc_event_t* events_h, const lmc_head_window* win,
+                                           uint32_t* job_status, lmc_stream_t stream) {
+  if (!win) return LMC_ERR_INVALID;
+  return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
+                         job_status, stream, nullptr, true, true, win);
 }
 
 int lmc_decode_chunks_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,

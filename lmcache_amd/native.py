@@ -11,7 +11,7 @@ import os
 import subprocess
 import sys
 import threading
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch  # must be imported before the .so so that a single libamdhip64 (torch's) is loaded
 
@@ -136,6 +136,24 @@ class RangePostStruct(ctypes.Structure):
                 ("scatter_tok0", ctypes.c_int32)]
 
 
+class HeadWindowStruct(ctypes.Structure):
+    """lmc_head_window (include/lmc_hip.h): the heads a decode takes out of every blob, and where they land in dst."""
+    _fields_ = [("src_heads", ctypes.c_int32), ("src_head_begin", ctypes.c_int32), ("nheads", ctypes.c_int32),
+                ("dst_head_begin", ctypes.c_int32)]
+
+
+class HeadWindow(NamedTuple):
+    """Heads [src_head_begin, src_head_begin + nheads) of blobs that have src_heads heads -> heads [dst_head_begin, ...)
+    of a destination with a head count of its own: KV stored under another tensor-parallel degree (resharding.py)."""
+    src_heads: int
+    src_head_begin: int
+    nheads: int
+    dst_head_begin: int
+
+    def struct(self) -> HeadWindowStruct:
+        return HeadWindowStruct(int(self.src_heads), int(self.src_head_begin), int(self.nheads), int(self.dst_head_begin))
+
+
 class BlobHeader(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint16), ("header_bytes", ctypes.c_uint16),
                 ("dtype", ctypes.c_uint32), ("num_layers", ctypes.c_uint32), ("ntokens", ctypes.c_uint32),
@@ -192,6 +210,10 @@ SYMBOLS = {
                                                         ctypes.POINTER(RangePostStruct), _vp, _vp]),
     "lmc_decode_chunks_fixed_split_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
                                                               ctypes.POINTER(RangePostStruct), _vp, _vp]),
+    "lmc_decode_chunks_heads_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
+                                                        ctypes.POINTER(HeadWindowStruct), _vp, _vp]),
+    "lmc_decode_chunks_fixed_heads_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
+                                                              ctypes.POINTER(HeadWindowStruct), _vp, _vp]),
     "lmc_decode_symbols": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "lmc_store_chunks": (ctypes.c_int, [_vp, _PL, _i32, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "lmc_load_chunks": (ctypes.c_int, [_vp, _vp, _vp, _i32, _PL, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -232,9 +254,10 @@ SYMBOLS = {
 }
 
 # where the lmc_range_post pointer stands among the last three arguments of the symbols that take one ("status, stream,
-# post" or "post, status, stream"): read off the argument types above
-_RP = ctypes.POINTER(RangePostStruct)
-_POST_SLOT = {name: args.index(_RP) - (len(args) - 3) for name, (_, args) in SYMBOLS.items() if _RP in args}
+# post" or "post, status, stream"): read off the argument types above.  The head-window schedules carry their
+# lmc_head_window pointer in the same place ("win, status, stream") and take no post: one slot table for both.
+_RP, _HW = ctypes.POINTER(RangePostStruct), ctypes.POINTER(HeadWindowStruct)
+_POST_SLOT = {name: args.index(t) - (len(args) - 3) for name, (_, args) in SYMBOLS.items() for t in (_RP, _HW) if t in args}
 
 ENCODE_PATHS = {"auto": 0, "two_kernels": 1, "fused": 2}  # LMC_ENCODE_PATH_*
 ERR_INVALID = -1      # LMC_ERR_INVALID
@@ -957,7 +980,8 @@ class Context:
 
     def _schedule(self, symbol: str, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
                   chunk_tokens: int, layer_ends, events, post, stream: Optional[int], status_ptr: Optional[int]) -> None:
-        """The marshalling of the four lmc_decode_chunks*_schedule* exports; layer_ends / events as decode_chunks_schedule."""
+        """The marshalling of the lmc_decode_chunks*_schedule* exports; layer_ends / events as decode_chunks_schedule.
+        `post`: the struct the symbol takes in its slot -- a RangePostStruct, or the head-window calls' HeadWindowStruct."""
         n = len(layer_ends)
         ends = layer_ends if isinstance(layer_ends, ctypes.Array) else (ctypes.c_int32 * n)(*layer_ends)
         evs = events if events is None or isinstance(events, ctypes.Array) else (ctypes.c_void_p * n)(*[e.handle for e in events])
@@ -996,6 +1020,22 @@ class Context:
         PAGED_SPLIT ("NHDB") one, stored into in place."""
         self._schedule("lmc_decode_chunks_fixed_split_schedule", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0,
                        chunk_tokens, layer_ends, events, post, stream, status_ptr)
+
+    def decode_chunks_heads_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,
+                                     chunk_tokens: int, layer_ends, events, heads: HeadWindow, stream: Optional[int] = None,
+                                     status_ptr: Optional[int] = None) -> None:
+        """lmc_decode_chunks_heads_schedule: decode_chunks_schedule of a window of heads of blobs that have heads.src_heads
+        heads, into heads [heads.dst_head_begin, ...) of `dst` (its own head count).  No post: see include/lmc_hip.h."""
+        self._schedule("lmc_decode_chunks_heads_schedule", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens,
+                       layer_ends, events, None if heads is None else HeadWindow(*heads).struct(), stream, status_ptr)
+
+    def decode_chunks_fixed_heads_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout,
+                                           dst_tok0: int, chunk_tokens: int, layer_ends, events, heads: HeadWindow,
+                                           stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
+        """lmc_decode_chunks_fixed_heads_schedule: the same for LMC_MODEL_FIXED blobs (rows or a 16-bit PAGED_SPLIT cache)."""
+        self._schedule("lmc_decode_chunks_fixed_heads_schedule", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0,
+                       chunk_tokens, layer_ends, events, None if heads is None else HeadWindow(*heads).struct(), stream,
+                       status_ptr)
 
     def store_chunks(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins, host_arena_ptr: int,
                      host_cap: int, offsets_ptr: int, sizes_ptr: int, stream: Optional[int] = None,

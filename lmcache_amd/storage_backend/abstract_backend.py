@@ -10,6 +10,8 @@ to the reference's chunk-tensor protocol otherwise:
   get_kv_range(keys, dst_layout, fmt, dst_tok0, chunk_tokens) -> int   leading chunks written (a key that has
       gone since `contains` ends the run: "None on a miss", never an exception); raises NativeError when a
       stored blob does not decode -- the engine then reports a miss instead of handing garbage to the model
+  get_kv_range(..., heads=native.HeadWindow(...))   backends with supports_head_window: the chunks were stored under
+      another tensor-parallel degree; a window of their heads goes to heads of dst_layout, which has its own head count
 """
 import abc
 from typing import Iterable, Optional, Tuple
@@ -25,6 +27,8 @@ logger = init_logger(__name__)
 class LMCBackendInterface(abc.ABC):
     # set by backends that implement put_kv_range / get_kv_range
     supports_kv_layout: bool = False
+    # set by backends whose get_kv_range takes heads= (retrieve(..., stored_world_size=...): lmcache_amd/resharding.py)
+    supports_head_window: bool = False
 
     @abc.abstractmethod
     def put(self, key: CacheEngineKey, kv_chunk: torch.Tensor, blocking: bool = True) -> None:

@@ -238,6 +238,9 @@ class LMCLocalBackend(LMCBackendInterface):
             raise ValueError(f"LMCLocalBackend: unsupported local_device {self.device!r}")
         if self.mode in ("cachegen", "hbm-cachegen"):
             self.model = "fixed" if config.local_serde == "cachegen-fixed" else "rans"
+        # get_kv_range(heads=...): a window of heads out of chunks stored under another tensor-parallel degree -- the
+        # decoders' business, so the two CacheGen tiers only (the raw tiers copy whole chunks)
+        self.supports_head_window = self.mode in ("cachegen", "hbm-cachegen")
         self.cachegen_config = None
         if self.mode in ("cachegen", "hbm-cachegen"):
             if metadata is None:
@@ -1070,7 +1073,7 @@ class LMCLocalBackend(LMCBackendInterface):
 
     def get_kv_range(self, keys: Sequence[CacheEngineKey], dst: native.KVLayout, fmt: str, dst_tok0: int,
                      chunk_tokens: int, layers_per_launch: Optional[int] = None, jobs_out: Optional[list] = None,
-                     post: Optional[native.RangePost] = None) -> int:
+                     post: Optional[native.RangePost] = None, heads: Optional[native.HeadWindow] = None) -> int:
         """Write chunk i (stored under keys[i]) to dst tokens dst_tok0 + i*chunk_tokens ...; tokens that land
         below 0 are dropped (retrieve()'s first-chunk trim, cache_engine.py:360-365).  Returns the number of
         leading chunks written (a key that has gone since `contains` ends the run, like the reference's break on
@@ -1081,13 +1084,27 @@ class LMCLocalBackend(LMCBackendInterface):
         per job: a retrieve that spans several stores is several jobs, each with its own token window.  A run of pinned
         blobs that are no pack (a store of one chunk, LMCACHE_AMD_PINNED_PACKS=0) crosses PCIe whole before its first
         range is decoded (CacheGenDeviceCodec.decode_host_post): its events mean what the others' mean, but layer 0 waits
-        for the run's whole transfer."""
+        for the run's whole transfer.
+        heads (CacheGen tiers; ValueError on the raw ones and together with `post`, before anything is queued): a
+        native.HeadWindow -- the chunks were stored under another tensor-parallel degree and have heads.src_heads heads,
+        of which a window goes to heads of `dst`, which has a head count of its own.  HBM blobs, coded or fixed-width, are
+        decoded where they lie and only the window's streams are read.  A pack chunk gives its blob (_own_blob) and the
+        WHOLE blob crosses PCIe before the window is decoded from it (CacheGenDeviceCodec.decode): moving only the
+        window's byte range of a pack is not built.  The decoders hold every blob's header against heads.src_heads."""
+        if heads is not None:
+            if not self.supports_head_window:
+                raise ValueError(f"get_kv_range(heads=...): the {self.mode!r} tier stores raw chunks; a window of heads is "
+                                 "decoded out of CacheGen blobs only (local_serde='cachegen' / 'cachegen-fixed')")
+            if post is not None:
+                raise ValueError("get_kv_range(heads=...) takes no post-op: it acts on every head of the destination; "
+                                 "apply it once behind the last window")
         # the tier lock is held from taking the entries to the last launch: an eviction either happens before (the keys
         # are gone: a shorter run) or after (the jobs launched here are among the events its release is fenced by)
         with self._tier_lock:
-            return self._get_kv_range_locked(keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out, post)
+            return self._get_kv_range_locked(keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out, post, heads)
 
-    def _get_kv_range_locked(self, keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out, post=None) -> int:
+    def _get_kv_range_locked(self, keys, dst, fmt, dst_tok0, chunk_tokens, layers_per_launch, jobs_out, post=None,
+                             heads=None) -> int:
         assert post is None or (jobs_out is not None and layers_per_launch and self.mode in ("cachegen", "hbm-cachegen")), \
             "a post-op rides on the layer ranges of the CacheGen tiers' decode jobs: it needs layers_per_launch and jobs_out"
         entries = self._prefix_entries(keys)
@@ -1103,7 +1120,7 @@ class LMCLocalBackend(LMCBackendInterface):
                 # (`entries` is the SAME list object for a repeated lookup of one prefix -- _prefix_entries -- and the codec
                 # keeps the uploaded address table of the last few lists it has seen)
                 job = codec.decode_device([e.blob for e in entries], dst, dst_tok0, chunk_tokens, layers_per_launch,
-                                          same_blobs_as=entries, post=post, model=self._run_model(entries))
+                                          same_blobs_as=entries, post=post, model=self._run_model(entries), heads=heads)
             self._touch(keys[:len(entries)], [job.done])
             if jobs_out is not None:
                 jobs_out.append((codec, job))
@@ -1124,7 +1141,8 @@ class LMCLocalBackend(LMCBackendInterface):
             def kind_of(e):
                 if isinstance(e, _DevChunk):
                     return "dev-fixed" if e.model == "fixed" else "dev"
-                return "pack" if isinstance(e, _PackChunk) and e.pack.chunk_tokens == chunk_tokens else "blobs"
+                # (a window of heads: a pack chunk gives its own blob, which crosses PCIe whole -- see get_kv_range)
+                return "pack" if isinstance(e, _PackChunk) and e.pack.chunk_tokens == chunk_tokens and heads is None else "blobs"
             while i < len(entries):
                 e = entries[i]
                 j = i + 1
@@ -1146,13 +1164,15 @@ class LMCLocalBackend(LMCBackendInterface):
                 with torch.cuda.device(dev):
                     if kind in ("dev", "dev-fixed"):
                         job = codec.decode_device([e.blob for e in entries[i:j]], dst, tok0, chunk_tokens, layers_per_launch,
-                                                  post=post, model=self._run_model(entries[i:j]))
+                                                  post=post, model=self._run_model(entries[i:j]), heads=heads)
                     elif kind == "pack":
                         job = codec.load_pack(entries[i].pack, entries[i].index, j - i, dst, tok0, layers_per_launch, post=post)
                     else:
                         # (a pack chunk of another chunk length -- never stored by this engine -- takes its blob from the pack)
                         blobs = [self._own_blob(e) if isinstance(e, _PackChunk) else e.blob for e in entries[i:j]]
-                        if post is not None:
+                        if heads is not None:
+                            job = codec.decode(blobs, dst, tok0, chunk_tokens, heads=heads)
+                        elif post is not None:
                             # (whole blobs over PCIe, then the ranges' decodes with the post-op in front of every event)
                             job = codec.decode_host_post(blobs, dst, tok0, chunk_tokens, layers_per_launch, post)
                         elif layerwise:
@@ -1162,7 +1182,7 @@ class LMCLocalBackend(LMCBackendInterface):
                         else:
                             job = codec.decode(blobs, dst, tok0, chunk_tokens)
                 events.append(job.done)
-                if layerwise or (kind in ("dev", "dev-fixed") and jobs_out is not None):
+                if (layerwise and not (heads is not None and kind == "blobs")) or (kind in ("dev", "dev-fixed") and jobs_out is not None):
                     jobs_out.append((codec, job))
                 else:
                     codec.finish_decode(job)  # this decode's event, then its own status word

@@ -124,6 +124,7 @@ class LMCPipelinedRemoteBackend(LMCRemoteBackend):
         from concurrent.futures import ThreadPoolExecutor
         self.fmt = metadata.fmt
         self.supports_kv_layout = config.remote_serde == "cachegen"
+        self.supports_head_window = self.supports_kv_layout  # get_kv_range(heads=...): the codec's window decode
         self.cachegen_config = None
         if self.supports_kv_layout:
             from lmcache_amd.storage_backend.serde.cachegen_basics import CacheGenConfig
@@ -221,12 +222,15 @@ class LMCPipelinedRemoteBackend(LMCRemoteBackend):
             self.put_queue.put(payload)
         return n
 
-    def get_kv_range(self, keys, dst, fmt: str, dst_tok0: int, chunk_tokens: int) -> int:
+    def get_kv_range(self, keys, dst, fmt: str, dst_tok0: int, chunk_tokens: int, heads=None) -> int:
         """Decode chunk i (stored under keys[i]) into dst tokens dst_tok0 + i*chunk_tokens ...  Returns the
         number of leading chunks written: a blob that has gone from the store since `contains` ends the run
         (the reference breaks on the first None chunk, cache_engine.py:339-345) and drops the key from the
         existing-keys cache.  Every fetched blob is checked on the host (header, geometry against `dst`, length)
-        before it goes to the GPU; a blob whose streams do not check out there raises NativeError."""
+        before it goes to the GPU; a blob whose streams do not check out there raises NativeError.
+        heads: a native.HeadWindow -- the blobs were stored under another tensor-parallel degree and have heads.src_heads
+        heads, of which a window goes to heads of `dst` (its own head count): the host check then holds (L, D) and
+        heads.src_heads against the header instead of dst.H.  The whole blob is fetched; the decode reads the window."""
         from lmcache_amd import native
         from lmcache_amd.storage_backend.serde.cachegen_device import get_codec
         codec = get_codec(dst.device.index)
@@ -237,7 +241,7 @@ class LMCPipelinedRemoteBackend(LMCRemoteBackend):
             nonlocal batch, first
             if batch:
                 with torch.cuda.device(dst.device):
-                    jobs.append(codec.decode(batch, dst, dst_tok0 + first * chunk_tokens, chunk_tokens))
+                    jobs.append(codec.decode(batch, dst, dst_tok0 + first * chunk_tokens, chunk_tokens, heads=heads))
                 first += len(batch)
                 batch = []
 
@@ -258,7 +262,8 @@ class LMCPipelinedRemoteBackend(LMCRemoteBackend):
                     h = native.blob_info(bs[:native.HEADER_BYTES].cpu().numpy().tobytes(), total_len=bs.numel())
                 else:
                     h = native.blob_info(bs)  # raises NativeError on a bad header / truncated blob
-                if (h.num_layers, h.num_heads, h.head_size) != (dst.L, dst.H, dst.D) or h.ntokens > chunk_tokens:
+                if (h.num_layers, h.num_heads, h.head_size) != (dst.L, dst.H if heads is None else heads.src_heads, dst.D) \
+                        or h.ntokens > chunk_tokens:
                     raise native.NativeError(f"chunk {idx}: blob geometry does not match the destination")
                 batch.append(bs)
                 # decode what has arrived as soon as the fetch thread falls behind, or a full batch is there

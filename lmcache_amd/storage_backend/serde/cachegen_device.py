@@ -697,6 +697,8 @@ class CacheGenDeviceCodec:
     _ENCODERS = {(None, False): "encode_chunks", (None, True): "encode_chunks_split",
                  ("fixed", False): "encode_chunks_fixed", ("fixed", True): "encode_chunks_fixed_split"}
     _SCHEDULES = {("fixed", False): "decode_chunks_fixed_schedule", ("fixed", True): "decode_chunks_fixed_split_schedule"}
+    # ... with a window of heads (native.HeadWindow): one export per model, which takes either layout
+    _HEAD_SCHEDULES = {("fixed", False): "decode_chunks_fixed_heads_schedule", ("fixed", True): "decode_chunks_fixed_heads_schedule"}
 
     # coder model of a group's HBM blobs -> the codec's method that turns them into entropy-coded blobs in front of the pack
     # leg of a demotion (None: they are coded already)
@@ -931,7 +933,8 @@ class CacheGenDeviceCodec:
     # ---- decode ------------------------------------------------------------------
     def decode_device(self, blobs: Sequence[torch.Tensor], dst: native.KVLayout, dst_tok0: int, chunk_tokens: int,
                       layers_per_launch: Optional[int] = None, same_blobs_as=None,
-                      post: Optional[native.RangePost] = None, model: Optional[str] = None) -> Optional[DecodeJob]:
+                      post: Optional[native.RangePost] = None, model: Optional[str] = None,
+                      heads: Optional[native.HeadWindow] = None) -> Optional[DecodeJob]:
         """Decode blobs that live in HBM (uint8 CUDA tensors, anywhere) straight into `dst` on the current stream,
         no staging copy: the kernel takes the blob addresses from a pointer table.  With layers_per_launch the
         retrieve is cut into one launch per range of layers with an event after each (DecodeJob.layer_events): the
@@ -941,12 +944,20 @@ class CacheGenDeviceCodec:
         post: a native.RangePost done to every range between its launch and its event, by the same C call
         (lmc_decode_chunks_schedule_post); its struct is filled here, per call -- the kept tables are not touched.
         model "fixed": the blobs are LMC_MODEL_FIXED (lmc_decode_chunks_fixed_schedule; `dst` is 16-bit rows, or a 16-bit
-        "NHDB" cache through lmc_decode_chunks_fixed_split_schedule); the ranges, their events and `post` are the same."""
+        "NHDB" cache through lmc_decode_chunks_fixed_split_schedule); the ranges, their events and `post` are the same.
+        heads: a native.HeadWindow -- the blobs have heads.src_heads heads, of which a window goes to heads of `dst`, which
+        has a head count of its own (lmc_decode_chunks_heads_schedule / _fixed_heads_schedule).  No `post` then: it would
+        act on every head of `dst`; the caller applies it once, behind the last window (RangePost.apply)."""
         n = len(blobs)
         if n == 0:
             return None
+        if heads is not None and post is not None:
+            raise ValueError("a head-window decode takes no post-op: apply it once behind the last window")
         # (the coded schedule without a post-op is an export of its own: lmc_decode_chunks_schedule)
-        schedule = self._entry(self._SCHEDULES, model, dst, "decode_chunks_schedule" if post is None else "decode_chunks_schedule_post")
+        if heads is not None:
+            schedule = self._entry(self._HEAD_SCHEDULES, model, dst, "decode_chunks_heads_schedule")
+        else:
+            schedule = self._entry(self._SCHEDULES, model, dst, "decode_chunks_schedule" if post is None else "decode_chunks_schedule_post")
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             # The blob addresses of THIS call: any number of chunks (a 128 k-token retrieve is 512 of them), uploaded
@@ -987,17 +998,21 @@ class CacheGenDeviceCodec:
                     self._table_cache[ptrs] = (table, cur)
             with self._launch(cur) as (st, st_ptr):
                 events = self._run_schedule(schedule, table, bound, n, dst, dst_tok0, chunk_tokens, layers_per_launch, post,
-                                            cur, st_ptr)
+                                            cur, st_ptr, heads)
             return DecodeJob(events[-1][1], events if layers_per_launch else None, table, status_idx=st, pool=self._status)
 
     @staticmethod
     def _run_schedule(schedule, table: torch.Tensor, bound: int, n: int, dst: native.KVLayout, dst_tok0: int, chunk_tokens: int,
-                      layers_per_launch, post: Optional[native.RangePost], cur, st_ptr: int) -> list:
+                      layers_per_launch, post: Optional[native.RangePost], cur, st_ptr: int,
+                      heads: Optional[native.HeadWindow] = None) -> list:
         """ONE C-ABI call (`schedule`) launches every range of layers over the n blobs `table` addresses, none larger than
-        `bound`, and records the range's event behind it, `post` in between -> [(first layer after the range, event)]."""
+        `bound`, and records the range's event behind it, `post` in between -> [(first layer after the range, event)].
+        heads: the window of a head-window schedule (which takes no post)."""
         ends = [l1 for _, l1 in layer_ranges(dst.L, layers_per_launch)]
         evs = [native.NativeEvent() for _ in ends]
         kw = {} if post is None else {"post": post.struct(*post.window(dst, dst_tok0, n, chunk_tokens))}
+        if heads is not None:
+            kw["heads"] = heads
         schedule(table.data_ptr(), bound, n, dst, dst_tok0, chunk_tokens, ends, evs, stream=cur.cuda_stream, status_ptr=st_ptr, **kw)
         return list(zip(ends, evs))
 
@@ -1426,11 +1441,13 @@ class CacheGenDeviceCodec:
         return self._dec_arena
 
     def decode(self, host_blobs: Sequence, dst: native.KVLayout, dst_tok0: int, chunk_tokens: int,
-               batch_chunks: Optional[int] = None) -> Optional[DecodeJob]:
+               batch_chunks: Optional[int] = None, heads: Optional[native.HeadWindow] = None) -> Optional[DecodeJob]:
         """H2D the blobs on the side stream and decode them on the current stream straight into `dst`,
         pipelined in batches of `decode_batch_chunks` (copy of batch b+1 overlaps the decode of batch b).
         host_blobs: HostBlob (pinned), bytes-like (staged through pinned memory) or uint8 CUDA tensors (blobs
         that are already in HBM: copied device to device).
+        heads: a native.HeadWindow (see decode_device): the blobs cross whole, and every batch is decoded through the
+        pointer-table call lmc_decode_chunks_heads_schedule with one range of all layers.
         Asynchronous: returns a DecodeJob; finish_decode(job) waits for it and raises on a corrupt blob."""
         n = len(host_blobs)
         if n == 0:
@@ -1462,7 +1479,7 @@ class CacheGenDeviceCodec:
                     B = batch_chunks or self.decode_batch_chunks
                     last = None
                     table, table_at = None, {}
-                    if dst.struct.paged_kind == native.PAGED_SPLIT:
+                    if dst.struct.paged_kind == native.PAGED_SPLIT or heads is not None:
                         # lmc_decode_chunks stands for from_bytes and writes rows only (include/lmc_hip.h): an "NHDB"
                         # cache takes the same slots through a pointer table -- ONE for all n slots, made before the
                         # first batch and uploaded stream-ordered from pinned memory (no host wait, as decode_device's table);
@@ -1495,7 +1512,11 @@ class CacheGenDeviceCodec:
                         ready = torch.cuda.Event()
                         ready.record(self.copy_stream)
                         cur.wait_event(ready)
-                        if table is not None:
+                        if heads is not None:
+                            self.ctx.decode_chunks_heads_schedule(table.data_ptr() + 8 * table_at[b0], stride, b1 - b0, dst,
+                                                                  dst_tok0 + b0 * chunk_tokens, chunk_tokens, [dst.L], None,
+                                                                  heads, stream=cur.cuda_stream, status_ptr=st_ptr)
+                        elif table is not None:
                             self.ctx.decode_chunks_layers(table.data_ptr() + 8 * table_at[b0], stride, b1 - b0, dst,
                                                           dst_tok0 + b0 * chunk_tokens, chunk_tokens, 0, dst.L,
                                                           stream=cur.cuda_stream, status_ptr=st_ptr)
