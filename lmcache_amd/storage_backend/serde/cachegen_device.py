@@ -1,7 +1,8 @@
 """Device-side plumbing shared by the CacheGen serializer, deserializer and the
-pinned-host backend: HBM blob arena, pinned host arena, side copy stream,
-stream/event ordering.  All compute goes through the C ABI (lmcache_amd.native);
-this file only sequences it.
+pinned-host backend: the jobs in flight, side copy stream, stream/event ordering.
+The pinned host arena and the HBM blob arena the blobs live in are in
+storage_backend/arena.py and re-exported here.  All compute goes through the
+C ABI (lmcache_amd.native); this file only sequences it.
 
 What it replaces in the reference: the implicit, synchronous data movement of
 `pickle.dump` of CUDA tensors (cachegen_basics.py:131-136), `.cuda()` after
@@ -23,251 +24,9 @@ import torch
 
 from lmcache_amd import native
 from lmcache_amd.logging import init_logger
-from lmcache_amd.storage_backend.tiering import FreeList
+from lmcache_amd.storage_backend.arena import ArenaFull, DeviceArena, HostBlob, PinnedArena, _stream_waits  # noqa: F401
 
 logger = init_logger(__name__)
-
-
-class ArenaFull(MemoryError):
-    """A bounded arena cannot take the allocation: over its budget, or no hole is large enough."""
-
-
-def _event_done(ev) -> bool:
-    try:
-        return bool(ev.query())
-    except Exception:
-        return False
-
-
-def _stream_waits(stream, events) -> None:
-    """`stream` runs behind `events` (torch events or native.NativeEvent): a stream-side wait, never a host wait."""
-    for ev in events:
-        if isinstance(ev, native.NativeEvent):
-            ev.wait(stream.cuda_stream)
-        else:
-            stream.wait_event(ev)
-
-
-class PinnedArena:
-    """Allocator over hipHostMalloc'ed slabs.  Without a budget it is a bump allocator that returns memory at close()
-    (the reference never evicts, hybrid_backend.py:24): free() only counts.  With a byte budget (constructor, or
-    set_budget() later) regions come from a first-fit free list with coalescing (storage_backend/tiering.py), free()
-    gives them back, and the bytes reserved from the system -- the sum of the slab sizes -- never exceed the budget
-    (an arena that was unbounded before keeps the slabs it has that still hold live bytes; it takes no new one while it
-    is over, and what it was given back while unbounded becomes holes).  A freed region carries the events of whoever may
-    still read it; alloc() makes the streams of the next owner wait for them."""
-
-    def __init__(self, slab_bytes: int = 256 << 20, budget: Optional[int] = None, buffer_factory=None):
-        self.slab_bytes = slab_bytes
-        self._new_buffer = buffer_factory or native.PinnedBuffer
-        self._slabs: List[native.PinnedBuffer] = []
-        self._spare: List[native.PinnedBuffer] = []   # slabs allocated ahead of need (reserve)
-        self._tops: List[int] = []                    # bump pointer each earlier slab was left at
-        self._used = 0
-        self._lock = threading.Lock()
-        self.total_allocated = 0
-        self._fl: Optional[FreeList] = None
-        # unbounded: the regions given back so far, (slab, offset, size, events) -- only counted while the arena is a bump
-        # allocator, holes of the free list once it turns bounded -- and how many of their bytes are tails that shrink()
-        # could not return to the bump pointer (total_allocated still counts those)
-        self._freed: List[tuple] = []
-        self.cut_bytes = 0
-        if budget is not None:
-            self.set_budget(budget)
-
-    # ---- bounded -------------------------------------------------------------------------------------------------
-    @property
-    def budget(self) -> Optional[int]:
-        return self._fl.budget if self._fl is not None else None
-
-    def set_budget(self, budget: Optional[int]) -> None:
-        """Bound the arena from now on (None on an unbounded arena: nothing changes; a bounded arena stays a free list
-        and only loses its limit).  What the bump allocator has handed out so far and not been given back counts as
-        live; what was given back meanwhile becomes holes.  Slabs that are one hole go back to the system while the
-        arena is over the new budget."""
-        with self._lock:
-            if self._fl is None:
-                if budget is None:
-                    return
-                fl = FreeList(budget, _event_done)
-                for k, b in enumerate(self._slabs):
-                    last = k == len(self._slabs) - 1
-                    fl.add_slab(b, b.nbytes, self._used if last else self._tops[k])
-                for b in self._spare:
-                    fl.add_slab(b, b.nbytes, 0)
-                for slab, off, size, events in self._freed:
-                    fl.free(slab, off, size, events)
-                self._freed, self.cut_bytes = [], 0
-                self._slabs, self._spare = self._slabs + self._spare, []
-                self._fl = fl
-                self.total_allocated = fl.live
-            else:
-                self._fl.budget = budget
-            self._release_empty_locked()
-
-    @property
-    def live_bytes(self) -> int:
-        return self._fl.live if self._fl is not None else self.total_allocated
-
-    @property
-    def reserved_bytes(self) -> int:
-        return sum(b.nbytes for b in self._slabs + self._spare)
-
-    def _alloc_bounded(self, nbytes: int, need: int, slab_hint: int, streams) -> "HostBlob":
-        fl = self._fl
-        got = fl.alloc(need)
-        if got is None and fl.fits_budget(need):
-            room = fl.room_for_slab()
-            if room is not None and room < need:
-                # no hole takes it and the budget leaves no slab of its size: slabs that are one hole go back to the
-                # system first (an arena whose groups have all gone must take a region larger than any slab it has)
-                self._release_empty_locked(until=need)
-                room = fl.room_for_slab()
-            size = max(self.slab_bytes, need, slab_hint)
-            if room is not None:
-                size = min(size, room) & ~15
-            if size >= need:
-                buf = self._new_buffer(size)
-                self._slabs.append(buf)
-                fl.add_slab(buf, size)
-                got = fl.alloc(need)
-        if got is None:
-            raise ArenaFull(f"pinned arena: {need} bytes do not fit ({fl.live} live of a budget of {fl.budget})")
-        slab, off, events = got
-        for st in streams:
-            _stream_waits(st, events)
-        self.total_allocated = fl.live
-        return HostBlob(slab, off, nbytes)
-
-    def free(self, hb: "HostBlob", events: Sequence = ()) -> None:
-        """Give `hb` back; `events`: what may still read or write it.  An unbounded arena reuses nothing: it only counts."""
-        size = native.r16(max(hb.nbytes, 16))
-        with self._lock:
-            if self._fl is None:
-                self.total_allocated -= size
-                self._freed.append((hb.slab, hb.offset, size, list(events)))
-                return
-            self._fl.free(hb.slab, hb.offset, size, events)
-            self.total_allocated = self._fl.live
-            self._release_empty_locked()
-
-    def _release_empty_locked(self, until: int = 0) -> None:
-        """Slabs that are one hole go back to the system while the arena is over its budget (an arena bounded after the
-        fact), or -- until > 0 -- until the budget leaves room for a new slab of `until` bytes.  A slab whose last
-        readers have not finished is waited for: the one host wait of the arena, on the rare path where memory has to
-        change hands with the system."""
-        fl = self._fl
-        if fl.budget is None:
-            return
-        for b in list(self._slabs):
-            if fl.reserved <= fl.budget and (until <= 0 or fl.budget - fl.reserved >= until):
-                break
-            if fl.is_empty(b):
-                for e in fl.holes[b][0][2]:
-                    if not _event_done(e) and hasattr(e, "synchronize"):
-                        e.synchronize()
-                fl.drop_slab(b)
-                self._slabs.remove(b)
-                b.free()
-
-    # ---- both ----------------------------------------------------------------------------------------------------
-    def alloc(self, nbytes: int, slab_hint: int = 0, streams: Sequence = ()) -> "HostBlob":
-        """slab_hint: size of the slab to allocate if a new one is needed (a pack is allocated at its bound and cut
-        to its size afterwards: a slab of a few bounds keeps the cut-off tails usable).  streams: who will write the
-        region (bounded arena: they wait for the events of its previous owner).  Bounded and full: ArenaFull."""
-        need = native.r16(max(nbytes, 16))
-        with self._lock:
-            if self._fl is not None:
-                return self._alloc_bounded(nbytes, need, slab_hint, streams)
-            if not self._slabs or self._used + need > self._slabs[-1].nbytes:
-                k = next((i for i, b in enumerate(self._spare) if b.nbytes >= need), None)
-                if self._slabs:
-                    self._tops.append(self._used)
-                self._slabs.append(self._spare.pop(k) if k is not None
-                                   else self._new_buffer(max(self.slab_bytes, need, slab_hint)))
-                self._used = 0
-            slab = self._slabs[-1]
-            off = self._used
-            self._used += need
-            self.total_allocated += need
-        return HostBlob(slab, off, nbytes)
-
-    def shrink(self, hb: "HostBlob", nbytes: int) -> "HostBlob":
-        """Give back the tail of `hb`.  Unbounded: only if it is still the arena's last allocation (a pack is allocated
-        at its bound and cut to its size once the GPU has written it); otherwise the tail stays unused.  Bounded: the
-        tail is freed like any region -- the budget was tested against the bound at alloc() and is corrected here
-        (nbytes 0: the whole region goes back)."""
-        keep = native.r16(max(nbytes, 16))
-        with self._lock:
-            if self._fl is not None:
-                old = native.r16(max(hb.nbytes, 16))
-                if nbytes <= 0:
-                    keep = 0
-                if old > keep:
-                    self._fl.free(hb.slab, hb.offset + keep, old - keep)
-                    self.total_allocated = self._fl.live
-            elif self._slabs and hb.slab is self._slabs[-1] and hb.offset + native.r16(max(hb.nbytes, 16)) == self._used:
-                self.total_allocated -= self._used - (hb.offset + keep)
-                self._used = hb.offset + keep
-            elif native.r16(max(hb.nbytes, 16)) > keep:
-                # (another allocation lies behind it: the tail stays unused and counted; a hole once the arena is bounded)
-                tail = native.r16(max(hb.nbytes, 16)) - keep
-                self._freed.append((hb.slab, hb.offset + keep, tail, []))
-                self.cut_bytes += tail
-        return HostBlob(hb.slab, hb.offset, nbytes)
-
-    def reserve(self, nbytes: int, slab_bytes: int = 0) -> None:
-        """Allocate slabs for `nbytes` more bytes now (hipHostMalloc of hundreds of MB takes tens of ms and stalls
-        the device: a backend sized for its working set pays that at start-up, not inside a store).  A bounded arena
-        takes its slabs as it needs them."""
-        slab = max(self.slab_bytes, slab_bytes)
-        with self._lock:
-            if self._fl is not None:
-                return
-            have = sum(b.nbytes for b in self._spare)
-            while have < nbytes:
-                self._spare.append(self._new_buffer(slab))
-                have += slab
-
-    def reset(self):
-        """Recycle the newest slab (callers that own every blob handed out so far)."""
-        with self._lock:
-            for s in self._slabs[:-1]:
-                s.free()
-            self._slabs = self._slabs[-1:]
-            self._tops = []
-            self._used = 0
-            self.total_allocated = 0
-            self._freed, self.cut_bytes = [], 0
-            if self._fl is not None:
-                budget = self._fl.budget
-                self._fl = FreeList(budget, _event_done)
-                for b in self._slabs:
-                    self._fl.add_slab(b, b.nbytes, 0)
-
-    def close(self):
-        with self._lock:
-            for s in self._slabs + self._spare:
-                s.free()
-            self._slabs, self._spare, self._tops = [], [], []
-            self._freed, self.cut_bytes = [], 0
-            if self._fl is not None:
-                self._fl = FreeList(self._fl.budget, _event_done)
-
-
-@dataclass
-class HostBlob:
-    """One encoded chunk resident in pinned host DRAM."""
-    slab: native.PinnedBuffer
-    offset: int
-    nbytes: int
-
-    @property
-    def ptr(self) -> int:
-        return self.slab.ptr + self.offset
-
-    def tobytes(self) -> bytes:
-        return ctypes.string_at(self.ptr, self.nbytes)
 
 
 class PinnedWords:
@@ -495,141 +254,6 @@ class DecodeJob(Job):
         super().__init__(done, **base)
         self.layer_events = layer_events
         self._table = table  # decode_device: the address table the kernels read, alive as long as the job
-
-
-class DeviceArena:
-    """Allocator over HBM slabs for encoded chunks that stay on the GPU (LMCLocalBackend, local_device="cuda" +
-    local_serde="cachegen": 4.2x more warm context in the 288 GB than raw chunks).  Unbounded it is a bump allocator
-    (free() only counts); with a byte budget it is PinnedArena's free list over HBM slabs: free() gives a blob's bytes
-    back with the events of the decodes and copies that may still read them, and alloc() makes the stream that writes
-    the region next wait for those."""
-
-    def __init__(self, device, slab_bytes: int = 512 << 20, budget: Optional[int] = None):
-        self.device, self.slab_bytes = device, slab_bytes
-        self._slabs: List[torch.Tensor] = []
-        self._tops: List[int] = []
-        self._used = 0
-        self._lock = threading.Lock()
-        self._fl: Optional[FreeList] = None
-        self._live = 0
-        self._freed: List[tuple] = []  # unbounded: (slab index, offset, size, events) given back so far (PinnedArena._freed)
-        self._ids: List[int] = []    # bounded: the free list's id of each slab
-        self._next_id = 0
-        if budget is not None:
-            self.set_budget(budget)
-
-    @property
-    def budget(self) -> Optional[int]:
-        return self._fl.budget if self._fl is not None else None
-
-    @property
-    def live_bytes(self) -> int:
-        return self._fl.live if self._fl is not None else self._live
-
-    def _new_slab(self, size: int) -> torch.Tensor:
-        return torch.empty(size, dtype=torch.uint8, device=self.device)
-
-    def _release_empty_locked(self, until: int = 0) -> None:
-        """See PinnedArena._release_empty_locked."""
-        fl = self._fl
-        if fl.budget is None:
-            return
-        for k in range(len(self._slabs) - 1, -1, -1):
-            if fl.reserved <= fl.budget and (until <= 0 or fl.budget - fl.reserved >= until):
-                break
-            sid = self._ids[k]
-            if fl.is_empty(sid):
-                for e in fl.holes[sid][0][2]:
-                    if not _event_done(e) and hasattr(e, "synchronize"):
-                        e.synchronize()
-                fl.drop_slab(sid)
-                del self._slabs[k], self._ids[k]
-
-    @property
-    def reserved_bytes(self) -> int:
-        return sum(t.numel() for t in self._slabs)
-
-    def set_budget(self, budget: Optional[int]) -> None:
-        """See PinnedArena.set_budget."""
-        with self._lock:
-            if self._fl is None:
-                if budget is None:
-                    return
-                fl = FreeList(budget, _event_done)
-                for k, t in enumerate(self._slabs):
-                    fl.add_slab(k, t.numel(), self._used if k == len(self._slabs) - 1 else self._tops[k])
-                for k, off, size, events in self._freed:  # (what was given back while unbounded: holes from now on)
-                    fl.free(k, off, size, events)
-                self._freed = []
-                self._ids = list(range(len(self._slabs)))
-                self._next_id = len(self._slabs)
-                self._fl = fl
-            else:
-                self._fl.budget = budget
-            self._release_empty_locked()
-
-    def alloc(self, nbytes: int, stream=None) -> torch.Tensor:
-        """stream: who writes the region (bounded arena: it waits for the events of the previous owner; None: the
-        current stream).  Bounded and full: ArenaFull."""
-        need = native.r16(max(nbytes, 16))
-        with self._lock:
-            if self._fl is not None:
-                fl = self._fl
-                got = fl.alloc(need)
-                if got is None and fl.fits_budget(need):
-                    room = fl.room_for_slab()
-                    if room is not None and room < need:
-                        self._release_empty_locked(until=need)
-                        room = fl.room_for_slab()
-                    size = max(self.slab_bytes, need)
-                    if room is not None:  # (None: a bounded arena whose limit has been taken away again)
-                        size = min(size, room) & ~15
-                    if size >= need:
-                        self._slabs.append(self._new_slab(size))
-                        self._ids.append(self._next_id)
-                        fl.add_slab(self._next_id, size)
-                        self._next_id += 1
-                        got = fl.alloc(need)
-                if got is None:
-                    raise ArenaFull(f"HBM arena: {need} bytes do not fit ({fl.live} live of a budget of {fl.budget})")
-                sid, off, events = got
-                if events:
-                    _stream_waits(stream if stream is not None else torch.cuda.current_stream(self.device), events)
-                return self._slabs[self._ids.index(sid)][off:off + nbytes]
-            if not self._slabs or self._used + need > self._slabs[-1].numel():
-                if self._slabs:
-                    self._tops.append(self._used)
-                self._slabs.append(self._new_slab(max(self.slab_bytes, need)))
-                self._used = 0
-            off = self._used
-            self._used += need
-            self._live += need
-            return self._slabs[-1][off:off + nbytes]
-
-    def free(self, t: torch.Tensor, events: Sequence = ()) -> None:
-        """Give the blob `t` (a view alloc() returned) back; `events`: what may still read it."""
-        size = native.r16(max(t.numel(), 16))
-        with self._lock:
-            p = t.data_ptr()
-            for k, slab in enumerate(self._slabs):
-                base = slab.data_ptr()
-                if base <= p < base + slab.numel():
-                    break
-            else:
-                raise ValueError("DeviceArena.free: not a region of this arena")
-            if self._fl is None:
-                self._live -= size
-                self._freed.append((k, p - base, size, list(events)))
-                return
-            self._fl.free(self._ids[k], p - base, size, events)
-            self._release_empty_locked()  # over budget (bounded after the fact): empty slabs go back
-
-    def close(self):
-        with self._lock:
-            self._slabs, self._tops, self._used, self._live, self._freed = [], [], 0, 0, []
-            if self._fl is not None:
-                self._fl = FreeList(self._fl.budget, _event_done)
-                self._ids, self._next_id = [], 0
 
 
 class CacheGenDeviceCodec:

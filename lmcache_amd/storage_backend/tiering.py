@@ -1,7 +1,7 @@
 """Bookkeeping of the bounded local tiers: what is free in an arena, and which store group goes next.
 
 Nothing here touches torch.cuda or the HIP library: regions are abstract (slab id, offset, size) records, events are
-whatever objects the caller hands in, and the movers of `Tiers` are callbacks -- the arenas (serde/cachegen_device.py)
+whatever objects the caller hands in, and the movers of `Tiers` are callbacks -- the arenas (storage_backend/arena.py)
 and LMCLocalBackend put memory and kernels behind them.
 
   FreeList   first-fit over the slabs of one arena with coalescing, and an optional byte budget.  A freed region

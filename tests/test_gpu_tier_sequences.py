@@ -1,5 +1,5 @@
 """The bounded local tiers under random operation sequences, at the level of the engine (LMCLocalBackend, tiering.py, the
-arenas of serde/cachegen_device.py): which region a decode reads, when it goes back, behind which events it is written again,
+arenas of storage_backend/arena.py): which region a decode reads, when it goes back, behind which events it is written again,
 and what a key points at after a demotion, a transcode, a promotion or a second store.
 
 Three configurations (tests/tier_sequences.py: make_engine), L = 2, H = 2, D = 64, bf16, chunks of 16 tokens:

@@ -155,6 +155,106 @@ def test_unbounded_pinned_arena_behaves_as_recorded():
     assert a.budget is None
 
 
+# (operation, where the region landed -- (index in _slabs, offset), "full" for ArenaFull --, live_bytes, slab sizes) of both
+# arenas through unbounded, bounded, over budget, unlimited again and bounded again: recorded with 4096-byte slabs from the
+# two separate implementations that were there before arena.SlabArena.  One row differs: over its budget the pinned arena
+# gives empty slabs back oldest first, the HBM arena newest first.
+_S4 = [4096, 4096, 6000, 5008]
+_S3 = [4096, 4096, 2304]
+RECORDED_BOTH = [(("alloc", "a", 3000), (0, 0), 3008, [4096]),
+                 (("alloc", "b", 2000), (1, 0), 5008, [4096, 4096]),
+                 (("alloc", "c", 6000), (2, 0), 11008, [4096, 4096, 6000]),
+                 (("alloc", "d", 5000), (3, 0), 16016, _S4),
+                 (("free", "b"), None, 14016, _S4),
+                 (("budget", 30000), None, 14016, _S4),
+                 (("alloc", "e", 1500), (1, 0), 15520, _S4),
+                 (("free", "c"), None, 9520, _S4),
+                 (("free", "d"), None, 4512, _S4),
+                 (("free", "e"), None, 3008, _S4),
+                 (("budget", 10500), None, 3008, {"pinned": [4096, 5008], "device": [4096, 4096]}),
+                 (("alloc", "f", 7000), "full", 3008, [4096]),   # (refused, and the empty slab has gone back all the same)
+                 (("alloc", "g", 4000), (1, 0), 7008, [4096, 4096]),
+                 (("alloc", "h", 2000), (2, 0), 9008, _S3),      # (a slab cut to the 2304 bytes the budget leaves)
+                 (("free", "a"), None, 6000, _S3),
+                 (("alloc", "i", 4500), "full", 6000, _S3),
+                 (("alloc", "j", 6000), "full", 6000, _S3),
+                 (("budget", None), None, 6000, _S3),            # (still a free list; later slabs get the unbounded size)
+                 (("alloc", "k", 9000), (3, 0), 15008, _S3 + [9008]),
+                 (("free", "g"), None, 11008, _S3 + [9008]),
+                 (("budget", 12000), None, 11008, [2304, 9008])]
+
+
+def _host_arena(kind, **kw):
+    """-> (arena, where(region) -> (index in _slabs, offset)); plain host tensors stand in for HBM."""
+    from lmcache_amd.storage_backend.serde.cachegen_device import DeviceArena
+    if kind == "pinned":
+        a = PinnedArena(slab_bytes=4096, buffer_factory=_FakeBuffer, **kw)
+        return a, lambda r: (next(k for k, s in enumerate(a._slabs) if s is r.slab), r.offset)
+    a = DeviceArena(torch.device("cpu"), slab_bytes=4096, **kw)
+    return a, lambda r: next((k, r.data_ptr() - s.data_ptr()) for k, s in enumerate(a._slabs)
+                             if s.data_ptr() <= r.data_ptr() < s.data_ptr() + s.numel())
+
+
+@pytest.mark.parametrize("kind", ["pinned", "device"])
+def test_both_arenas_behave_as_recorded_through_every_mode(kind):
+    a, where = _host_arena(kind)
+    held, out = {}, []
+    for op, _, _, _ in RECORDED_BOTH:
+        at = None
+        if op[0] == "alloc":
+            try:
+                held[op[1]] = a.alloc(op[2])
+                at = where(held[op[1]])
+            except ArenaFull:
+                at = "full"
+        elif op[0] == "free":
+            a.free(held.pop(op[1]))
+        else:
+            a.set_budget(op[1])
+        out.append((op, at, a.live_bytes, [s.nbytes for s in a._slabs]))
+    assert out == [(op, at, live, sizes[kind] if isinstance(sizes, dict) else sizes) for op, at, live, sizes in RECORDED_BOTH]
+    assert a.reserved_bytes == 2304 + 9008 and a.budget == 12000
+    if kind == "pinned":
+        assert a.total_allocated == a.live_bytes
+
+
+class _WaitLog:
+    def __init__(self):
+        self.waited = []
+
+    def wait_event(self, e):
+        self.waited.append(e)
+
+
+@pytest.mark.parametrize("kind", ["pinned", "device"])
+def test_a_fence_given_back_while_unbounded_is_waited_for_once_the_arena_is_bounded(kind):
+    """Freed with an event while the arena only counts, allocated after a budget was set: the stream named at alloc() waits
+    for exactly that event, and for nothing when it takes bytes nobody gave back."""
+    a, where = _host_arena(kind)
+    alloc = (lambda n, st: a.alloc(n, streams=[st])) if kind == "pinned" else (lambda n, st: a.alloc(n, stream=st))
+    x, y = a.alloc(1000), a.alloc(1000)
+    ev = object()
+    a.free(x, [ev])
+    a.set_budget(8192)
+    st = _WaitLog()
+    assert where(alloc(1000, st)) == (0, 0) and st.waited == [ev]
+    st2 = _WaitLog()
+    assert where(alloc(1000, st2)) == (0, 2016) and st2.waited == []   # (behind the bump pointer: never handed out)
+    a.free(y)
+    assert where(a.alloc(1000)) == (0, 1008)   # no stream named, no event: the HBM arena does not ask for the current stream
+
+
+def test_every_stream_named_at_alloc_waits_for_a_fence_given_back_while_unbounded():
+    a, where = _host_arena("pinned")
+    x = a.alloc(1000)
+    ev = object()
+    a.free(x, [ev])
+    a.set_budget(4096)
+    s1, s2 = _WaitLog(), _WaitLog()
+    assert where(a.alloc(1000, streams=[s1, s2])) == (0, 0)
+    assert s1.waited == [ev] and s2.waited == [ev]
+
+
 def test_bounded_pinned_arena_reserves_no_more_than_its_budget_and_reuses_what_is_freed():
     _FakeBuffer.made = 0
     a = PinnedArena(slab_bytes=4096, budget=6000, buffer_factory=_FakeBuffer)
