@@ -467,6 +467,30 @@ int lmc_decode_chunks_fixed_split_schedule(lmc_ctx* ctx, const void* const* blob
                                            const lmc_range_post* post, uint32_t* job_status, lmc_stream_t stream);
 
 /*
+ * lmc_decode_chunks_fixed_split_schedule with the ROTATION of `post` done INSIDE each range's decode launch (additive in
+ * ABI 6; k_fixed.h: k_fixed_decode_rope): the dequantised fp32 key is rotated before its only cast and written once,
+ * where the twin writes the keys, reads them back, rotates them and rounds them a second time.  The keys therefore
+ * differ in bits from the twin's: with e the exact rotation of the dequantised fp32 pair (x1, x2), every rotated key is
+ * within u |e| + 2^-22 (|x1| + |x2|) of e (u = 2^-8 bf16, 2^-11 fp16, + 2^-25 for fp16) -- one rounding of the output
+ * type plus rope_pair's fp32 arithmetic.  V planes, channels at or past rot_dim, tokens outside [tok_begin, tok_begin +
+ * ntok) and everything not written are the twin's bits.
+ *   post   required, with a rotation (cos_sin); held against the twin's rules first.  Any destination form of the twin:
+ *          rows rotated where they are decoded (scatter_dst NULL); a staged chunk of rows whose scatter_dst is an
+ *          LMC_PAGED_SPLIT cache -- the scatter is still queued per range in front of the range's event; a split `dst`
+ *          that names itself (the in-place form of lmc_range_post) -- nothing is queued behind the decode.
+ * A per-token |delta| outside the table: that token's keys are stored unrotated, LMC_STATUS_BAD_POSITION in the context's
+ * sticky word, as for the twin.  Blob validation, check words (a head's streams are one wave's work, each stream held
+ * against its own word: LMC_STATUS_BAD_STREAM) and scale checksums are the twin's.
+ * Not served -- LMC_ERR_INVALID before anything is queued, the caller takes the twin: fp8; rows that do not take 16-byte
+ * vectors of 8 channels; a head size outside {8, 16, 32, 64, 128, 192, 256}; a table that is not 16-byte aligned; NeoX
+ * with rot_dim / 2, GPT-J with rot_dim, not a multiple of 8; rot_dim > head_size.  There is no head-window form.
+ */
+int lmc_decode_chunks_fixed_rope_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint64_t max_blob_bytes,
+                                          int32_t nchunks, const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens,
+                                          int32_t nranges, const int32_t* layer_ends_h, const lmc_event_t* events_h,
+                                          const lmc_range_post* post, uint32_t* job_status, lmc_stream_t stream);
+
+/*
  * A WINDOW OF HEADS out of every blob (additive in ABI 6): KV stored under one tensor-parallel degree, retrieved under
  * another.  The blobs have src_heads heads; heads [src_head_begin, src_head_begin + nheads) of every blob are written to
  * heads [dst_head_begin, dst_head_begin + nheads) of `dst`, whose num_heads is ITS OWN (a TP = 8 rank takes one eighth of

@@ -54,6 +54,10 @@ class LMCacheEngine:
         # there (lmc_rope_shift_split) where LMCACHE_AMD_SPLIT_ROPE=1 is set (read here, once); the default keeps what the
         # tiers have always done with that call -- the coded tiers raise, the fixed-width tier stages
         self.split_rope = os.environ.get("LMCACHE_AMD_SPLIT_ROPE", "0") == "1"
+        # LMCACHE_AMD_FUSED_ROPE=1 (read here, once): a retrieve with `rope` from the fixed-width HBM tier rotates the keys
+        # INSIDE the decode (lmc_decode_chunks_fixed_rope_schedule) instead of in a second pass behind it.  Off by default:
+        # the fused keys are rounded once and are not the bits the two-pass path leaves
+        self.fused_rope = os.environ.get("LMCACHE_AMD_FUSED_ROPE", "0") == "1"
         logger.debug("Current storage backend type %s", type(self.engine_))
 
     # ------------------------------------------------------------------ index (pure Python)
@@ -402,12 +406,27 @@ class LMCacheEngine:
             raise ValueError(f"{what} across tensor-parallel degrees is not built: a window of heads has no per-range "
                              "post-op; use the one-piece call")
 
-    def _direct_retrieve(self, direct: bool, layout: str, rope: Optional[RopeShift] = None) -> bool:
+    def _fused_rope_tier(self) -> bool:
+        """Whether a retrieve with `rope` rotates inside the decode: the switch is on, the tier is the fixed-width HBM one,
+        and this is not a stored_at() view (a window of heads has no fused form)."""
+        return (getattr(self, "fused_rope", False) and getattr(self.engine_, "model", None) == "fixed"
+                and getattr(self, "_stored_ws", None) is None)
+
+    def _fused_direct(self, direct: bool, layout: str, rope: Optional[RopeShift], head_size: Optional[int]) -> bool:
+        """direct=True with `rope` on "NHDB" made legal by LMCACHE_AMD_FUSED_ROPE=1 alone: the fixed-width decoder rotates
+        the keys on their way into the split blocks.  Only where k_fixed_decode_rope serves the head size and the rotation
+        (native.RangePost.fused_ok is the full rule); everything else takes the path it took without the switch."""
+        if not (direct and layout == "NHDB" and rope is not None and self._fused_rope_tier()):
+            return False
+        return head_size in (8, 16, 32, 64, 128, 192, 256) and rope.rot_dim % (16 if rope.is_neox else 8) == 0
+
+    def _direct_retrieve(self, direct: bool, layout: str, rope: Optional[RopeShift] = None,
+                         head_size: Optional[int] = None) -> bool:
         """`direct` as the backend honours it.  The fixed-width HBM tier (local_serde="cachegen-fixed") decodes straight
         into an "NHDB" cache (lmc_decode_chunks_fixed_split_schedule); asked for that together with a `rope` it does not
         raise as the coded tiers do but takes the staged path, where the keys are rotated (logged once).  With
         LMCACHE_AMD_SPLIT_ROPE=1 (self.split_rope) every tier honours it: the keys are rotated in the split blocks."""
-        if getattr(self, "split_rope", False):
+        if getattr(self, "split_rope", False) or self._fused_direct(direct, layout, rope, head_size):
             return direct
         if direct and layout == "NHDB" and rope is not None and getattr(self.engine_, "model", None) == "fixed":
             if not getattr(self, "_fixed_direct_logged", False):
@@ -418,15 +437,23 @@ class LMCacheEngine:
         return direct
 
     @staticmethod
-    def _check_rope(rope: RopeShift, kv_caches, layout: str, ntokens: int) -> None:
-        """What retrieve_into_paged refuses of a RopeShift before anything is queued (ValueError)."""
+    def _cache_ref(kv_caches, layout: str):
+        """(a tensor of the first layer's cache, the head size) of a paged cache in `layout`."""
         first = kv_caches[0]
         if layout == "NHDB":  # [2, num_blocks, H, D, block_size], or the (key_cache, value_cache [num_blocks, H, D, block_size]) pair
             pair = isinstance(first, (tuple, list))
             ref = first[1] if pair else first
-            D = ref.shape[2] if pair else ref.shape[3]
-        else:
-            ref, D = first, first.shape[-1]
+            return ref, (ref.shape[2] if pair else ref.shape[3])
+        return first, first.shape[-1]
+
+    @staticmethod
+    def _head_size(kv_caches, layout: str) -> int:
+        return int(LMCacheEngine._cache_ref(kv_caches, layout)[1])
+
+    @staticmethod
+    def _check_rope(rope: RopeShift, kv_caches, layout: str, ntokens: int) -> None:
+        """What retrieve_into_paged refuses of a RopeShift before anything is queued (ValueError)."""
+        ref, D = LMCacheEngine._cache_ref(kv_caches, layout)
         if ref.dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"rope: a {ref.dtype} cache cannot be shifted (rotating fp8 keys would round them to 3 or 2 "
                              "mantissa bits a second time); only bfloat16 / float16 caches are")
@@ -594,6 +621,16 @@ class LMCacheEngine:
                     pending = None  # (the decode jobs do it, range by range)
                     got = self.engine_.get_kv_range(keys if hits == len(keys) else keys[:hits], dst, fmt, -extra, cs,
                                                     layers_per_launch=layers_per_launch, jobs_out=jobs_out, **kw)
+                elif pending is not None and pending.fused and pending.cos_sin is not None:
+                    # the one-piece retrieve with the rotation INSIDE the fixed-width decode (LMCACHE_AMD_FUSED_ROPE): the
+                    # post-op rides in the decode jobs as ONE range of all layers, and the jobs are finished here, as
+                    # get_kv_range finishes the ones it does not hand out
+                    fused_post, pending, jobs = pending, None, []
+                    got = self.engine_.get_kv_range(keys if hits == len(keys) else keys[:hits], dst, fmt, -extra, cs,
+                                                    layers_per_launch=L, jobs_out=jobs, post=fused_post)
+                    for codec, job in jobs:
+                        if job is not None:
+                            codec.finish_decode(job)
                 else:
                     got = self.engine_.get_kv_range(keys if hits == len(keys) else keys[:hits], dst, fmt, -extra, cs)
             except native.NativeError:
@@ -745,9 +782,12 @@ class _PagedTarget:
         assert engine.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
         self.num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
-        direct = engine._direct_retrieve(direct, layout, rope)
+        self.fused = rope is not None and engine._fused_rope_tier()  # the rotation rides inside the fixed-width decode
+        head_size = engine._head_size(kv_caches, layout) if self.fused else None
+        direct = engine._direct_retrieve(direct, layout, rope, head_size)
         if rope is not None:
-            if direct and layout == "NHDB" and not getattr(engine, "split_rope", False):
+            if (direct and layout == "NHDB" and not getattr(engine, "split_rope", False)
+                    and not engine._fused_direct(direct, layout, rope, head_size)):
                 raise ValueError("direct=True with rope: the keys are re-rotated in the staged chunk (lmc_rope_shift does "
                                  "not address an \"NHDB\" cache); use the staged retrieve")
             engine._check_rope(rope, kv_caches, layout, len(tokens))
@@ -775,7 +815,7 @@ class _PagedTarget:
                 deltas=None if rope is None else rope.deltas_for(skip, nret, self.ntokens, dst.device),
                 # (a split cache that is filled directly names ITSELF: the keys are rotated where the decoder put them,
                 # native.RangePost.in_place / the in-place form of lmc_range_post)
-                scatter_dst=dst if self.staged or (rope is not None and layout == "NHDB") else None)
+                scatter_dst=dst if self.staged or (rope is not None and layout == "NHDB") else None, fused=self.fused)
         self.hold = (chunk, self._post)
         return rows
 

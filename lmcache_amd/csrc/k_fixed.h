@@ -55,6 +55,7 @@
 #include "k_encode.h"
 #include "k_quantize.h"
 #include "k_decode.h"
+#include "k_rope.h"  // rope_pair, rope_cast: k_fixed_decode_rope's arithmetic is the rotation pass's
 
 __device__ __forceinline__ u32 fixed_stream_bytes_dev(u32 bins, u32 O) {  // lmc_fixed_stream_bytes
   return (bins <= LMC_FIXED_NARROW_BINS ? 256u : 320u) * O + LMC_FIXED_TAIL_BYTES;
@@ -496,6 +497,400 @@ __global__ __launch_bounds__(64 * FIXED_DEC_WAVES) void k_fixed_decode(FixedDecA
   const u32 got = wave_sum_u32(acc);
   const u32 tw = lane < 4 ? ((const LMC_GLOBAL u32*)(sbytes + ssize - LMC_FIXED_TAIL_BYTES))[lane] : 0u;
   if (__ballot(lane < 4 && tw != (lane == 0 ? got : 0u)) != 0ull) fail(LMC_ST_BAD_STREAM);
+}
+
+// ---- k_fixed_decode_rope: k_fixed_decode that re-rotates the keys before their only cast (RoPE shift, one pass) -------
+// What lmc_rope_shift / lmc_rope_shift_split do in a second pass over the K planes -- read the 16-bit keys back, rotate,
+// round again, write again -- is done here on the dequantised fp32 value, which is then cast ONCE and stored ONCE
+// (lmc_decode_chunks_fixed_rope_schedule).  Possible in this decoder and not in k_decode because a fixed-width stream is
+// random-access and has no token loop: nothing ties a wave to one stream.
+//   work split   A V stream is one wave's work, as in k_fixed_decode.  A K plane is cut into HEAD UNITS of U = max(1, D / 64)
+//                consecutive streams; one wave owns a unit and walks the 32-token tiles of its U streams together, so that
+//                both NeoX partners (d, d + rot/2) of every head of the unit are in this wave's LDS.  D | 64: a stream holds
+//                64 / D whole heads, U = 1.  64 | D: a head is U whole streams (D in {8, 16, 32, 64, 128, 192, 256}; the
+//                host refuses the rest).  Work items: the launch's K units first, then its V streams -- a unit lives U times
+//                as long as a stream, so the long items start first.
+//   data         per tile and stream the loads of k_fixed_decode (16 bytes of `lo`, a dword of `hi`, non-temporal, the next
+//                tile's in flight while this one is stored), each stream's check word summed over exactly what was
+//                loaded; the U tiles staged side by side in the wave's LDS (U x 320 dwords + scales + LUT: 5.4 KiB at
+//                U = 4, sized by the launch).  Read back transposed a lane holds 8 channels of one token: its own vector
+//                and, NeoX, the partner vector d0 +- rot/2 from the tile of the stream that holds it (D = 128: the same
+//                lane slot of the unit's other stream; D = 64: lane slot cj +- 4 of the same stream).  GPT-J partners are
+//                neighbours in the lane's own vector.  A lane whose channels lie at or past rot (partial rotary) stores
+//                what k_fixed_decode stores.
+//   cos / sin    k_rope_vec's: the one row of a uniform delta goes to LDS once per workgroup, per-token rows come from
+//                global memory as 16-byte fp32 vectors.  Destination token t takes deltas[t - tok_begin] where
+//                tok_begin <= t < tok_begin + ntok (lmc_range_post) and is not rotated outside that window.
+//   arithmetic   x = lut[q] * scale rounded to fp32; rope_pair (k_rope.h: every product and sum rounded to fp32 by itself);
+//                ONE cast, rope_cast<DT>.  A NeoX lane needs one of the pair's two results: o2 = x2 c + x1 s is computed as
+//                rope_pair's o1 with the sign of s flipped (a + b and a - (-b) are the same fp32 sum).
+//   outside the table   a token whose |delta| is not a row of the table is stored unrotated, LMC_STATUS_BAD_POSITION in
+//                `rope_status` (k_rope.h).
+// Validation, the V planes and the stores are k_fixed_decode's, line for line: its code is repeated here and not shared
+// with it, so that its instances stay the binary they were.  No head window (DecodeArgs): the host does not combine them.
+struct FixedRopeArgs {
+  DecodeArgs d;
+  const float* cos_sin;  // [table_rows][rot], 16-byte aligned
+  const int* deltas;     // [ntok]: of destination token tok_begin + i; or null: `delta` for all (inside the table: the host has looked)
+  u32* rope_status;
+  int rot, table_rows, delta, tok_begin, ntok;
+  int U;  // streams of a head unit: max(1, D / 64)
+};
+
+#define FIXED_ROPE_MAX_U 4
+// dwords of a wave's LDS: U tiles (lo 256 | hi 64) | scales of the tile's tokens | LUT
+__host__ __device__ __forceinline__ u32 fixed_rope_wave_dwords(u32 U) { return U * 320u + 64u; }
+
+template <int DT>
+__device__ __forceinline__ u32 fixed_cast16(float val) {  // k_fixed_decode's cast of an unrotated value
+  if constexpr (DT == LMC_DTYPE_BF16) return (u32)__builtin_bit_cast(unsigned short, (__bf16)val);
+  else {
+    asm volatile("" : "+v"(val));  // the product is rounded to fp32 first, to fp16 second (k_decode.h)
+    return f2fp16(val);
+  }
+}
+
+// The transposed read of a staged tile: the 8 channels of lane slot cj, token tj of oct oo -> x = lut[q] * scale
+__device__ __forceinline__ void fixed_deq8(const u32* lo_t, const u32* hi_t, u32 oo, u32 cj, u32 tj, bool wide, const float* lut,
+                                           float scale, float (&x)[8]) {
+  const u32x4_t wa = *reinterpret_cast<const u32x4_t*>(lo_t + oo * 64u + 8u * cj);
+  const u32x4_t wb = *reinterpret_cast<const u32x4_t*>(lo_t + oo * 64u + 8u * cj + 4u);
+  const u32x2_t hb = *reinterpret_cast<const u32x2_t*>(hi_t + oo * 16u + 2u * cj);
+  const u32 w[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+  const u32 sh = 8u * (tj & 3u) + 4u * (tj >> 2);
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    u32 q = (w[e] >> sh) & 15u;
+    if (wide) q |= ((((e < 4 ? hb.x : hb.y) >> (8 * (e & 3))) >> tj) & 1u) << 4;
+    x[e] = __fmul_rn(lut[q], scale);
+  }
+}
+
+// Compiled without the packed fp32 instructions (two-lane multiplies and adds the vectoriser forms out of the eight
+// independent products of a vector): a per-kernel target feature, so that the rest of the library is built as it was.
+// A function with other features than its caller is inlined only where it must be: the lambdas below are always_inline,
+// and ballot, atomic OR and the workgroup barrier are written as builtins instead of the HIP header's wrappers.
+#ifdef __HIP_DEVICE_COMPILE__
+#define FIXED_ROPE_NO_PK __attribute__((target("no-packed-fp32-ops")))
+#else
+#define FIXED_ROPE_NO_PK  // (the host pass knows no such feature)
+#endif
+__device__ __forceinline__ void fixed_rope_barrier() {  // __syncthreads()
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+template <int DT_OUT, int KIND, bool NEOX>
+__global__ __launch_bounds__(64 * FIXED_DEC_WAVES) FIXED_ROPE_NO_PK void k_fixed_decode_rope(FixedRopeArgs ra) {
+  static_assert(!lmc_dtype_fp8(DT_OUT), "16-bit elements");
+  constexpr bool SPLIT = KIND == DEC_PAGED_SPLIT;
+  constexpr int MU = FIXED_ROPE_MAX_U;
+  extern __shared__ __attribute__((aligned(16))) u32 fixed_rope_lds[];  // cos/sin row [rot] | FIXED_DEC_WAVES x wave dwords
+  const DecodeArgs& a = ra.d;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const u32 U = (u32)ra.U, rot = (u32)ra.rot, half = rot >> 1;
+  const float* const row_lds = reinterpret_cast<const float*>(fixed_rope_lds);
+  if (!ra.deltas) {  // one delta: its table row, once per workgroup (every wave is still here)
+    const u32 row = ra.delta < 0 ? 0u - (u32)ra.delta : (u32)ra.delta;
+    const LMC_GLOBAL f32x4_t* g = (const LMC_GLOBAL f32x4_t*)(ra.cos_sin + (size_t)row * rot);
+    for (u32 i = threadIdx.x; i < rot / 4u; i += 64u * FIXED_DEC_WAVES) reinterpret_cast<f32x4_t*>(fixed_rope_lds)[i] = g[i];
+    fixed_rope_barrier();
+  }
+  // ---- the work item: a head unit of a K plane, or a V stream ------------------------------------------------------------
+  const u32 G = (u32)a.G, NU = G / U, nl = (u32)a.layer_count;  // (U > 1: G = H * U)
+  const u32 nK = (u32)a.nchunks * nl * NU, nV = (u32)a.nchunks * nl * G;
+  const u32 gid = blockIdx.x * (u32)FIXED_DEC_WAVES + (u32)wave;
+  if (gid >= nK + nV) return;
+  const bool is_k = gid < nK;  // (wave-uniform, like everything down to the destination)
+  const u32 per_plane = is_k ? NU : G, item = is_k ? gid : gid - nK;
+  const int chunk = (int)(item / (nl * per_plane));
+  const u32 r = item - (u32)chunk * nl * per_plane;
+  const int pidx = (int)(r / per_plane);
+  const int g0 = (int)((r - (u32)pidx * per_plane) * (is_k ? U : 1u));  // the item's first stream
+  const u32 ns = is_k ? U : 1u;                                         // ... and how many it owns
+  const int p = is_k ? a.layer_begin + pidx : (a.P >> 1) + a.layer_begin + pidx;
+  u32* const tiles = fixed_rope_lds + rot + (u32)wave * fixed_rope_wave_dwords(U);  // tile u: lo at 320 u, hi at 320 u + 256
+  float* const sc_t = reinterpret_cast<float*>(tiles + U * 320u);
+  float* const lut = sc_t + 32;
+  const u8* const blob = a.blob_ptrs ? (const u8*)uniform_ptr(a.blob_ptrs[chunk]) : a.blobs + (long long)chunk * a.blob_stride;
+  auto fail = [&](u32 bit) __attribute__((always_inline)) { if (lane == 0) __hip_atomic_fetch_or(a.status, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+
+  // ---- header (the host has seen to it that 128 bytes may be read) -----------------------------------------------------
+  const u32 hv = ((const LMC_GLOBAL u32*)blob)[lane & 31];
+  auto hdw = [&](int i) __attribute__((always_inline)) { return (u32)__builtin_amdgcn_readlane((int)hv, i); };
+  const u32 T = hdw(4), src_dtype = hdw(2);
+  const BlobOff bo = lmc_blob_off((u32)a.P, T, (u32)a.G);
+  if (hdw(0) != LMC_BLOB_MAGIC || (hdw(1) & 0xffffu) != LMC_BLOB_VERSION || hdw(7) != (u32)a.C || T == 0u || T > 65535u ||
+      T > (u32)a.chunk_tokens || hdw(8) != (u32)a.P || hdw(22) != LMC_MODEL_FIXED || hdw(15) != bo.streams ||
+      (src_dtype != (u32)LMC_DTYPE_BF16 && src_dtype != (u32)LMC_DTYPE_FP16) ||
+      (unsigned long long)hdw(15) + (unsigned long long)hdw(16) != (unsigned long long)hdw(17) ||
+      (unsigned long long)hdw(17) > (unsigned long long)a.blob_stride) {
+    return fail(LMC_ST_BAD_HEADER);
+  }
+  // ---- the layout the bins say (they lie in front of off_streams <= total_bytes <= the blob's room) -------------------
+  const u32 O = (T + 7u) >> 3;
+  u32 mine = 0, before = 0;
+  bool bad = false;
+  for (int q = lane; q < a.P; q += 64) {
+    const u32 b = (u32)((const LMC_GLOBAL u8*)blob)[LMC_HEADER_BYTES + q];
+    bad = bad || b < 4u || b > (u32)LMC_MAX_BINS;
+    const u32 sz = (u32)a.G * fixed_stream_bytes_dev(b, O);
+    mine += sz;
+    if (q < p) before += sz;
+  }
+  const u32 total = wave_sum_u32(mine);
+  const u32 pbeg = wave_sum_u32(before);
+  const u32 bins_p = (u32)__builtin_amdgcn_readfirstlane((int)(u32)((const LMC_GLOBAL u8*)blob)[LMC_HEADER_BYTES + p]);
+  const u32 ssize = fixed_stream_bytes_dev(bins_p, O);
+  const u32 beg = pbeg + (u32)g0 * ssize;  // the item's streams lie side by side: stream u at beg + u * ssize
+  // lane u holds the directory entry of the item's stream u
+  const u32x2_t gd = (u32)lane < ns ? *(const LMC_GLOBAL u32x2_t*)(blob + bo.gdir + 8u * ((u32)(p * a.G + g0) + (u32)lane)) : u32x2_t{0u, 0u};
+  const bool gbad = (u32)lane < ns && (gd.x != beg + (u32)lane * ssize || gd.y != beg + ((u32)lane + 1u) * ssize);
+  if (__builtin_amdgcn_ballot_w64(bad || gbad) != 0ull || total != hdw(16)) return fail(LMC_ST_BAD_HEADER);
+  const u8* const sbytes = blob + bo.streams + beg;  // beg + ns * ssize <= total: inside the blob
+  const bool wide = bins_p > LMC_FIXED_NARROW_BINS;  // (wave-uniform, the plane's)
+
+  const u16* const scl = reinterpret_cast<const u16*>(blob + bo.scales) + (long long)p * T;
+  if (g0 == 0) {  // the plane's first wave checks the scales (the others do not wait for the verdict)
+    const u32 want = (u32)__builtin_amdgcn_readfirstlane((int)((const LMC_GLOBAL u32*)(blob + bo.scsum))[p]);
+    if (scale_checksum(scl, T, lane) != want) return fail(LMC_ST_BAD_SCALES);
+  }
+  if (lane < 32) {  // (q - C) / C, k_decode.h's table
+    const float Cf = (float)((int)bins_p / 2 - 1);
+    const float v = (float)lane - Cf;
+    lut[lane] = v / Cf;
+  }
+
+  // ---- destination: per stream of the item, the lane's 8 channels (lane slot cj) of token tj -----------------------------
+  typedef typename KvElem<DT_OUT>::T E;
+  const u32 cj = (u32)lane & 7u, tj = (u32)lane >> 3;
+  E* const pbase = const_cast<E*>(lmc_plane_base<E>(a.dst, p));
+  const bool is_v = SPLIT && !is_k;
+  const u32 bs = (u32)a.dst.block_size;
+  const bool aligned = SPLIT && ((((uintptr_t)pbase) & 15u) | (uintptr_t)((a.dst.stride_block | a.dst.stride_head) & 7)) == 0;
+  bool cok[MU], rme[MU], first[MU];  // in the plane | rotated (its channels lie below rot) | NeoX: the pair's x1 side
+  long long coff[MU];                // rows: the 8 channels are contiguous from here
+  u32 k_in[MU], pu[MU], pcj[MU], ci[MU];  // split K: the lane's part | NeoX partner: its stream and lane slot | first cos of the lane
+#pragma unroll
+  for (int u = 0; u < MU; u++) {
+    const int c0 = (g0 + u) * 64 + 8 * (int)cj;
+    const int h0 = c0 / a.dst.D, d0 = c0 - h0 * a.dst.D;
+    cok[u] = (u32)u < ns && c0 < a.C;
+    coff[u] = (long long)h0 * a.dst.stride_head + d0;
+    k_in[u] = (u32)h0 * (u32)a.dst.stride_head + ((u32)d0 >> 3) * (bs * 8u);
+    rme[u] = is_k && cok[u] && (u32)d0 < rot;
+    first[u] = (u32)d0 < half;
+    if constexpr (NEOX) {
+      const u32 dp = first[u] ? (u32)d0 + half : (u32)d0 - half;  // (used under rme only)
+      const u32 cp = (u32)(h0 * a.dst.D) + dp;
+      pu[u] = (cp >> 6) - (u32)g0;
+      pcj[u] = (cp & 63u) >> 3;
+      ci[u] = first[u] ? (u32)d0 : dp;
+    } else {
+      pu[u] = 0u; pcj[u] = 0u;
+      ci[u] = (u32)d0 >> 1;
+    }
+  }
+  // a V plane of a split cache keeps what it loaded (k_fixed_decode): oct lane >> 4, channels vc0 .. vc0 + 3 of one head
+  const int vc0 = g0 * 64 + 4 * (lane & 15);
+  const bool vcok = vc0 < a.C;
+  const int vh = vc0 / a.dst.D;
+  const u32 v_in = (u32)vh * (u32)a.dst.stride_head + (u32)(vc0 - vh * a.dst.D) * bs;
+  const int tdst0 = a.dst_tok0 + chunk * a.chunk_tokens;
+
+  const u32 ntile = (O + 3u) >> 2;
+  u32 acc[MU];
+  struct Tile { u32x4_t lo; u32 hi; };
+  Tile cur[MU];
+  u32 cur_sc;
+  auto load_tile = [&](u32 tile) __attribute__((always_inline)) {
+    const bool in = tile * 4u + ((u32)lane >> 4) < O;
+#pragma unroll
+    for (int u = 0; u < MU; u++) {
+      const bool inu = in && (u32)u < ns;
+      const u8* const sb = sbytes + (size_t)u * ssize;
+      cur[u].lo = inu ? __builtin_nontemporal_load((const LMC_GLOBAL u32x4_t*)sb + (tile * 64u + (u32)lane)) : u32x4_t{0u, 0u, 0u, 0u};
+      cur[u].hi = (wide && inu) ? __builtin_nontemporal_load((const LMC_GLOBAL u32*)(sb + 256u * (size_t)O) + (tile * 64u + (u32)lane)) : 0u;
+    }
+    const u32 tt = tile * 32u + (u32)lane;
+    cur_sc = (lane < 32 && tt < T) ? (u32)scl[tt] : 0u;
+  };
+#pragma unroll
+  for (int u = 0; u < MU; u++) acc[u] = 0u;
+  bool badpos = false;
+  load_tile(0);
+  for (u32 tile = 0; tile < ntile; tile++) {
+    {  // the check words over exactly what was loaded; then the tiles go to LDS as they lie in the streams
+      const u32 i0 = tile * 256u + 4u * (u32)lane;
+#pragma unroll
+      for (int u = 0; u < MU; u++) {
+        if ((u32)u >= ns) continue;
+        acc[u] += (2u * i0 + 1u) * cur[u].lo.x + (2u * i0 + 3u) * cur[u].lo.y + (2u * i0 + 5u) * cur[u].lo.z + (2u * i0 + 7u) * cur[u].lo.w;
+        acc[u] += (2u * (64u * O + tile * 64u + (u32)lane) + 1u) * cur[u].hi;
+        if (!is_v) {
+          *reinterpret_cast<u32x4_t*>(tiles + 320 * u + 4 * lane) = cur[u].lo;
+          tiles[320 * u + 256 + lane] = cur[u].hi;
+        }
+      }
+      if (lane < 32) sc_t[lane] = h2f_rt(cur_sc, (int)src_dtype);
+    }
+    wave_lds_fence();
+    const Tile mine0 = cur[0];
+    if (tile + 1u < ntile) load_tile(tile + 1u);  // in flight while this tile is stored
+    if constexpr (SPLIT) {
+      if (is_v) {
+        // the lane's oct: slots of its live tokens only (t < T, not trimmed), and nothing of a token that is not live
+        const u32 oo = (u32)lane >> 4, t0 = (tile * 4u + oo) * 8u;
+        bool live[8], all = vcok, any = false;
+        u32 sl[8];
+#pragma unroll
+        for (int r8 = 0; r8 < 8; r8++) {
+          live[r8] = vcok && t0 + (u32)r8 < T && tdst0 + (int)(t0 + (u32)r8) >= 0;
+          sl[r8] = live[r8] ? (u32)a.dst.slot_mapping[tdst0 + (int)(t0 + (u32)r8)] : 0u;
+          all = all && live[r8];
+          any = any || live[r8];
+        }
+        const u32 b0 = sl[0] / bs, w0 = sl[0] - b0 * bs;
+        bool run = all && aligned && (w0 & 7u) == 0u && (bs & 7u) == 0u;
+#pragma unroll
+        for (int r8 = 1; r8 < 8; r8++) run = run && sl[r8] == sl[0] + (u32)r8;
+        const u32 lw[4] = {mine0.lo.x, mine0.lo.y, mine0.lo.z, mine0.lo.w};
+        u32 bits[4][8];
+#pragma unroll
+        for (int r8 = 0; r8 < 8; r8++) {
+          const float scale = sc_t[oo * 8u + (u32)r8];
+#pragma unroll
+          for (int e = 0; e < 4; e++) {
+            u32 q = (lw[e] >> (8u * ((u32)r8 & 3u) + 4u * ((u32)r8 >> 2))) & 15u;
+            if (wide) q |= ((mine0.hi >> (8u * (u32)e + (u32)r8)) & 1u) << 4;
+            bits[e][r8] = fixed_cast16<DT_OUT>(lut[q] * scale);
+          }
+        }
+        if (__builtin_amdgcn_ballot_w64(any && !run) == 0ull) {  // every oct of the tile that writes at all is a whole aligned run
+          if (run) {
+            LMC_GLOBAL u16* const blk = (LMC_GLOBAL u16*)(pbase + (long long)b0 * a.dst.stride_block);
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+              *(LMC_GLOBAL u32x4_t*)(blk + (v_in + (u32)e * bs + w0)) = u32x4_t{bits[e][0] | (bits[e][1] << 16), bits[e][2] | (bits[e][3] << 16),
+                                                                               bits[e][4] | (bits[e][5] << 16), bits[e][6] | (bits[e][7] << 16)};
+          }
+        } else {
+#pragma unroll
+          for (int r8 = 0; r8 < 8; r8++) {
+            if (!live[r8]) continue;
+            const u32 br = sl[r8] / bs, wr = sl[r8] - br * bs;
+            LMC_GLOBAL u16* const blk = (LMC_GLOBAL u16*)(pbase + (long long)br * a.dst.stride_block);
+#pragma unroll
+            for (int e = 0; e < 4; e++) blk[v_in + (u32)e * bs + wr] = (u16)bits[e][r8];
+          }
+        }
+        wave_lds_fence();  // the scales have been read
+        continue;
+      }
+    }
+    const u32 noct = min(4u, O - tile * 4u);
+    for (u32 oo = 0; oo < noct; oo++) {
+      const u32 t = (tile * 4u + oo) * 8u + tj;
+      const int tdst = tdst0 + (int)t;
+      const bool tok = t < T && tdst >= 0;
+      const float scale = sc_t[oo * 8u + tj];
+      // the token's rotation: deltas[tdst - tok_begin] inside the post's window, none outside it or outside the table
+      bool trot = false, neg = false;
+      u32 row = 0u;
+      if (is_k && tok) {
+        const int ri = tdst - ra.tok_begin;
+        if (ri >= 0 && ri < ra.ntok) {
+          const int dl = ra.deltas ? ((const LMC_GLOBAL int*)ra.deltas)[ri] : ra.delta;
+          neg = dl < 0;
+          row = neg ? 0u - (u32)dl : (u32)dl;
+          trot = row < (u32)ra.table_rows;
+          badpos = badpos || !trot;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < MU; u++) {
+        if ((u32)u >= ns) continue;
+        const bool ok = cok[u] && tok;
+        float x[8];
+        fixed_deq8(tiles + 320 * u, tiles + 320 * u + 256, oo, cj, tj, wide, lut, scale, x);
+        u32 bits[8];
+        if (rme[u] && trot) {
+          constexpr int NC = NEOX ? 2 : 1;  // 16-byte vectors of cos (and of sin) of the lane's channels
+          f32x4_t cv[NC], sv[NC];
+          if (ra.deltas) {
+            const LMC_GLOBAL float* g = (const LMC_GLOBAL float*)(ra.cos_sin + (size_t)row * rot);
+#pragma unroll
+            for (int k = 0; k < NC; k++) {
+              cv[k] = *(const LMC_GLOBAL f32x4_t*)(g + ci[u] + 4 * k);
+              sv[k] = *(const LMC_GLOBAL f32x4_t*)(g + half + ci[u] + 4 * k);
+            }
+          } else {
+#pragma unroll
+            for (int k = 0; k < NC; k++) {
+              cv[k] = *reinterpret_cast<const f32x4_t*>(row_lds + ci[u] + 4 * k);
+              sv[k] = *reinterpret_cast<const f32x4_t*>(row_lds + half + ci[u] + 4 * k);
+            }
+          }
+          float c[4 * NC], s[4 * NC];
+#pragma unroll
+          for (int k = 0; k < NC; k++) {
+            c[4 * k] = cv[k].x; c[4 * k + 1] = cv[k].y; c[4 * k + 2] = cv[k].z; c[4 * k + 3] = cv[k].w;
+            s[4 * k] = sv[k].x; s[4 * k + 1] = sv[k].y; s[4 * k + 2] = sv[k].z; s[4 * k + 3] = sv[k].w;
+          }
+          if constexpr (NEOX) {
+            float y[8];  // the partner vector, out of the tile of the stream that holds it
+            fixed_deq8(tiles + 320u * pu[u], tiles + 320u * pu[u] + 256u, oo, pcj[u], tj, wide, lut, scale, y);
+            // x1 side: o1 = x c - y s.  x2 side: o2 = x c + y s = x c - y (-s).  A negative delta flips s once more.
+            const bool flip = neg == first[u];
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+              float o1, o2;
+              rope_pair(x[e], y[e], c[e], flip ? -s[e] : s[e], o1, o2);
+              bits[e] = rope_cast<DT_OUT>(o1);
+            }
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              float o1, o2;
+              rope_pair(x[2 * k], x[2 * k + 1], c[k], neg ? -s[k] : s[k], o1, o2);
+              bits[2 * k] = rope_cast<DT_OUT>(o1);
+              bits[2 * k + 1] = rope_cast<DT_OUT>(o2);
+            }
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; e++) bits[e] = fixed_cast16<DT_OUT>(x[e]);
+        }
+        const u32x4_t v = {bits[0] | (bits[1] << 16), bits[2] | (bits[3] << 16), bits[4] | (bits[5] << 16), bits[6] | (bits[7] << 16)};
+        if constexpr (SPLIT) {
+          if (ok) {
+            LMC_GLOBAL u16* const gp = (LMC_GLOBAL u16*)(pbase + dec_tok_off_split(a.dst, tdst, 8u)) + k_in[u];
+            if (aligned) {
+              *(LMC_GLOBAL u32x4_t*)gp = v;
+            } else {
+#pragma unroll
+              for (int e = 0; e < 8; e++) gp[e] = (u16)bits[e];
+            }
+          }
+        } else if (ok) {  // (rows that take 16-byte vectors: the host refuses the others)
+          const long long toff = KIND == DEC_ROWS ? (long long)tdst * a.dst.stride_token : dec_tok_off(a.dst, tdst);
+          __builtin_nontemporal_store(v, (LMC_GLOBAL u32x4_t*)(pbase + toff + coff[u]));
+        }
+      }
+    }
+    wave_lds_fence();  // the tiles have been read: the next ones may take their place
+  }
+  if (__builtin_amdgcn_ballot_w64(badpos) != 0ull && lane == 0) __hip_atomic_fetch_or(ra.rope_status, LMC_STATUS_BAD_POSITION, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  bool sbad = false;
+#pragma unroll
+  for (int u = 0; u < MU; u++) {
+    if ((u32)u >= ns) continue;
+    const u32 got = wave_sum_u32(acc[u]);
+    const u32 tw = lane < 4 ? ((const LMC_GLOBAL u32*)(sbytes + (size_t)(u + 1) * ssize - LMC_FIXED_TAIL_BYTES))[lane] : 0u;
+    sbad = sbad || (lane < 4 && tw != (lane == 0 ? got : 0u));
+  }
+  if (__builtin_amdgcn_ballot_w64(sbad) != 0ull) fail(LMC_ST_BAD_STREAM);
 }
 
 // ---- k_fixed_expand: fixed-width blobs -> what k_quantize<true> leaves for the same chunks ----------------------------

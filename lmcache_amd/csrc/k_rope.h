@@ -5,8 +5,10 @@
 // fp32: row r = cos(r f_i) for i < rot/2, then sin(r f_i)).  Replaces the connector's gather-K / rotary / scatter-K in
 // torch behind a retrieve of a segment that was prefilled on its own (BASELINE configs[4]): three passes and one
 // temporary per layer become one pass over the K planes, read once and written once.  It is a kernel of its own and not
-// part of k_decode: a decoder wave owns 64 adjacent channels, and the NeoX partners (i, i + rot/2) of a 128-wide head
-// lie in two waves.
+// part of k_decode: a wave of the CODED decoder is tied to one rANS stream of 64 adjacent channels by its token loop, and
+// the NeoX partners (i, i + rot/2) of a 128-wide head lie in two waves.  The fixed-width decoder has no such tie -- its
+// streams are random-access -- and k_fixed.h's k_fixed_decode_rope gives a wave a whole head's streams and does this
+// rotation on the dequantised fp32 value (rope_pair and rope_cast below are its arithmetic too).
 //
 // The arithmetic, the same in all kernels of this file and in the CPU statement the tests hold them to (bit for bit): with
 // d the token's delta, c = table[|d|][i], s = sign(d) table[|d|][rot/2 + i],

@@ -1191,12 +1191,37 @@ static void launch_fixed_decode(const lmc_kv_layout* dst, long long nstreams, hi
   });
 }
 
+// k_fixed_decode_rope: k_fixed_decode with the rotation of `rope` (a post that fused_rope_ok has passed) inside it.  A K
+// plane is G / U head units of U = max(1, D / 64) streams, a unit one wave's work; the launch's K units stand in front of
+// its V streams (k_fixed.h).
+static void launch_fixed_decode_rope(lmc_ctx* c, const lmc_kv_layout* dst, const lmc_range_post* rope, hipStream_t s, const DecodeArgs& a) {
+  FixedRopeArgs ra;
+  ra.d = a;
+  ra.cos_sin = rope->cos_sin; ra.deltas = rope->deltas; ra.rope_status = c->status_h;  // (a bad position: the context's word, as range_post)
+  ra.rot = rope->rot_dim; ra.table_rows = rope->table_rows; ra.delta = rope->delta;
+  ra.tok_begin = rope->tok_begin; ra.ntok = rope->ntok;
+  ra.U = std::max(1, dst->head_size / 64);
+  const long long nwaves = (long long)a.nchunks * a.layer_count * (a.G / ra.U + a.G);
+  const dim3 grid((unsigned)((nwaves + FIXED_DEC_WAVES - 1) / FIXED_DEC_WAVES)), block(64 * FIXED_DEC_WAVES);
+  const size_t lds = 4 * ((size_t)ra.rot + FIXED_DEC_WAVES * (size_t)fixed_rope_wave_dwords((u32)ra.U));
+  with_kv_dtype16(dst->dtype, [&](auto dt) {
+    with_decode_kind(dst, [&](auto kind) {
+      with_bool(rope->is_neox != 0, [&](auto nx) {
+        hipLaunchKernelGGL((k_fixed_decode_rope<decltype(dt)::value, decltype(kind)::value, decltype(nx)::value>), grid, block, lds, s, ra);
+      });
+    });
+  });
+}
+
+// `fused` (lmc_decode_chunks_fixed_rope_schedule): the rotation of this post is part of the fixed-width decode launch.
 static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev,
-                               lmc_ctx* c = nullptr, const lmc_range_post* post = nullptr, bool fixed = false) {
+                               lmc_ctx* c = nullptr, const lmc_range_post* post = nullptr, bool fixed = false,
+                               const lmc_range_post* fused = nullptr) {
   a.layer_begin = l0; a.layer_count = nl;
   const long long n = (long long)a.nchunks * 2 * nl * a.wGw;  // (wGw == G but for a head window: the groups it touches)
   const dim3 grid((unsigned)((n + DEC_WAVES - 1) / DEC_WAVES));
-  if (fixed) launch_fixed_decode(dst, n, s, a);
+  if (fused) launch_fixed_decode_rope(c, dst, fused, s, a);
+  else if (fixed) launch_fixed_decode(dst, n, s, a);
   else launch_decode(dst, grid, s, a);
   HIP_TRY(hipGetLastError());
   if (post) {  // (none of its launches needs the lock)
@@ -1210,13 +1235,13 @@ static int decode_range_locked(DecodeArgs& a, const lmc_kv_layout* dst, int l0, 
 // The same for the decode entry points, which do not hold the lock: taken here, and the launch bracketed by the
 // profiling marks (the range's event follows the second mark).
 static int decode_range(lmc_ctx* c, DecodeArgs& a, const lmc_kv_layout* dst, int l0, int nl, hipStream_t s, lmc_event_t ev,
-                        const lmc_range_post* post = nullptr, bool fixed = false) {
+                        const lmc_range_post* post = nullptr, bool fixed = false, const lmc_range_post* fused = nullptr) {
   int rc;
   {
     std::lock_guard<std::mutex> lk(c->mu);
     c->pn = 0;
     if ((rc = prof_mark(c, s))) return rc;
-    if ((rc = decode_range_locked(a, dst, l0, nl, s, nullptr, nullptr, nullptr, fixed))) return rc;
+    if ((rc = decode_range_locked(a, dst, l0, nl, s, nullptr, c, nullptr, fixed, fused))) return rc;
     if ((rc = prof_mark(c, s))) return rc;
   }
   if (post && (rc = range_post(c, dst, post, l0, nl, s))) return rc;
@@ -1248,6 +1273,8 @@ int lmc_decode_chunks_layers(lmc_ctx* c, const void* const* blob_ptrs, uint64_t 
 }
 
 static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* post);
+static bool post_in_place(const lmc_kv_layout* dst, const lmc_range_post* post);
+static bool fused_rope_ok(const lmc_kv_layout* dst, const lmc_range_post* post);
 
 // One body for the two schedules: the coded models' k_decode, or -- `fixed` -- k_fixed_decode for LMC_MODEL_FIXED blobs,
 // which fills 16-bit rows and -- `fixed_split`: lmc_decode_chunks_fixed_split_schedule -- a 16-bit LMC_PAGED_SPLIT cache
@@ -1261,7 +1288,7 @@ static int decode_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t ma
                            const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
                            const int32_t* layer_ends_h, const lmc_event_t* events_h, uint32_t* job_status,
                            lmc_stream_t stream, const lmc_range_post* post, bool fixed, bool fixed_split = false,
-                           const lmc_head_window* win = nullptr) {
+                           const lmc_head_window* win = nullptr, bool fused_rope = false) {
   DecodeArgs a;
   int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, !fixed || fixed_split);
   if (rc) return rc;
@@ -1285,9 +1312,20 @@ static int decode_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t ma
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)  // the whole schedule is checked before anything is launched
     if (layer_ends_h[i] <= prev || layer_ends_h[i] > dst->num_layers) return LMC_ERR_INVALID;
   if (layer_ends_h[nranges - 1] != dst->num_layers || !post_ok(dst, post)) return LMC_ERR_INVALID;
+  // fused_rope: the post's rotation is k_fixed_decode_rope's; what is left to do per range behind the launch is the scatter
+  // of a staged chunk (the post without its rotation), or -- rows rotated where they lie, the in-place split form -- nothing
+  const lmc_range_post* fused = nullptr;
+  lmc_range_post scatter;
+  if (fused_rope) {
+    if (!fused_rope_ok(dst, post)) return LMC_ERR_INVALID;
+    fused = post;
+    scatter = *post;
+    scatter.cos_sin = nullptr;
+    post = post->scatter_dst && !post_in_place(dst, post) ? &scatter : nullptr;
+  }
   HIP_TRY(hipSetDevice(c->device));
   for (int i = 0, prev = 0; i < nranges; prev = layer_ends_h[i], i++)
-    if ((rc = decode_range(c, a, dst, prev, layer_ends_h[i] - prev, (hipStream_t)stream, events_h ? events_h[i] : nullptr, post, fixed)))
+    if ((rc = decode_range(c, a, dst, prev, layer_ends_h[i] - prev, (hipStream_t)stream, events_h ? events_h[i] : nullptr, post, fixed, fused)))
       return rc;
   return LMC_OK;
 }
@@ -1314,6 +1352,14 @@ int lmc_decode_chunks_fixed_split_schedule(lmc_ctx* c, const void* const* blob_p
                                            uint32_t* job_status, lmc_stream_t stream) {
   return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
                          job_status, stream, post, true, true);
+}
+
+int lmc_decode_chunks_fixed_rope_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
+                                          const lmc_kv_layout* dst, int32_t dst_tok0, int32_t chunk_tokens, int32_t nranges,
+                                          const int32_t* layer_ends_h, const lmc_event_t* events_h, const lmc_range_post* post,
+                                          uint32_t* job_status, lmc_stream_t stream) {
+  return decode_schedule(c, blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0, chunk_tokens, nranges, layer_ends_h, events_h,
+                         job_status, stream, post, true, true, nullptr, true);
 }
 
 int lmc_decode_chunks_heads_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t max_blob_bytes, int32_t nchunks,
@@ -1577,6 +1623,17 @@ static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* p) {
                          !copy_kv_ok(dst, p->tok_begin, p->ntok, p->scatter_dst, p->scatter_tok0)))
     return false;
   return !p->cos_sin || rope_ok(dst, p->tok_begin, p->ntok, post_rope(p));  // (a split `dst` has no rows to rotate: refused)
+}
+// What lmc_decode_chunks_fixed_rope_schedule serves, asked of a post that post_ok has passed (rot_dim <= D, 16-bit, the
+// delta inside the table): a rotation; rows that take 16-byte vectors, or a split cache; a head size whose heads are whole
+// streams or whole parts of one (k_fixed.h: head units); and what k_rope_vec asks -- a 16-byte aligned table, pair halves
+// that are whole vectors of 8 channels (NeoX: rot_dim / 2 a multiple of 8; GPT-J: rot_dim a multiple of 8).
+static bool fused_rope_ok(const lmc_kv_layout* dst, const lmc_range_post* p) {
+  if (!p || !p->cos_sin || lmc_dtype_fp8(dst->dtype)) return false;
+  if (dst->paged_kind != LMC_PAGED_SPLIT && !layout_ok(dst)) return false;
+  const int D = dst->head_size;
+  if (D < 8 || D > 64 * FIXED_ROPE_MAX_U || (D <= 64 ? 64 % D : D % 64)) return false;
+  return rope_vec_ok(post_rope(p)) && p->rot_dim <= D;
 }
 // A bad position is reported where lmc_rope_shift reports it for the one-shot retrieve: the context's sticky word (the
 // job's own word says whether its blobs decoded).

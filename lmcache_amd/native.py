@@ -210,6 +210,8 @@ SYMBOLS = {
                                                         ctypes.POINTER(RangePostStruct), _vp, _vp]),
     "lmc_decode_chunks_fixed_split_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
                                                               ctypes.POINTER(RangePostStruct), _vp, _vp]),
+    "lmc_decode_chunks_fixed_rope_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
+                                                             ctypes.POINTER(RangePostStruct), _vp, _vp]),
     "lmc_decode_chunks_heads_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
                                                         ctypes.POINTER(HeadWindowStruct), _vp, _vp]),
     "lmc_decode_chunks_fixed_heads_schedule": (ctypes.c_int, [_vp, _vp, _u64, _i32, _PL, _i32, _i32, _i32, _vp, _vp,
@@ -699,11 +701,14 @@ class RangePost:
     (lmc_rope_shift_split), nothing is copied.  Keeps the tensors the kernels read alive."""
 
     def __init__(self, cos_sin: Optional[torch.Tensor] = None, rot_dim: int = 0, is_neox: bool = True, delta: int = 0,
-                 deltas: Optional[torch.Tensor] = None, scatter_dst: Optional["KVLayout"] = None, scatter_tok0: int = 0):
+                 deltas: Optional[torch.Tensor] = None, scatter_dst: Optional["KVLayout"] = None, scatter_tok0: int = 0,
+                 fused: bool = False):
+        """fused: a decode of fixed-width blobs may do the rotation inside its launches (fused_ok; the engine's
+        LMCACHE_AMD_FUSED_ROPE switch) -- the keys are then rounded once and differ in bits from the two-pass result."""
         if cos_sin is not None:
             Context._check_rope_args(cos_sin, rot_dim, deltas, None)
         self.cos_sin, self.rot_dim, self.is_neox, self.delta, self.deltas = cos_sin, int(rot_dim), bool(is_neox), int(delta), deltas
-        self.scatter_dst, self.scatter_tok0 = scatter_dst, int(scatter_tok0)
+        self.scatter_dst, self.scatter_tok0, self.fused = scatter_dst, int(scatter_tok0), bool(fused)
 
     @staticmethod
     def window(dst: "KVLayout", dst_tok0: int, nchunks: int, chunk_tokens: int) -> Tuple[int, int]:
@@ -718,6 +723,19 @@ class RangePost:
         s = self.scatter_dst
         return (self.cos_sin is not None and s is not None and self.scatter_tok0 == 0
                 and dst.struct.paged_kind == PAGED_SPLIT and (s is dst or bytes(s.struct) == bytes(dst.struct)))
+
+    def fused_ok(self, dst: "KVLayout") -> bool:
+        """Whether lmc_decode_chunks_fixed_rope_schedule serves this post into `dst` (fused_rope_ok in lmc_api.hip is the
+        same rule): a rotation, 16-bit elements, rows that take 16-byte vectors or a split cache, a head size whose heads
+        are whole streams or whole parts of one, and a table and rot_dim that k_rope_vec's 16-byte accesses take."""
+        if self.cos_sin is None or elem_bytes(dst.dtype) != 2:
+            return False
+        if dst.struct.paged_kind != PAGED_SPLIT and not dst.vector_readable():
+            return False
+        D = dst.D
+        if D not in (8, 16, 32, 64, 128, 192, 256) or self.rot_dim > D:
+            return False
+        return self.rot_dim % (16 if self.is_neox else 8) == 0 and self.cos_sin.data_ptr() % 16 == 0
 
     def struct(self, tok_begin: int, ntok: int) -> RangePostStruct:
         """The lmc_range_post of the job that fills destination tokens [tok_begin, +ntok): filled per call, nothing kept."""
@@ -1019,6 +1037,15 @@ class Context:
         """lmc_decode_chunks_fixed_split_schedule: decode_chunks_fixed_schedule for any destination it takes and a 16-bit
         PAGED_SPLIT ("NHDB") one, stored into in place."""
         self._schedule("lmc_decode_chunks_fixed_split_schedule", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0,
+                       chunk_tokens, layer_ends, events, post, stream, status_ptr)
+
+    def decode_chunks_fixed_rope_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout,
+                                          dst_tok0: int, chunk_tokens: int, layer_ends, events, post: RangePostStruct,
+                                          stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
+        """lmc_decode_chunks_fixed_rope_schedule: decode_chunks_fixed_split_schedule with the rotation of `post` inside
+        each range's decode launch (k_fixed_decode_rope) -- keys rounded once, not the staged call's bits.  What it does
+        not serve (RangePost.fused_ok says which) is LMC_ERR_INVALID."""
+        self._schedule("lmc_decode_chunks_fixed_rope_schedule", blob_ptrs, max_blob_bytes, nchunks, dst, dst_tok0,
                        chunk_tokens, layer_ends, events, post, stream, status_ptr)
 
     def decode_chunks_heads_schedule(self, blob_ptrs: int, max_blob_bytes: int, nchunks: int, dst: KVLayout, dst_tok0: int,

@@ -289,6 +289,7 @@ class CacheGenDeviceCodec:
         self.pack_parts = max(1, min(16, int(os.environ.get("LMCACHE_AMD_PACK_PARTS", "8"))))
         self._layer_streams: List[torch.cuda.Stream] = []    # side streams of finished layer-wise encode jobs, for the next ones
         self._warned_wide_split = False                      # direct store of an NHDB cache with planes the split quantiser does not read
+        self._warned_unfused = False                         # a fused-rope retrieve of a geometry k_fixed_decode_rope does not serve
         self._same_blobs: dict = {}                          # id(caller's list) -> (the list, its blobs' address tuple, largest blob)
         self._table_cache: dict = {}                         # blob-address tuple -> (device table, upload stream)
 
@@ -582,6 +583,16 @@ class CacheGenDeviceCodec:
             schedule = self._entry(self._HEAD_SCHEDULES, model, dst, "decode_chunks_heads_schedule")
         else:
             schedule = self._entry(self._SCHEDULES, model, dst, "decode_chunks_schedule" if post is None else "decode_chunks_schedule_post")
+            if model == "fixed" and post is not None and post.fused and post.cos_sin is not None:
+                # the rotation inside the decode launches (k_fixed_decode_rope) where the geometry is served; the two
+                # passes of the schedule above for the rest
+                if post.fused_ok(dst):
+                    schedule = self.ctx.decode_chunks_fixed_rope_schedule
+                elif not self._warned_unfused:
+                    self._warned_unfused = True
+                    logger.info("fused rope: head size %d / rot_dim %d (%s) is not served by the fused fixed-width decode; "
+                                "the keys are rotated in a second pass (logged once)", dst.D, post.rot_dim,
+                                "NeoX" if post.is_neox else "GPT-J")
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             # The blob addresses of THIS call: any number of chunks (a 128 k-token retrieve is 512 of them), uploaded
