@@ -111,6 +111,10 @@ int lmc_abi_version(void);
  *     Planes of at most 1024 channels (H * D), stride_head >= 0 and ((H-1)*stride_head + D*block_size)*E <= 0xfffffff0;
  *     beyond that LMC_ERR_INVALID before anything is queued.  lmc_encode_chunks_fixed_split reads it the same way
  *     (k_fixed.h, one kernel) under the same limits, for 16-bit elements.
+ *     WIDER PLANES, up to LMC_MAX_CHANNELS: taken by these calls -- not by the layer-wise jobs -- where the process
+ *     environment holds LMCACHE_AMD_SPLIT_WIDE=1 at the call (2 or 4 waves share a row oct, 1024 channels each, as they
+ *     do for rows; same blobs).  Without it they are refused as before: the variable is looked up only for such a
+ *     source, so no job that was taken without it reads the environment.
  *   - NOT lmc_encode_chunks and lmc_quantize: they stand for the reference's to_bytes / torch_quant_vectorized, whose
  *     caller holds a tensor of rows.  NOT lmc_encode_chunks_fixed and lmc_decode_chunks_fixed_schedule either: their
  *     _split twins are the ones that take it.
@@ -257,7 +261,8 @@ int lmc_encode_chunks(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin,
  * vLLM's ROCm paged-attention kernels is read in place, no staged chunk and no lmc_copy_kv in front.  The blobs are
  * byte for byte those lmc_encode_chunks writes from the gathered chunk.  A split source always takes k_quantize +
  * k_cdf_encode, whatever lmc_ctx_set_encode_path says; with more than 1024 channels per plane it is LMC_ERR_INVALID and
- * nothing is launched.  Any other source: exactly lmc_encode_chunks.
+ * nothing is launched, unless LMCACHE_AMD_SPLIT_WIDE=1 is set (lmc_kv_layout: then up to LMC_MAX_CHANNELS).  Any other
+ * source: exactly lmc_encode_chunks.
  */
 int lmc_encode_chunks_split(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end,
                             int32_t chunk_tokens, const int32_t* bins_h, void* blobs, uint64_t blob_stride,
@@ -279,7 +284,8 @@ int lmc_encode_chunks_fixed(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_
  * lmc_encode_chunks_fixed for any source it takes AND a 16-bit LMC_PAGED_SPLIT one (additive in ABI 6; what
  * lmc_encode_chunks_split is to lmc_encode_chunks): the cache is read in place by k_fixed_encode's split instances, no
  * staged chunk and no lmc_copy_kv in front, and the blobs are byte for byte those lmc_encode_chunks_fixed writes from the
- * gathered chunk.  Only slots of the job's own tokens are read.  A split source with more than 1024 channels per plane,
+ * gathered chunk.  Only slots of the job's own tokens are read.  A split source with more than 1024 channels per plane
+ * (with LMCACHE_AMD_SPLIT_WIDE=1: more than LMC_MAX_CHANNELS; see lmc_kv_layout),
  * stride_head < 0 or ((H-1)*stride_head + D*block_size)*E > 0xfffffff0, or fp8 elements, is LMC_ERR_INVALID and nothing
  * is launched.  Any other source: exactly lmc_encode_chunks_fixed.
  */

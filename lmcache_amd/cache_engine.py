@@ -58,6 +58,10 @@ class LMCacheEngine:
         # INSIDE the decode (lmc_decode_chunks_fixed_rope_schedule) instead of in a second pass behind it.  Off by default:
         # the fused keys are rounded once and are not the bits the two-pass path leaves
         self.fused_rope = os.environ.get("LMCACHE_AMD_FUSED_ROPE", "0") == "1"
+        # LMCACHE_AMD_SPLIT_WIDE=1 (read here, once): store_paged(direct=True) hands an "NHDB" cache with planes of more
+        # than 1024 channels to the encoders as it is instead of staging it (csrc/k_quantize.h, WIDE).  Off by default:
+        # profiles/paged_split_encode_wide.md
+        self.split_wide = native.split_wide_enabled()
         logger.debug("Current storage backend type %s", type(self.engine_))
 
     # ------------------------------------------------------------------ index (pure Python)
@@ -194,7 +198,10 @@ class LMCacheEngine:
                   k_cdf_encode, never by the fused kernel, and on the pinned tier its pack leaves as one part, without the
                   overlap of the part copies with the encode: it buys memory first, time only
                   where profiles/paged_split_encode.md says so.  Planes of more than 1024 channels (H * D) are staged all
-                  the same.  It means nothing for "NBHD" / "NHBD", which are read in place anyway, and nothing for the raw
+                  the same (with the warning, once), unless LMCACHE_AMD_SPLIT_WIDE=1 was set when the engine was built
+                  (engine.split_wide): then they are read in place too, by the encoders' wide split instances, on
+                  either CacheGen tier (profiles/paged_split_encode_wide.md); a layer-wise store of such a model still
+                  falls back to this one-piece store inside finish(), which then goes direct as well.  It means nothing for "NBHD" / "NHBD", which are read in place anyway, and nothing for the raw
                   tiers and the chunk-tensor backends, whose gather IS the store.  The stored bytes are the same.
                   The fixed-width HBM tier (local_serde="cachegen-fixed") reads the split blocks with its one kernel
                   (lmc_encode_chunks_fixed_split; k_fixed.h) under the same 1024-channel limit: no gather there either,
@@ -267,7 +274,7 @@ class LMCacheEngine:
 
     def _put_range(self, keys, src: native.KVLayout, t0: int, t1: int, blocking: bool, direct: bool) -> int:
         """Tokens [t0, t1) of `src` under `keys`: read in place by a backend that takes a layout, else gathered -> chunks stored."""
-        fmt, kw = self.metadata.fmt, {"direct": True} if direct else {}
+        fmt, kw = self.metadata.fmt, {"direct": native.DIRECT_WIDE if getattr(self, "split_wide", False) else True} if direct else {}
         if getattr(self.engine_, "supports_kv_layout", False):
             return self.engine_.put_kv_range(keys, src, fmt, t0, t1, self.chunk_size, blocking=blocking, **kw)
         return self.engine_.batched_put(self._gather_chunks(keys, src, fmt, t0, t1), blocking=blocking)

@@ -35,7 +35,8 @@
 //
 // LMC_PAGED_SPLIT ("NHDB", the cache of vLLM's ROCm paged-attention kernels: include/lmc_hip.h) on both sides, 16-bit
 // elements.  k_fixed_encode<..., NHDB = true>: quantize_task's split source form (k_quantize.h, split_load_oct) with the
-// same sink -- the loads differ, the blob does not; planes of up to 1024 channels (SPLIT == 1).
+// same sink -- the loads differ, the blob does not; planes of up to 1024 channels (SPLIT == 1).  Wider planes of a split
+// cache: k_fixed_wide_split below, SPLIT = 2 / 4 waves per oct as the rows have them (k_quantize.h: WIDE).
 // k_fixed_decode<DT, DEC_PAGED_SPLIT>: a K plane goes through the same transpose, and the lane's 8 channels of a token are
 // one x-granule (x = 8): the same 16-byte store at block * stride_block + h * stride_head + (d / 8) * (block_size * 8) +
 // w * 8.  A V plane skips the transpose: AS LOADED, lane l holds `lo` dwords 4 l .. 4 l + 3 and `hi` dword l of the tile,
@@ -128,7 +129,7 @@ struct FixedSink {
 template <int G, int NITER, int DT, int SPLIT, bool NHDB = false, bool LAYER = false>
 __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncArgs a) {
   constexpr int NW = FIXED_ENC_WAVES;
-  static_assert(!NHDB || SPLIT == 1, "a split source: planes of up to 1024 channels");
+  static_assert(!NHDB || SPLIT == 1, "a split source: planes of up to 1024 channels (wider: k_fixed_wide_split)");
   static_assert(!LAYER || SPLIT == 1, "layer launches: planes of up to 1024 channels (the split tasks meet at barriers)");
   static_assert(SPLIT == 1 || (G == LMC_WAVE && NITER == 2 && (SPLIT == 2 || SPLIT == 4)), "split tasks: whole waves");
   constexpr int RPW = LMC_WAVE / G;
@@ -201,6 +202,83 @@ __global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_encode(FixedEncA
   if (p == 0 && wave == NW - 1) {  // (the last wave: not the one that stores the tails)
     write_blob_static(blob, bo, e, (u32)Tc, total, lane);
     if (lane == 22) reinterpret_cast<u32*>(blob)[22] = LMC_MODEL_FIXED;  // (the lane that wrote the coded models' word)
+    if (lane == 0 && e.sizes) e.sizes[chunk] = bo.streams + total;
+  }
+}
+
+// ---- k_fixed_wide_split: k_fixed_encode for planes of MORE than 1024 channels of an LMC_PAGED_SPLIT cache ---------------
+// A kernel of its own (k_fixed_encode's instances stay the binaries they were; its one-piece body is repeated here for
+// G = 64, NITER = 2, as k_fixed_decode_rope repeats k_fixed_decode's).  grid = (P, nchunks): the workgroup owns a plane of
+// a chunk, its 8 waves take 8 / SPLIT row octs per pass, SPLIT waves to an oct -- wave `slice` quantises channels
+// [slice, slice + 1) * 1024 out of the split blocks (k_quantize.h: split_load_oct's WIDE form) and hands its nibble dwords
+// to the sink; the row maxima meet in `xmax` behind quantize_task's barrier.  npass is the workgroup's, so every wave walks
+// every pass and reaches every barrier -- a wave without an oct (ovalid false) or without a channel (its slice starts at or
+// past C) included.  Check words, scsum, tails, directory and the static sections: on chip and stored once, as there.
+template <int DT, int SPLIT>
+__global__ __launch_bounds__(64 * FIXED_ENC_WAVES) void k_fixed_wide_split(FixedEncArgs a) {
+  constexpr int NW = FIXED_ENC_WAVES;
+  static_assert(SPLIT == 2 || SPLIT == 4, "two or four waves to a row oct");
+  static_assert(!lmc_dtype_fp8(DT), "16-bit elements");
+  constexpr int PER_PASS = NW / SPLIT;  // row octs a workgroup takes at a time
+  __shared__ u32 xmax[PER_PASS * 8 * SPLIT];
+  __shared__ u32 chk[LMC_MAX_CHANNELS / 64];
+  __shared__ u32 scs_all;
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const EncodeArgs& e = a.e;
+  const int p = (int)blockIdx.x, chunk = (int)blockIdx.y;
+  const int tok0 = e.tok_begin + chunk * e.chunk_tokens;
+  const int Tc = min(e.chunk_tokens, e.tok_end - tok0);
+  const u32 O = ((u32)Tc + 7u) >> 3, NG = (u32)e.G;
+  const int bins = (int)e.bins.b[p];
+  const float maxf = (float)(bins / 2 - 1);
+  u32 beg = 0, total = 0;  // this plane's first stream, the streams section (wave-uniform: scalar code)
+  for (int q = 0; q < e.P; q++) {
+    const u32 sz = NG * fixed_stream_bytes_dev((u32)e.bins.b[q], O);
+    if (q < p) beg += sz;
+    total += sz;
+  }
+  const u32 ssize = fixed_stream_bytes_dev((u32)bins, O);
+  const BlobOff bo = lmc_blob_off((u32)e.P, (u32)Tc, NG);
+  u8* const blob = e.blobs + (long long)chunk * e.blob_stride;
+  if (tid < LMC_MAX_CHANNELS / 64) chk[tid] = 0u;
+  if (tid == 0) scs_all = 0u;
+  __syncthreads();
+
+  FixedSink sink;
+  sink.plane_streams = blob + bo.streams + beg;
+  sink.chk = (LdsU32*)chk;
+  sink.ssize = ssize; sink.O = O; sink.NG = NG; sink.oct_i = 0u; sink.scs = 0u;
+  sink.wide = !lmc_sym_nibbles(bins);
+  const int slice = wave % SPLIT;
+  u32* const xm = xmax + (wave / SPLIT) * 8 * SPLIT;
+  const u32 npass = (O + PER_PASS - 1u) / PER_PASS;  // the same for every wave: the tasks meet at barriers
+  for (u32 pass = 0; pass < npass; pass++) {
+    int oct = (int)pass * PER_PASS + wave / SPLIT;
+    const bool ovalid = (u32)oct < O;
+    if (!ovalid) oct = 0;
+    sink.oct_i = (u32)oct;
+    u16* const scale_out = reinterpret_cast<u16*>(blob + bo.scales) + ((long long)p * Tc + oct * 8);
+    if (lmc_sym_nibbles(bins))
+      quantize_task<LMC_WAVE, 2, DT, true, true, 8, 2, SPLIT, false, true, FixedSink>(a.src, p, tok0, Tc, oct * 8, ovalid, true, e.C, maxf,
+                                                                                      nullptr, nullptr, scale_out, lane, slice, xm, 0u, 0, &sink);
+    else
+      quantize_task<LMC_WAVE, 2, DT, true, false, 8, 2, SPLIT, false, true, FixedSink>(a.src, p, tok0, Tc, oct * 8, ovalid, true, e.C, maxf,
+                                                                                       nullptr, nullptr, scale_out, lane, slice, xm, 0u, 0, &sink);
+    __syncthreads();  // the next pass writes the exchange slots this one has read
+  }
+  if (sink.scs) __hip_atomic_fetch_add((LdsU32*)&scs_all, sink.scs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __syncthreads();
+  if ((u32)tid < NG) {  // tails and directory entries of the plane's streams
+    u8* const sb = sink.plane_streams + (size_t)tid * ssize;
+    *(LMC_GLOBAL u32x4_t*)(sb + ssize - LMC_FIXED_TAIL_BYTES) = u32x4_t{chk[tid], 0u, 0u, 0u};
+    const u32 b0 = beg + (u32)tid * ssize;
+    *(LMC_GLOBAL u32x2_t*)(blob + bo.gdir + 8u * ((u32)p * NG + (u32)tid)) = u32x2_t{b0, b0 + ssize};
+  }
+  if (tid == 0) reinterpret_cast<u32*>(blob + bo.scsum)[p] = scs_all;
+  if (p == 0 && wave == NW - 1) {  // (the last wave: not the one that stores the tails)
+    write_blob_static(blob, bo, e, (u32)Tc, total, lane);
+    if (lane == 22) reinterpret_cast<u32*>(blob)[22] = LMC_MODEL_FIXED;
     if (lane == 0 && e.sizes) e.sizes[chunk] = bo.streams + total;
   }
 }

@@ -86,6 +86,21 @@ __device__ __forceinline__ u32 quant_special(float x, float factor, float maxf) 
 // a run that enters a block at offset 5 or breaks inside the oct, a base 2 bytes off -- is loaded element by element
 // into the token-major registers.  Decided per task; a ballot sends the whole wave (G < 64: several octs) one way.
 // Only slots of the job's own tokens are turned into addresses, and a token at or past Tc is zero in the registers.
+//
+// WIDE (planes of more than 1024 channels: the SPLIT waves of a quantize_task share the oct, G = 64).  The work split is
+// the wide tasks': wave `slice` owns channels [slice, slice + 1) * 1024 of every token of the oct -- whole heads, or whole
+// granule runs of a head, of the blocks' dense (head, D * block_size) runs -- and c0[it] goes through the same (h, d)
+// arithmetic.  A slice that starts at or past C (C = 1032: the second slice has one run, C = 2056: the fourth none) has
+// no valid channel: it loads nothing, holds zeros and walks on to the task's barrier with maxima of 0.
+// The form is decided from the oct alone -- the plane, Tc, the eight slots, block_size, base and strides: nothing of it
+// depends on the lane or on the slice -- so the slots are made scalars (readfirstlane) and the verdict is a scalar
+// condition, no ballot: the SPLIT waves of a task compute the same verdict from the same words of slot_mapping.  They
+// could not part ways around the barrier even if they did not: the barrier stands in quantize_task BEHIND the point where
+// the two forms have rejoined with mrow[0..7] per token, every wave of the workgroup passes it once per task, and the form
+// only chooses the loads and the max reduction in front of it.
+// Registers (compiler remarks, gfx950; profiles/paged_split_encode_wide.md): with the slots, b0, w0 and the masks in SGPRs
+// a wave holds the task in the registers of the 1024-channel split instance, whose task this is per wave, and nothing
+// goes to scratch (native.build refuses a k_fixed_wide_split that uses any).
 
 // 8 elements p[0], p[step], ..., p[7 * step] as kv_ld8 would hold them
 template <int DT>
@@ -99,7 +114,7 @@ __device__ __forceinline__ uint4 split_ld_elems(const typename KvElem<DT>::T* p,
 }
 
 // The loads of one row oct from a split source.  -> true: the V form (v[e][it]), false: token-major (v[r][it]).
-template <int NITER, int DT>
+template <int NITER, int DT, bool WIDE = false>
 __device__ __forceinline__ bool split_load_oct(const KvAddr& src, int p, int tok0, int Tc, int t_first, bool qvalid,
                                                const int (&c0)[NITER], const bool (&cval)[NITER], uint4 (&v)[8][NITER],
                                                bool (&tv)[8]) {
@@ -114,6 +129,7 @@ __device__ __forceinline__ bool split_load_oct(const KvAddr& src, int p, int tok
   for (int r = 0; r < 8; r++) {
     tv[r] = qvalid && t_first + r < Tc;
     s[r] = tv[r] ? (u32)src.slot_mapping[tok0 + t_first + r] : 0u;
+    if constexpr (WIDE) s[r] = (u32)__builtin_amdgcn_readfirstlane((int)s[r]);  // (the wave's one oct: every lane loaded this word)
   }
   const u32 b0 = s[0] / bs, w0 = s[0] - b0 * bs;  // (the valid tokens of an oct are its first: tv[0] or none)
   // the lane's channel runs inside a block
@@ -129,7 +145,8 @@ __device__ __forceinline__ bool split_load_oct(const KvAddr& src, int p, int tok
     bool run = aligned && (w0 & 7u) == 0u && (bs & 7u) == 0u;
 #pragma unroll
     for (int r = 1; r < 8; r++) run = run && (!tv[r] || s[r] == s[0] + (u32)r);
-    if (__ballot(tv[0] && !run) == 0ull) {
+    // WIDE: `run` and tv[0] are scalars of the oct -- the verdict of this wave is the verdict of the task's other waves
+    if (WIDE ? (!tv[0] || run) : __ballot(tv[0] && !run) == 0ull) {
       // tokens at or past Tc share the vector with the oct's own: cleared
       u32 msk[4];
       if constexpr (!lmc_dtype_fp8(DT)) {
@@ -175,7 +192,7 @@ __device__ __forceinline__ bool split_load_oct(const KvAddr& src, int p, int tok
       }
     }
   };
-  if (__ballot(!same) == 0ull) load_tokens(BoolTag<true>{});
+  if (WIDE ? same : __ballot(!same) == 0ull) load_tokens(BoolTag<true>{});
   else load_tokens(BoolTag<false>{});
   return false;
 }
@@ -198,6 +215,10 @@ __device__ __forceinline__ bool split_load_oct(const KvAddr& src, int p, int tok
 // quantises row octs of ONE plane).
 // NHDB: the source is an LMC_PAGED_SPLIT cache (split_load_oct above): the loads, and for a V oct on its fast path the
 // max and the conversion in their channel-major form; from o[][][] on the task is the same.
+// NHDB with SPLIT > 1 (split_load_oct's WIDE form): each of the SPLIT waves reduces its 1024 channels to mrow[0..7] PER
+// TOKEN in either form -- token-major across the lane's runs and then the wave, V form across the lane's 16 channels
+// (packed max, two tokens per dword) and then the wave -- before the maxima enter xmax[r * SPLIT + slice]; tokens at or
+// past Tc and channels at or past C are zeros in the registers and add nothing.  One barrier per task, as without NHDB.
 // SINK (k_fixed.h, the fixed-width model): the task's symbols do not go to the workspace but to `sink`, in registers --
 // sink.oct(c0, lo quad dwords, hi quad dwords) per channel run of a valid task, runs past C included (their dwords are 0),
 // and sink.scale(token, bits) with every scale the task stores.  NoSink: the task as it always was.
@@ -215,7 +236,8 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
   static_assert(ROWS == 2 || ROWS == 4 || (ROWS == 8 && NQ == 2), "rows in flight: a power of two within the task");
   static_assert(QUAD || (!NIB && NQ == 1), "nibble packing and two-quad tasks are workspace formats");
   static_assert(!NIB || NQ == 2, "a nibble dword holds two row quads");
-  static_assert(!NHDB || (QUAD && ROWS == 8 && SPLIT == 1 && !HIST), "a split source: whole octs into the workspace");
+  static_assert(!NHDB || (QUAD && ROWS == 8 && !HIST), "a split source: whole octs into the workspace");
+  static_assert(!NHDB || SPLIT == 1 || (G == LMC_WAVE && NITER == 2), "a wide split source: a wave per slice of the oct");
   // per-lane channel runs (row independent)
   long long coff[NITER];
   int c0[NITER];
@@ -245,7 +267,7 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
     bool tv[ROWS];
     bool vform = false;  // NHDB, a V oct on its fast path: v[e][it] = the 8 tokens of channel c0[it] + e
     if constexpr (NHDB) {
-      vform = split_load_oct<NITER, DT>(src, p, tok0, Tc, t_first, qvalid, c0, cval, v, tv);
+      vform = split_load_oct<NITER, DT, (SPLIT > 1)>(src, p, tok0, Tc, t_first, qvalid, c0, cval, v, tv);
     } else {
 #pragma unroll
       for (int r = 0; r < ROWS; r++) {
@@ -484,8 +506,8 @@ __device__ __forceinline__ void quantize_task(const KvAddr& src, int p, int tok0
 // get the nibble-packed workspace format (one dword per channel for the oct), the others two row quads.
 // grid = (ceil(TO / (4 * RPW)), P, chunks), TO = ceil(TQ / 2): plane and chunk come straight from the block
 // index, and with G = 64 everything but the channel offset is wave-uniform and lives in SGPRs.
-// NHDB: the instances that read an LMC_PAGED_SPLIT source (workspace form, up to 1024 channels); every other instance is
-// what it was before they existed.
+// NHDB: the instances that read an LMC_PAGED_SPLIT source (workspace form, up to 1024 channels; wider planes of such a
+// source: k_quantize_wide_split below); every other instance is what it was before they existed.
 template <int G, int NITER, int DT, bool QUAD, int SPLIT = 1, bool NHDB = false>
 __global__ __launch_bounds__(256) void k_quantize(QuantArgs a) {
   static_assert(SPLIT == 1 || (QUAD && G == LMC_WAVE && (SPLIT == 2 || SPLIT == 4)), "split tasks: whole waves, workspace output");
@@ -532,4 +554,45 @@ __global__ __launch_bounds__(256) void k_quantize(QuantArgs a) {
                                                 sym8_plane, scale_out + 4 * hq, sl);
     }
   }
+}
+
+// ---- k_quantize_wide_split: the workspace form for planes of MORE than 1024 channels of an LMC_PAGED_SPLIT source --------
+// A kernel of its own, not further k_quantize instances: that family stays the set of binaries it was.  SPLIT = 2 (up to
+// 2048 channels) or 4 waves share a row oct, wave `slice` takes channels [slice, slice + 1) * 1024 through split_load_oct's
+// WIDE form, and the row maxima meet in `xmax` behind the task's one barrier (quantize_task<..., SPLIT, ..., NHDB>); a
+// workgroup of four waves holds 4 / SPLIT tasks.  grid = (ceil(TO / (4 / SPLIT)), planes, chunks), as k_quantize's split
+// instances have it: every wave of a workgroup runs quantize_task exactly once, whether its oct exists, whether its slice
+// holds a channel.  Workspace, scales, granule and size-word clearing are k_quantize's, line for line.
+template <int DT, int SPLIT>
+__global__ __launch_bounds__(256) void k_quantize_wide_split(QuantArgs a) {
+  static_assert(SPLIT == 2 || SPLIT == 4, "two or four waves to a row oct");
+  __shared__ u32 xmax[(4 / SPLIT) * 8 * SPLIT];  // row maxima of the tasks of this workgroup
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int p = a.plane0 + (int)blockIdx.y * (a.plane_step ? a.plane_step : 1), chunk = (int)blockIdx.z;
+  if (a.agg || a.sizes) {  // the launch has at least 256 threads per plane-chunk, a plane-chunk at most 64 granules
+    const long long i = (((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    if (a.agg && i < a.agg_n) a.agg[i] = 0ull;
+    if (a.sizes && i < a.nchunks) a.sizes[i] = 0u;
+  }
+  const int TO = (a.TQ + 1) >> 1;
+  int oct = ((int)blockIdx.x * 4 + wave) / SPLIT;
+  const int slice = wave % SPLIT;
+  const bool ovalid = oct < TO && chunk * a.P + p < a.pc_limit;
+  if (!ovalid) oct = 0;
+  const int tok0 = a.tok_begin + chunk * a.chunk_tokens;
+  const int Tc = min(a.chunk_tokens, a.tok_end - tok0);
+  const int bins = (int)a.bins.b[p];
+  const float maxf = (float)(bins / 2 - 1);
+  u16* scale_out = reinterpret_cast<u16*>(a.scale_base + (long long)chunk * a.scale_stride) + ((long long)p * Tc + oct * 8);
+  u32* const sym_pc = a.sym4 + ((long long)chunk * gridDim.y + blockIdx.y) * a.sym_stride;  // this plane-chunk's workspace
+  u32* const sym_out = sym_pc + (long long)oct * (lmc_sym_nibbles(bins) ? 1 : 2) * a.C;
+  const bool q1valid = 2 * oct + 1 < a.TQ;
+  u32* const xm = xmax + (wave / SPLIT) * 8 * SPLIT;  // this task's exchange slots
+  if (lmc_sym_nibbles(bins))
+    quantize_task<LMC_WAVE, 2, DT, true, true, 8, 2, SPLIT, false, true>(a.src, p, tok0, Tc, oct * 8, ovalid, q1valid, a.C, maxf, sym_out,
+                                                                         nullptr, scale_out, lane, slice, xm);
+  else
+    quantize_task<LMC_WAVE, 2, DT, true, false, 8, 2, SPLIT, false, true>(a.src, p, tok0, Tc, oct * 8, ovalid, q1valid, a.C, maxf, sym_out,
+                                                                          nullptr, scale_out, lane, slice, xm);
 }

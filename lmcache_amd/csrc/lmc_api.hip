@@ -410,12 +410,20 @@ static bool split_range_ok(const lmc_kv_layout* l) {
 // they take a buffer).  *nchunks: the job's chunks -- at most 65535, they ride on gridDim.z of k_quantize.
 // `split_ok`: the entry point takes an LMC_PAGED_SPLIT source (lmc_encode_chunks_split and the stores; lmc_encode_chunks
 // does not) -- the twin of decode_common's flag.  Such a source is asked what lmc_copy_kv asks of a split side (a slot
-// mapping, block_size >= 1, whole x-granules), split_range_ok, and planes of at most 1024 channels.
+// mapping, block_size >= 1, whole x-granules) and split_range_ok.  Its planes have at most 1024 channels, or -- `wide_ok`:
+// the one-piece encodes and the stores, not the layer-wise jobs, and only where split_wide_enabled() -- up to
+// LMC_MAX_CHANNELS (layout_ok): the SPLIT = 2 / 4 instances of k_quantize and k_fixed_encode (k_quantize.h, WIDE).
+// LMCACHE_AMD_SPLIT_WIDE=1 (include/lmc_hip.h), looked up only for a source that is refused without it: no job that was
+// taken before these instances existed reads the environment.
+static bool split_wide_enabled() {
+  const char* e = getenv("LMCACHE_AMD_SPLIT_WIDE");
+  return e && e[0] == '1' && !e[1];
+}
 static bool encode_job_ok(const lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t tok_end, int32_t chunk_tokens,
-                          int* nchunks, bool split_ok = false) {
+                          int* nchunks, bool split_ok = false, bool wide_ok = false) {
   const bool nhdb = src && src->paged_kind == LMC_PAGED_SPLIT;
   if (nhdb ? !(split_ok && layout_ok(src, false, true) && split_range_ok(src)) : !layout_ok(src)) return false;
-  if (nhdb && (long long)src->num_heads * src->head_size > 1024) return false;  // k_quantize's split instances stop there
+  if (nhdb && (long long)src->num_heads * src->head_size > 1024 && !(wide_ok && split_wide_enabled())) return false;
   if (!c || tok_begin < 0 || tok_end <= tok_begin || chunk_tokens < 1 || chunk_tokens > 65535) return false;
   *nchunks = (tok_end - tok_begin + chunk_tokens - 1) / chunk_tokens;
   return *nchunks <= 65535;
@@ -444,7 +452,8 @@ static bool chunk_geometry_ok(int32_t nchunks, int32_t L, int32_t H, int32_t D, 
   return (uint64_t)ntokens <= (uint64_t)nchunks * (uint32_t)chunk_tokens && (uint64_t)ntokens > (uint64_t)(nchunks - 1) * (uint32_t)chunk_tokens;
 }
 
-// NHDB: the source is an LMC_PAGED_SPLIT cache (k_quantize.h: instances of their own, planes of up to 1024 channels)
+// NHDB: the source is an LMC_PAGED_SPLIT cache (k_quantize.h: instances of their own; wider than 1024 channels:
+// k_quantize_wide_split, SPLIT = 2 for up to 2048, 4 above, as for rows)
 template <int DT, bool QUAD, bool NHDB = false>
 static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
   const int C = a.C;
@@ -460,8 +469,11 @@ static int launch_quant_dt(const QuantArgs& a, hipStream_t s) {
   };
   const IntTag<64> g64;
   if (with_plane_width(C, [&](auto g, auto n) { launch(g, n, IntTag<1>{}); })) {
-  } else if constexpr (NHDB) {
-    return LMC_ERR_INVALID;
+  } else if constexpr (NHDB) {  // k_quantize_wide_split: the rows' work split, split_load_oct's WIDE loads
+    if (C > LMC_MAX_CHANNELS) return LMC_ERR_INVALID;
+    const int TO = (a.TQ + 1) / 2;  // row octs per plane-chunk; a workgroup takes 4 / SPLIT of them
+    if (C <= 2048) hipLaunchKernelGGL((k_quantize_wide_split<DT, 2>), dim3((unsigned)((TO + 1) / 2), ny, nz), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_quantize_wide_split<DT, 4>), dim3((unsigned)TO, ny, nz), dim3(256), 0, s, a);
   } else if (C > 4096) {
     return LMC_ERR_INVALID;
   } else if (QUAD) {  // (a plain `if`, here and below: either QUAD builds both arms, as it always has -- the set of kernels stays)
@@ -528,8 +540,8 @@ static int reserve_locked(lmc_ctx::Workspace* c, int L, int H, int D, int chunk_
 
 // ---- LMC_MODEL_FIXED (k_fixed.h): one launch, a workgroup per (plane, chunk); no workspace, so no context state beyond
 // the profiling marks ------------------------------------------------------------------------------------------------
-// NHDB: the source is an LMC_PAGED_SPLIT cache (k_quantize.h, split_load_oct): instances of their own, planes of up to
-// 1024 channels (encode_job_ok)
+// NHDB: the source is an LMC_PAGED_SPLIT cache (k_quantize.h, split_load_oct): instances of their own, and
+// k_fixed_wide_split for planes of more than 1024 channels (encode_job_ok)
 // LAYER: a layer's launch of a layer-wise job (FixedEncArgs): e.nplanes planes of every chunk in `slices` workgroups each,
 // instances of their own (16: the one-piece instances stay the code they were), planes of up to 1024 channels.
 template <int DT, bool LAYER = false>
@@ -541,9 +553,10 @@ static int launch_fixed_encode(const FixedEncArgs& fa, hipStream_t s, bool nhdb,
       hipLaunchKernelGGL((k_fixed_encode<decltype(g)::value, decltype(n)::value, DT, 1, decltype(split)::value, LAYER>), grid, block, 0, s, fa);
     });
   });
-  if (!common) {  // wider than 1024 channels: rows in one piece only, SPLIT waves to a row oct
+  if (!common) {  // wider than 1024 channels: in one piece only, SPLIT waves to a row oct -- of rows or of a split cache
     if constexpr (LAYER) return LMC_ERR_INVALID;
-    else if (nhdb) return LMC_ERR_INVALID;
+    else if (nhdb && C <= 2048) hipLaunchKernelGGL((k_fixed_wide_split<DT, 2>), grid, block, 0, s, fa);
+    else if (nhdb) hipLaunchKernelGGL((k_fixed_wide_split<DT, 4>), grid, block, 0, s, fa);
     else if (C <= 2048) hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 2>), grid, block, 0, s, fa);
     else hipLaunchKernelGGL((k_fixed_encode<64, 2, DT, 4>), grid, block, 0, s, fa);  // C <= LMC_MAX_CHANNELS: layout_ok
   }
@@ -613,7 +626,7 @@ static int encode_job(lmc_ctx* c, const lmc_kv_layout* src, const FixedSrc* fx, 
   const int L = src ? src->num_layers : fx->L, H = src ? src->num_heads : fx->H, D = src ? src->head_size : fx->D;
   const int kv_dtype = src ? src->dtype : fx->dtype;
   const int P = 2 * L, C = H * D, G = (C + 63) / 64;  // (C <= LMC_MAX_CHANNELS: layout_ok)
-  // an LMC_PAGED_SPLIT source (at most 1024 channels per plane: encode_job_ok): k_quantize's split instances, then
+  // an LMC_PAGED_SPLIT source (encode_job_ok: planes of any width layout_ok lets): k_quantize's split instances, then
   // k_cdf_encode -- never the fused kernel, so the job is one part
   const bool nhdb = src && src->paged_kind == LMC_PAGED_SPLIT;
   BinsArg bins;
@@ -818,7 +831,7 @@ static int encode_chunks_parts(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok
                                const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
                                lmc_stream_t stream, int nparts, const AfterPart* after_part, bool split_ok) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok)) return LMC_ERR_INVALID;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok, /*wide_ok=*/split_ok)) return LMC_ERR_INVALID;
   return encode_job(c, src, nullptr, nchunks, tok_begin, tok_end, chunk_tokens, bins_h, blobs, blob_stride, sizes, job_status, stream,
                     nparts, after_part);
 }
@@ -861,7 +874,7 @@ static int encode_fixed(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin,
                         const int32_t* bins_h, void* blobs, uint64_t blob_stride, uint32_t* sizes, uint32_t* job_status,
                         lmc_stream_t stream, bool split_ok) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok) || lmc_dtype_fp8(src->dtype)) return LMC_ERR_INVALID;
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, split_ok, /*wide_ok=*/split_ok) || lmc_dtype_fp8(src->dtype)) return LMC_ERR_INVALID;
   const int L = src->num_layers, H = src->num_heads, D = src->head_size;
   FixedEncArgs fa;
   memset(&fa, 0, sizeof fa);
@@ -1896,7 +1909,7 @@ int lmc_store_chunks(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, in
                      const int32_t* bins_h, void* host_arena_h, uint64_t host_cap, uint64_t* offsets_h,
                      uint32_t* sizes_h, uint32_t* job_status, lmc_stream_t stream) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true) || !host_arena_h || ((uintptr_t)host_arena_h & 15) ||
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true, /*wide_ok=*/true) || !host_arena_h || ((uintptr_t)host_arena_h & 15) ||
       !offsets_h || !sizes_h)
     return LMC_ERR_INVALID;
   const uint64_t stride = blob_stride(src->num_layers, chunk_tokens, src->num_heads, src->head_size);
@@ -1990,7 +2003,7 @@ static int store_pack_impl(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_beg
                            const int32_t* bins_h, void* pack_h, uint64_t pack_cap, uint32_t* sizes_h, int32_t nparts,
                            uint64_t* part_info_h, const lmc_event_t* part_events, uint32_t* job_status, lmc_stream_t stream) {
   int nchunks;
-  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true) || !pack_h || ((uintptr_t)pack_h & 15) || !sizes_h ||
+  if (!encode_job_ok(c, src, tok_begin, tok_end, chunk_tokens, &nchunks, true, /*wide_ok=*/true) || !pack_h || ((uintptr_t)pack_h & 15) || !sizes_h ||
       nparts < 0 || nparts > 16 || (nparts > 0 && !part_info_h))
     return LMC_ERR_INVALID;
   const int L = src->num_layers, P = 2 * L;

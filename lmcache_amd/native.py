@@ -65,13 +65,13 @@ def _check_fixed_registers() -> None:
     import json
     res = json.load(open(RESOURCES_PATH))
     bad = {k: v.get("ScratchSize") for k, v in res.items()
-           if ("k_fixed_encode" in k or "k_fixed_layers_finish" in k) and v.get("ScratchSize") != 0}
+           if ("k_fixed_encode" in k or "k_fixed_layers_finish" in k or "k_fixed_wide_split" in k) and v.get("ScratchSize") != 0}
     if bad:
         try:
             os.remove(SO_PATH)
         except OSError:
             pass
-        raise RuntimeError(f"k_fixed_encode / k_fixed_layers_finish must not use scratch (k_fixed.h); got {bad}")
+        raise RuntimeError(f"k_fixed_encode / k_fixed_wide_split / k_fixed_layers_finish must not use scratch (k_fixed.h); got {bad}")
 
 
 def _check_decoder_registers() -> None:
@@ -126,6 +126,18 @@ class KvLayoutStruct(ctypes.Structure):
 
 
 PAGED_ROWS, PAGED_SPLIT = 0, 1  # LMC_PAGED_*: lmc_kv_layout.paged_kind
+# `direct` of a store (CacheGenDeviceCodec._readable) where the engine was built under LMCACHE_AMD_SPLIT_WIDE=1: a
+# PAGED_SPLIT source goes to the encoder as it is whatever its planes' width -- above 1024 channels (H * D) the
+# library's wide split instances read it (csrc/k_quantize.h, WIDE).  Truthy, so every layer that only asks `if direct`
+# and hands it on needs no word about it.
+DIRECT_WIDE = 2
+
+
+def split_wide_enabled() -> bool:
+    """LMCACHE_AMD_SPLIT_WIDE=1: the engine reads it once, when it is built (LMCacheEngine.split_wide).  The library
+    looks the variable up itself at every call that brings it such a source (include/lmc_hip.h) and refuses the source
+    without it, so it has to stay set for as long as the engine stores."""
+    return os.environ.get("LMCACHE_AMD_SPLIT_WIDE", "0") == "1"
 
 
 class RangePostStruct(ctypes.Structure):
@@ -924,7 +936,8 @@ class Context:
     def encode_chunks_split(self, src: KVLayout, tok_begin: int, tok_end: int, chunk_tokens: int, bins,
                             blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
                             status_ptr: Optional[int] = None) -> int:
-        """encode_chunks for any source it takes and a PAGED_SPLIT ("NHDB") one, read in place (lmc_encode_chunks_split)."""
+        """encode_chunks for any source it takes and a PAGED_SPLIT ("NHDB") one, read in place (lmc_encode_chunks_split):
+        planes of up to 1024 channels, under LMCACHE_AMD_SPLIT_WIDE=1 (split_wide_enabled) of up to 4096."""
         return self._encode_job("lmc_encode_chunks_split", src, tok_begin, tok_end, chunk_tokens, bins, blobs_ptr, blob_stride,
                                 sizes_ptr, stream, status_ptr)
 
@@ -939,7 +952,8 @@ class Context:
                                   blobs_ptr: int, blob_stride: int, sizes_ptr: int, stream: Optional[int] = None,
                                   status_ptr: Optional[int] = None) -> int:
         """encode_chunks_fixed for any source it takes and a 16-bit PAGED_SPLIT ("NHDB") one of up to 1024 channels per
-        plane, read in place (lmc_encode_chunks_fixed_split)."""
+        plane (under LMCACHE_AMD_SPLIT_WIDE=1, split_wide_enabled: up to 4096), read in place
+        (lmc_encode_chunks_fixed_split)."""
         return self._encode_job("lmc_encode_chunks_fixed_split", src, tok_begin, tok_end, chunk_tokens, bins, blobs_ptr,
                                 blob_stride, sizes_ptr, stream, status_ptr)
 

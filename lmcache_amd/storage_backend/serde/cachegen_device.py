@@ -302,11 +302,12 @@ class CacheGenDeviceCodec:
         the device (lmc_copy_kv: element-wise for the former, k_copy_split.h's gather for the latter) and encoded from
         there.  direct: an "NHDB" cache with planes of at most 1024 channels goes to the encoder as it is
         (lmc_encode_chunks_split, lmc_encode_chunks_fixed_split and the stores read the split blocks: k_quantize.h); wider
-        planes are staged all the same, whichever coder model."""
+        planes are staged all the same, whichever coder model -- unless direct is native.DIRECT_WIDE (an engine built
+        under LMCACHE_AMD_SPLIT_WIDE=1): then they too go as they are, to the same calls (k_quantize.h, WIDE)."""
         if src.vector_readable():
             return src, tok_begin, tok_end
         if direct and src.struct.paged_kind == native.PAGED_SPLIT:
-            if src.H * src.D <= 1024:
+            if src.H * src.D <= 1024 or direct == native.DIRECT_WIDE:
                 return src, tok_begin, tok_end
             if not self._warned_wide_split:
                 self._warned_wide_split = True
