@@ -769,6 +769,34 @@ int lmc_load_pack(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t
 int lmc_load_pack_post(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
                        const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
                        uint32_t* job_status, lmc_stream_t stream, const lmc_range_post* post);
+/*
+ * lmc_load_pack of a WINDOW OF HEADS (lmc_head_window, above; additive in ABI 6; csrc/k_pack_window.h): the pack was
+ * stored under another tensor-parallel degree, and only the window's streams cross PCIe.  The streams of a plane lie in
+ * group order, so the window of segment (plane, chunk) is one contiguous run of bytes whose ends stand in the chunk's
+ * stream directory.  Offset table and static slots go first by DMA, as for lmc_load_pack; then per range of layers
+ * k_pack_window, on the context's copy queue, gathers the runs of the range's K planes and of its V planes out of the
+ * pack where it lies -- pack_h must be memory the device can address: mapped pinned host memory (lmc_pinned_alloc) --
+ * to the offsets they have in the pack, and the range's decode follows on `stream` with the pack's segment table AND the
+ * head window set; range_events[r] behind it, if given.  The rest of each segment is neither moved nor read.
+ *   win   required; the pack's num_heads must be win->src_heads and its head_size dst->head_size, dst->num_heads is the
+ *         destination's own.  LMC_ERR_INVALID with nothing queued: everything lmc_load_pack refuses, everything
+ *         lmc_decode_chunks_heads_schedule refuses for `win` and `dst`, and a pack the device cannot address.
+ * On the device a static slot is held against the pack's table as lmc_unpack_blobs holds it, and the window against the
+ * slot's directory (inside the plane, on 16-byte boundaries), before a byte of the host pack is read for the chunk:
+ * LMC_STATUS_BAD_HEADER, nothing of that chunk is moved or decoded, its tokens in `dst` are not written; the other chunks
+ * are not touched by it.  Everything else is lmc_decode_chunks_heads_schedule's: only bytes of heads [dst_head_begin,
+ * dst_head_begin + nheads) of the call's own tokens are written, there is no `post`.
+ * A window that is the whole blob is lmc_load_pack itself: DMA copies, no gather.
+ * lmc_pack_window_bytes -- host only: the stream bytes the call above moves for chunks [chunk_begin, chunk_begin +
+ *   nchunks) (nchunks 0 = all that follow), read from the directories in the pack; for the whole blob, the size of the
+ *   chunks' segments.  win->dst_head_begin is not looked at.  LMC_ERR_INVALID: a pack that does not check out, win NULL,
+ *   win->src_heads other than the pack's num_heads, a window outside [0, src_heads).
+ */
+int lmc_load_pack_heads(lmc_ctx* ctx, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
+                        const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
+                        const lmc_head_window* win, uint32_t* job_status, lmc_stream_t stream);
+int lmc_pack_window_bytes(const void* pack_h, uint64_t nbytes, int32_t chunk_begin, int32_t nchunks,
+                          const lmc_head_window* win, uint64_t* stream_bytes_out);
 
 /*
  * Moving encoded chunks BETWEEN the two local tiers without re-encoding them (bounded tiers: the HBM tier demotes its

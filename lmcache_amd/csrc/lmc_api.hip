@@ -25,6 +25,7 @@
 #include "k_fused.h"
 #include "k_layers.h"
 #include "k_offload.h"
+#include "k_pack_window.h"
 #include "k_quantize.h"
 #include "k_repack.h"
 #include "k_rope.h"
@@ -1289,6 +1290,24 @@ static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* post);
 static bool post_in_place(const lmc_kv_layout* dst, const lmc_range_post* post);
 static bool fused_rope_ok(const lmc_kv_layout* dst, const lmc_range_post* post);
 
+// decode_window -- the head window of a job that decode_common has filled for `dst` (the head-window schedules and
+// lmc_load_pack_heads): false for a window the calls refuse.  The blob's C and G and the window's channels and groups
+// replace what decode_common derived from dst's own head count.
+static bool decode_window(DecodeArgs& a, const lmc_kv_layout* dst, const lmc_head_window* win) {
+  const long long D = dst->head_size, Cs = (long long)win->src_heads * D;
+  if (win->src_heads < 1 || win->nheads < 1 || win->src_head_begin < 0 || win->dst_head_begin < 0 ||
+      (long long)win->src_head_begin + win->nheads > win->src_heads ||
+      (long long)win->dst_head_begin + win->nheads > dst->num_heads || (Cs & 7) || Cs > LMC_MAX_CHANNELS)
+    return false;
+  a.C = (int)Cs; a.G = (a.C + 63) / 64;
+  if ((long long)a.nchunks * a.P * a.G >= (1ll << 31)) return false;  // decode_geometry's bound, on the blob's groups
+  a.wc_lo = win->src_head_begin * (int)D; a.wc_hi = a.wc_lo + win->nheads * (int)D;
+  a.wg_lo = a.wc_lo / 64; a.wGw = (a.wc_hi - 1) / 64 - a.wg_lo + 1;
+  a.wh_shift = win->dst_head_begin - win->src_head_begin;
+  a.w_src_heads = win->src_heads;
+  return true;
+}
+
 // One body for the two schedules: the coded models' k_decode, or -- `fixed` -- k_fixed_decode for LMC_MODEL_FIXED blobs,
 // which fills 16-bit rows and -- `fixed_split`: lmc_decode_chunks_fixed_split_schedule -- a 16-bit LMC_PAGED_SPLIT cache
 // (lmc_decode_chunks_fixed_schedule keeps refusing one: such a cache is filled through a staged chunk and
@@ -1305,19 +1324,7 @@ static int decode_schedule(lmc_ctx* c, const void* const* blob_ptrs, uint64_t ma
   DecodeArgs a;
   int rc = decode_common(c, nchunks, dst, dst_tok0, chunk_tokens, job_status, a, !fixed || fixed_split);
   if (rc) return rc;
-  if (win) {
-    const long long D = dst->head_size, Cs = (long long)win->src_heads * D;
-    if (win->src_heads < 1 || win->nheads < 1 || win->src_head_begin < 0 || win->dst_head_begin < 0 ||
-        (long long)win->src_head_begin + win->nheads > win->src_heads ||
-        (long long)win->dst_head_begin + win->nheads > dst->num_heads || (Cs & 7) || Cs > LMC_MAX_CHANNELS)
-      return LMC_ERR_INVALID;
-    a.C = (int)Cs; a.G = (a.C + 63) / 64;
-    if ((long long)nchunks * a.P * a.G >= (1ll << 31)) return LMC_ERR_INVALID;  // decode_geometry's bound, on the blob's groups
-    a.wc_lo = win->src_head_begin * (int)D; a.wc_hi = a.wc_lo + win->nheads * (int)D;
-    a.wg_lo = a.wc_lo / 64; a.wGw = (a.wc_hi - 1) / 64 - a.wg_lo + 1;
-    a.wh_shift = win->dst_head_begin - win->src_head_begin;
-    a.w_src_heads = win->src_heads;
-  }
+  if (win && !decode_window(a, dst, win)) return LMC_ERR_INVALID;
   if (fixed && (lmc_dtype_fp8(dst->dtype) || max_blob_bytes < LMC_HEADER_BYTES)) return LMC_ERR_INVALID;
   if (!decode_blobs(a, blob_ptrs, (max_blob_bytes + 15) & ~(uint64_t)15, blob_ptrs) || nranges < 1 || !layer_ends_h)
     return LMC_ERR_INVALID;
@@ -2209,6 +2216,112 @@ int lmc_load_pack(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t c
                   uint32_t* job_status, lmc_stream_t stream) {
   return lmc_load_pack_post(c, pack_h, pack_bytes, chunk_begin, nchunks, dst, dst_tok0, layers_per_range, range_events, job_status,
                             stream, nullptr);
+}
+
+// ---- a head window out of a pack: only the window's streams cross PCIe (k_pack_window.h) ------------------------------
+// The geometry words k_pack_window and the host walk below compute section offsets from must be a geometry's, and the
+// blobs' head count the window's.
+static bool pack_window_geometry_ok(const lmc_pack_header& h, const lmc_head_window* win) {
+  const uint64_t C = (uint64_t)h.num_heads * h.head_size;
+  if (!win || win->src_heads < 1 || (uint32_t)win->src_heads != h.num_heads || C < 8 || (C & 7) || C > LMC_MAX_CHANNELS) return false;
+  lmc_pack_header ref;
+  lmc_pack_layout(h.nchunks, h.num_layers, h.chunk_tokens, h.num_heads, h.head_size, &ref);
+  return h.ngroups == ref.ngroups && h.static_stride == ref.static_stride;
+}
+
+int lmc_load_pack_heads(lmc_ctx* c, const void* pack_h, uint64_t pack_bytes, int32_t chunk_begin, int32_t nchunks,
+                        const lmc_kv_layout* dst, int32_t dst_tok0, int32_t layers_per_range, lmc_event_t* range_events,
+                        const lmc_head_window* win, uint32_t* job_status, lmc_stream_t stream) {
+  lmc_pack_header h;
+  if (!win || layers_per_range < 0 || nchunks < 0 || chunk_begin < 0 || !pack_ok((const u8*)pack_h, pack_bytes, &h) ||
+      (uint32_t)chunk_begin >= h.nchunks || (uint32_t)nchunks > h.nchunks - (uint32_t)chunk_begin)
+    return LMC_ERR_INVALID;
+  const int n = (int)h.nchunks, c0 = chunk_begin, m = nchunks ? nchunks : n - c0;  // chunks c0 .. c0 + m of the pack
+  DecodeArgs da;
+  int rc = decode_common(c, m, dst, dst_tok0, (long long)h.chunk_tokens, job_status, da, true);
+  if (rc) return rc;
+  const int L = dst->num_layers;
+  if ((uint32_t)L != h.num_layers || (uint32_t)dst->head_size != h.head_size || !pack_window_geometry_ok(h, win) ||
+      !decode_window(da, dst, win))
+    return LMC_ERR_INVALID;
+  if (win->src_heads == dst->num_heads && win->src_head_begin == 0 && win->dst_head_begin == 0 && win->nheads == win->src_heads)
+    return lmc_load_pack_post(c, pack_h, pack_bytes, chunk_begin, nchunks, dst, dst_tok0, layers_per_range, range_events, job_status,
+                              stream, nullptr);  // the whole blob: DMA copies, no gather
+  HIP_TRY(hipSetDevice(c->device));
+  // the kernel reads the pack where it lies: it must be memory the device can address (mapped pinned host memory)
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, pack_h) != hipSuccess || at.type == hipMemoryTypeUnregistered || !at.devicePointer) {
+    (void)hipGetLastError();  // (not left for the next launch to report)
+    return LMC_ERR_INVALID;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int step = layers_per_range > 0 && layers_per_range < L ? layers_per_range : L;
+  std::lock_guard<std::mutex> lk(c->mu);
+  hipStream_t queues[2];
+  if ((rc = load_acquire(c, (size_t)h.total_bytes, 1, queues))) return rc;
+  hipStream_t cs = queues[0];  // ONE queue: the ranges must arrive in layer order
+  // as for lmc_load_pack: table and static slots land where they lie in the pack, by DMA, in front of the gathers
+  const u8* b = (const u8*)pack_h;
+  u8* dev = c->load_slots.p;
+  HIP_TRY(hipMemcpyAsync(dev + h.off_table, b + h.off_table, 8 * (2 * (size_t)L * n + 1), hipMemcpyHostToDevice, cs));
+  HIP_TRY(hipMemcpyAsync(dev + h.off_static + (size_t)c0 * h.static_stride, b + h.off_static + (size_t)c0 * h.static_stride,
+                         (size_t)m * h.static_stride, hipMemcpyHostToDevice, cs));
+  da.blobs = dev + h.off_static + (size_t)c0 * h.static_stride; da.blob_stride = (long long)h.static_stride;  // (the static slots)
+  da.seg_off = (const unsigned long long*)(dev + h.off_table) + c0; da.seg_streams = dev + h.off_streams; da.seg_n = n;
+  PackWindowArgs wa;
+  memset(&wa, 0, sizeof wa);
+  wa.pack_h = (const u8*)at.devicePointer; wa.stage = dev;
+  wa.off_table = h.off_table; wa.off_static = h.off_static; wa.off_streams = h.off_streams;
+  wa.streams_bytes = h.total_bytes - h.off_streams; wa.static_stride = h.static_stride;
+  wa.n = n; wa.c0 = c0; wa.m = m; wa.L = L; wa.G = da.G; wa.chunk_tokens = h.chunk_tokens;
+  wa.wg_lo = da.wg_lo; wa.wGw = da.wGw;
+  wa.status = da.status;
+  int r = 0;
+  for (int l0 = 0; l0 < L; l0 += step, r++) {
+    const int nl = l0 + step <= L ? step : L - l0;
+    for (int kv = 0; kv < 2; kv++) {  // the range's K planes, then its V planes (pack v3: plane order)
+      wa.p0 = kv * L + l0; wa.np = nl;
+      const long long items = (long long)nl * m;
+      hipLaunchKernelGGL(k_pack_window, dim3((unsigned)std::min<long long>(items, PACK_WINDOW_WGS)), dim3(256), 0, cs, wa);
+      HIP_TRY(hipGetLastError());
+    }
+    if ((rc = stream_follows(c, s, cs))) return rc;
+    if ((rc = decode_range_locked(da, dst, l0, nl, s, range_events ? range_events[r] : nullptr))) return rc;
+  }
+  return load_release(c, s);
+}
+
+int lmc_pack_window_bytes(const void* pack_h, uint64_t nbytes, int32_t chunk_begin, int32_t nchunks, const lmc_head_window* win,
+                          uint64_t* stream_bytes_out) {
+  lmc_pack_header h;
+  const u8* b = (const u8*)pack_h;
+  if (!win || !stream_bytes_out || nchunks < 0 || chunk_begin < 0 || !pack_ok(b, nbytes, &h) || (uint32_t)chunk_begin >= h.nchunks ||
+      (uint32_t)nchunks > h.nchunks - (uint32_t)chunk_begin || !pack_window_geometry_ok(h, win) || win->nheads < 1 ||
+      win->src_head_begin < 0 || (long long)win->src_head_begin + win->nheads > win->src_heads)
+    return LMC_ERR_INVALID;
+  const uint32_t c0 = (uint32_t)chunk_begin, m = nchunks ? (uint32_t)nchunks : h.nchunks - c0, P = 2 * h.num_layers, G = h.ngroups;
+  // the window's groups, as decode_window finds them
+  const uint32_t wc_lo = (uint32_t)win->src_head_begin * h.head_size, wc_hi = wc_lo + (uint32_t)win->nheads * h.head_size;
+  const uint32_t wg_lo = wc_lo / 64, wg_hi = (wc_hi - 1) / 64 + 1;
+  uint64_t sum = 0;
+  for (uint32_t ch = c0; ch < c0 + m; ch++) {
+    const u8* st = b + h.off_static + (uint64_t)ch * h.static_stride;
+    lmc_blob_header bh;
+    // (lmc_blob_info reads the header alone and is told the blob's length, which a static slot does not hold: any; it finds
+    // the directory where lmc_blob_layout puts it, in front of off_streams)
+    if (lmc_blob_info(st, 0xffffffffu, &bh) != LMC_OK || bh.nplanes != P || bh.ngroups != G || bh.off_streams > h.static_stride)
+      return LMC_ERR_INVALID;
+    const uint32_t* gdir = (const uint32_t*)(st + bh.off_gdir);
+    for (uint32_t p = 0; p < P; p++) {
+      const uint32_t wb = gdir[2 * (p * G + wg_lo)];
+      const uint32_t we = wg_hi < G ? gdir[2 * (p * G + wg_hi)] : p + 1 < P ? gdir[2 * ((p + 1) * G)] : bh.stream_bytes;
+      if (we < wb) return LMC_ERR_INVALID;
+      sum += we - wb;
+    }
+  }
+  *stream_bytes_out = sum;
+  return LMC_OK;
 }
 
 // ---- bounded tiers: blobs of earlier stores -> a pack (demotion), a pack -> blobs (promotion) ------------------------

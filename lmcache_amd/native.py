@@ -238,6 +238,10 @@ SYMBOLS = {
     "lmc_load_pack": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _PL, _i32, _i32, _vp, _vp, _vp]),
     "lmc_load_pack_post": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _PL, _i32, _i32, _vp, _vp, _vp,
                                           ctypes.POINTER(RangePostStruct)]),
+    "lmc_load_pack_heads": (ctypes.c_int, [_vp, _vp, _u64, _i32, _i32, _PL, _i32, _i32, _vp,
+                                           ctypes.POINTER(HeadWindowStruct), _vp, _vp]),
+    "lmc_pack_window_bytes": (ctypes.c_int, [_vp, _u64, _i32, _i32, ctypes.POINTER(HeadWindowStruct),
+                                             ctypes.POINTER(ctypes.c_uint64)]),
     "lmc_pack_blobs": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _u64, _vp, _vp]),
     "lmc_transcode_fixed": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _u64, _vp, _vp,
                                            _vp]),
@@ -365,6 +369,15 @@ def pack_chunk_bytes(pack_ptr: int, nbytes: int, chunk: int) -> int:
     size = ctypes.c_uint32(0)
     check(lib().lmc_pack_chunk_bytes(pack_ptr, nbytes, chunk, ctypes.byref(size)), "lmc_pack_chunk_bytes")
     return int(size.value)
+
+
+def pack_window_bytes(pack_ptr: int, nbytes: int, chunk_begin: int, nchunks: int, heads: HeadWindow) -> int:
+    """Stream bytes Context.load_pack_heads moves for chunks [chunk_begin, chunk_begin + nchunks) (0 = all that follow) of
+    a pack in host memory and the window `heads` (lmc_pack_window_bytes, host only)."""
+    out = ctypes.c_uint64(0)
+    win = None if heads is None else ctypes.byref(HeadWindow(*heads).struct())
+    check(lib().lmc_pack_window_bytes(pack_ptr, nbytes, chunk_begin, nchunks, win, ctypes.byref(out)), "lmc_pack_window_bytes")
+    return int(out.value)
 
 
 def pack_bound(n: int, L: int, chunk_tokens: int, H: int, D: int) -> int:
@@ -1125,6 +1138,15 @@ class Context:
         """lmc_load_pack_post: load_pack with `post` (RangePost.struct) done to every range between its decode and its event."""
         self._call_post("lmc_load_pack_post", dst.device, stream, status_ptr, post, pack_ptr, pack_bytes, chunk_begin, nchunks,
                         ctypes.byref(dst.struct), dst_tok0, layers_per_range, range_events_ptr)
+
+    def load_pack_heads(self, pack_ptr: int, pack_bytes: int, chunk_begin: int, nchunks: int, dst: KVLayout, dst_tok0: int,
+                        layers_per_range: int, range_events_ptr: Optional[int], heads: HeadWindow,
+                        stream: Optional[int] = None, status_ptr: Optional[int] = None) -> None:
+        """lmc_load_pack_heads: load_pack of a window of heads of a pack whose blobs have heads.src_heads heads, into heads
+        [heads.dst_head_begin, ...) of `dst` (its own head count); only the window's streams cross PCIe (k_pack_window)."""
+        self._call_post("lmc_load_pack_heads", dst.device, stream, status_ptr, None if heads is None else HeadWindow(*heads).struct(),
+                        pack_ptr, pack_bytes, chunk_begin, nchunks, ctypes.byref(dst.struct), dst_tok0, layers_per_range,
+                        range_events_ptr)
 
     def pack_blobs(self, blob_ptrs: int, blob_bytes_ptr: int, nchunks: int, L: int, H: int, D: int, chunk_tokens: int,
                    ntokens: int, pack_ptr: int, pack_cap: int, device, stream: Optional[int] = None,

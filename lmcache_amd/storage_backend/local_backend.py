@@ -282,6 +282,10 @@ class LMCLocalBackend(LMCBackendInterface):
         # LMCACHE_AMD_FIXED_LAYERWISE=1 is set (read here, once): the default keeps what the tier has always done with a
         # layer-wise store -- one encode of the whole context behind the last layer
         self.fixed_layerwise = self.model == "fixed" and os.environ.get("LMCACHE_AMD_FIXED_LAYERWISE", "0") == "1"
+        # LMCACHE_AMD_PACK_WINDOW=1 (read here, once): a window of heads (get_kv_range(heads=...)) of a run of pack chunks is
+        # loaded from the pack where it lies and only the window's streams cross PCIe (lmc_load_pack_heads); the default
+        # keeps what such a run has always done -- every chunk's whole blob, rebuilt in a pinned allocation of its own
+        self.pack_window = os.environ.get("LMCACHE_AMD_PACK_WINDOW", "0") == "1"
         self._tiers = Tiers(self._lru, self._demote_group if self._demotes() else None, self._drop_group, self._demoted_size)
         self.put_queue: "queue.Queue" = queue.Queue()
         self.put_thread = threading.Thread(target=self.put_worker, daemon=True)
@@ -1089,8 +1093,10 @@ class LMCLocalBackend(LMCBackendInterface):
         native.HeadWindow -- the chunks were stored under another tensor-parallel degree and have heads.src_heads heads,
         of which a window goes to heads of `dst`, which has a head count of its own.  HBM blobs, coded or fixed-width, are
         decoded where they lie and only the window's streams are read.  A pack chunk gives its blob (_own_blob) and the
-        WHOLE blob crosses PCIe before the window is decoded from it (CacheGenDeviceCodec.decode): moving only the
-        window's byte range of a pack is not built.  The decoders hold every blob's header against heads.src_heads."""
+        WHOLE blob crosses PCIe before the window is decoded from it (CacheGenDeviceCodec.decode) -- unless
+        LMCACHE_AMD_PACK_WINDOW=1 was set when the backend was built (self.pack_window): then a run of pack chunks is one
+        lmc_load_pack_heads, which gathers only the window's streams out of the pack where it lies (k_pack_window) and
+        allocates nothing.  The decoders hold every blob's header against heads.src_heads."""
         if heads is not None:
             if not self.supports_head_window:
                 raise ValueError(f"get_kv_range(heads=...): the {self.mode!r} tier stores raw chunks; a window of heads is "
@@ -1141,8 +1147,10 @@ class LMCLocalBackend(LMCBackendInterface):
             def kind_of(e):
                 if isinstance(e, _DevChunk):
                     return "dev-fixed" if e.model == "fixed" else "dev"
-                # (a window of heads: a pack chunk gives its own blob, which crosses PCIe whole -- see get_kv_range)
-                return "pack" if isinstance(e, _PackChunk) and e.pack.chunk_tokens == chunk_tokens and heads is None else "blobs"
+                # (a window of heads: a pack chunk gives its own blob, which crosses PCIe whole, unless the backend was built
+                # with LMCACHE_AMD_PACK_WINDOW=1 -- see get_kv_range)
+                return ("pack" if isinstance(e, _PackChunk) and e.pack.chunk_tokens == chunk_tokens
+                        and (heads is None or getattr(self, "pack_window", False)) else "blobs")
             while i < len(entries):
                 e = entries[i]
                 j = i + 1
@@ -1166,7 +1174,8 @@ class LMCLocalBackend(LMCBackendInterface):
                         job = codec.decode_device([e.blob for e in entries[i:j]], dst, tok0, chunk_tokens, layers_per_launch,
                                                   post=post, model=self._run_model(entries[i:j]), heads=heads)
                     elif kind == "pack":
-                        job = codec.load_pack(entries[i].pack, entries[i].index, j - i, dst, tok0, layers_per_launch, post=post)
+                        job = codec.load_pack(entries[i].pack, entries[i].index, j - i, dst, tok0, layers_per_launch, post=post,
+                                              heads=heads)
                     else:
                         # (a pack chunk of another chunk length -- never stored by this engine -- takes its blob from the pack)
                         blobs = [self._own_blob(e) if isinstance(e, _PackChunk) else e.blob for e in entries[i:j]]

@@ -831,18 +831,28 @@ class CacheGenDeviceCodec:
         return HostPack(arena.shrink(region, total), job.nchunks, job.chunk_tokens)
 
     def load_pack(self, pack: HostPack, chunk_begin: int, nchunks: int, dst: native.KVLayout, dst_tok0: int,
-                  layers_per_range, post: Optional[native.RangePost] = None) -> DecodeJob:
+                  layers_per_range, post: Optional[native.RangePost] = None,
+                  heads: Optional[native.HeadWindow] = None) -> DecodeJob:
         """Chunks [chunk_begin, chunk_begin + nchunks) of a pack -> decoded KV through ONE C-ABI call (lmc_load_pack): the streams of a
         range of layers are one contiguous transfer, the range's decode follows it, an event per range
         (DecodeJob.layer_events) lets the model run layer 0 while the later ranges are still crossing PCIe.
         layers_per_range: see range_step.  post: a native.RangePost done to every range between its decode and its event
-        (lmc_load_pack_post)."""
+        (lmc_load_pack_post).
+        heads: a native.HeadWindow -- the pack's blobs have heads.src_heads heads, of which a window goes to heads of `dst`,
+        which has a head count of its own (lmc_load_pack_heads): only the window's streams cross PCIe, gathered by
+        k_pack_window from the pack where it lies.  No `post` then, as for decode_device."""
+        if heads is not None and post is not None:
+            raise ValueError("a head-window load takes no post-op: apply it once behind the last window")
         step = range_step(dst.L, layers_per_range)
         with self._lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             with self._launch(cur) as (st, st_ptr):
                 events, handles = self._range_events(dst.L, step)
-                if post is None:
+                if heads is not None:
+                    self.ctx.load_pack_heads(pack.blob.ptr, pack.blob.nbytes, chunk_begin, nchunks, dst, dst_tok0, step,
+                                             ctypes.cast(handles, ctypes.c_void_p).value, heads,
+                                             stream=cur.cuda_stream, status_ptr=st_ptr)
+                elif post is None:
                     self.ctx.load_pack(pack.blob.ptr, pack.blob.nbytes, chunk_begin, nchunks, dst, dst_tok0, step,
                                        ctypes.cast(handles, ctypes.c_void_p).value, stream=cur.cuda_stream, status_ptr=st_ptr)
                 else:
