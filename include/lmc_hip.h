@@ -121,11 +121,29 @@ int lmc_abi_version(void);
  *   - lmc_rope_shift_split (16-bit elements): the keys re-rotated in the split blocks themselves, under the decoders'
  *     rule for the 32-bit offsets; NOT lmc_rope_shift, which rotates rows.
  * Every other entry point -- lmc_rope_shift among them -- reads and writes rows and returns LMC_ERR_INVALID for it: bring
- * the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot read.  Any other paged_kind is
- * LMC_ERR_INVALID; a caller that zeroes the struct gets LMC_PAGED_ROWS.
+ * the range into a chunk with lmc_copy_kv first, as for any layout the encoders cannot read.
+ *
+ * paged_kind = LMC_PAGED_SHUFFLE (3; additive in ABI 6) is the shuffled KV cache that vLLM's AITER attention backend keeps
+ * for its assembly paged-attention kernels: key_cache [num_blocks, H, D/x, block_size, x] -- the same bytes as
+ * LMC_PAGED_SPLIT's -- and value_cache [num_blocks, H, block_size/x, D, x]: per x consecutive slots one [D][x] tile.
+ * slot_mapping and block_size are required, head_size % x == 0 and block_size % x == 0, stride_token is ignored;
+ * stride_head and stride_block count elements as for LMC_PAGED_SPLIT (a dense cache: stride_head = D*block_size):
+ *   K addr = plane_base(l,0) + b*stride_block + h*stride_head + (d / x)*(block_size*x) + w*x + d % x      [elements]
+ *   V addr = plane_base(l,1) + b*stride_block + h*stride_head + (w / x)*(D*x) + d*x + w % x
+ * Who takes such a layout:
+ *   - lmc_copy_kv, as its source or as its destination; the other side is any LMC_PAGED_ROWS layout (not LMC_PAGED_SPLIT,
+ *     not another shuffled one): k_copy_shuffle.h; the scatter_dst of an lmc_range_post, as a destination;
+ *   - lmc_kv_deviation, as one side (k_blend.h);
+ *   - lmc_rope_shift_split (16-bit elements): only keys are touched, and they lie as in LMC_PAGED_SPLIT; the rule for
+ *     the 32-bit offsets is that layout's.
+ * NOT the encoders and the decoders, whichever entry point: LMC_ERR_INVALID before anything is queued -- a store gathers
+ * the range into a chunk with lmc_copy_kv, a retrieve decodes into a chunk and scatters it (lmc_range_post.scatter_dst
+ * per layer range).
+ * Any other paged_kind -- 2 among them -- is LMC_ERR_INVALID; a caller that zeroes the struct gets LMC_PAGED_ROWS.
  */
 #define LMC_PAGED_ROWS 0
 #define LMC_PAGED_SPLIT 1
+#define LMC_PAGED_SHUFFLE 3
 typedef struct lmc_kv_layout {
   int32_t dtype;      /* LMC_DTYPE_BF16 / FP16 / FP8_E4M3 / FP8_E5M2 (elements of 2 or 1 bytes; strides count elements) */
   int32_t num_layers; /* L */
@@ -139,7 +157,7 @@ typedef struct lmc_kv_layout {
   int64_t stride_head;
   const int64_t* slot_mapping; /* device [ntokens] or NULL */
   int32_t block_size;
-  int32_t paged_kind; /* LMC_PAGED_ROWS / LMC_PAGED_SPLIT (this word was padding, zero, before) */
+  int32_t paged_kind; /* LMC_PAGED_ROWS / LMC_PAGED_SPLIT / LMC_PAGED_SHUFFLE (this word was padding, zero, before) */
   int64_t stride_block;
 } lmc_kv_layout;
 
@@ -406,7 +424,7 @@ int lmc_decode_chunks_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint6
  *   `dst` below is the job's decode destination; the post-op works on the layer window [l0, l0 + nl) of the layouts
  *   cos_sin .. deltas  a rotation as lmc_rope_shift takes it (cos_sin NULL: none); deltas[i] belongs to token tok_begin + i
  *   tok_begin, ntok    the tokens of `dst` this job filled (the caller knows: dst_tok0, the chunks, the first-chunk trim)
- *   scatter_dst        NULL, or an LMC_PAGED_SPLIT cache: `dst` is a staged chunk of rows, and token tok_begin + i of the
+ *   scatter_dst        NULL, or an LMC_PAGED_SPLIT or LMC_PAGED_SHUFFLE cache: `dst` is a staged chunk of rows, and token tok_begin + i of the
  *                      range's layers is scattered to token scatter_tok0 + i of scatter_dst (lmc_copy_kv's scatter)
  * Per range:  rotation -- lmc_rope_shift's kernels in place on the window of `dst` (rows);  scatter -- lmc_copy_kv's
  * scatter of the window;  both -- the rotation of the staged window, then its scatter, two launches (a scatter that
@@ -419,7 +437,7 @@ int lmc_decode_chunks_schedule(lmc_ctx* ctx, const void* const* blob_ptrs, uint6
  * `dst` with scatter_dst NULL, or with a scatter_dst that differs from `dst` in any field, or with
  * scatter_tok0 != tok_begin, stays LMC_ERR_INVALID.)
  * The whole post-op is held against lmc_rope_shift's and lmc_copy_kv's rules before anything of the job is queued
- * (LMC_ERR_INVALID): a rotation of an LMC_PAGED_SPLIT `dst`, of fp8, a scatter_dst that is not LMC_PAGED_SPLIT or differs
+ * (LMC_ERR_INVALID): a rotation of an LMC_PAGED_SPLIT `dst`, of fp8, a scatter_dst that is neither LMC_PAGED_SPLIT nor LMC_PAGED_SHUFFLE or differs
  * from `dst` in geometry or dtype, ntok < 1, ...  A per-token |delta| outside the table is reported as lmc_rope_shift
  * reports it with job_status NULL: LMC_STATUS_BAD_POSITION in the context's sticky word, that token copied unrotated (the
  * job's own word stays the verdict on its blobs).
@@ -552,7 +570,9 @@ int lmc_decode_symbols(lmc_ctx* ctx, const void* blob, int32_t L, int32_t H, int
  * connector's slot_mapping gather / reshape_and_cache_flash scatter
  * (LLM_Engine.rst:91-122).  Both layouts share L, H, D and dtype.
  * dst token index = dst_tok0 + (t - tok_begin).
- * One side (not both) may be LMC_PAGED_SPLIT: the gather from / scatter into vLLM's ROCm paged-attention cache.
+ * One side (not both) may be LMC_PAGED_SPLIT: the gather from / scatter into vLLM's ROCm paged-attention cache
+ * (k_copy_split.h), or LMC_PAGED_SHUFFLE: the same for the AITER backend's shuffled cache (k_copy_shuffle.h); the other
+ * side is then an LMC_PAGED_ROWS layout.
  */
 int lmc_copy_kv(lmc_ctx* ctx, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok,
                 const lmc_kv_layout* dst, int32_t dst_tok0, lmc_stream_t stream);
@@ -596,7 +616,8 @@ int lmc_rope_shift(lmc_ctx* ctx, const lmc_kv_layout* kv, int32_t tok_begin, int
  * paged-attention kernels -- behind a DIRECT decode (lmc_decode_chunks_schedule, lmc_decode_chunks_fixed_split_schedule,
  * lmc_load_pack, a scatter by lmc_copy_kv) there is no staged chunk of rows to rotate first.  The NeoX partners of a pair
  * lie in granules j and j + rot_dim/16 of one (block, head, slot), the GPT-J partners inside one granule.
- *   `kv` must be LMC_PAGED_SPLIT with 16-bit elements (bf16 / fp16); every other argument, the arithmetic, the status
+ *   `kv` must be LMC_PAGED_SPLIT -- or LMC_PAGED_SHUFFLE, whose key planes lie the same way -- with 16-bit elements
+ *   (bf16 / fp16); every other argument, the arithmetic, the status
  *   bit and every refusal are lmc_rope_shift's.  LMC_ERR_INVALID with nothing launched as well for: a rows layout
  *   (lmc_rope_shift takes that), a split layout beyond the 32-bit offsets stated at lmc_kv_layout for the decoders, and
  *   ntok * num_heads * (work items of a head) >= 2^31.
@@ -631,7 +652,7 @@ int lmc_rope_shift_split(lmc_ctx* ctx, const lmc_kv_layout* kv, int32_t tok_begi
  *   dev_k, dev_v   device fp32 [ntok]; either may be NULL (that plane is skipped), not both
  *   Tokens are addressed through each layout's own slot_mapping and strides, exactly as lmc_copy_kv addresses its two
  *   sides, and the layouts follow lmc_copy_kv's rules: any strides, any LMC_PAGED_ROWS layout, at most one side
- *   LMC_PAGED_SPLIT; num_heads, head_size and dtype equal on both sides -- num_layers may differ (`a` is typically the
+ *   LMC_PAGED_SPLIT or LMC_PAGED_SHUFFLE; num_heads, head_size and dtype equal on both sides -- num_layers may differ (`a` is typically the
  *   model's fresh [T,H,D] pair of one layer, `b` the whole cache).  bf16 and fp16 only: fp8 is refused as lmc_rope_shift
  *   refuses it (a blended fp8 cache cannot be position-shifted in the first place).
  *   LMC_ERR_INVALID, nothing launched and nothing written: a layout lmc_copy_kv would refuse, a mismatch of H, D or dtype,

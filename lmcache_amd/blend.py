@@ -25,11 +25,16 @@ import torch
 from lmcache_amd import native
 
 _PLANES = ("k", "v", "kv")
-_LAYOUTS = ("NBHD", "NHBD", "NHDB")
+_LAYOUTS = ("NBHD", "NHBD", "NHDB", "NHBDx")
 
 
 def _cache_geometry(cache, layout: str) -> Tuple[torch.Tensor, int, int, int]:
     """(a tensor of the layer's cache, H, D, block size) of one entry of kv_caches in `layout`."""
+    if layout == "NHBDx":  # (key_cache, value_cache [num_blocks, H, block_size / x, D, x]): the pair only
+        if not isinstance(cache, (tuple, list)) or len(cache) != 2 or cache[0].dim() != 5 or cache[1].dim() != 5:
+            raise ValueError("NHBDx pair: (key_cache [num_blocks, H, D/x, block_size, x], value_cache [num_blocks, H, block_size/x, D, x])")
+        _, H, _, D, _ = cache[1].shape
+        return cache[1], H, D, cache[0].shape[3]
     if layout == "NHDB" and isinstance(cache, (tuple, list)):
         if len(cache) != 2 or cache[1].dim() != 4:
             raise ValueError("NHDB pair: (key_cache [num_blocks, H, D/x, block_size, x], value_cache [num_blocks, H, D, block_size])")
@@ -127,7 +132,7 @@ def kv_deviation(fresh_k: torch.Tensor, fresh_v: torch.Tensor, kv_caches, layer:
       fresh_k, fresh_v   the model's [T, H, D] tensors of that layer (bf16 / fp16, head dimension contiguous); read in
                          place (native.KVLayout.from_kv_tuple), never copied
       kv_caches, slot_mapping, block_size, layout   what retrieve_into_paged takes (native.KVLayout.paged): "NBHD", "NHBD"
-                         or "NHDB"; token t is compared with slot slot_mapping[t]
+                         "NHDB" or "NHBDx"; token t is compared with slot slot_mapping[t]
       planes             "v" (the deviation CacheBlend uses), "k", or "kv": the fp32 sum of the two
     ValueError before anything is queued: shapes, dtypes or devices that do not match, an fp8 or uint8 cache."""
     T = _check(fresh_k, fresh_v, kv_caches, layer, slot_mapping, block_size, layout, planes)

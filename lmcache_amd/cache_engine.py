@@ -205,7 +205,12 @@ class LMCacheEngine:
                   tiers and the chunk-tensor backends, whose gather IS the store.  The stored bytes are the same.
                   The fixed-width HBM tier (local_serde="cachegen-fixed") reads the split blocks with its one kernel
                   (lmc_encode_chunks_fixed_split; k_fixed.h) under the same 1024-channel limit: no gather there either,
-                  and on block-ordered slots less time as well (profiles/fixed_model.md)."""
+                  and on block-ordered slots less time as well (profiles/fixed_model.md).
+        layout "NHBDx" is the shuffled cache of vLLM's AITER attention backend: per layer the pair (key_cache [num_blocks,
+        H, D/x, block_size, x], value_cache [num_blocks, H, block_size/x, D, x]).  It is staged exactly as "NHDB" is
+        without `direct` (the gather is k_copy_shuffle.h's); no encoder reads it in place: direct=True is a ValueError
+        before anything is queued."""
+        self._refuse_direct_shuffle(layout, direct)
         self._check_paged_store(tokens, kv_caches, slot_mapping)
         self._store_from(tokens, lambda: native.KVLayout.paged(kv_caches, slot_mapping, block_size, layout),
                          skip_existing, blocking, direct=direct and layout == "NHDB")
@@ -237,7 +242,9 @@ class LMCacheEngine:
         does not take, and an "NHDB" cache without `direct` -- it has no token rows to read per layer, and its staging
         gather needs every layer.  save_layer is then a no-op, layer_event(l) is None (nothing has been read: the cache
         must keep every layer until finish), and finish() runs today's store_paged path for the keys resolved here.
-        That is correct, not layer-wise -- the rule retrieve_into_paged_layerwise states for its side; logged once."""
+        That is correct, not layer-wise -- the rule retrieve_into_paged_layerwise states for its side; logged once.
+        An "NHBDx" cache is always staged, so it always falls back; direct=True with it is a ValueError."""
+        self._refuse_direct_shuffle(layout, direct)
         self._check_paged_store(tokens, kv_caches, slot_mapping)
         fmt, cs, ntok = self.metadata.fmt, self.chunk_size, len(tokens)
         plan = self._plan_store(tokens, skip_existing)
@@ -247,7 +254,7 @@ class LMCacheEngine:
         direct = direct and layout == "NHDB"
         src = native.KVLayout.paged(kv_caches, slot_mapping, block_size, layout)
         put = None
-        if layout != "NHDB" or direct:
+        if layout not in ("NHDB", "NHBDx") or direct:
             begin = getattr(self.engine_, "begin_put_kv_layers", None)
             if begin is not None and getattr(self.engine_, "supports_kv_layout", False):
                 put = begin(keys, src, fmt, first * cs, ntok, cs)
@@ -256,6 +263,12 @@ class LMCacheEngine:
             logger.info("store_paged_layerwise: no layer-wise path for this backend / job: storing in one piece at finish() "
                         "(logged once)")
         return LayerwiseStore(self, put, keys, src, first * cs, ntok, direct)
+
+    @staticmethod
+    def _refuse_direct_shuffle(layout: str, direct: bool) -> None:
+        if direct and layout == "NHBDx":
+            raise ValueError("direct=True with layout \"NHBDx\": no encoder reads and no decoder writes the shuffled cache in "
+                             "place; use the staged path (direct=False)")
 
     def _check_paged_store(self, tokens: torch.Tensor, kv_caches, slot_mapping: torch.Tensor) -> None:
         assert self.metadata.fmt == "vllm", "paged KV is a vLLM layout"
@@ -374,7 +387,10 @@ class LMCacheEngine:
                 of native.RangePost), before the decode is queued.
         On stored_at(W) -- the chunks were stored under another tensor-parallel degree -- the cache is still this rank's
         own (its head count); the rotation and the staged scatter are queued ONCE, behind the last source's window.  With
-        direct=True the known caveat holds: slots of a miss may hold garbage."""
+        direct=True the known caveat holds: slots of a miss may hold garbage.
+        layout "NHBDx" (the AITER backend's shuffled cache, see store_paged) is STAGED as "NHDB" is by default, with or
+        without `rope` (the staged rows are rotated, then scattered by k_copy_shuffle.h); direct=True with it is a
+        ValueError before anything is queued."""
         target = _PagedTarget(self, tokens, kv_caches, slot_mapping, block_size, layout, mask, rope, direct)
         # (without jobs_out no decode job takes the post-ops: _retrieve_into queues them itself, native.RangePost.apply
         # over tokens [0, got) behind the last write, and only when the retrieve did not miss)
@@ -447,6 +463,8 @@ class LMCacheEngine:
     def _cache_ref(kv_caches, layout: str):
         """(a tensor of the first layer's cache, the head size) of a paged cache in `layout`."""
         first = kv_caches[0]
+        if layout == "NHBDx":  # the (key_cache, value_cache [num_blocks, H, block_size / x, D, x]) pair
+            return first[1], first[1].shape[3]
         if layout == "NHDB":  # [2, num_blocks, H, D, block_size], or the (key_cache, value_cache [num_blocks, H, D, block_size]) pair
             pair = isinstance(first, (tuple, list))
             ref = first[1] if pair else first
@@ -788,6 +806,7 @@ class _PagedTarget:
     def __init__(self, engine: "LMCacheEngine", tokens, kv_caches, slot_mapping, block_size: int, layout: str, mask, rope, direct):
         assert engine.metadata.fmt == "vllm", "paged KV is a vLLM layout"
         assert len(tokens) == slot_mapping.numel(), "one slot per token"
+        engine._refuse_direct_shuffle(layout, direct)
         self.num_skip_tok = 0 if mask is None else int(len(mask) - int(torch.sum(mask)))
         self.fused = rope is not None and engine._fused_rope_tier()  # the rotation rides inside the fixed-width decode
         head_size = engine._head_size(kv_caches, layout) if self.fused else None
@@ -799,7 +818,7 @@ class _PagedTarget:
                                  "not address an \"NHDB\" cache); use the staged retrieve")
             engine._check_rope(rope, kv_caches, layout, len(tokens))
         self._cache = (kv_caches, slot_mapping, block_size, layout)
-        self.ntokens, self.rope, self.staged = len(tokens), rope, layout == "NHDB" and not direct
+        self.ntokens, self.rope, self.staged = len(tokens), rope, layout in ("NHDB", "NHBDx") and not direct
         self.L = self.device = self._post = None
         self.hold = (None, None)  # what a caller that returns before the kernels have run keeps alive
 
@@ -808,7 +827,7 @@ class _PagedTarget:
         skip, rope = self.num_skip_tok, self.rope
         dst = native.KVLayout.paged(kv_caches, slot_mapping[skip:skip + nret], block_size, layout)
         assert dst.L == L and native.torch_dtype(dst.dtype) == dtype, "cache geometry / dtype differs from the stored chunks"
-        assert layout != "NHDB" or (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
+        assert layout not in ("NHDB", "NHBDx") or (dst.H, dst.D) == (H, D), "cache geometry differs from the stored chunks"
         self.L, self.device = L, dst.device
         rows, chunk = dst, None  # where the tokens lie as rows
         if self.staged:

@@ -17,7 +17,7 @@
 //       rows, vector-addressable (lmc_copy_kv's `vec` rule, plane base on a 16-byte boundary)   one 16-byte load
 //       rows, anything else (odd strides, head_size % 8 with the heads apart, a base 2 bytes off) eight element loads
 //       split K   the run is one x-granule of the token: one 16-byte load (strides multiples of 8, aligned base), else 8
-//       split V   eight elements block_size apart
+//       split V   eight elements block_size apart (LMC_PAGED_SHUFFLE: 8 apart, inside the token's [D][8] tile)
 //     The LPT lanes fold their sums with xor-shuffles; lane 0 of the group stores.
 //   TILE form (a V plane with one LMC_PAGED_SPLIT side): a wave takes a tile of 8 consecutive tokens, the tiles anchored at
 //     the first token's slot % 8 as in k_copy_split.h, so that the tiles of a block-ordered mapping are eight consecutive
@@ -27,6 +27,10 @@
 //     sums, one per token.  They are folded by a reduce-scatter (4 + 2 + 1 exchanges halve what a lane holds, three more
 //     finish a token: 10 exchanges for 8 tokens).  Any other tile -- the range's ragged ends, random slots, a run that
 //     enters a block at offset 5, an unaligned base -- goes token by token through dev_ld8: correct, slow.
+//     The same form has an instance for an LMC_PAGED_SHUFFLE side (DEV_TILE_SHUFFLE): such a run of eight slots is one
+//     [D][8] tile of the value cache, whose granule d IS channel d of the eight tokens -- the lanes' 16-byte loads are
+//     consecutive (1 KB a wave) where the split cache has them block_size elements apart.  Everything behind the load --
+//     the order of the sums, the reduce-scatter -- is the split instance's, line for line.
 // A slot is read from slot_mapping only for a token of the range.  Plane, block and token offsets are 64-bit.
 #pragma once
 #include "lmc_device.h"
@@ -37,7 +41,8 @@ struct DevSide {
   KvAddr kv;
   int tok0, plane_k, plane_v;  // the two planes of the side's layer (p = kv * L + layer)
   int vec;                     // host: every stride lets the side be read 16 bytes at a time (the kernel adds the base)
-  int split;                   // LMC_PAGED_SPLIT
+  int split;                   // LMC_PAGED_SPLIT or LMC_PAGED_SHUFFLE: no rows, K planes x-split
+  int shuffle;                 // LMC_PAGED_SHUFFLE: V planes in [D][8] tiles of eight slots
 };
 struct DeviationArgs {
   DevSide a, b;
@@ -54,14 +59,14 @@ struct DevPlane {
   const u16* pb;
   long long stride_head, stride_block;
   u32 D, bs;
-  bool vec, split, is_k;
+  bool vec, split, shuffle, is_k;
 };
 __device__ __forceinline__ DevPlane dev_plane(const DevSide& s, int kv) {
   DevPlane p;
   p.pb = lmc_plane_base(s.kv, kv ? s.plane_v : s.plane_k);
   p.stride_head = s.kv.stride_head; p.stride_block = s.kv.stride_block;
   p.D = (u32)s.kv.D; p.bs = (u32)s.kv.block_size;
-  p.split = s.split != 0; p.is_k = kv == 0;
+  p.split = s.split != 0; p.shuffle = s.shuffle != 0; p.is_k = kv == 0;
   p.vec = s.vec != 0 && (((uintptr_t)p.pb) & 15u) == 0u;
   return p;
 }
@@ -97,6 +102,10 @@ __device__ __forceinline__ uint4 dev_ld8(const DevPlane& p, long long toff, u32 
     if (p.vec) return ld_global_u4_nt(q);
 #pragma unroll
     for (u32 k = 0; k < 8; k++) e[k] = q[k];
+  } else if (p.shuffle) {
+    q += (long long)(w >> 3) * (p.D * 8u) + (long long)d0 * 8 + (w & 7u);
+#pragma unroll
+    for (u32 k = 0; k < 8; k++) e[k] = q[k * 8u];
   } else {
     q += (long long)d0 * p.bs + w;
 #pragma unroll
@@ -124,9 +133,10 @@ __device__ __forceinline__ float dev_wave_sum(float v, int lanes) {  // over ali
   return v;
 }
 
-// TILE: the instance of a V plane with a split side; the other instance is the group form alone, which needs a third of
-// the registers and so keeps twice the waves resident (a wave is a chain of dependent loads: occupancy is its rate).
-template <int DT, bool TILE>
+// TILE: the instances of a V plane with a split / a shuffled side; the other instance is the group form alone, which needs
+// a third of the registers and so keeps twice the waves resident (a wave is a chain of dependent loads: occupancy is its rate).
+enum { DEV_GROUP = 0, DEV_TILE_SPLIT = 1, DEV_TILE_SHUFFLE = 2 };
+template <int DT, int TILE>
 __global__ __launch_bounds__(64 * BLEND_WAVES) void k_kv_deviation(DeviationArgs g) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int kv = g.plane_kv[blockIdx.y];
@@ -134,7 +144,7 @@ __global__ __launch_bounds__(64 * BLEND_WAVES) void k_kv_deviation(DeviationArgs
   const DevPlane pa = dev_plane(g.a, kv), pb = dev_plane(g.b, kv);
   const u32 C8 = (u32)g.C >> 3;
 
-  if constexpr (!TILE) {  // GROUP form
+  if constexpr (TILE == DEV_GROUP) {
     const int lpt = g.lpt, tpw = 64 / lpt;
     const u32 j0 = (u32)(lane & (lpt - 1));
     const long long nitems = ((long long)g.ntok + tpw - 1) / tpw;
@@ -171,14 +181,17 @@ __global__ __launch_bounds__(64 * BLEND_WAVES) void k_kv_deviation(DeviationArgs
     const bool fast = runs && lo == 0 && hi == 8 && (s_first & 7u) == 0u && __ballot(tv && s != s_first + (u32)lane) == 0ull;
     if (fast) {
       const u32 blk = s_first / bs, w0 = s_first - blk * bs;
-      const u16* const spt = psp.pb + (long long)blk * psp.stride_block + w0;
+      // tile position 0, channel 0; a channel's granule is `cstep` elements from the next
+      constexpr bool SHUF = TILE == DEV_TILE_SHUFFLE;
+      const u16* const spt = psp.pb + (long long)blk * psp.stride_block + (SHUF ? (long long)(w0 >> 3) * (psp.D * 8u) : (long long)w0);
+      const u32 cstep = SHUF ? 8u : bs;
       long long ro[8];
 #pragma unroll
       for (int k = 0; k < 8; k++) ro[k] = __shfl(roff, k);
       float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       for (u32 c = (u32)lane; c < (u32)g.C; c += 64u) {
         const u32 h = c / psp.D, d = c - h * psp.D;
-        const uint4 v = ld_global_u4_nt(spt + (long long)h * psp.stride_head + (long long)d * bs);
+        const uint4 v = ld_global_u4_nt(spt + (long long)h * psp.stride_head + (long long)d * cstep);
         const u16* const rp = prw.pb + (long long)h * prw.stride_head + d;
         const u32 vw[4] = {v.x, v.y, v.z, v.w};
         u32 r[8];

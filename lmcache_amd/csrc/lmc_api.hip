@@ -18,6 +18,7 @@
 #include "../../include/lmc_hip.h"
 #include "k_blend.h"
 #include "k_copy.h"
+#include "k_copy_shuffle.h"
 #include "k_copy_split.h"
 #include "k_decode.h"
 #include "k_encode_counts.h"
@@ -270,12 +271,16 @@ int lmc_device_status(lmc_ctx* c, int clear) {
 // `split`: the caller addresses LMC_PAGED_SPLIT itself (lmc_copy_kv, the decode entry points that decode_common lets and
 // the encode entry points that encode_job_ok lets); everybody else reads and writes rows and must refuse such a layout
 // rather than address it as rows.
-static bool layout_ok(const lmc_kv_layout* l, bool vec = true, bool split = false) {
+// `shuffle`: the caller addresses LMC_PAGED_SHUFFLE as well (lmc_copy_kv, lmc_kv_deviation, lmc_rope_shift_split: nobody
+// else -- a caller that takes LMC_PAGED_SPLIT alone would address the value planes wrongly).
+static bool layout_ok(const lmc_kv_layout* l, bool vec = true, bool split = false, bool shuffle = false) {
   if (!l) return false;
-  if (l->paged_kind != LMC_PAGED_ROWS && l->paged_kind != LMC_PAGED_SPLIT) return false;
-  if (l->paged_kind == LMC_PAGED_SPLIT) {
+  if (l->paged_kind != LMC_PAGED_ROWS && l->paged_kind != LMC_PAGED_SPLIT && l->paged_kind != LMC_PAGED_SHUFFLE) return false;
+  if (l->paged_kind != LMC_PAGED_ROWS) {
+    const int x = lmc_dtype_fp8(l->dtype) ? 16 : 8;
     if (!split || vec || !l->slot_mapping || l->block_size < 1) return false;
-    if (l->head_size < 1 || l->head_size % (lmc_dtype_fp8(l->dtype) ? 16 : 8)) return false;  // whole x-granules
+    if (l->head_size < 1 || l->head_size % x) return false;  // whole x-granules
+    if (l->paged_kind == LMC_PAGED_SHUFFLE && (!shuffle || l->block_size % x)) return false;  // whole [D][x] value tiles
   }
   if (l->dtype != LMC_DTYPE_BF16 && l->dtype != LMC_DTYPE_FP16 && !lmc_dtype_fp8(l->dtype)) return false;
   if (l->num_layers < 1 || 2 * l->num_layers > LMC_MAX_PLANES) return false;
@@ -322,7 +327,7 @@ static bool layout_ok(const lmc_kv_layout* l, bool vec = true, bool split = fals
 static bool decode_dst_ok(const lmc_kv_layout* d, long long chunk_tokens) {
   typedef __int128 wide;  // (the products of two 64-bit strides and counts)
   const wide E = lmc_dtype_fp8(d->dtype) ? 1 : 2;
-  if (d->paged_kind == LMC_PAGED_SPLIT) {
+  if (d->paged_kind == LMC_PAGED_SPLIT || d->paged_kind == LMC_PAGED_SHUFFLE) {  // (the latter for lmc_rope_shift_split: a block's head is as long)
     if (d->stride_head < 0) return false;
     return ((wide)(d->num_heads - 1) * d->stride_head + (wide)d->head_size * d->block_size) * E + 7 * 16 <= (wide)0xfffffff0ll;
   }
@@ -1455,15 +1460,16 @@ int lmc_transcode_to_fixed(lmc_ctx* c, const void* const* blob_ptrs, const uint3
 
 }  // extern "C"
 
-// One side of lmc_copy_kv is LMC_PAGED_SPLIT (k_copy_split.h): a wave per (plane, head, tile of TT tokens).
+// One side of lmc_copy_kv is LMC_PAGED_SPLIT (k_copy_split.h) or LMC_PAGED_SHUFFLE (k_copy_shuffle.h, whose tiles are a
+// multiple of X tokens: block_size % X == 0 is the layout's rule): a wave per (plane, head, tile of TT tokens).
 static int copy_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst,
                       int32_t dst_tok0, hipStream_t stream) {
-  const bool gather = src->paged_kind == LMC_PAGED_SPLIT;
+  const bool gather = src->paged_kind != LMC_PAGED_ROWS;
   const lmc_kv_layout* sp = gather ? src : dst;
   const lmc_kv_layout* rw = gather ? dst : src;
-  const bool b8 = lmc_dtype_fp8(sp->dtype);
+  const bool b8 = lmc_dtype_fp8(sp->dtype), shuffle = sp->paged_kind == LMC_PAGED_SHUFFLE;
   const int X = b8 ? 16 : 8;  // elements of a 16-byte granule
-  const int tt = sp->block_size % 32 == 0 ? 32 : sp->block_size % 16 == 0 ? 16 : 8;
+  const int tt = sp->block_size % 32 == 0 ? 32 : sp->block_size % 16 == 0 ? 16 : 8;  // (shuffle, fp8: block_size % 16 == 0, never 8)
   SplitCopyArgs a;
   memset(&a, 0, sizeof a);
   a.sp = to_addr(sp); a.rw = to_addr(rw);
@@ -1485,7 +1491,11 @@ static int copy_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, i
     with_bool(gather, [&](auto g) {
       with_int<32, 16, 8>(tt, [&](auto t) {
         using E = std::conditional_t<decltype(e8)::value, u8, u16>;
-        hipLaunchKernelGGL((k_copy_split<E, decltype(g)::value, decltype(t)::value>), dim3((unsigned)blocks), dim3(64 * SPLIT_WAVES), lds, stream, a);
+        constexpr bool G = decltype(g)::value;
+        constexpr int TT = decltype(t)::value;
+        if (!shuffle) hipLaunchKernelGGL((k_copy_split<E, G, TT>), dim3((unsigned)blocks), dim3(64 * SPLIT_WAVES), lds, stream, a);
+        else if constexpr (TT % (16 / (int)sizeof(E)) == 0)
+          hipLaunchKernelGGL((k_copy_shuffle<E, G, TT>), dim3((unsigned)blocks), dim3(64 * SPLIT_WAVES), lds, stream, a);
       });
     });
   });
@@ -1495,11 +1505,11 @@ static int copy_split(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, i
 
 // What lmc_copy_kv asks of its two layouts and its range (every refusal LMC_ERR_INVALID, nothing launched).
 static bool copy_kv_ok(const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst, int32_t dst_tok0) {
-  if (!layout_ok(src, false, true) || !layout_ok(dst, false, true) || ntok < 1 || tok_begin < 0 || dst_tok0 < 0) return false;
+  if (!layout_ok(src, false, true, true) || !layout_ok(dst, false, true, true) || ntok < 1 || tok_begin < 0 || dst_tok0 < 0) return false;
   if (src->num_layers != dst->num_layers || src->num_heads != dst->num_heads || src->head_size != dst->head_size ||
       src->dtype != dst->dtype)
     return false;
-  return !(src->paged_kind == LMC_PAGED_SPLIT && dst->paged_kind == LMC_PAGED_SPLIT);  // one side is rows
+  return src->paged_kind == LMC_PAGED_ROWS || dst->paged_kind == LMC_PAGED_ROWS;  // one side is rows
 }
 
 // A rotation as lmc_rope_shift takes it.
@@ -1575,7 +1585,8 @@ static int rope_split_per_head(const lmc_kv_layout* kv, const RopeSpec& r) {
 }
 // What lmc_rope_shift_split asks: rope_ok's rules for a 16-bit split cache, whose 32-bit offsets follow the decoders' rule.
 static bool rope_split_ok(const lmc_kv_layout* kv, int32_t tok_begin, int32_t ntok, const RopeSpec& r) {
-  if (!layout_ok(kv, false, true) || kv->paged_kind != LMC_PAGED_SPLIT || lmc_dtype_fp8(kv->dtype) || !decode_dst_ok(kv, 0))
+  // (LMC_PAGED_SHUFFLE: its key planes are LMC_PAGED_SPLIT's, and only keys are touched)
+  if (!layout_ok(kv, false, true, true) || kv->paged_kind == LMC_PAGED_ROWS || lmc_dtype_fp8(kv->dtype) || !decode_dst_ok(kv, 0))
     return false;
   if (ntok < 1 || tok_begin < 0 || (long long)tok_begin + ntok > INT32_MAX || !r.cos_sin || r.table_rows < 1) return false;
   if (r.rot_dim < 2 || (r.rot_dim & 1) || r.rot_dim > kv->head_size) return false;
@@ -1639,7 +1650,7 @@ static bool post_in_place(const lmc_kv_layout* dst, const lmc_range_post* p) {
 static bool post_ok(const lmc_kv_layout* dst, const lmc_range_post* p) {
   if (!p || (!p->cos_sin && !p->scatter_dst)) return true;
   if (post_in_place(dst, p)) return rope_split_ok(dst, p->tok_begin, p->ntok, post_rope(p));
-  if (p->scatter_dst && (p->scatter_dst->paged_kind != LMC_PAGED_SPLIT ||
+  if (p->scatter_dst && (p->scatter_dst->paged_kind == LMC_PAGED_ROWS ||
                          !copy_kv_ok(dst, p->tok_begin, p->ntok, p->scatter_dst, p->scatter_tok0)))
     return false;
   return !p->cos_sin || rope_ok(dst, p->tok_begin, p->ntok, post_rope(p));  // (a split `dst` has no rows to rotate: refused)
@@ -1677,7 +1688,7 @@ extern "C" {
 int lmc_copy_kv(lmc_ctx* c, const lmc_kv_layout* src, int32_t tok_begin, int32_t ntok, const lmc_kv_layout* dst,
                 int32_t dst_tok0, lmc_stream_t stream) {
   if (!c || !copy_kv_ok(src, tok_begin, ntok, dst, dst_tok0)) return LMC_ERR_INVALID;
-  if (src->paged_kind == LMC_PAGED_SPLIT || dst->paged_kind == LMC_PAGED_SPLIT)
+  if (src->paged_kind != LMC_PAGED_ROWS || dst->paged_kind != LMC_PAGED_ROWS)
     return copy_split(c, src, tok_begin, ntok, dst, dst_tok0, (hipStream_t)stream);
   const bool vec = layout_ok(src) && layout_ok(dst);  // else one element per thread (any strides, any head_size)
   CopyArgs a;
@@ -1721,9 +1732,9 @@ int lmc_rope_shift_split(lmc_ctx* c, const lmc_kv_layout* kv, int32_t tok_begin,
 // elements only (every refusal LMC_ERR_INVALID, nothing launched).
 static bool deviation_ok(const lmc_kv_layout* a, int32_t a_layer, int32_t a_tok0, const lmc_kv_layout* b, int32_t b_layer,
                          int32_t b_tok0, int32_t ntok, const float* dev_k, const float* dev_v) {
-  if (!layout_ok(a, false, true) || !layout_ok(b, false, true) || ntok < 1 || a_tok0 < 0 || b_tok0 < 0) return false;
+  if (!layout_ok(a, false, true, true) || !layout_ok(b, false, true, true) || ntok < 1 || a_tok0 < 0 || b_tok0 < 0) return false;
   if (a->num_heads != b->num_heads || a->head_size != b->head_size || a->dtype != b->dtype || lmc_dtype_fp8(a->dtype)) return false;
-  if (a->paged_kind == LMC_PAGED_SPLIT && b->paged_kind == LMC_PAGED_SPLIT) return false;  // one side is rows
+  if (a->paged_kind != LMC_PAGED_ROWS && b->paged_kind != LMC_PAGED_ROWS) return false;  // one side is rows
   if (a_layer < 0 || a_layer >= a->num_layers || b_layer < 0 || b_layer >= b->num_layers) return false;
   if ((long long)a_tok0 + ntok > INT32_MAX || (long long)b_tok0 + ntok > INT32_MAX) return false;
   return dev_k || dev_v;
@@ -1735,7 +1746,7 @@ static DevSide deviation_side(const lmc_kv_layout* l, int32_t layer, int32_t tok
   memset(&s, 0, sizeof s);
   s.kv = to_addr(l);
   s.tok0 = tok0; s.plane_k = layer; s.plane_v = l->num_layers + layer;
-  s.split = l->paged_kind == LMC_PAGED_SPLIT;
+  s.split = l->paged_kind != LMC_PAGED_ROWS; s.shuffle = l->paged_kind == LMC_PAGED_SHUFFLE;
   auto mult = [](int64_t v) { return v % 8 == 0; };
   s.vec = s.split ? mult(l->stride_block) && mult(l->stride_head) && (l->plane_ptrs || (mult(l->stride_layer) && mult(l->stride_kv)))
                   : layout_ok(l);
@@ -1750,7 +1761,7 @@ int lmc_kv_deviation(lmc_ctx* c, const lmc_kv_layout* a, int32_t a_layer, int32_
   DeviationArgs g;
   memset(&g, 0, sizeof g);
   // the kernel's tile form wants the split side second: the squared difference does not care
-  const bool swap = a->paged_kind == LMC_PAGED_SPLIT;
+  const bool swap = a->paged_kind != LMC_PAGED_ROWS;
   g.a = swap ? deviation_side(b, b_layer, b_tok0) : deviation_side(a, a_layer, a_tok0);
   g.b = swap ? deviation_side(a, a_layer, a_tok0) : deviation_side(b, b_layer, b_tok0);
   g.ntok = ntok; g.C = a->num_heads * a->head_size;
@@ -1762,23 +1773,23 @@ int lmc_kv_deviation(lmc_ctx* c, const lmc_kv_layout* a, int32_t a_layer, int32_
   if (dev_v) g.plane_kv[g.nplanes++] = 1;
   HIP_TRY(hipSetDevice(c->device));
   // a wave of the group form takes 64 / lpt tokens, a wave of the tile form a tile; grid-stride beyond 32 workgroups per CU
-  auto launch = [&](bool tile, long long items) {
+  auto launch = [&](int tile, long long items) {
     long long blocks = (items + BLEND_WAVES - 1) / BLEND_WAVES;
     if (blocks > 32LL * c->num_cus) blocks = 32LL * c->num_cus;
     with_kv_dtype16(a->dtype, [&](auto dt) {
-      with_bool(tile, [&](auto tl) {
+      with_int<DEV_GROUP, DEV_TILE_SPLIT, DEV_TILE_SHUFFLE>(tile, [&](auto tl) {
         hipLaunchKernelGGL((k_kv_deviation<decltype(dt)::value, decltype(tl)::value>), dim3((unsigned)blocks, (unsigned)g.nplanes),
                            dim3(64 * BLEND_WAVES), 0, (hipStream_t)stream, g);
       });
     });
   };
   const long long tpw = 64 / g.lpt, groups = (ntok + tpw - 1) / tpw;
-  if (!g.b.split) launch(false, groups);  // both planes in one launch
+  if (!g.b.split) launch(DEV_GROUP, groups);  // both planes in one launch
   else {  // a split side: the K plane in the group form, the V plane in the tile form, a launch each
     const int want_k = dev_k != nullptr, want_v = dev_v != nullptr;
     g.nplanes = 1;
-    if (want_k) { g.plane_kv[0] = 0; launch(false, groups); }
-    if (want_v) { g.plane_kv[0] = 1; launch(true, g.ntiles); }
+    if (want_k) { g.plane_kv[0] = 0; launch(DEV_GROUP, groups); }
+    if (want_v) { g.plane_kv[0] = 1; launch(g.b.shuffle ? DEV_TILE_SHUFFLE : DEV_TILE_SPLIT, g.ntiles); }
   }
   HIP_TRY(hipGetLastError());
   return LMC_OK;

@@ -126,6 +126,7 @@ class KvLayoutStruct(ctypes.Structure):
 
 
 PAGED_ROWS, PAGED_SPLIT = 0, 1  # LMC_PAGED_*: lmc_kv_layout.paged_kind
+PAGED_SHUFFLE = 3               # (2 is nobody's layout)
 # `direct` of a store (CacheGenDeviceCodec._readable) where the engine was built under LMCACHE_AMD_SPLIT_WIDE=1: a
 # PAGED_SPLIT source goes to the encoder as it is whatever its planes' width -- above 1024 channels (H * D) the
 # library's wide split instances read it (csrc/k_quantize.h, WIDE).  Truthy, so every layer that only asks `if direct`
@@ -624,9 +625,10 @@ class KVLayout:
         """vLLM paged KV: per layer a tensor [2, num_blocks, ...] addressed through slot_mapping
         (LLM_Engine.rst:91-122).  layout "NBHD" = [num_blocks, block_size, H, D] (flash layout),
         "NHBD" = [num_blocks, H, block_size, D] (BASELINE.json north star), "NHDB" = the cache of vLLM's ROCm
-        paged-attention kernels (_paged_split below)."""
-        if layout == "NHDB":
-            return KVLayout._paged_split(kv_caches, slot_mapping, block_size)
+        paged-attention kernels (_paged_split below), "NHBDx" = the shuffled cache of vLLM's AITER attention backend, per
+        layer the pair (key_cache [num_blocks, H, D/x, block_size, x], value_cache [num_blocks, H, block_size/x, D, x])."""
+        if layout in ("NHDB", "NHBDx"):
+            return KVLayout._paged_split(kv_caches, slot_mapping, block_size, shuffle=layout == "NHBDx")
         c0 = kv_caches[0]
         assert c0.is_cuda and c0.dim() == 5 and c0.shape[0] == 2
         st = c0.stride()
@@ -652,7 +654,7 @@ class KVLayout:
         return KVLayout(s, keep + [table, sm], sm.numel(), c0.device)
 
     @staticmethod
-    def _paged_split(kv_caches, slot_mapping: torch.Tensor, block_size: int) -> "KVLayout":
+    def _paged_split(kv_caches, slot_mapping: torch.Tensor, block_size: int, shuffle: bool = False) -> "KVLayout":
         """layout "NHDB": the cache that paged_attention_rocm and paged_attention_v1 / v2 read, as
         PagedAttention.split_kv_cache views it.  With x = 16 / element bytes (8 for bf16 / fp16, 16 for fp8), per layer
           - one tensor [2, num_blocks, H, D, block_size]: a copy-free .view of vLLM's [2, num_blocks, block_size * H * D];
@@ -661,16 +663,40 @@ class KVLayout:
         A token's channels are not contiguous there (K: x-element granules block_size * x apart, V: every element
         block_size apart), so the layout is not vector_readable(): the encoders cannot read it.  lmc_copy_kv gathers from and
         scatters into it (k_copy_split.h), and the decoders store into it (k_decode.h, DEC_PAGED_SPLIT) -- all of them but
-        decode_chunks, whose callers want a tensor."""
+        decode_chunks, whose callers want a tensor.
+        shuffle: layout "NHBDx" (PAGED_SHUFFLE), the shuffled cache of vLLM's AITER attention backend: the same key cache,
+        and a value cache [num_blocks, H, block_size / x, D, x] -- per x consecutive slots one [D][x] tile -- so only the
+        pair form exists, and block_size % x must be 0.  lmc_copy_kv gathers from and scatters into it (k_copy_shuffle.h);
+        neither the encoders nor the decoders take it: the engine's paths are the staged ones."""
         first = kv_caches[0]
         pair = isinstance(first, (tuple, list))
+        name = "NHBDx" if shuffle else "NHDB"
+        if shuffle and not pair:
+            raise ValueError("NHBDx: a layer cache is the pair (key_cache [num_blocks, H, D/x, block_size, x], value_cache "
+                             "[num_blocks, H, block_size/x, D, x]): the two caches have different shapes")
         v0 = first[1] if pair else first
         if not v0.is_cuda:
             raise ValueError("the paged KV cache must live on the GPU")
         x = 16 // elem_bytes(dtype_code(v0.dtype))  # (a uint8 cache is refused here: pass its fp8 view)
         planes = []  # per layer (K base, V base, H, D, block size, (stride_block, stride_head, inner strides...) of K and of V)
         for c in kv_caches:
-            if pair:
+            if shuffle:
+                k, v = c
+                if k.dim() != 5 or v.dim() != 5:
+                    raise ValueError(f"NHBDx pair: key_cache [num_blocks, H, D/x, block_size, x] and value_cache [num_blocks, H, "
+                                     f"block_size/x, D, x] expected, got {tuple(k.shape)} and {tuple(v.shape)}")
+                nb, H, _, D, _ = v.shape
+                bs = k.shape[3]
+                if bs % x:
+                    raise ValueError(f"NHBDx: block_size {bs} is no multiple of x = {x} (16 bytes of {v0.dtype}): the value "
+                                     "cache keeps one [D][x] tile per x slots")
+                if tuple(k.shape) != (nb, H, D // x, bs, x) or tuple(v.shape) != (nb, H, bs // x, D, x) or D % x:
+                    raise ValueError(f"NHBDx pair: key_cache {tuple(k.shape)} and value_cache {tuple(v.shape)} are not [num_blocks, "
+                                     f"H, D/x, block_size, x] and [num_blocks, H, block_size/x, D, x] with x = {x}")
+                ks, vs = k.stride(), v.stride()
+                dense = ks[2:] == (bs * x, x, 1) and vs[2:] == (D * x, x, 1)
+                outer = (ks[0], ks[1]) if (ks[0], ks[1]) == (vs[0], vs[1]) else None
+            elif pair:
                 k, v = c
                 if k.dim() != 5 or v.dim() != 4:
                     raise ValueError(f"NHDB pair: key_cache [num_blocks, H, D/x, block_size, x] and value_cache [num_blocks, H, D, "
@@ -693,15 +719,15 @@ class KVLayout:
             if k.dtype != v0.dtype or v.dtype != v0.dtype or k.device != v0.device or v.device != v0.device:
                 raise ValueError("all layer caches must share dtype and device")
             if bs != block_size:
-                raise ValueError(f"NHDB: the cache's blocks hold {bs} slots, block_size is {block_size}")
+                raise ValueError(f"{name}: the cache's blocks hold {bs} slots, block_size is {block_size}")
             if D % x:
-                raise ValueError(f"NHDB: head_size {D} is no multiple of x = {x} (16 bytes of {v0.dtype}): the key cache "
+                raise ValueError(f"{name}: head_size {D} is no multiple of x = {x} (16 bytes of {v0.dtype}): the key cache "
                                  "splits a head into x-element granules")
             if not dense:
-                raise ValueError("NHDB: the inner dimensions of a block's head (D/x, block_size, x for keys; D, block_size "
-                                 "for values) must be dense")
+                raise ValueError(f"{name}: the inner dimensions of a block's head (D/x, block_size, x for keys; D, block_size "
+                                 "or block_size/x, D, x for values) must be dense")
             if outer is None:
-                raise ValueError("NHDB pair: key_cache and value_cache must share their block and head strides")
+                raise ValueError(f"{name} pair: key_cache and value_cache must share their block and head strides")
             planes.append((k, v, H, D, outer))
         _, _, H, D, (stride_block, stride_head) = planes[0]
         if any(pl[2:] != planes[0][2:] for pl in planes):
@@ -713,13 +739,14 @@ class KVLayout:
         table = _pointer_tables.get(ptrs, v0.device)
         sm = slot_mapping.to(device=v0.device, dtype=torch.int64).contiguous()
         s = _layout_struct(v0.dtype, len(planes), H, D, 0, stride_head, plane_ptrs=table.data_ptr(), slot_mapping=sm.data_ptr(),
-                           block_size=block_size, stride_block=stride_block, paged_kind=PAGED_SPLIT)
+                           block_size=block_size, stride_block=stride_block,
+                           paged_kind=PAGED_SHUFFLE if shuffle else PAGED_SPLIT)
         return KVLayout(s, keep + [table, sm], sm.numel(), v0.device)
 
 
 class RangePost:
     """Python owner of what becomes one lmc_range_post per decode job: a rotation as Context.rope_shift takes it and / or
-    the LMC_PAGED_SPLIT cache the decode destination (then a staged chunk of rows) is scattered into.  Written in the
+    the LMC_PAGED_SPLIT or LMC_PAGED_SHUFFLE cache the decode destination (then a staged chunk of rows) is scattered into.  Written in the
     decode destination's tokens: deltas[t] belongs to destination token t, and destination token t goes to token
     scatter_tok0 + t of scatter_dst.  A rotation whose scatter_dst is the (PAGED_SPLIT) decode destination ITSELF, with
     scatter_tok0 0, is the in-place form: the decoder wrote the split blocks and the keys are rotated there

@@ -1,4 +1,4 @@
-"""LDS bank conflicts of the permuted phases of k_copy_split.h, enumerated on the host (no GPU) with the MI355X's
+"""LDS bank conflicts of the permuted phases of k_copy_split.h and k_copy_shuffle.h, enumerated on the host (no GPU) with the MI355X's
 per-instruction lane groups:
 
   ds_write_b128        eight groups of 8 consecutive lanes, bank = (address / 4) mod 32: the 16-byte slot is position mod 8
@@ -10,6 +10,9 @@ for every head size D up to 512, both element sizes and the three tile lengths, 
 
   Pg(w, g) = w * NG + (g + rot(w)) mod NG,  rot(w) = (NG even ? w : 0) + w / 8        (row image)
   Ps(g, w) = g * TT + (w + g) mod TT                                                   (split image, K scatter)
+
+k_copy_shuffle.h shares the K phases; its V phase has the lanes in another order over the same row image: lane v holds
+channel d = v % D of token group part = v / D (split: d = v / GPR, part = v % GPR).
 
 Prints, per phase, how many geometries are N-way at worst, and lists those above two-way.
 
@@ -51,7 +54,7 @@ def main(min_ng=4):
                 NV = TT * NG
                 if NV * 16 > 16384:  # SPLIT_MAX_IMAGE
                     continue
-                kg = ks = vv = 0
+                kg = ks = vv = sv = 0
                 for v0 in range(0, NV, 64):
                     lanes = range(v0, v0 + 64)
                     kg = max(kg, worst(W128, [Pg(v % TT, v // TT, NG) if v < NV else None for v in lanes], 8))
@@ -61,17 +64,17 @@ def main(min_ng=4):
                 if TT < X:
                     continue  # V has no 16-byte run there: element path
                 GPR = TT // X
+
+                def dword(part, d, k):
+                    return (Pg(part * X + k, d // X, NG) * 16 + (d % X) * eb) // 4
+
                 for v0 in range(0, NV, 64):
                     for k in range(X):
-                        dwords = []
-                        for v in range(v0, v0 + 64):
-                            if v >= NV:
-                                dwords.append(None)
-                                continue
-                            d, part = v // GPR, v % GPR
-                            dwords.append((Pg(part * X + k, d // X, NG) * 16 + (d % X) * eb) // 4)
-                        vv = max(vv, worst(H32, dwords, 32))
+                        lanes = range(v0, v0 + 64)
+                        vv = max(vv, worst(H32, [dword(v % GPR, v // GPR, k) if v < NV else None for v in lanes], 32))
+                        sv = max(sv, worst(H32, [dword(v // D, v % D, k) if v < NV else None for v in lanes], 32))
                 res.setdefault(("V gather / scatter: split-side single elements of the row image", vv), []).append((eb, TT, D))
+                res.setdefault(("V gather / scatter, shuffled cache: single elements of the row image", sv), []).append((eb, TT, D))
     for key in sorted(res):
         geoms = res[key]
         print(f"{key[0]}: {key[1]}-way at worst for {len(geoms)} geometries" +
